@@ -20,7 +20,9 @@ N > 1: BASELINE config C4 -- the SAME 100 M-point cloud sharded in contiguous po
 the ranks ("scaling": "strong"), depth MIN / accumulator SUM exchanged per frame; the weak-scaling
 figure (100 M points per GPU) is measured afterwards and reported under `weak_scaling`.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").  With --dump-outputs DIR (N = 1) the frame of
+the last timed step is also written to DIR as float32 .npy files (dump_outputs): the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -37,6 +39,9 @@ import __graft_entry__ as entry  # noqa: E402
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 SEEDS = {"C2": 0xC0FFEE02, "C3": 0xC0FFEE03}
 PREFILTER_BYTES_PER_PIXEL = 50.0
+DUMP_BYTES_MAX = 64_000_000  # --dump-outputs: every file written, .npy headers included
+DUMP_HEADER_SLACK = 4096
+DUMP_SAMPLE_SEED = 0xC0FFEE04
 
 
 def parse():
@@ -88,6 +93,10 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=0, help="0 = pick so the leg takes about 10-20 s (>= 3)")
     ap.add_argument("--no-parity", action="store_true", help="skip the full-size oracle parity gate on pose 0")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N=1: after the timed steps, write the frame of the last timed step (depth, image and, with the "
+                         "prefilter, the fp16 tensor) as DIR/<name>.npy in float32, for output-for-output comparisons "
+                         "of two builds (at most 64 MB: larger frames are written as a fixed, seeded pixel sample)")
     return ap.parse_args()
 
 
@@ -197,6 +206,34 @@ def measured_traffic(scene, n_local, W, H, with_filter, pack=1):
     return None, None, None
 
 
+def dump_outputs(outdir, pkg, proj, with_filter):
+    """--dump-outputs: the frame the last timed step left in `proj`'s buffers, as a caller of rtr_render receives it --
+    depth (float32 [H, W]: FLT_MAX where empty, -1 where the prefilter removed the pixel), image (float32 [H, W, 3] of
+    the u8 channels) and, with the prefilter, the U-Net tensor (float32 [5, H, W] of the fp16 values); every value
+    exact.  A frame above DUMP_BYTES_MAX is written as one fixed, seeded sample of pixels taken from every array (pixel
+    axis flattened: depth [k], image [k, 3], tensor [5, k]) plus their row-major pixel numbers (pixel_index)."""
+    H, W = proj.H, proj.W
+    npix = H * W
+    depth = proj.download(pkg._lib.BUF_DEPTH).view(np.float32)
+    image = proj.download(pkg._lib.BUF_IMAGE).astype(np.float32)
+    tensor = (proj.download(pkg._lib.BUF_TENSOR).view(np.float16).reshape(5, H, W).astype(np.float32)
+              if with_filter else None)
+    outs = {"depth": depth, "image": image}
+    if tensor is not None:
+        outs["tensor"] = tensor
+    floats_per_px = 1 + 3 + (5 if tensor is not None else 0)
+    if floats_per_px * 4 * npix + DUMP_HEADER_SLACK > DUMP_BYTES_MAX:
+        k = (DUMP_BYTES_MAX - DUMP_HEADER_SLACK) // (floats_per_px * 4 + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(npix, k, replace=False))
+        outs = {"depth": depth.reshape(npix)[idx], "image": image.reshape(npix, 3)[idx],
+                "pixel_index": idx.astype(np.float64)}
+        if tensor is not None:
+            outs["tensor"] = tensor.reshape(5, npix)[:, idx]
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start N rank processes as CHILDREN (torch.distributed.run as a
     subprocess; this process has not imported torch, let alone touched the GPU, and never replaces itself), wait for
@@ -215,6 +252,8 @@ def self_launch(n):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or args.force_exchange or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        sys.exit("--dump-outputs writes the single-GPU frame: N = 1 without --force-exchange only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
     import torch
@@ -518,6 +557,8 @@ def main():
     timed_poses = poses[args.warmup:args.warmup + args.steps]
 
     dt, timing, exchange_info = run_exchange_forms(S, renderers, args.steps, args.warmup)
+    if args.dump_outputs:  # (before anything else renders into the frame buffers)
+        dump_outputs(args.dump_outputs, pkg, S.projs[(args.steps - 1) % depth_k], with_filter)
     stream_bpp = S.projs[0].get_option("packed_millibytes_per_point") / 1000.0  # 12.0 unless the cloud is packed
     n_local = S.hi - S.lo
     main_stats = sample_stats(S.projs[0], timed_poses, with_filter)  # (the local slice's own frames)
@@ -653,8 +694,8 @@ def main():
             p1.render(poses1[k], False)
         p1.synchronize()
         t1 = time.perf_counter()
-        for k in range(50):
-            p1.render(poses1[k], False)
+        for k in range(args.steps):
+            p1.render(poses1[k % len(poses1)], False)
         p1.synchronize()
         dg1 = time.perf_counter() - t1
         p1.close()
@@ -663,7 +704,8 @@ def main():
                       "host loop timed, the GPU frame of the same arrays as the check of the plumbing" % (n1, W1, H1),
               "cpu_naive": {"value": n1 * frames1 / dt1 / 1e6, "unit": "Mpoints/s", "cores": 1, "kind": "port",
                             "ms_per_frame": dt1 / frames1 * 1e3, "frames": frames1},
-              "gpu": {"value": n1 * 50 / dg1 / 1e6, "unit": "Mpoints/s", "ms_per_step": dg1 / 50 * 1e3, "steps": 50},
+              "gpu": {"value": n1 * args.steps / dg1 / 1e6, "unit": "Mpoints/s", "ms_per_step": dg1 / args.steps * 1e3,
+                      "steps": args.steps},
               "blocks": int(len(g1.keys)),
               "parity_vs_oracle": bool(np.array_equal(d1.view(np.uint32), ref1["depth_bits"]) and
                                        np.array_equal(i1, ref1["img"]))}
