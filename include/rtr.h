@@ -116,6 +116,12 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          (the largest coordinate difference inside a lane, measured once per upload): a 256-point chunk with
  *          no lane near the frustum is neither decoded nor projected in full.  Every point still goes through
  *          the exact arithmetic before it can reach a pixel; 0 = every point of every chunk, as before.
+ *  "chunk_test": 1 (default) = with the packed coordinates, the tile-binned point kernel first tests 64
+ *          chunks at once on the boxes their headers give (the five frustum half-spaces, with the slack of
+ *          option "cull") and streams only the chunks that may reach the frustum; the lane test and the exact
+ *          arithmetic then run on those as before.  0 = every chunk through the stream (the loop structure
+ *          of round 4, in a kernel instance of its own).  Same
+ *          frame either way; no effect on unpacked clouds or with "cull" = 1.
  *  "pack": the tile-binned point kernel reads the coordinates from a LOSSLESS packed form, built once after
  *          every upload / generation / sort (and at once for the resident cloud when the option is set): per
  *          256-point chunk and axis the fp32 bit patterns are a common prefix + the 0..25 (or 32) bits below it

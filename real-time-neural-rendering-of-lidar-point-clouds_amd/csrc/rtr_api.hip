@@ -34,6 +34,7 @@ struct rtr_ctx {
     float *spread = nullptr;    // lane spread per 256-point chunk (rtr::Cloud::spread: T1's lane test)
     float absmax[3] = {0.f, 0.f, 0.f};  // largest finite |x|, |y|, |z| of the resident cloud
     int opt_lane_test = 1;      // T1 tests one point per lane first (option "lane_test")
+    int opt_chunk_test = 1;     // T1 tests packed chunks on their header boxes first (option "chunk_test")
     int opt_keep_soa = 0;       // 1: the fp32 SoA arrays stay resident beside the packed form (option "keep_soa")
     int opt_pool_worst = 0;     // 1: the extent pool is always sized for the worst case, 2 n entries (option "pool_worst_case")
     bool pool_worst = false;    // ... for this cloud: a frame overflowed the adaptive pool, or the peers map it
@@ -818,6 +819,11 @@ int rtr_set_option(rtr_ctx *c, const char *key, int value) {
         c->list_valid = false;
         return RTR_OK;
     }
+    if (!strcmp(key, "chunk_test")) {  // T1, packed clouds: the chunks' header boxes first (k_project_bin); 0 = as in round 4
+        c->opt_chunk_test = value != 0;
+        c->list_valid = false;
+        return RTR_OK;
+    }
     if (!strcmp(key, "pack")) {  // applies to the resident cloud at once, and to every later one
         NEED(c, value >= 0 && value <= 2, "pack must be 0 (never), 1 (when it pays) or 2 (always, verified)");
         c->opt_pack = value;
@@ -867,6 +873,8 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "order_ratio_ppm")) *value = (int)(c->order_ratio * 1e6f);  // chunk / cloud diagonal as uploaded
     else if (!strcmp(key, "cull")) *value = c->opt_cull;
     else if (!strcmp(key, "lane_test")) *value = c->opt_lane_test;
+    else if (!strcmp(key, "chunk_test")) *value = c->opt_chunk_test;
+    else if (!strcmp(key, "phases")) *value = c->opt_phases;
     else if (!strcmp(key, "lean")) *value = c->opt_lean;
     else if (!strcmp(key, "lean_identity")) *value = c->opt_lean_identity;
     else if (!strcmp(key, "lean_early")) *value = c->opt_lean_early;
@@ -1256,7 +1264,7 @@ static int bin_points(rtr_ctx *c, const float P[16], bool overlapped, bool clear
     {
         Timed tm(c, RTR_K_MIN_DEPTH, s1, true);
         rtr::launch_project_bin(s1, cloud_of(c), make_proj(P), c->W, c->H, t, c->opt_cull ? c->bounds : nullptr,
-                                (clear_split ? 1 : 0) | (no_split ? 2 : 0) | (c->opt_lane_test ? 0 : 4) | (lean ? 8 : 0),
+                                (clear_split ? 1 : 0) | (no_split ? 2 : 0) | (c->opt_lane_test ? 0 : 4) | (lean ? 8 : 0) | (c->opt_chunk_test ? 0 : 16),
                                 c->opt_phases, c->opt_xp, tm.a, tm.b);
         c->p2p.occ_from_scan = c->p2p.open;
     }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rtr_chunk_box.h"
+
 namespace rtr {
 
 // Rows 0..2 of the row-major camera matrix (row 3 is never used: render.cu:33-40
@@ -31,7 +33,6 @@ struct Proj {
 // Spatially ordered clouds need 16-21 bits per coordinate (neighbours share sign, exponent and leading
 // mantissa bits): 5-8 B/pt instead of 12 (round 2 stored whole bytes: 6.5-9.2 B/pt).
 constexpr uint32_t kPackMaxBits = 25;  // shift (<= 31) + b <= 64, + 3 b <= 128 bits of a lane's two loads
-constexpr uint32_t kPackWideFlag = 1u << 18;
 struct PackedXyz {
     const uint4 *hdr;        // null: not packed
     const uint32_t *planes;  // the A streams (every lane's first value); one allocation with ...

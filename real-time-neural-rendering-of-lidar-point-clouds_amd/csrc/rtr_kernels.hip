@@ -1005,8 +1005,16 @@ __device__ __forceinline__ void unpack_chunk(const ChunkRawA &ca, const ChunkRaw
 // what is needed -- ~0.15 m for a room and a 1080p camera.)  Nearer lanes just stay candidates.  A chunk with any
 // candidate lane takes the full path below (all four points per lane, the exact arithmetic decides as before), so
 // frames stay bit-identical; chunks with a non-finite or huge coordinate carry s = +inf and always take it.
+// The FRONT step has the same kind of error to absorb: the rows are rounded, so a point the exact test keeps (its
+// rounded r.z > 0) has a real r.z > -4 u T (T = |m8 x| + |m9 y| + |m10 z| + |m11|), and p_0's rounded r.z errs by as much
+// again: a lane is rejected only when r.z(p_0) + lz s <= -zfront, zfront = 2^-20 x T over the cloud's bounding box, twice
+// the 2^-21 T needed (before round 5 the comparison was with 0: a lane within rounding of the camera plane could go).
+// The CHUNK TEST in front of it (packed clouds, option "chunk_test") rejects a chunk whose header box (chunk_box) lies
+// outside one of the five half-spaces of CULL below by more than 1e-4 x the magnitude of its terms; for r.z >= 0 that
+// is the same argument: a kept point has a real r.z > -4 u T, the box's computed maximum of r.z errs by a few u of the
+// box's magnitude sum, and 1e-4 x that sum is thousands of times more.
 struct LaneTest {
-    float lz, lall, zsafe;
+    float lz, lall, zsafe, zfront;
 };
 static LaneTest lane_test_consts(const Proj &P, int W, int H, const float absmax[3]) {
     LaneTest t;
@@ -1019,12 +1027,16 @@ static LaneTest lane_test_consts(const Proj &P, int W, int H, const float absmax
     auto mag = [&](int r) { return fabsf(m[4 * r]) * absmax[0] + fabsf(m[4 * r + 1]) * absmax[1] + fabsf(m[4 * r + 2]) * absmax[2] + fabsf(m[4 * r + 3]); };
     const float rx = mag(0), ry = mag(1), rz = mag(2);
     t.zsafe = 0x1p-18f * ((rx > ry ? rx : ry) + hi * rz);
+    t.zfront = 0x1p-20f * rz;
     if (!(t.zsafe >= 1e-30f)) t.zsafe = __builtin_inff();  // (NaN / no finite box: the margin step never applies)
-    if (!(t.lz < 3e38f) || !(t.lall < 3e38f)) t.zsafe = __builtin_inff(), t.lz = t.lall = 3e38f;
+    if (!(t.zfront < 3e38f)) t.zfront = __builtin_inff();  // (... nor does the front step)
+    if (!(t.lz < 3e38f) || !(t.lall < 3e38f)) t.zsafe = t.zfront = __builtin_inff(), t.lz = t.lall = 3e38f;
     return t;
 }
 
-template <bool CULL, bool GROUPS, bool PACKED>
+// CTEST (packed, !CULL only): the chunk test of option "chunk_test" -- its own instance, so that the round-4 loop
+// (chunk_test = 0) keeps its own register allocation
+template <bool CULL, bool GROUPS, bool PACKED, bool CTEST = false>
 __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void k_project_bin(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
                                                         const float4 *__restrict__ z4,
                                                         const uint4 *__restrict__ rgba4, uint32_t n4, Proj P, int W,
@@ -1105,6 +1117,11 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
         mv[k] = P.m[k];
         asm volatile("" : "+v"(mv[k]));
     }
+    // (the lane test's front slack: in a vector register for the fp32 kernel -- as a scalar it cost 8 more spilled scalar
+    // registers there --, a scalar for the packed one, which is short of vector registers: a vector one was spilled to
+    // scratch, and its reload's vmcnt(0) drained the ring on every chunk)
+    float nzfront = -lt.zfront;
+    if constexpr (!PACKED) asm volatile("" : "+v"(nzfront));
 #define RTR_M(k) mv[k]
     auto project_rows = [&](const float4 &X, const float4 &Y, const float4 &Z, Rows &r) {
         const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
@@ -1116,7 +1133,7 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
     auto lane_maybe = [&](float x0, float y0, float z0, float sp, bool live) -> bool {
         const float rz0 = f_add(fmaf(RTR_M(10), z0, fmaf(RTR_M(9), y0, f_mul(RTR_M(8), x0))), RTR_M(11));
         const float sz = f_mul(sp, lt.lz);
-        const bool front = live && (f_add(rz0, sz) > 0.0f);
+        const bool front = live && (f_add(rz0, sz) > nzfront);
         if (__ballot(front) == 0ull) return false;
         const float rx0 = f_add(fmaf(RTR_M(2), z0, fmaf(RTR_M(1), y0, f_mul(RTR_M(0), x0))), RTR_M(3));
         const float ry0 = f_add(fmaf(RTR_M(6), z0, fmaf(RTR_M(5), y0, f_mul(RTR_M(4), x0))), RTR_M(7));
@@ -1367,40 +1384,17 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
             const uint32_t lds = ring_lds + 4u * (uint32_t)kSlotDw * (q & (uint32_t)kRing);
             if (lane < 48) asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(lane16), "s"(src), "s"(lds) : "memory", "m0");
         };
-        // (prologue: one drain, ~1.5 us once per launch, so that every wait below may count two requests per iteration)
-        uint32_t c_req = c_first;
-#pragma unroll
-        for (int k = 0; k < kRingH; ++k) {
-            req_hdr((uint32_t)k, (uint32_t)k < R ? c_req : nchunks);
-            c_req = next_chunk(c_req);
-        }
-#pragma unroll
-        for (int k = 0; k < kRing; ++k) {
-            asm volatile("s_waitcnt vmcnt(%0)" : : "n"(kRingH - 1) : "memory");  // header k: kRingH - 1 requests behind it
-            req_data((uint32_t)k);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #ifdef RTR_EXPERIMENT
         uint32_t xp_sink = 0;
 #endif
-        uint32_t c_use = c_first;
-        for (uint32_t q = 0; q < R; ++q) {
-            req_hdr(q + (uint32_t)kRingH, q + (uint32_t)kRingH < R ? c_req : nchunks);
-            c_req = next_chunk(c_req);
-            asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * kLead) : "memory");  // header q + kRing (requested kLead iterations ago, or drained)
-            req_data(q + (uint32_t)kRing);
-            asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * kRing) : "memory");  // data q (requested kRing iterations ago, or drained)
-            const lds_u32 *const slot = (const lds_u32 *)(uintptr_t)(ring_lds + 4u * (uint32_t)kSlotDw * (q & (uint32_t)kRing));
-            const lds_u32 *const hs = (const lds_u32 *)(uintptr_t)(rhdr_lds + 32u * (q & (uint32_t)kRingH));
-            typedef uint32_t u32x4_l __attribute__((ext_vector_type(4)));
-            const u32x4_l g0 = *reinterpret_cast<const u32x4_l __attribute__((address_space(3))) *>(hs);
-            const u32x4_l g1 = *reinterpret_cast<const u32x4_l __attribute__((address_space(3))) *>(hs + 4);
+        typedef uint32_t u32x4_l __attribute__((ext_vector_type(4)));
+        typedef u32x4_l __attribute__((address_space(3))) lds_u32x4;
+        // one chunk out of its slot: the lane test on its A streams, then (a candidate) the long path.  g0 / g1: its header
+        // words, c: its chunk (< nchunks)
+        auto chunk_body = [&](const lds_u32 *slot, const u32x4_l &g0, const u32x4_l &g1, uint32_t c) {
             const uint32_t ww = (uint32_t)__builtin_amdgcn_readfirstlane((int)g0.w);
             const uint32_t bx = g0.x, by = g0.y, bz = g0.z;  // (vector registers: they are only ever OR-ed into values)
-            const uint32_t cq = c_use < nchunks ? (c_use | 0x80000000u) : nchunks - 1u;
-            c_use = next_chunk(c_use);
             const uint32_t wx = ww & 63u, wy = (ww >> 6) & 63u, wz = (ww >> 12) & 63u;
-            if (!(cq >> 31)) continue;  // (wave-uniform) past the wave's last chunk
             // the lane's two dwords of each A stream (bit b l: dword (b l) >> 5, shift (b l) & 31 -- one product for both)
             ChunkRawA raw;
             uint32_t px, py, pz;
@@ -1418,7 +1412,7 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
 #ifdef RTR_EXPERIMENT
             if (RTR_XP(128)) {  // the stream alone: headers, A streams, loop bookkeeping
                 xp_sink ^= raw.a[0].d[0] ^ raw.a[1].d[1] ^ raw.a[2].d[0] ^ raw.a[0].d[1] ^ raw.a[1].d[0] ^ raw.a[2].d[1];
-                continue;
+                return;
             }
 #endif
             // lane test: one point per lane; (wave-uniform) chunks with a 32-bit axis or without a finite spread skip it
@@ -1437,8 +1431,8 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
                 const float z0 = value0(raw.a[2].d[0], raw.a[2].d[1], pz, wz, bz);
                 cand = lane_maybe(x0, y0, z0, __uint_as_float(sp_c), true);
             }
-            if (!cand) continue;
-            uint32_t i_c = (cq & 0x7FFFFFFFu) * 64u + (uint32_t)lane;
+            if (!cand) return;
+            uint32_t i_c = c * 64u + (uint32_t)lane;
             const bool live_c = i_c < n4;
             i_c = live_c ? i_c : n4 - 1u;  // (masked lanes: any valid address for the colour load)
             {
@@ -1454,16 +1448,136 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
                 } else
 #endif
                 raw_b = load_chunk_b(pk_planes_b, hc0, hc1, lane);
+                if constexpr (CTEST) {
+                    // (all three B loads are waited for HERE: the decode skips an axis of width 0 -- a wall of the room --,
+                    // and a load left pending makes the compiler wait for it where its register is next written, with a
+                    // vmcnt(0) right behind the ring's wait on the next survivor: the ring drained)
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) asm volatile("" : "+v"(raw_b.a[a].d[0]), "+v"(raw_b.a[a].d[1]), "+v"(raw_b.a[a].d[2]), "+v"(raw_b.a[a].d[3]));
+                }
                 unpack_chunk(raw, raw_b, ww, sbx, sby, sbz, X, Y, Z, lane);
                 project_rows(X, Y, Z, r);
             }
 #ifdef RTR_EXPERIMENT
             if (RTR_XP(256)) {  // ... + decode + the three matrix rows
                 xp_sink ^= __float_as_uint(r.rz[0]) ^ __float_as_uint(r.rz[1]) ^ __float_as_uint(r.rz[2]) ^ __float_as_uint(r.rz[3]);
-                continue;
+                return;
             }
 #endif
             do_quad(i_c, live_c, r);
+        };
+        if constexpr (CTEST) {
+            // THE CHUNK TEST (round 5).  Nine chunks in ten hold no point inside the frustum, and the lane test above found
+            // that out only after the ring had brought the chunk's A streams and the wave had decoded and projected a point
+            // per lane: ~135 instructions a chunk, about 60 % of what the launch issued.  Every header already gives a box
+            // for its chunk (chunk_box), so the wave tests 64 of its chunks at once, one per lane -- a 32-byte header load
+            // and the five half-spaces of CULL -- and only the survivors enter the ring; the next 64 headers are in flight
+            // meanwhile.  The lane test and the long path run on the survivors as before (the header boxes are up to twice
+            // a chunk's extent: the lane test still rejects the chunks whose loose box reached the frustum).
+            // Survivor k of the wave goes into slot k & kRing: its header words from the lane that tested it (an ordinary
+            // LDS store; word 7 = its chunk, ~0 past the wave's last survivor) and its A streams by LDS-DMA, kRing
+            // survivors ahead.  Every call of req issues exactly ONE request (past the last survivor: a dummy one of
+            // the A array's first bytes), so "data k has landed" is vmcnt(kRing) with no drain in the prologue; the
+            // header loads (the compiler's) only ever add requests behind it, which makes that count conservative.
+            uint4 cur0, cur1;  // lane l: the header of position qb + l of the current batch
+            uint32_t qb = 0;
+            unsigned long long pmask = 0ull;  // survivors of the current batch not requested yet
+            auto load_batch = [&](uint32_t q0, uint4 &h0, uint4 &h1) {
+                const uint32_t c = chunk_of(q0 + (uint32_t)lane);
+                const uint32_t cc = c < nchunks ? c : nchunks - 1u;
+                h0 = pk_hdr[2 * (size_t)cc];
+                h1 = pk_hdr[2 * (size_t)cc + 1];
+            };
+            auto test_batch = [&]() {
+                const uint32_t c = chunk_of(qb + (uint32_t)lane);
+                bool keep = c < nchunks;
+                float lo[3], hi[3];
+                if (keep && chunk_box(cur0.x, cur0.y, cur0.z, cur0.w, lo, hi)) {
+                    // (the planes from the matrix in vector registers, once per batch: the barrier keeps the compiler
+                    // from holding forty of them through the loop)
+                    float m[12];
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) {
+                        m[k] = mv[k];
+                        asm volatile("" : "+v"(m[k]));
+                    }
+                    keep = !box_outside(frustum_planes(m, fW, fH), lo, hi);
+                }
+                cur1.w = c;
+                // (every header word is consumed HERE, where the batch is tested: a word whose load is still pending when
+                // the survivor's header is written would make the compiler wait for it there -- with a vmcnt(0), which
+                // drains the ring's requests on every survivor)
+                asm volatile("" : "+v"(cur0.x), "+v"(cur0.y), "+v"(cur0.z), "+v"(cur0.w), "+v"(cur1.x), "+v"(cur1.y), "+v"(cur1.z));
+                pmask = __ballot(keep);
+            };
+            auto req = [&](uint32_t k) {
+                while (pmask == 0ull && qb + 64u < R) {  // (wave-uniform) the next batch
+                    qb += 64u;
+                    load_batch(qb, cur0, cur1);
+                    test_batch();
+                }
+                const uint32_t hs = rhdr_lds + 32u * (k & (uint32_t)kRing), lds = ring_lds + 4u * (uint32_t)kSlotDw * (k & (uint32_t)kRing);
+                if (pmask != 0ull) {
+                    const int l = __ffsll((long long)pmask) - 1;
+                    pmask &= pmask - 1ull;
+                    if (lane == l) {
+                        *(lds_u32x4 *)(uintptr_t)hs = u32x4_l{cur0.x, cur0.y, cur0.z, cur0.w};
+                        *(lds_u32x4 *)(uintptr_t)(hs + 16u) = u32x4_l{cur1.x, cur1.y, cur1.z, cur1.w};
+                    }
+                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)cur1.x, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)cur1.y, l);
+                    const uint8_t *src = reinterpret_cast<const uint8_t *>(pk_planes) + (((((uint64_t)hi) << 32) | (uint64_t)lo) << 3);
+                    if (lane < 48) asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(lane16), "s"(src), "s"(lds) : "memory", "m0");
+                } else {
+                    if (lane == 0) *(lds_u32 *)(uintptr_t)(hs + 28u) = ~0u;
+                    if (lane < 48) asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(lane16), "s"(pk_planes), "s"(lds) : "memory", "m0");
+                }
+            };
+            load_batch(0u, cur0, cur1);
+            test_batch();
+#pragma unroll
+            for (int k = 0; k < kRing; ++k) req((uint32_t)k);
+            for (uint32_t k = 0;; ++k) {
+                req(k + (uint32_t)kRing);
+                asm volatile("s_waitcnt vmcnt(%0)" : : "n"(kRing) : "memory");  // data k: kRing requests behind it
+                const lds_u32 *const slot = (const lds_u32 *)(uintptr_t)(ring_lds + 4u * (uint32_t)kSlotDw * (k & (uint32_t)kRing));
+                const lds_u32 *const hs = (const lds_u32 *)(uintptr_t)(rhdr_lds + 32u * (k & (uint32_t)kRing));
+                const u32x4_l g0 = *reinterpret_cast<const lds_u32x4 *>(hs);
+                const u32x4_l g1 = *reinterpret_cast<const lds_u32x4 *>(hs + 4);
+                const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)g1.w);
+                if (c >= nchunks) break;  // (wave-uniform) past the wave's last survivor
+                chunk_body(slot, g0, g1, c);
+            }
+        } else {
+            // (option chunk_test = 0: every chunk of the wave through the ring, the loop of round 4)
+            // (prologue: one drain, ~1.5 us once per launch, so that every wait below may count two requests per iteration)
+            uint32_t c_req = c_first;
+#pragma unroll
+            for (int k = 0; k < kRingH; ++k) {
+                req_hdr((uint32_t)k, (uint32_t)k < R ? c_req : nchunks);
+                c_req = next_chunk(c_req);
+            }
+#pragma unroll
+            for (int k = 0; k < kRing; ++k) {
+                asm volatile("s_waitcnt vmcnt(%0)" : : "n"(kRingH - 1) : "memory");  // header k: kRingH - 1 requests behind it
+                req_data((uint32_t)k);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            uint32_t c_use = c_first;
+            for (uint32_t q = 0; q < R; ++q) {
+                req_hdr(q + (uint32_t)kRingH, q + (uint32_t)kRingH < R ? c_req : nchunks);
+                c_req = next_chunk(c_req);
+                asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * kLead) : "memory");  // header q + kRing (requested kLead iterations ago, or drained)
+                req_data(q + (uint32_t)kRing);
+                asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * kRing) : "memory");  // data q (requested kRing iterations ago, or drained)
+                const lds_u32 *const slot = (const lds_u32 *)(uintptr_t)(ring_lds + 4u * (uint32_t)kSlotDw * (q & (uint32_t)kRing));
+                const lds_u32 *const hs = (const lds_u32 *)(uintptr_t)(rhdr_lds + 32u * (q & (uint32_t)kRingH));
+                const u32x4_l g0 = *reinterpret_cast<const lds_u32x4 *>(hs);
+                const u32x4_l g1 = *reinterpret_cast<const lds_u32x4 *>(hs + 4);
+                const uint32_t c = c_use;
+                c_use = next_chunk(c_use);
+                if (c >= nchunks) continue;  // (wave-uniform) past the wave's last chunk
+                chunk_body(slot, g0, g1, c);
+            }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the requests past the wave's last chunk: into LDS, before it is left)
 #ifdef RTR_EXPERIMENT
@@ -1507,19 +1621,7 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
     } else {
         // 64 of the wave's chunks are tested at once, one per lane, then only the survivors are
         // streamed: the box test costs 1/64 and its load latency is paid once per 64 chunks.
-        float pl[5][4], plm[5][3], pld[5];  // half-space coefficients, |coefficients| row sums, |offset| sums
-        {
-            const float comb[5][3] = {{0.f, 0.f, 1.f}, {1.f, 0.f, 1.f}, {-1.f, 0.f, fW}, {0.f, 1.f, 1.f}, {0.f, -1.f, fH}};
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) pl[q][k] = comb[q][0] * P.m[k] + comb[q][1] * P.m[4 + k] + comb[q][2] * P.m[8 + k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    plm[q][k] = fabsf(comb[q][0] * P.m[k]) + fabsf(comb[q][1] * P.m[4 + k]) + fabsf(comb[q][2] * P.m[8 + k]);
-                pld[q] = fabsf(comb[q][0] * P.m[3]) + fabsf(comb[q][1] * P.m[7]) + fabsf(comb[q][2] * P.m[11]);
-            }
-        }
+        const FrustumPlanes fpl = frustum_planes(P.m, fW, fH);
         for (uint32_t g0 = 0; g0 < R; g0 += 64) {
             const uint32_t chunk = chunk_of(g0 + (uint32_t)lane);
             const bool valid = chunk < nchunks;
@@ -1528,20 +1630,7 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
             if (valid) {
                 const float *b = bounds + 6 * (size_t)chunk;
                 const float lo[3] = {b[0], b[1], b[2]}, hi[3] = {b[3], b[4], b[5]};
-                bool culled = false;
-#pragma unroll
-                for (int q = 0; q < 5; ++q) {
-                    float v = pl[q][3], m = pld[q];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        float t0 = pl[q][k] * lo[k], t1 = pl[q][k] * hi[k];
-                        v += t0 > t1 ? t0 : t1;
-                        float e0 = fabsf(lo[k]), e1 = fabsf(hi[k]);
-                        m += plm[q][k] * (e0 > e1 ? e0 : e1);
-                    }
-                    culled = culled || (v < -1e-4f * m);  // NaN / inf boxes compare false: never culled
-                }
-                keep = !culled;
+                keep = !box_outside(fpl, lo, hi);  // NaN / inf boxes compare false: never culled
             }
             unsigned long long mask = __ballot(keep);
             while (mask) {
@@ -2590,20 +2679,21 @@ void launch_project_bin(hipStream_t s, const Cloud &c, const Proj &P, int W, int
         }
         return cached;
     };
-#define RTR_T1(CULL, GROUPS, PACKED)                                                                                          \
+#define RTR_T1(CULL, GROUPS, PACKED, CTEST)                                                                                   \
     do {                                                                                                                      \
         static int cached_grid[kGridCacheDevices] = {0};                                                                      \
-        const dim3 grid(point_grid(n4, c.grid == kDefaultPointGrid ? default_grid(k_project_bin<CULL, GROUPS, PACKED>, cached_grid) : c.grid)); \
-        hipExtLaunchKernelGGL((k_project_bin<CULL, GROUPS, PACKED>), grid, block, 0, s, ev_start, ev_stop, 0, x, y, z, col,    \
+        const dim3 grid(point_grid(n4, c.grid == kDefaultPointGrid ? default_grid(k_project_bin<CULL, GROUPS, PACKED, CTEST>, cached_grid) : c.grid)); \
+        hipExtLaunchKernelGGL((k_project_bin<CULL, GROUPS, PACKED, CTEST>), grid, block, 0, s, ev_start, ev_stop, 0, x, y, z, col,    \
                               (uint32_t)n4, P, W, H, S, CULL ? bounds : (packed ? nullptr : c.spread), clear_split,          \
                               (uint32_t)phases, xp, lt);                                                                      \
     } while (0)
+    const bool ctest = (clear_split & 16) == 0;  // (option "chunk_test")
     if (bounds) {
-        if (packed) RTR_T1(true, true, true); else RTR_T1(true, true, false);
+        if (packed) RTR_T1(true, true, true, false); else RTR_T1(true, true, false, false);
     } else if (c.incoherent) {
-        if (packed) RTR_T1(false, false, true); else RTR_T1(false, false, false);
+        if (packed && ctest) RTR_T1(false, false, true, true); else if (packed) RTR_T1(false, false, true, false); else RTR_T1(false, false, false, false);
     } else {
-        if (packed) RTR_T1(false, true, true); else RTR_T1(false, true, false);
+        if (packed && ctest) RTR_T1(false, true, true, true); else if (packed) RTR_T1(false, true, true, false); else RTR_T1(false, true, false, false);
     }
 #undef RTR_T1
 }
