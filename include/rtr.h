@@ -95,6 +95,11 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          Frames never depend on the point order; rtr_download_points returns the RESIDENT order, a
  *          permutation of the uploaded one when rtr_get_option("reordered") reads 1
  *          ("order_ratio_ppm": the measured chunk / cloud diagonal ratio in millionths).
+ *  "point_ids": 1 = a cloud the library sorts (option "auto_reorder", rtr_reorder_points) keeps its u32 upload-order
+ *          permutation resident (+4 B per point, counted in "resident_millibytes_per_point"), so that rtr_point_pass can
+ *          still name points by their upload index.  Read when a cloud is uploaded or sorted; a cloud that is never
+ *          sorted needs nothing.  Default 0: nothing about residency or frames changes, and the point pass of a sorted
+ *          cloud fails with RTR_ERR_INVALID.
  *  "cull": 1 = skip 256-point chunks whose bounding box is provably outside the frustum
  *          (exact: same frame; an algorithmic byte reduction, off by default and reported
  *          separately from the roofline figure; needs a spatially coherent point order).
@@ -316,11 +321,38 @@ typedef enum {
     RTR_BUF_IMAGE = 2,  /* u8  [H*W*3]  interleaved, input channel order         (project_cloud.h:26) */
     RTR_BUF_TENSOR = 3, /* f16 [5*H*W]  planar {1,5,H,W}                         (project_cloud.h:32) */
     RTR_BUF_MASK = 4,   /* u8  [H*W]    final keep-mask of the prefilter                              */
-    RTR_BUF_MINMAX = 5  /* u32 [2]      depth min / max bits (project_cloud.h:30-31)                  */
+    RTR_BUF_MINMAX = 5, /* u32 [2]      depth min / max bits (project_cloud.h:30-31)                  */
+    RTR_BUF_POINT_ID = 6, /* u32 [H*W]  upload index of the point each pixel shows (rtr_point_pass)       */
+    RTR_BUF_VISIBLE = 7   /* u32 [(n + 31) / 32]  bit i % 32 of word i / 32: point i contributed (ditto)  */
 } rtr_buffer;
 int rtr_device_buffer(rtr_ctx *ctx, int which, void **dev_ptr, size_t *bytes);
 /* Synchronous device->host copy of one buffer (bytes must equal its size). */
 int rtr_download_buffer(rtr_ctx *ctx, int which, void *host, size_t bytes);
+
+/* ---- 6b. point pass: which points a frame shows ------------------------------------
+ * Take the frame the depth buffer holds (RTR_BUF_DEPTH as the frame left it: after a filtered frame, pixels the
+ * prefilter removed hold the bits of -1.0f; pixels no point reached hold RTR_EMPTY_DEPTH), made with matrix P.  For
+ * point i (UPLOAD order: the index in the rtr_upload_points array, or i - first of rtr_generate_synthetic) the
+ * projection of the frame gives (pix, d) or nothing.
+ *   RTR_BUF_POINT_ID: pixel p holds the smallest i with pix == p and bits(d) == depth[p]; 0xFFFFFFFF where there is
+ *     none (empty pixels and pixels the prefilter removed).  Ties on equal depth bits go to the smallest upload index,
+ *     so the buffer does not depend on the resident order or on any option.
+ *   RTR_BUF_VISIBLE: bit i % 32 of word i / 32 is set iff point i projects and !(d > depth[pix] + depth_window) -- the
+ *     accumulate pass's own test (render.cu:106).  On an unfiltered frame the visible points of pixel p number
+ *     RTR_BUF_ACCUM[4 p + 3] and their colours sum to RTR_BUF_ACCUM[4 p .. 4 p + 2]; removed pixels contribute none.
+ *     Bits past n are clear.
+ * rtr_point_pass computes the buffers `what` asks for (RTR_POINTS_IDS | RTR_POINTS_VISIBLE), queued on the context's
+ * stream behind the frame; P is passed explicitly like in the phase calls.  rtr_device_buffer / rtr_download_buffer
+ * then serve them.  A frame that a synchronising call renders again (option "pool_worst_case") is rendered together
+ * with the point pass queued right behind it; a point pass that read a frame reported incomplete otherwise makes
+ * rtr_download_buffer of its outputs fail with RTR_ERR_INTERNAL.
+ * Errors: RTR_ERR_INVALID without a cloud or a resolution, for `what` outside 1..3, and when the cloud was sorted
+ * without option "point_ids" (rtr_last_error says so); RTR_ERR_UNSUPPORTED for 2^32 points or more.
+ * Sharded frames: on a rank the indices are rank-local (its own upload), and only its own points are tested against
+ * the depth buffer it holds; a global ID needs the rank's offset and a MIN across ranks, which the library does not do. */
+#define RTR_POINTS_IDS 1
+#define RTR_POINTS_VISIBLE 2
+int rtr_point_pass(rtr_ctx *ctx, const float P[16], int what);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

@@ -16,6 +16,10 @@
 // Return codes as in project_cloud.cu:268-312: 1 on success, -1 when both outputs are null.
 // Unlike the reference (exit(1) on CUDA errors, project_cloud.cu:13-17) failures throw.
 //
+// Beyond the reference: computePointIds / visible_points (rtr.h section 6b) name the points a frame shows, by their
+// index in the grid's flattened vertex order (the order the constructor uploads); construct with point_ids = true
+// when the library may sort the cloud (its default upload policy does for unordered clouds).
+//
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
 // methods and tensor(), the device pointer computeFull hands to the U-Net.
@@ -41,7 +45,8 @@ namespace rtr {
 class ProjectCloud {
 public:
     template <class Grid>
-    explicit ProjectCloud(const Grid& grid, const std::string& modelFilename = std::string(""), int device = 0)
+    explicit ProjectCloud(const Grid& grid, const std::string& modelFilename = std::string(""), int device = 0,
+                          bool point_ids = false)
         : model_filename_(modelFilename) {
         // OctreeGrid::getVertexPositions / getVertexColors (Octreegrid.h:162-180)
         std::vector<float> xyzw;
@@ -58,6 +63,7 @@ public:
             throw std::runtime_error("librtr_hip.so has ABI version " + std::to_string(rtr_abi_version()) +
                                      ", this header is version " + std::to_string(RTR_ABI_VERSION));
         check(nullptr, rtr_create(&ctx_, device));
+        if (point_ids) check(ctx_, rtr_set_option(ctx_, "point_ids", 1));
         // (the library's default upload policy: the point order is measured and the cloud Morton-sorted once when its
         // 256-point chunks are not compact -- the grid's 0.25 m blocks are unordered inside -- then packed losslessly)
         check(ctx_, rtr_upload_points(ctx_, xyzw.data(), 16, rgba.data(), 4, xyzw.size() / 4));
@@ -151,6 +157,30 @@ public:
     }
     rtr_ctx* context() const { return ctx_; }
 
+    // Renders the frame (computeRGBD / computeFilteredRGBD without host copies) and returns, per pixel (row-major
+    // H x W), the vertex index of the point it shows, -1 for none (empty or prefiltered-away pixels).
+    template <class Calibration, class Extrinsics>
+    std::vector<int64_t> computePointIds(const Calibration& calibration, const Extrinsics& extrinsics, bool filtered = false) {
+        point_pass(calibration, extrinsics, filtered, RTR_POINTS_IDS);
+        std::vector<uint32_t> ids((size_t)calibration.getWidth() * calibration.getHeight());
+        check(ctx_, rtr_download_buffer(ctx_, RTR_BUF_POINT_ID, ids.data(), ids.size() * 4));
+        std::vector<int64_t> out(ids.size());
+        for (size_t p = 0; p < ids.size(); ++p) out[p] = ids[p] == 0xFFFFFFFFu ? -1 : (int64_t)ids[p];
+        return out;
+    }
+    // Renders the frame and returns one flag per vertex: 1 for the points that contributed to its colour.
+    template <class Calibration, class Extrinsics>
+    std::vector<uint8_t> visible_points(const Calibration& calibration, const Extrinsics& extrinsics, bool filtered = false) {
+        point_pass(calibration, extrinsics, filtered, RTR_POINTS_VISIBLE);
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        std::vector<uint32_t> words((size_t)((n + 31) / 32));
+        check(ctx_, rtr_download_buffer(ctx_, RTR_BUF_VISIBLE, words.data(), words.size() * 4));
+        std::vector<uint8_t> out((size_t)n);
+        for (size_t i = 0; i < out.size(); ++i) out[i] = (uint8_t)((words[i / 32] >> (i % 32)) & 1u);
+        return out;
+    }
+
 private:
     template <class Calibration, class Extrinsics>
     static void projection(const Calibration& calibration, const Extrinsics& extrinsics, float P[16]) {
@@ -187,6 +217,14 @@ private:
         float* d32 = depth ? depth->template ptr<float>() : nullptr;
         check(ctx_, filtered ? rtr_project_filtered(ctx_, P, c8, d32) : rtr_project(ctx_, P, c8, d32));
         return 1;
+    }
+    template <class Calibration, class Extrinsics>
+    void point_pass(const Calibration& calibration, const Extrinsics& extrinsics, bool filtered, int what) {
+        float P[16];
+        projection(calibration, extrinsics, P);
+        check(ctx_, rtr_set_resolution(ctx_, calibration.getWidth(), calibration.getHeight()));
+        check(ctx_, rtr_render(ctx_, P, filtered ? 1 : 0));
+        check(ctx_, rtr_point_pass(ctx_, P, what));
     }
     static void check(const rtr_ctx* c, int rc) {
         if (rc != RTR_OK) throw std::runtime_error(std::string("rtr: ") + rtr_last_error(c));

@@ -110,6 +110,22 @@ struct rtr_ctx {
     int opt_auto_reorder = 2;   // Morton-sort a cloud right after upload / generation: 0 never, 1 always, 2 when its
                                 // 256-point chunks are not spatially compact (default)
     bool reordered = false;     // the resident cloud was sorted by the library
+    int opt_point_ids = 0;      // 1: a sorted cloud keeps its upload order as a resident permutation (option "point_ids")
+    uint32_t *perm = nullptr;   // [cap] upload index of every resident point (only while `reordered`)
+
+    // point pass (rtr_point_pass): per-pixel point IDs [H*W] (per resolution) and the visibility mask (8 words per
+    // 256-point chunk; (n + 31) / 32 of them are the buffer)
+    uint32_t *pp_ids = nullptr, *pp_vis = nullptr;
+    uint64_t pp_vis_words = 0;
+    bool pp_vis_current = false;  // the mask was computed for the resident cloud
+    // a point pass read the frame that a synchronising call may have to render again (the adaptive extent pool
+    // overflowed): queued right after that frame -> repeated with it; otherwise its outputs are marked incomplete
+    bool pp_after_last = false;   // queued after the last whole frame (rtr_render), nothing rendered since
+    bool pp_since_sync = false;   // queued, and not yet known to have read a complete frame
+    bool pp_invalid = false;      // its outputs came from a frame the tile store reported incomplete
+    float pp_P[16] = {0};
+    int pp_what = 0;
+    hipEvent_t pp_done = nullptr;  // recorded behind the last point pass
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
     int opt_grid = rtr::kDefaultPointGrid;  // workgroups of the point kernels
 
@@ -251,6 +267,7 @@ void free_frame(rtr_ctx *c) {
     free_host_out(c);
     p2p_release(c);
     dfree(c->depth); dfree(c->acc); dfree(c->img); dfree(c->mask); dfree(c->part_min); dfree(c->part_max); dfree(c->tensor);
+    dfree(c->pp_ids);
     for (int i = 1; i <= 8; ++i) dfree(c->lv.lv[i]);
     for (auto &f : c->fs) {
         dfree(f.store.ext0); dfree(f.store.meta);
@@ -284,7 +301,9 @@ void free_pack(rtr_ctx *c) {
 }
 
 void free_cloud(rtr_ctx *c) {
-    dfree(c->x); dfree(c->y); dfree(c->z); dfree(c->rgba); dfree(c->bounds); dfree(c->spread);
+    dfree(c->x); dfree(c->y); dfree(c->z); dfree(c->rgba); dfree(c->bounds); dfree(c->spread); dfree(c->perm);
+    dfree(c->pp_vis);
+    c->pp_vis_words = 0;
     free_pack(c);
     free_lists(c);
     c->n = c->cap = 0;
@@ -422,6 +441,7 @@ int alloc_cloud(rtr_ctx *c, uint64_t n) {
     c->n = n;
     c->list_valid = false;
     c->last_valid = false;
+    c->pp_vis_current = false;
     c->split_cooldown = kSplitCooldown;  // (a new cloud: nothing is known about its frames)
     return RTR_OK;
 }
@@ -482,6 +502,10 @@ int check_store_error(rtr_ctx *c, bool *retry = nullptr) {
     if (retry) *retry = false;
     if (!c->err_host) return RTR_OK;
     const uint32_t e = __atomic_exchange_n(c->err_host, 0u, __ATOMIC_ACQUIRE);
+    if (c->pp_since_sync) {  // (a point pass has read a frame: complete unless this word says otherwise)
+        if (e != 0u) c->pp_invalid = true;  // (finish_sync_rerender repeats it when it followed the frame repeated there)
+        if (e != 0u || hipEventQuery(c->pp_done) == hipSuccess) c->pp_since_sync = false;
+    }
     if (e == 0u) return RTR_OK;
     if (e == 2u && c->opt_debug_dyn_cap < 0 && c->F().dyn_cap < pool_worst_cap(c)) {
         c->pool_worst = true;  // (ensure_lists re-allocates before the next T1)
@@ -651,6 +675,7 @@ int rtr_destroy(rtr_ctx *c) {
     if (c->err_host) (void)hipHostFree(c->err_host);
     if (c->entries_host) (void)hipHostFree(c->entries_host);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    if (c->pp_done) (void)hipEventDestroy(c->pp_done);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return RTR_OK;
@@ -801,6 +826,11 @@ int rtr_set_option(rtr_ctx *c, const char *key, int value) {
         c->opt_cull = value != 0;
         return RTR_OK;
     }
+    if (!strcmp(key, "point_ids")) {  // read when a cloud is uploaded or sorted (rtr_point_pass)
+        NEED(c, value == 0 || value == 1, "point_ids must be 0 or 1");
+        c->opt_point_ids = value;
+        return RTR_OK;
+    }
     if (!strcmp(key, "lean")) {  // whole frames without T1's epilogue when nothing needs it (rtr_render)
         c->opt_lean = value != 0;
         return RTR_OK;
@@ -872,6 +902,7 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "reordered")) *value = c->reordered ? 1 : 0;  // the resident cloud was sorted by the library
     else if (!strcmp(key, "order_ratio_ppm")) *value = (int)(c->order_ratio * 1e6f);  // chunk / cloud diagonal as uploaded
     else if (!strcmp(key, "cull")) *value = c->opt_cull;
+    else if (!strcmp(key, "point_ids")) *value = c->opt_point_ids;
     else if (!strcmp(key, "lane_test")) *value = c->opt_lane_test;
     else if (!strcmp(key, "chunk_test")) *value = c->opt_chunk_test;
     else if (!strcmp(key, "phases")) *value = c->opt_phases;
@@ -885,7 +916,8 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
         // device memory this context holds for the cloud and its frames, per point: coordinates (fp32 SoA and / or packed
         // form), colours, chunk boxes and lane spreads, tile stores and extent pools, frame buffers
         const uint64_t nchunks = ((c->cap / 4) + 63) / 64;
-        uint64_t b = (c->x ? 12 * c->cap : 0) + (c->rgba ? 4 * c->cap : 0) + nchunks * 28 + (c->pk_hdr ? c->pk_bytes + 64 : 0);
+        uint64_t b = (c->x ? 12 * c->cap : 0) + (c->rgba ? 4 * c->cap : 0) + nchunks * 28 + (c->pk_hdr ? c->pk_bytes + 64 : 0) +
+                     (c->perm ? 4 * c->cap : 0);
         for (const auto &f : c->fs) {
             b += f.dyn ? f.dyn_cap * 8 : 0;
             b += f.store.ext0 ? ((uint64_t)f.nst * rtr::kS0 + 16) * 8 + rtr::ts_meta_words(f.nst, f.ntiles) * 4 : 0;
@@ -944,9 +976,14 @@ int rtr_reset_stream(rtr_ctx *c) {
 // one (rtr_render and what is built on it), that frame is rendered again with the grown pool -- the device buffers hold
 // the right frame when the call returns.
 static int finish_sync_rerender(rtr_ctx *c) {
-    float P[16];
+    float P[16], Q[16];
     memcpy(P, c->last_P, sizeof P);
-    return rtr_render(c, P, c->last_filter);
+    memcpy(Q, c->pp_P, sizeof Q);
+    const bool pass = c->pp_after_last;  // (a point pass queued behind that frame is repeated with it)
+    const int what = c->pp_what;
+    int rc = rtr_render(c, P, c->last_filter);
+    if (!rc && pass) rc = rtr_point_pass(c, Q, what);
+    return rc;
 }
 static int finish_sync(rtr_ctx *c) {
     bool retry = false;
@@ -1033,6 +1070,7 @@ static int pack_cloud(rtr_ctx *c) {
 
 static int auto_reorder(rtr_ctx *c) {
     c->reordered = false;
+    dfree(c->perm);  // (a new cloud: upload order = resident order until it is sorted)
     c->order_ratio = 0.f;
     c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();  // (unknown: the lane test's margin step stays off)
     if (c->n < 1) return RTR_OK;
@@ -1121,8 +1159,17 @@ int rtr_reorder_points(rtr_ctx *c) {
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
     c->list_valid = false;
+    c->pp_vis_current = false;
     if (int rc = ensure_soa(c)) return rc;
-    int e = rtr::reorder_morton(c->stream, c->x, c->y, c->z, c->rgba, c->n);
+    // option "point_ids": the permutation travels with the points (starting from the identity while the cloud is in
+    // upload order; a cloud sorted before without it has lost its upload order for good)
+    if (c->opt_point_ids && (!c->reordered || c->perm)) {
+        if (!c->perm) HIP_TRY(c, hipMalloc((void **)&c->perm, c->cap * 4));
+        if (!c->reordered) rtr::launch_iota(c->stream, c->perm, c->n);
+    } else {
+        dfree(c->perm);
+    }
+    int e = rtr::reorder_morton(c->stream, c->x, c->y, c->z, c->rgba, c->n, c->perm);
     if (e != 0) return fail(c, RTR_ERR_HIP, "reorder failed: %s", hipGetErrorString((hipError_t)e));
     c->reordered = true;
     free_pack(c);
@@ -1388,6 +1435,7 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
     if (!c) return RTR_ERR_INVALID;
     NEED(c, P != nullptr, "P is NULL");
     if (int rc = check_frame(c)) return rc;
+    c->pp_after_last = false;
     if (with_filter) {  // fail before touching the frame buffers
         DevGuard g(c->device);
         if (int rc = ensure_pyramid(c)) return rc;
@@ -1838,6 +1886,48 @@ int rtr_p2p_render_owned(rtr_ctx *c, const float P[16], int with_filter, int fra
     return RTR_OK;
 }
 
+// ---- point pass ----------------------------------------------------------------------
+// Which points the frame in the depth buffer shows (rtr.h section 6b): one stream over the RESIDENT coordinates
+// (rtr_kernels.hip, k_point_pass), queued behind the frame like the phase calls.  The ID buffer is cleared here, not by
+// the frame; the visibility mask only when its bits go through the permutation (in upload order every word is stored).
+
+int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, P != nullptr, "P is NULL");
+    NEED(c, what >= 1 && what <= 3, "what must be a non-empty mask of RTR_POINTS_IDS (1) and RTR_POINTS_VISIBLE (2)");
+    NEED(c, c->cap > 0, "no cloud: rtr_upload_points / rtr_generate_synthetic first");
+    if (int rc = check_frame(c)) return rc;
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point IDs are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    NEED(c, !c->reordered || c->perm,
+         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be formed: set "
+         "point_ids = 1 before the upload (or upload with auto_reorder = 0)");
+    DevGuard g(c->device);
+    const size_t npix = (size_t)c->W * c->H;
+    const uint64_t words = (((c->n + 3) / 4 + 63) / 64) * 8;  // (8 per 256-point chunk: whole-chunk stores)
+    if (!c->pp_done) HIP_TRY(c, hipEventCreateWithFlags(&c->pp_done, hipEventDisableTiming));
+    if ((what & RTR_POINTS_IDS) && !c->pp_ids) HIP_TRY(c, hipMalloc((void **)&c->pp_ids, npix * 4));
+    if ((what & RTR_POINTS_VISIBLE) && (!c->pp_vis || c->pp_vis_words < words)) {
+        HIP_TRY(c, sync_streams(c));  // (a pass in flight may still write the old mask)
+        dfree(c->pp_vis);
+        c->pp_vis_words = words > 8 ? words : 8;
+        HIP_TRY(c, hipMalloc((void **)&c->pp_vis, c->pp_vis_words * 4));
+    }
+    uint32_t *ids = (what & RTR_POINTS_IDS) ? c->pp_ids : nullptr, *vis = (what & RTR_POINTS_VISIBLE) ? c->pp_vis : nullptr;
+    const uint32_t *perm = c->reordered ? c->perm : nullptr;
+    if (ids) HIP_TRY(c, hipMemsetAsync(ids, 0xFF, npix * 4, c->stream));
+    if (vis && (perm || words == 0)) HIP_TRY(c, hipMemsetAsync(vis, 0, c->pp_vis_words * 4, c->stream));
+    rtr::launch_point_pass(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->depth, c->prm.depth_window, ids, vis, perm);
+    if (int rc = launch_check(c, "point_pass")) return rc;
+    HIP_TRY(c, hipEventRecord(c->pp_done, c->stream));
+    if (vis) c->pp_vis_current = true;
+    memcpy(c->pp_P, P, sizeof c->pp_P);
+    c->pp_what = what;
+    c->pp_after_last = c->last_valid;  // (what a synchronising call repeats with the frame: finish_sync_rerender)
+    c->pp_since_sync = true;
+    c->pp_invalid = false;
+    return RTR_OK;
+}
+
 // ---- buffers -----------------------------------------------------------------------
 
 int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
@@ -1854,6 +1944,12 @@ int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
         case RTR_BUF_TENSOR: p = c->tensor; b = npix * 10; break;
         case RTR_BUF_MASK: p = c->mask; b = npix; break;
         case RTR_BUF_MINMAX: p = c->minmax; b = 8; break;
+        case RTR_BUF_POINT_ID:
+            NEED(c, c->pp_ids != nullptr, "RTR_BUF_POINT_ID: no rtr_point_pass with RTR_POINTS_IDS at this resolution yet");
+            p = c->pp_ids; b = npix * 4; break;
+        case RTR_BUF_VISIBLE:
+            NEED(c, c->pp_vis != nullptr && c->pp_vis_current, "RTR_BUF_VISIBLE: no rtr_point_pass with RTR_POINTS_VISIBLE for the resident cloud yet");
+            p = c->pp_vis; b = (size_t)((c->n + 31) / 32) * 4; break;
         default: return fail(c, RTR_ERR_INVALID, "unknown buffer id %d", which);
     }
     *ptr = p;
@@ -1873,11 +1969,17 @@ int rtr_download_buffer(rtr_ctx *c, int which, void *host, size_t bytes) {
     HIP_TRY(c, sync_streams(c));
     bool retry = false;
     rc = check_store_error(c, c->last_valid ? &retry : nullptr);
-    if (rc || !retry) return rc;
-    if ((rc = finish_sync_rerender(c))) return rc;  // (the adaptive extent pool overflowed: the frame again, then the copy)
-    HIP_TRY(c, hipMemcpyAsync(host, p, b, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, sync_streams(c));
-    return check_store_error(c);
+    if (!rc && retry) {  // (the adaptive extent pool overflowed: the frame -- and a point pass behind it -- again, then the copy)
+        if ((rc = finish_sync_rerender(c))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(host, p, b, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, sync_streams(c));
+        rc = check_store_error(c);
+    }
+    if (!rc && (which == RTR_BUF_POINT_ID || which == RTR_BUF_VISIBLE) && c->pp_invalid)
+        rc = fail(c, RTR_ERR_INTERNAL, "the last rtr_point_pass read a frame the tile store reported incomplete (the adaptive "
+                  "extent pool overflowed and a later frame was rendered before a synchronising call): render the frame and "
+                  "run the point pass again");
+    return rc;
 }
 
 // ---- measurement -------------------------------------------------------------------

@@ -259,7 +259,8 @@ void pack_write(hipStream_t s, const Cloud &c, const uint4 *hdr, uint32_t *plane
 void pack_verify(hipStream_t s, const Cloud &c, const uint4 *hdr, const uint32_t *planes, const uint32_t *planes_b, uint64_t *mismatches);
 // x, y, z (padded to a multiple of 4 points) back from the packed form, bit for bit
 void unpack_to_soa(hipStream_t s, const PackedXyz &pk, uint64_t n, float *x, float *y, float *z);
-int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n);  // rtr_reorder.hip
+// rtr_reorder.hip; perm (may be null) is permuted with the points (option "point_ids": upload index per resident point)
+int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n, uint32_t *perm = nullptr);
 // mean diagonal of the 256-point chunk boxes / diagonal of the cloud's box, from launch_chunk_bounds' output
 // absmax[3]: the largest finite |x|, |y|, |z| over the chunk boxes (+inf when no chunk has a finite box)
 int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, float absmax[3]);
@@ -315,5 +316,13 @@ void launch_soa_to_aos(hipStream_t s, const float *x, const float *y, const floa
 // (a, b: device buffers padded to 16 bytes; ha, hb: device pointers of mapped pinned host buffers, padded likewise)
 void launch_copy_to_host(hipStream_t s, const void *a, void *ha, size_t bytes_a, const void *b, void *hb, size_t bytes_b);
 void launch_pad_nan(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n, uint64_t n_pad);
+// rtr_point_pass: streams the RESIDENT coordinates once (packed: chunks rejected on their header boxes, survivors
+// decoded; else the fp32 SoA) and, for the frame `depth` holds, atomicMin's the upload index of every point whose
+// depth bits are its pixel's into ids[H*W] (cleared to 0xFFFFFFFF by the caller) and sets the bit of every point the
+// accumulate pass would count in vis (8 u32 per 256-point chunk; with perm == null every word is stored, with perm
+// the caller clears it and the bits go through perm[resident index] = upload index).  ids / vis may be null.
+void launch_point_pass(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, const uint32_t *depth, float window,
+                       uint32_t *ids, uint32_t *vis, const uint32_t *perm);
+void launch_iota(hipStream_t s, uint32_t *out, uint64_t n);  // out[i] = i
 
 }  // namespace rtr

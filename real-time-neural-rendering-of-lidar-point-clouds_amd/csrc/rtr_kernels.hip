@@ -4029,4 +4029,152 @@ void launch_pad_nan(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba,
     if (n_pad > n) hipLaunchKernelGGL(k_pad_nan, dim3(1), dim3(64), 0, s, x, y, z, rgba, n, n_pad);
 }
 
+// ---------------------------------------------------------------------------------
+// Point pass (rtr_point_pass): which points a finished frame shows.  One wave per 256-point chunk (lane l: points
+// 4 l .. 4 l + 3), the exact project_point of the frame, one load of depth[pix] per projected point, then
+//   IDs:        atomicMin(ids[pix], upload index) for the points whose depth bits ARE the pixel's -- about one per lit
+//               pixel, so plain per-lane atomics (ids cleared to 0xFFFFFFFF by the caller);
+//   visibility: the accumulate pass's predicate (render.cu:106) on the same depth.  In upload order (PERM = false) the
+//               chunk's 256 bits are four ballots, interleaved into eight whole words stored by lanes 0..7 -- no
+//               atomics, and a rejected chunk stores eight zero words; through the permutation (PERM) the mask was
+//               cleared by the caller and only the visible points set their bit with atomicOr.
+// PACKED: the wave tests 64 chunks at once on their header boxes (chunk_box + box_outside: the chunk test of T1) and
+// decodes only the survivors (load_chunk_a / load_chunk_b / unpack_chunk); else the fp32 SoA stream, every chunk.
+// Chunks are dealt to the waves round robin (wave w: chunks w, w + waves, ...), also the 64 of a header test: the
+// chunks in view are long runs of a spatially ordered cloud, and 64 consecutive ones in one wave left a few waves
+// decoding a whole run each, one after the other ("Point pass").
+// Points at or past n (NaN padding, the copies of the last quad that fill a packed chunk) are masked by index.
+// `vis` holds 8 words per chunk (the caller allocates nchunks * 32 bytes), so whole-chunk stores stay inside it.
+struct PointPassArgs {
+    const float4 *x4, *y4, *z4;  // fp32 SoA (not PACKED)
+    PackedXyz pk;                // packed form (PACKED)
+    uint64_t n;
+    const uint32_t *depth;
+    uint32_t *ids, *vis;         // null: not requested
+    const uint32_t *perm;        // resident index -> upload index (PERM)
+    float window;
+};
+__device__ __forceinline__ uint32_t spread_nibbles(uint32_t b) {  // bit m of the low byte -> bit 4 m
+    uint32_t x = b & 0xFFu;
+    x = (x | (x << 12)) & 0x000F000Fu;
+    x = (x | (x << 6)) & 0x03030303u;
+    x = (x | (x << 3)) & 0x11111111u;
+    return x;
+}
+template <bool PERM>
+__device__ __forceinline__ void point_pass_chunk(const PointPassArgs &a, const Proj &P, int W, int H, float fW, float fH,
+                                                 uint64_t c, const float4 &X, const float4 &Y, const float4 &Z, int lane) {
+    const uint64_t i0 = c * 256u + 4u * (uint64_t)lane;
+    const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
+    int pix[4];
+    float d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pix[k] = project_point(P, xs[k], ys[k], zs[k], W, H, fW, fH, d[k]);
+        if (i0 + k >= a.n) pix[k] = -1;
+    }
+    uint32_t m[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m[k] = pix[k] >= 0 ? a.depth[pix[k]] : 0u;  // (the four loads in flight together)
+    bool vis[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) vis[k] = pix[k] >= 0 && !(d[k] > f_add(__uint_as_float(m[k]), a.window));  // render.cu:106
+    if (a.ids) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (pix[k] >= 0 && __float_as_uint(d[k]) == m[k]) {
+                const uint32_t u = PERM ? a.perm[i0 + k] : (uint32_t)(i0 + k);
+                atomicMin(a.ids + pix[k], u);
+            }
+    }
+    if (a.vis) {
+        if (PERM) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (vis[k]) {
+                    const uint32_t u = a.perm[i0 + k];
+                    atomicOr(a.vis + (u >> 5), 1u << (u & 31u));
+                }
+        } else {
+            // word j of the chunk = points 32 j .. 32 j + 31 = lanes 8 j .. 8 j + 7; point 4 l + k is bit l of ballot k
+            const unsigned long long b0 = __ballot(vis[0]), b1 = __ballot(vis[1]), b2 = __ballot(vis[2]), b3 = __ballot(vis[3]);
+            if (lane < 8) {
+                const int sh = 8 * lane;
+                a.vis[8 * c + lane] = spread_nibbles((uint32_t)(b0 >> sh)) | (spread_nibbles((uint32_t)(b1 >> sh)) << 1) |
+                                      (spread_nibbles((uint32_t)(b2 >> sh)) << 2) | (spread_nibbles((uint32_t)(b3 >> sh)) << 3);
+            }
+        }
+    }
+}
+template <bool PACKED, bool PERM>
+__global__ __launch_bounds__(kBlock) void k_point_pass(PointPassArgs a, Proj P, int W, int H) {
+    const float fW = (float)W, fH = (float)H;
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    const uint64_t n4 = (a.n + 3) / 4, nchunks = (n4 + 63) / 64;
+    if (!PACKED) {
+        for (uint64_t c = wave; c < nchunks; c += nwaves) {  // (wave-uniform)
+            const uint64_t i = c * 64u + (uint64_t)lane, ic = i < n4 ? i : n4 - 1u;
+            const float4 X = ld_stream(a.x4 + ic), Y = ld_stream(a.y4 + ic), Z = ld_stream(a.z4 + ic);
+            point_pass_chunk<PERM>(a, P, W, H, fW, fH, c, X, Y, Z, lane);
+        }
+        return;
+    }
+    const FrustumPlanes fpl = frustum_planes(P.m, fW, fH);
+    for (uint64_t j0 = 0; wave + nwaves * j0 < nchunks; j0 += 64u) {  // (wave-uniform)
+        const uint64_t chunk = wave + nwaves * (j0 + (uint64_t)lane);
+        const bool valid = chunk < nchunks;
+        bool keep = false;
+        if (valid) {
+            const uint4 h0 = a.pk.hdr[2 * chunk];
+            float lo[3], hi[3];
+            keep = !(chunk_box(h0.x, h0.y, h0.z, h0.w, lo, hi) && box_outside(fpl, lo, hi));
+        }
+        if (!PERM && a.vis && valid && !keep) {  // (no point of a rejected chunk is visible)
+            uint4 *w = reinterpret_cast<uint4 *>(a.vis + 8 * chunk);
+            w[0] = make_uint4(0u, 0u, 0u, 0u);
+            w[1] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        unsigned long long mask = __ballot(keep);
+        while (mask) {
+            const int l = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const uint64_t cc = wave + nwaves * (j0 + (uint64_t)l);
+            const uint4 h0 = a.pk.hdr[2 * cc], h1 = a.pk.hdr[2 * cc + 1];
+            const ChunkRawA raw_a = load_chunk_a(a.pk.planes, h0, h1, lane);
+            const ChunkRaw raw = load_chunk_b(a.pk.planes_b, h0, h1, lane);
+            float4 X, Y, Z;
+            unpack_chunk(raw_a, raw, h0.w, h0.x, h0.y, h0.z, X, Y, Z, lane);
+            point_pass_chunk<PERM>(a, P, W, H, fW, fH, cc, X, Y, Z, lane);
+        }
+    }
+}
+
+void launch_point_pass(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, const uint32_t *depth, float window,
+                       uint32_t *ids, uint32_t *vis, const uint32_t *perm) {
+    const uint64_t n4 = (c.n + 3) / 4, nchunks = (n4 + 63) / 64;
+    if (nchunks == 0) return;
+    PointPassArgs a{(const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, c.pk, c.n, depth, ids, vis, perm, window};
+    const bool packed = c.pk.hdr != nullptr;
+    const uint64_t blocks = (nchunks + 3) / 4;  // (up to 8 waves per CU, every chunk dealt round robin)
+    const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048)), block(kBlock);
+    if (packed) {
+        if (perm) hipLaunchKernelGGL((k_point_pass<true, true>), grid, block, 0, s, a, P, W, H);
+        else hipLaunchKernelGGL((k_point_pass<true, false>), grid, block, 0, s, a, P, W, H);
+    } else {
+        if (perm) hipLaunchKernelGGL((k_point_pass<false, true>), grid, block, 0, s, a, P, W, H);
+        else hipLaunchKernelGGL((k_point_pass<false, false>), grid, block, 0, s, a, P, W, H);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_iota(uint32_t *__restrict__ out, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) out[i] = (uint32_t)i;
+}
+void launch_iota(hipStream_t s, uint32_t *out, uint64_t n) {
+    if (n == 0) return;
+    const uint64_t blocks = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_iota, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, out, n);
+}
+
 }  // namespace rtr

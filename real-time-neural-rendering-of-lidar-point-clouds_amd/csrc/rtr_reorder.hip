@@ -98,6 +98,11 @@ __global__ __launch_bounds__(256) void k_gather(const uint32_t *__restrict__ per
     }
 }
 
+__global__ __launch_bounds__(256) void k_gather_u32(const uint32_t *__restrict__ perm, uint64_t n,
+                                                    const uint32_t *__restrict__ v, uint32_t *__restrict__ ov) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) ov[i] = v[perm[i]];
+}
+
 // How spatially compact the 256-point chunks are: sum of the chunk boxes' diagonals, number of
 // chunks with a finite box, and the cloud's bounding box -- all from the chunk bounds
 // (k_chunk_bounds), i.e. 24 bytes per 256 points.
@@ -178,15 +183,16 @@ int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, 
     return 0;
 }
 
-// Sorts the n points in place (through scratch copies).  Returns a hipError_t as int.
-int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n) {
+// Sorts the n points in place (through scratch copies), and `perm` (if not null: the upload index of every resident
+// point) with them.  Returns a hipError_t as int.
+int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n, uint32_t *perm) {
     if (n < 2) return 0;
     if (n >= (1ull << 32)) return (int)hipErrorInvalidValue;  // the permutation is 32-bit
     uint32_t *bb = nullptr;
     uint64_t *k0 = nullptr, *k1 = nullptr;
     uint32_t *v0 = nullptr, *v1 = nullptr;
     float *tx = nullptr, *ty = nullptr, *tz = nullptr;
-    uint32_t *tc = nullptr;
+    uint32_t *tc = nullptr, *tp = nullptr;
     void *tmp = nullptr;
     size_t tmp_bytes = 0;
     hipError_t e = hipSuccess;
@@ -218,16 +224,20 @@ int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, 
         }
     }
     if (e == hipSuccess && ok(hipMalloc((void **)&tx, n * 4)) && ok(hipMalloc((void **)&ty, n * 4)) &&
-        ok(hipMalloc((void **)&tz, n * 4)) && ok(hipMalloc((void **)&tc, n * 4))) {
+        ok(hipMalloc((void **)&tz, n * 4)) && ok(hipMalloc((void **)&tc, n * 4)) && (!perm || ok(hipMalloc((void **)&tp, n * 4)))) {
         hipLaunchKernelGGL(k_gather, dim3(grid), dim3(256), 0, s, v1, n, x, y, z, rgba, tx, ty, tz, tc);
         ok(hipMemcpyAsync(x, tx, n * 4, hipMemcpyDeviceToDevice, s));
         ok(hipMemcpyAsync(y, ty, n * 4, hipMemcpyDeviceToDevice, s));
         ok(hipMemcpyAsync(z, tz, n * 4, hipMemcpyDeviceToDevice, s));
         ok(hipMemcpyAsync(rgba, tc, n * 4, hipMemcpyDeviceToDevice, s));
+        if (perm) {
+            hipLaunchKernelGGL(k_gather_u32, dim3(grid), dim3(256), 0, s, v1, n, perm, tp);
+            ok(hipMemcpyAsync(perm, tp, n * 4, hipMemcpyDeviceToDevice, s));
+        }
         ok(hipStreamSynchronize(s));
     }
     (void)hipFree(bb); (void)hipFree(k0); (void)hipFree(k1); (void)hipFree(v0); (void)hipFree(v1);
-    (void)hipFree(tx); (void)hipFree(ty); (void)hipFree(tz); (void)hipFree(tc); (void)hipFree(tmp);
+    (void)hipFree(tx); (void)hipFree(ty); (void)hipFree(tz); (void)hipFree(tc); (void)hipFree(tp); (void)hipFree(tmp);
     if (e == hipSuccess) e = hipGetLastError();
     return (int)e;
 }

@@ -93,9 +93,13 @@ class Projector:
         self._chk(self._lib.rtr_stream_probe(self._ctx, _vp(P)))
 
     # -- cloud
-    def upload_points(self, xyz, rgb):
+    def upload_points(self, xyz, rgb, point_ids=None):
         """xyz: float32 [n,3|4] (the reference's float4 (x,y,z,1) or tight xyz);
-        rgb: uint8 [n,3|4] (uchar4 (c0,c1,c2,255) or tight triples)."""
+        rgb: uint8 [n,3|4] (uchar4 (c0,c1,c2,255) or tight triples).
+        point_ids: True / False sets option "point_ids" first (a sorted cloud keeps its upload order for
+        point_pass, +4 B per point); None leaves it as it is."""
+        if point_ids is not None:
+            self.set_option("point_ids", 1 if point_ids else 0)
         xyz = np.ascontiguousarray(xyz, dtype=np.float32)
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
         if xyz.ndim != 2 or xyz.shape[1] not in (3, 4) or rgb.ndim != 2 or rgb.shape[1] not in (3, 4) \
@@ -172,6 +176,15 @@ class Projector:
         P = self._P(P)
         self._chk(self._lib.rtr_render(self._ctx, _vp(P), 1 if with_filter else 0))
 
+    # -- point pass (rtr.h section 6b)
+    def point_pass(self, P, ids=True, visible=True):
+        """Per-pixel point IDs (BUF_POINT_ID: upload index, NO_POINT for none) and / or the per-point visibility
+        mask (BUF_VISIBLE) of the frame in the depth buffer, made with P; queued behind it, read with download /
+        device_buffer."""
+        P = self._P(P)
+        what = (L.POINTS_IDS if ids else 0) | (L.POINTS_VISIBLE if visible else 0)
+        self._chk(self._lib.rtr_point_pass(self._ctx, _vp(P), what))
+
     # -- phases (multi-GPU: reduce the device buffers between them)
     def clear(self):
         self._chk(self._lib.rtr_clear(self._ctx))
@@ -199,17 +212,23 @@ class Projector:
             L.BUF_IMAGE: (np.uint8, "|u1", lambda w, h: (h, w, 3)),
             L.BUF_TENSOR: (np.uint16, "<f2", lambda w, h: (1, 5, h, w)),
             L.BUF_MASK: (np.uint8, "|u1", lambda w, h: (h, w)),
-            L.BUF_MINMAX: (np.uint32, "<u4", lambda w, h: (2,))}
+            L.BUF_MINMAX: (np.uint32, "<u4", lambda w, h: (2,)),
+            L.BUF_POINT_ID: (np.uint32, "<u4", lambda w, h: (h, w)),
+            L.BUF_VISIBLE: (np.uint32, "<u4", lambda w, h, n: ((n + 31) // 32,))}  # (by the point count, not W / H)
+
+    def _shape(self, which):
+        shp = self._BUF[which][2]
+        return shp(self.W, self.H, self.num_points) if which == L.BUF_VISIBLE else shp(self.W, self.H)
 
     def device_buffer(self, which, typestr=None):
         ptr, nbytes = C.c_void_p(), C.c_size_t()
         self._chk(self._lib.rtr_device_buffer(self._ctx, which, C.byref(ptr), C.byref(nbytes)))
-        _, ts, shp = self._BUF[which]
-        return DeviceBuffer(ptr.value, shp(self.W, self.H), typestr or ts)
+        _, ts, _ = self._BUF[which]
+        return DeviceBuffer(ptr.value, self._shape(which), typestr or ts)
 
     def download(self, which):
-        dt, _, shp = self._BUF[which]
-        out = np.empty(shp(self.W, self.H), dt)
+        dt = self._BUF[which][0]
+        out = np.empty(self._shape(which), dt)
         self._chk(self._lib.rtr_download_buffer(self._ctx, which, _vp(out), out.nbytes))
         return out
 
@@ -287,10 +306,12 @@ class ProjectCloud:
     post-processes its output (project_cloud.cu:471-487).  `set_model` accepts any callable
     instead of a file."""
 
-    def __init__(self, vertices, colors, modelFilename="", device=0, reorder=True):
+    def __init__(self, vertices, colors, modelFilename="", device=0, reorder=True, point_ids=False):
         """reorder: True keeps the library's default upload policy (the cloud is Morton-sorted once when its
         256-point chunks are not spatially compact -- the grid's 0.25 m blocks are unordered inside); False never
-        sorts.  Frames do not depend on the point order."""
+        sorts.  Frames do not depend on the point order.  point_ids: a sorted cloud keeps its upload order resident
+        (+4 B per point) so that computePointIds / visible_points work whatever the policy sorted; without it they
+        work on clouds that were not sorted."""
         self.modelFilename = modelFilename
         self.model = None
         self._device = device
@@ -306,7 +327,7 @@ class ProjectCloud:
         self._p = Projector(device)
         if not reorder:
             self._p.set_option("auto_reorder", 0)
-        self._p.upload_points(vertices, colors)
+        self._p.upload_points(vertices, colors, point_ids=bool(point_ids))
 
     def set_model(self, model):
         """Use `model` (a callable taking the fp16 {1,5,H,W} cuda tensor) in computeFull."""
@@ -374,6 +395,31 @@ class ProjectCloud:
             if depth is not None:
                 depth[...] = self._p.download(L.BUF_DEPTH).view(np.float32)  # :485
         return 1
+
+    def _point_pass(self, calibration, extrinsics, filtered, ids, visible):
+        W, H = calibration.getWidth(), calibration.getHeight()
+        self._p.set_resolution(W, H)
+        P = compose_projection(calibration.getIntrinsicsMatrix(), extrinsics)
+        self._p.render(P, filtered)
+        self._p.point_pass(P, ids=ids, visible=visible)
+
+    def computePointIds(self, calibration, extrinsics, filtered=False):
+        """Renders the frame (like computeRGBD / computeFilteredRGBD) and returns which point each pixel shows:
+        int64 [H, W], the index into the uploaded vertex array, -1 for none (empty or prefiltered-away pixels).
+        image[p] of an attribute array `a` is then a[ids[p]] where ids[p] >= 0."""
+        self._point_pass(calibration, extrinsics, filtered, True, False)
+        ids = self._p.download(L.BUF_POINT_ID)
+        out = ids.astype(np.int64)
+        out[ids == L.NO_POINT] = -1
+        return out
+
+    def visible_points(self, calibration, extrinsics, filtered=False):
+        """Renders the frame and returns a bool mask over the uploaded vertices: True for the points that
+        contributed to its colour (passed the z-buffer and depth window; after the prefilter, on a kept pixel)."""
+        self._point_pass(calibration, extrinsics, filtered, False, True)
+        words = self._p.download(L.BUF_VISIBLE)
+        bits = np.unpackbits(words.astype("<u4").view(np.uint8), bitorder="little")
+        return bits[:self._p.num_points].astype(bool)
 
     def tensor_device_buffer(self):
         """The planar fp16 {1,5,H,W} device tensor computeFull feeds to the U-Net
