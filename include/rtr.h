@@ -144,10 +144,12 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *  "pool_worst_case": 0 (default) = the pool of dynamic stream extents is sized by the frames the cloud has had (8 x the
  *          most in-frustum entries a completed frame reported, at least n / 2: 4 B per point instead of 16).  A frame
  *          whose entries jump past that overflows it; the next synchronising call (every call that copies results to the
- *          host, rtr_synchronize, rtr_download_buffer) then sizes the pool for the worst case and renders that frame
- *          again before it returns -- transparent, except for whoever consumes frames on the stream without ever
- *          synchronising, and for rtr_wait (asynchronous outputs), which reports RTR_ERR_INTERNAL once and asks for
- *          the frame again.  1 = sized for the worst case (2 n entries) from the start.
+ *          host, rtr_synchronize, rtr_download_buffer, rtr_wait) then sizes the pool for the worst case and renders that
+ *          frame again before it returns -- rtr_wait every slot whose frame was queued before the pool grew, into its
+ *          own buffers.  Transparent, except for whoever consumes frames on the stream without ever synchronising.
+ *          The phase calls are consumed that way (a sharded frame is reduced first): a binned rtr_min_depth_pass
+ *          sizes the pool for the worst case for the rest of the cloud's life.  computeFull synchronises before its
+ *          model runs.  1 = sized for the worst case (2 n entries) from the start.
  *          rtr_get_option("resident_millibytes_per_point"): device memory held for the cloud and its frames, per point.
  *  "keep_accum": 1 = the whole-frame calls also write RTR_BUF_ACCUM (default 0; the phase
  *          calls always do).
@@ -239,7 +241,9 @@ int rtr_render(rtr_ctx *ctx, const float P[16], int with_filter);
  * device and queues their copies into the library's PINNED host buffers of `slot` on a second stream; it does
  * not wait.  With the slots used in rotation, frame k's copies run beside frame k + 1's kernels.
  * rtr_wait(slot) blocks until that slot's outputs are complete (slot = -1: all of them) and reports errors of
- * the frames since the last synchronising call; the buffers (rtr_host_output_buffers: W*H*3 u8, W*H float,
+ * the frames since the last synchronising call.  When the adaptive extent pool overflowed in one of them
+ * (option "pool_worst_case"), every slot still queued is rendered again with the grown pool, synchronously,
+ * before RTR_OK is returned; a slot whose cloud has been replaced since fails instead.  The buffers (rtr_host_output_buffers: W*H*3 u8, W*H float,
  * valid until the next rtr_set_resolution) may be read until the slot is used again.  A caller that needs the
  * frame in its own arrays copies from there (or keeps using the synchronous calls). */
 #define RTR_ASYNC_SLOTS 2

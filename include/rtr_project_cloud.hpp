@@ -110,7 +110,8 @@ public:
     // (:475) and converted like cv::Mat::convertTo(CV_8UC3, 255.0) (:480: scale, round half to even,
     // saturate); depth <- the prefiltered depth buffer (:485).  Either output may be null; returns 1.
     // The projector runs on HIP's default stream here, which is torch's current stream unless the caller
-    // changed it: kernels and the model are ordered without a host synchronisation.
+    // changed it.  One host synchronisation sits between the frame and the model: a frame that overflowed the
+    // adaptive extent pool is rendered again there, so the model never reads a tensor with dropped entries.
     template <class Calibration, class Extrinsics, class Image>
     int computeFull(const Calibration& calibration, const Extrinsics& extrinsics, Image* color, Image* depth) {
         if (!has_model_) throw std::runtime_error("rtr: No model file name given, computeFull will not work");  // :247
@@ -119,6 +120,8 @@ public:
         projection(calibration, extrinsics, P);
         check(ctx_, rtr_set_resolution(ctx_, W, H));
         check(ctx_, rtr_render(ctx_, P, 1));
+        // (a frame that overflowed the adaptive extent pool is rendered again here, before the model reads it)
+        check(ctx_, rtr_synchronize(ctx_));
         torch::Tensor input = torch::from_blob(tensor(), {1, 5, H, W},
                                                torch::TensorOptions().dtype(torch::kFloat16).device(torch::kCUDA, device_));
         torch::NoGradGuard no_grad;

@@ -177,6 +177,16 @@ struct rtr_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
     double total_ms[RTR_K_COUNT] = {0};
     uint64_t launches[RTR_K_COUNT] = {0};
+
+    // the frame queued into each async slot, for rtr_wait to render again: `stale` = it was queued before the adaptive
+    // extent pool grew (check_store_error), so it may have lost entries; `cloud` = cloud_seq when it was queued
+    struct SlotFrame {
+        float P[16] = {0};
+        int with_filter = 0;
+        bool stale = false;
+        uint64_t cloud = 0;
+    } slot_frame[RTR_ASYNC_SLOTS];
+    uint64_t cloud_seq = 0;  // +1 per upload / generation (alloc_cloud)
 };
 
 static thread_local std::string g_create_err;
@@ -439,6 +449,7 @@ int alloc_cloud(rtr_ctx *c, uint64_t n) {
         if (c->entries_host) *c->entries_host = 0u;
     }
     c->n = n;
+    ++c->cloud_seq;
     c->list_valid = false;
     c->last_valid = false;
     c->pp_vis_current = false;
@@ -509,6 +520,8 @@ int check_store_error(rtr_ctx *c, bool *retry = nullptr) {
     if (e == 0u) return RTR_OK;
     if (e == 2u && c->opt_debug_dyn_cap < 0 && c->F().dyn_cap < pool_worst_cap(c)) {
         c->pool_worst = true;  // (ensure_lists re-allocates before the next T1)
+        for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)  // (every frame still on its way to a slot was queued before the growth: rtr_wait repeats it)
+            if (c->ho[k].busy) c->slot_frame[k].stale = true;
         if (retry) {
             *retry = true;
             return RTR_OK;
@@ -1332,6 +1345,9 @@ int rtr_min_depth_pass(rtr_ctx *c, const float P[16]) {
     c->list_valid = false;
     c->last_valid = false;
     if (use_tiles(c)) {
+        // (the phase calls' frames are consumed on the stream -- a sharded frame is reduced before anything synchronises
+        // -- and no synchronising call can render them again: the extent pool is sized for the worst case at once)
+        c->pool_worst = true;
         if (int rc = bin_points(c, P, false, c->p2p.whole_frame)) return rc;
         Timed t(c, RTR_K_TILE);
         rtr::launch_tile(c->stream, 1, c->W, c->H, c->F().store, c->prm.depth_window, c->depth, c->acc, c->img,
@@ -1569,13 +1585,8 @@ int rtr_host_output_buffers(rtr_ctx *c, int slot, uint8_t **img, float **depth) 
     return RTR_OK;
 }
 
-int rtr_project_async(rtr_ctx *c, const float P[16], int slot, int with_filter) {
-    if (!c) return RTR_ERR_INVALID;
-    NEED(c, P != nullptr, "P is NULL");
-    NEED(c, slot >= 0 && slot < RTR_ASYNC_SLOTS, "slot out of range");
-    if (int rc = check_frame(c)) return rc;
-    DevGuard g(c->device);
-    if (int rc = ensure_host_out(c)) return rc;
+// queues frame P into `slot`: render, snapshot on the device, copy to the pinned buffers on the copy stream
+static int queue_slot(rtr_ctx *c, const float P[16], int slot, int with_filter) {
     auto &h = c->ho[slot];
     // (the slot's previous frame may still be on its way to the host: its snapshot must not be overwritten yet)
     if (h.busy) HIP_TRY(c, hipStreamWaitEvent(c->stream, h.done, 0));
@@ -1587,20 +1598,74 @@ int rtr_project_async(rtr_ctx *c, const float P[16], int slot, int with_filter) 
     HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, h.snap, 0));
     rtr::launch_copy_to_host(c->copy_stream, h.ddepth, h.depth_map, npix * 4, h.dimg, h.img_map, npix * 3);
     HIP_TRY(c, hipEventRecord(h.done, c->copy_stream));
+    auto &f = c->slot_frame[slot];
+    memcpy(f.P, P, sizeof f.P);
+    f.with_filter = with_filter;
+    f.stale = false;
+    f.cloud = c->cloud_seq;
     h.busy = true;
     return RTR_OK;
+}
+
+int rtr_project_async(rtr_ctx *c, const float P[16], int slot, int with_filter) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, P != nullptr, "P is NULL");
+    NEED(c, slot >= 0 && slot < RTR_ASYNC_SLOTS, "slot out of range");
+    if (int rc = check_frame(c)) return rc;
+    DevGuard g(c->device);
+    if (int rc = ensure_host_out(c)) return rc;
+    return queue_slot(c, P, slot, with_filter);
+}
+
+// The adaptive extent pool overflowed in a frame queued before some slot's frame was complete (check_store_error marked
+// those slots stale): every stale slot is rendered again with the grown pool, in slot order, and so is the last whole
+// frame, which the device buffers hold.  Everything queued so far is finished first and its error word read: those
+// frames are the ones being repeated.
+static int repair_slots(rtr_ctx *c) {
+    HIP_TRY(c, sync_streams(c));
+    bool retry = false;
+    if (int rc = check_store_error(c, &retry)) return rc;
+    const bool last = c->last_valid, pass = c->pp_after_last;  // (the slots' frames below replace them)
+    const int last_filter = c->last_filter;
+    float last_P[16];
+    memcpy(last_P, c->last_P, sizeof last_P);
+    for (int k = 0; k < RTR_ASYNC_SLOTS; ++k) {
+        const auto &f = c->slot_frame[k];
+        if (!c->ho[k].busy || !f.stale) continue;
+        if (f.cloud != c->cloud_seq)
+            return fail(c, RTR_ERR_INTERNAL, "rtr_wait: the frame of slot %d lost entries in an overflowing extent pool and "
+                        "the cloud has been replaced since: it cannot be rendered again", k);
+        float P[16];
+        memcpy(P, f.P, sizeof P);
+        if (int rc = queue_slot(c, P, k, f.with_filter)) return rc;
+    }
+    if (!last) return RTR_OK;
+    memcpy(c->last_P, last_P, sizeof last_P);
+    c->last_filter = last_filter;
+    c->pp_after_last = pass;
+    return finish_sync_rerender(c);
 }
 
 int rtr_wait(rtr_ctx *c, int slot) {
     if (!c) return RTR_ERR_INVALID;
     NEED(c, slot >= -1 && slot < RTR_ASYNC_SLOTS, "slot out of range (-1: every slot)");
     DevGuard g(c->device);
-    for (int k = 0; k < RTR_ASYNC_SLOTS; ++k) {
-        if ((slot >= 0 && k != slot) || !c->ho[k].busy) continue;
-        HIP_TRY(c, hipEventSynchronize(c->ho[k].done));
-        c->ho[k].busy = false;
+    for (int attempt = 0;; ++attempt) {
+        for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
+            if ((slot < 0 || k == slot) && c->ho[k].busy) HIP_TRY(c, hipEventSynchronize(c->ho[k].done));
+        bool retry = false;
+        int rc = check_store_error(c, attempt == 0 ? &retry : nullptr);
+        bool stale = false;
+        for (int k = 0; k < RTR_ASYNC_SLOTS; ++k) stale |= c->ho[k].busy && c->slot_frame[k].stale;
+        if (!rc && (retry || stale) && attempt == 0) {  // (once: the pool is worst-case sized from now on)
+            if ((rc = repair_slots(c))) return rc;
+            continue;
+        }
+        if (!rc && retry) rc = fail(c, RTR_ERR_INTERNAL, "rtr_wait: the extent pool overflowed again");
+        for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
+            if (slot < 0 || k == slot) c->ho[k].busy = false;
+        return rc;
     }
-    return check_store_error(c);
 }
 
 int rtr_project_filtered(rtr_ctx *c, const float P[16], uint8_t *host_img, float *host_depth) {

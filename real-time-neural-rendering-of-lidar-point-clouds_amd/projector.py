@@ -377,7 +377,7 @@ class ProjectCloud:
                 raise ValueError("%s must be a C-contiguous %s array of shape %s (main.cpp:93-94)" % (name, dt, shape))
         dev = torch.device("cuda", self._device)
         with torch.cuda.device(dev):
-            # kernels and the model share torch's current stream, so the hand-off needs no sync
+            # kernels and the model share torch's current stream
             stream = torch.cuda.current_stream(dev).cuda_stream
             if self._bound_stream != stream:
                 self._p.set_stream(stream)
@@ -385,6 +385,8 @@ class ProjectCloud:
             self._p.set_resolution(W, H)
             P = compose_projection(calibration.getIntrinsicsMatrix(), extrinsics)
             self._p.render(P, True)
+            # (a frame that overflowed the adaptive extent pool is rendered again here, before the model reads it)
+            self._p.synchronize()
             inp = torch.as_tensor(self._p.device_buffer(L.BUF_TENSOR), device=dev)  # zero copy (from_blob, :471)
             with torch.no_grad():
                 out = self.model(inp)

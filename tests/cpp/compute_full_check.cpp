@@ -3,7 +3,9 @@
 // resident fp16 {1,5,H,W} tensor -- checked by pointer through a second model that returns its input --
 // and its output goes through the convertTo(CV_8UC3, 255.0) step.  Stand-in input types as in
 // facade_check.cpp (TEST INPUT TYPES, not a build of the reference).
-//   compute_full_check <cloud.bin> <W> <H> <K9+E16 doubles .bin> <model.pt name> <out_prefix>
+//   compute_full_check <cloud.bin> <W> <H> <K9+E16 doubles .bin> <model.pt name> <out_prefix> [footprint]
+// With "footprint", <out_prefix>.footprint receives option resident_millibytes_per_point (two int32) after the upload
+// and after the first computeFull: whether that frame grew the extent pool.
 #define RTR_WITH_TORCH
 #include <cstdio>
 #include <cstdlib>
@@ -71,7 +73,11 @@ int main(int argc, char** argv) {
         rtr::ProjectCloud pc(grid, argv[5]);
         Img rgb, depth;
         rgb.bytes.resize((size_t)W * H * 3); depth.bytes.resize((size_t)W * H * 4);
+        int footprint[2] = {0, 0};
+        if (rtr_get_option(pc.context(), "resident_millibytes_per_point", &footprint[0]) != RTR_OK) return 9;
         if (pc.computeFull(cal, E, &rgb, &depth) != 1) return 3;
+        if (rtr_get_option(pc.context(), "resident_millibytes_per_point", &footprint[1]) != RTR_OK) return 9;
+        if (argc > 7 && std::string(argv[7]) == "footprint") dump(out + ".footprint", footprint, sizeof footprint);
         dump(out + ".rgb", rgb.bytes.data(), rgb.bytes.size());
         dump(out + ".depth", depth.bytes.data(), depth.bytes.size());
         Img conly;
