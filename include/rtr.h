@@ -179,7 +179,8 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          heavy tile overflows it and the error path (RTR_ERR_INTERNAL) can be exercised.
  *  "xp": only in RTR_EXPERIMENT builds (make experiment): switches parts of the point kernel off for
  *          timing attribution -- frames are WRONG while it is non-zero; the shipped library rejects it.
- *  "probe_variant": measurement aid of tools/probe_variants.py (selects the rtr_stream_probe kernel). */
+ *  "probe_variant": measurement aid of tools/probe_variants.py (selects the rtr_stream_probe kernel).
+ *  rtr_get_option("views") reads the view count of the last rtr_render_views batch (section 6c; 0: none current). */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
 /* Reads an option back; also "p2p_open" (see "p2p_timeout_ms"), "reordered" (1: the resident cloud was sorted by the library),
  * "order_ratio_ppm" (mean chunk-box diagonal / cloud diagonal as uploaded, in millionths), "packed" and
@@ -327,7 +328,12 @@ typedef enum {
     RTR_BUF_MASK = 4,   /* u8  [H*W]    final keep-mask of the prefilter                              */
     RTR_BUF_MINMAX = 5, /* u32 [2]      depth min / max bits (project_cloud.h:30-31)                  */
     RTR_BUF_POINT_ID = 6, /* u32 [H*W]  upload index of the point each pixel shows (rtr_point_pass)       */
-    RTR_BUF_VISIBLE = 7   /* u32 [(n + 31) / 32]  bit i % 32 of word i / 32: point i contributed (ditto)  */
+    RTR_BUF_VISIBLE = 7,  /* u32 [(n + 31) / 32]  bit i % 32 of word i / 32: point i contributed (ditto)  */
+    /* the last rtr_render_views batch of `count` views (section 6c), view-major: */
+    RTR_BUF_VIEW_DEPTH = 8,   /* u32 [count, H, W]                                                       */
+    RTR_BUF_VIEW_IMAGE = 9,   /* u8  [count, H, W, 3]                                                    */
+    RTR_BUF_VIEW_TENSOR = 10, /* f16 [count, 5, H, W]  one contiguous batch tensor                       */
+    RTR_BUF_VIEW_MINMAX = 11  /* u32 [count, 2]                                                          */
 } rtr_buffer;
 int rtr_device_buffer(rtr_ctx *ctx, int which, void **dev_ptr, size_t *bytes);
 /* Synchronous device->host copy of one buffer (bytes must equal its size). */
@@ -357,6 +363,27 @@ int rtr_download_buffer(rtr_ctx *ctx, int which, void *host, size_t bytes);
 #define RTR_POINTS_IDS 1
 #define RTR_POINTS_VISIBLE 2
 int rtr_point_pass(rtr_ctx *ctx, const float P[16], int what);
+
+/* ---- 6c. several views: one pass over the cloud for up to RTR_MAX_VIEWS poses ----------------
+ * rtr_render_views renders `count` poses (P: count x 16 floats, each row-major like rtr_render's) at the context's
+ * resolution and rtr_params into the RTR_BUF_VIEW_* buffers: view v is bit for bit what rtr_render(ctx, P + 16 v,
+ * with_filter) would leave in RTR_BUF_DEPTH / IMAGE (and, filtered, TENSOR / MINMAX; unfiltered batches leave those
+ * two undefined, as rtr_render leaves them stale).  rtr_get_option(ctx, "views", &k) gives the last batch's count.
+ * The single frame is left alone: RTR_BUF_DEPTH .. RTR_BUF_VISIBLE, the frame rtr_synchronize would repeat, the
+ * asynchronous slots and the point pass keep what they held.
+ * Binned form (option "mode" 1, <= 4096 tiles, no open p2p group, option "overlap" 0): ONE point-kernel launch
+ * streams the cloud for every view (timed as RTR_K_MIN_DEPTH), then one tile launch per view (RTR_K_TILE) and the
+ * prefilter.  Every other case -- mode 0, more than 4096 tiles, an open p2p group, option "overlap" 1 -- loops over
+ * the two-pass atomic form into the view buffers: exact, no sharing.
+ * Asynchronous like rtr_render.  Each view has its own tile store (a 32 KB static extent per 32x16 storage tile:
+ * ~134 MB per view at 1920x1080) and adaptive extent pool, allocated on first use for the largest count seen (stores
+ * per resolution, pools per cloud).  A batch that overflows an adaptive pool is rendered again by the next
+ * rtr_synchronize or rtr_download_buffer(RTR_BUF_VIEW_*), with every view's pool worst-case sized (16 B per point and
+ * view) from then on for this cloud; a caller who consumes batches on the stream without such a call sets option
+ * "pool_worst_case" 1.
+ * Errors: count outside 1..RTR_MAX_VIEWS, P NULL, no cloud or no resolution -> RTR_ERR_INVALID, nothing changed. */
+#define RTR_MAX_VIEWS 8
+int rtr_render_views(rtr_ctx *ctx, int count, const float *P, int with_filter);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

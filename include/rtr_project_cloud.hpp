@@ -27,6 +27,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -82,6 +83,19 @@ public:
     template <class Calibration, class Extrinsics, class Image>
     int computeFilteredRGBD(const Calibration& calibration, const Extrinsics& extrinsics, Image* color, Image* depth) {
         return frame(calibration, extrinsics, color, depth, true);
+    }
+    // Several views in one pass over the cloud (rtr.h section 6c): extrinsics[v] -> colors[v] / depths[v] (either entry
+    // may be null; both vectors as long as `extrinsics`, at most RTR_MAX_VIEWS), what computeRGBD /
+    // computeFilteredRGBD would write for that pose.  Returns 1, or -1 when every output is null.
+    template <class Calibration, class Extrinsics, class Image>
+    int computeRGBDViews(const Calibration& calibration, const std::vector<Extrinsics>& extrinsics,
+                         const std::vector<Image*>& colors, const std::vector<Image*>& depths) {
+        return views(calibration, extrinsics, colors, depths, false);
+    }
+    template <class Calibration, class Extrinsics, class Image>
+    int computeFilteredRGBDViews(const Calibration& calibration, const std::vector<Extrinsics>& extrinsics,
+                                 const std::vector<Image*>& colors, const std::vector<Image*>& depths) {
+        return views(calibration, extrinsics, colors, depths, true);
     }
     // literal nullptr for one output, as in cloudreader.cpp:246 `computeRGBD(calib, pose, nullptr, &depth)`
     template <class Calibration, class Extrinsics, class Image>
@@ -219,6 +233,31 @@ private:
         uint8_t* c8 = color ? color->template ptr<uint8_t>() : nullptr;
         float* d32 = depth ? depth->template ptr<float>() : nullptr;
         check(ctx_, filtered ? rtr_project_filtered(ctx_, P, c8, d32) : rtr_project(ctx_, P, c8, d32));
+        return 1;
+    }
+    template <class Calibration, class Extrinsics, class Image>
+    int views(const Calibration& calibration, const std::vector<Extrinsics>& extrinsics, const std::vector<Image*>& colors,
+              const std::vector<Image*>& depths, bool filtered) {
+        const size_t k = extrinsics.size();
+        if (k < 1 || k > RTR_MAX_VIEWS || colors.size() != k || depths.size() != k)
+            throw std::invalid_argument("rtr: 1..RTR_MAX_VIEWS extrinsics, one colour and one depth entry (or null) each");
+        bool any = false;
+        for (size_t v = 0; v < k; ++v) any = any || colors[v] != nullptr || depths[v] != nullptr;
+        if (!any) return -1;
+        std::vector<float> P(16 * k);
+        for (size_t v = 0; v < k; ++v) projection(calibration, extrinsics[v], P.data() + 16 * v);
+        const int W = calibration.getWidth(), H = calibration.getHeight();
+        check(ctx_, rtr_set_resolution(ctx_, W, H));
+        check(ctx_, rtr_render_views(ctx_, (int)k, P.data(), filtered ? 1 : 0));
+        const size_t npix = (size_t)W * H;
+        std::vector<uint8_t> img(k * npix * 3);
+        std::vector<float> depth(k * npix);
+        check(ctx_, rtr_download_buffer(ctx_, RTR_BUF_VIEW_DEPTH, depth.data(), depth.size() * 4));
+        check(ctx_, rtr_download_buffer(ctx_, RTR_BUF_VIEW_IMAGE, img.data(), img.size()));
+        for (size_t v = 0; v < k; ++v) {
+            if (colors[v]) std::memcpy(colors[v]->template ptr<uint8_t>(), img.data() + v * npix * 3, npix * 3);
+            if (depths[v]) std::memcpy(depths[v]->template ptr<float>(), depth.data() + v * npix, npix * 4);
+        }
         return 1;
     }
     template <class Calibration, class Extrinsics>

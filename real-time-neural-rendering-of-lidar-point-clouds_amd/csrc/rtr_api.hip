@@ -187,6 +187,30 @@ struct rtr_ctx {
         uint64_t cloud = 0;
     } slot_frame[RTR_ASYNC_SLOTS];
     uint64_t cloud_seq = 0;  // +1 per upload / generation (alloc_cloud)
+
+    // several views (rtr_render_views): one tile store and extent pool per view, allocated on first use up to the largest
+    // count seen (stores per resolution, pools per cloud); frame buffers [count_cap] x the single frame's; scratch that
+    // the views of a batch take in turn (accumulators, prefilter mask, pyramid levels, min / max partials)
+    struct Views {
+        rtr_ctx::FrontSet fs[RTR_MAX_VIEWS];
+        int parity[RTR_MAX_VIEWS] = {0};  // lean-frame parity of each view's store
+        int cap = 0;                      // views the frame buffers hold
+        uint32_t *depth = nullptr, *minmax = nullptr, *acc = nullptr, *part_min = nullptr, *part_max = nullptr;
+        uint8_t *img = nullptr, *mask = nullptr;
+        uint16_t *tensor = nullptr;
+        float *lv[9] = {nullptr};
+        int lv_levels = 0;
+        void *tab_host = nullptr, *tab_dev = nullptr;  // rtr::launch_project_bin_views' table (pinned / device)
+        hipEvent_t tab_copied = nullptr;                // ... the last copy of tab_host has been read
+        bool tab_pending = false;
+        uint32_t *err_host = nullptr, *err_dev = nullptr;          // mapped words of the views' stores (StoreConsts)
+        uint32_t *entries_host = nullptr, *entries_dev = nullptr;
+        uint64_t entries_max = 0;
+        bool pool_worst = false;  // a batch overflowed the adaptive pools: worst-case sized for this cloud
+        float P[RTR_MAX_VIEWS * 16] = {0};  // the last batch, what a synchronising call repeats after an overflow
+        int count = 0, with_filter = 0;
+        bool valid = false;
+    } vw;
 };
 
 static thread_local std::string g_create_err;
@@ -287,6 +311,18 @@ void free_frame(rtr_ctx *c) {
     c->lv.lv[0] = nullptr;
     c->W = c->H = 0;
     c->lv_levels = 0;
+    auto &v = c->vw;
+    for (auto &f : v.fs) {
+        dfree(f.store.ext0); dfree(f.store.meta);
+        f.nst = f.ntiles = 0;
+        f.consts = rtr::StoreConsts{};
+    }
+    dfree(v.depth); dfree(v.minmax); dfree(v.acc); dfree(v.part_min); dfree(v.part_max); dfree(v.img); dfree(v.mask);
+    dfree(v.tensor);
+    for (int i = 1; i <= 8; ++i) dfree(v.lv[i]);
+    v.lv_levels = 0;
+    v.cap = 0;
+    v.valid = false;
 }
 
 void free_lists(rtr_ctx *c) {  // the dynamic extent pools (sized by the point count)
@@ -302,6 +338,15 @@ void free_lists(rtr_ctx *c) {  // the dynamic extent pools (sized by the point c
     c->entries_max = 0;
     if (c->entries_host) *c->entries_host = 0u;
     c->last_valid = false;
+    for (auto &f : c->vw.fs) {
+        dfree(f.dyn);
+        f.dyn_cap = 0;
+        f.pool_n = 0;
+    }
+    c->vw.pool_worst = false;
+    c->vw.entries_max = 0;
+    if (c->vw.entries_host) *c->vw.entries_host = 0u;
+    c->vw.valid = false;
 }
 
 void free_pack(rtr_ctx *c) {
@@ -321,15 +366,13 @@ void free_cloud(rtr_ctx *c) {
 
 // Per-resolution part of the tile store: a static 32 KB extent, a stream length, an extent directory
 // per 32x16 storage tile, and the tile kernel's work list.  s: the stream T1 will run on.
-int ensure_tiles(rtr_ctx *c, hipStream_t s) {
+int alloc_store(rtr_ctx *c, rtr_ctx::FrontSet &f, hipStream_t s) {
     const int nt = rtr::tile_count(c->W, c->H), nst = rtr::storage_tile_count(c->W, c->H);
-    auto &f = c->F();
     auto &t = f.store;
     if (!(t.ext0 && f.nst == nst && f.ntiles == nt)) {
         dfree(t.ext0); dfree(t.meta);
         f.nst = f.ntiles = 0;
         f.consts = rtr::StoreConsts{};
-        c->list_valid = false;
         const size_t meta_bytes = rtr::ts_meta_words(nst, nt) * sizeof(uint32_t);
         // (+ 16 entries of slack: the tile kernel's sweeps read a few entries past the piece they are masking)
         HIP_TRY(c, hipMalloc((void **)&t.ext0, ((size_t)nst * rtr::kS0 + 16) * sizeof(uint64_t)));
@@ -347,6 +390,21 @@ int ensure_tiles(rtr_ctx *c, hipStream_t s) {
             HIP_TRY(c, hipStreamSynchronize(s));  // `ident` goes out of scope
         }
     }
+    return RTR_OK;
+}
+int upload_consts(rtr_ctx *c, rtr_ctx::FrontSet &f, hipStream_t s, const rtr::StoreConsts &want) {
+    if (memcmp(&want, &f.consts, sizeof want) != 0) {
+        f.consts = want;
+        HIP_TRY(c, hipMemcpyAsync(rtr::ts_hdr(f.store) + rtr::kHdrConsts, &f.consts, sizeof f.consts, hipMemcpyHostToDevice, s));
+    }
+    return RTR_OK;
+}
+int ensure_tiles(rtr_ctx *c, hipStream_t s) {
+    auto &f = c->F();
+    if (!(f.store.ext0 && f.nst == rtr::storage_tile_count(c->W, c->H) && f.ntiles == rtr::tile_count(c->W, c->H))) {
+        c->list_valid = false;
+        if (int rc = alloc_store(c, f, s)) return rc;
+    }
     // header constants: the buffers T1's last workgroup resets for split tiles / writes the occupancy
     // bitmap to, the dynamic extent pool, the split parameters (uploaded only when one of them changes)
     rtr::StoreConsts want{};
@@ -358,11 +416,7 @@ int ensure_tiles(rtr_ctx *c, hipStream_t s) {
     want.entries_host = c->entries_dev;
     want.heavy = c->opt_heavy > 0 ? (uint32_t)c->opt_heavy : 0xFFFFFFFFu;
     want.slice = (uint32_t)c->opt_slice;
-    if (memcmp(&want, &f.consts, sizeof want) != 0) {
-        f.consts = want;
-        HIP_TRY(c, hipMemcpyAsync(rtr::ts_hdr(t) + rtr::kHdrConsts, &f.consts, sizeof f.consts, hipMemcpyHostToDevice, s));
-    }
-    return RTR_OK;
+    return upload_consts(c, f, s, want);
 }
 
 // The dynamic extents of one frame sum to less than twice its entries (every extent doubles its stream,
@@ -687,6 +741,11 @@ int rtr_destroy(rtr_ctx *c) {
     if (c->split_host) (void)hipHostFree(c->split_host);
     if (c->err_host) (void)hipHostFree(c->err_host);
     if (c->entries_host) (void)hipHostFree(c->entries_host);
+    if (c->vw.err_host) (void)hipHostFree(c->vw.err_host);
+    if (c->vw.entries_host) (void)hipHostFree(c->vw.entries_host);
+    if (c->vw.tab_host) (void)hipHostFree(c->vw.tab_host);
+    dfree(c->vw.tab_dev);
+    if (c->vw.tab_copied) (void)hipEventDestroy(c->vw.tab_copied);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->pp_done) (void)hipEventDestroy(c->pp_done);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -925,6 +984,7 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "p2p_open")) *value = c->p2p.open ? 1 : 0;  // the peers' buffers are mapped (rtr_p2p_open)
     else if (!strcmp(key, "keep_soa")) *value = c->opt_keep_soa;
     else if (!strcmp(key, "pool_worst_case")) *value = c->opt_pool_worst;
+    else if (!strcmp(key, "views")) *value = c->vw.valid ? c->vw.count : 0;  // views of the last rtr_render_views
     else if (!strcmp(key, "resident_millibytes_per_point")) {
         // device memory this context holds for the cloud and its frames, per point: coordinates (fp32 SoA and / or packed
         // form), colours, chunk boxes and lane spreads, tile stores and extent pools, frame buffers
@@ -937,6 +997,11 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
         }
         const uint64_t npix = (uint64_t)c->W * c->H;
         b += c->depth ? npix * (4 + 16 + 3 + 1 + 10) : 0;
+        for (const auto &f : c->vw.fs) {  // (several views: their stores, pools and frame buffers)
+            b += f.dyn ? f.dyn_cap * 8 : 0;
+            b += f.store.ext0 ? ((uint64_t)f.nst * rtr::kS0 + 16) * 8 + rtr::ts_meta_words(f.nst, f.ntiles) * 4 : 0;
+        }
+        b += c->vw.cap ? npix * (16 + 1 + (uint64_t)c->vw.cap * (4 + 3 + 10)) : 0;
         *value = c->n ? (int)((b * 1000) / c->n > 0x7FFFFFFFull ? 0x7FFFFFFF : (b * 1000) / c->n) : 0;
     }
     else if (!strcmp(key, "pack")) *value = c->opt_pack;
@@ -1007,11 +1072,21 @@ static int finish_sync(rtr_ctx *c) {
     return check_store_error(c);
 }
 
+static int views_check(rtr_ctx *c, bool *again);
+static int views_enqueue(rtr_ctx *c, int count, const float *P, int with_filter);
 int rtr_synchronize(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
-    return finish_sync(c);
+    int rc = finish_sync(c);
+    bool again = false;
+    if (!rc) rc = views_check(c, &again);
+    if (!rc && again) {  // (a batch overflowed the adaptive pools: rendered again with worst-case ones)
+        if ((rc = views_enqueue(c, c->vw.count, c->vw.P, c->vw.with_filter))) return rc;
+        HIP_TRY(c, sync_streams(c));
+        rc = views_check(c, nullptr);
+    }
+    return rc;
 }
 
 // ---- cloud -------------------------------------------------------------------------
@@ -1993,12 +2068,248 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
     return RTR_OK;
 }
 
+// ---- several views -----------------------------------------------------------------
+// rtr_render_views (rtr.h, section 6c).  Binned batches: ONE point-kernel launch appends every view's points to that
+// view's tile store (rtr::launch_project_bin_views), then per view a lean tile launch (and the prefilter) writes the
+// view's slices of the batch buffers.  Every other form loops over the atomic form into the same slices.  Neither
+// touches the single frame's buffers, its tile stores, last_P or the asynchronous slots.
+// The views' extent pools are adaptive like the single frame's (sized by the densest frame or view seen); a batch that
+// overflows one reports it through its own mapped word, and the next synchronising call (rtr_synchronize, a download
+// of RTR_BUF_VIEW_*) sizes every view's pool for the worst case -- 16 B per point and view -- and repeats the batch.
+
+static int views_mapped_word(rtr_ctx *c, uint32_t **host, uint32_t **dev) {
+    if (*host) return RTR_OK;
+    HIP_TRY(c, hipHostMalloc((void **)host, sizeof(uint32_t), hipHostMallocMapped));
+    **host = 0u;
+    void *d = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer(&d, *host, 0));
+    *dev = static_cast<uint32_t *>(d);
+    return RTR_OK;
+}
+
+static bool views_binned(const rtr_ctx *c) {  // the binned form serves batches; the rest loop over the atomic form
+    return c->opt_mode == 1 && rtr::tile_count(c->W, c->H) <= 4096 && !c->p2p.open && !c->opt_overlap;
+}
+
+// buffers, scratch and (binned) tile stores / pools for `count` views at this resolution and cloud
+static int ensure_views(rtr_ctx *c, int count, int with_filter) {
+    auto &v = c->vw;
+    const size_t npix = (size_t)c->W * c->H;
+    if (count > v.cap) {
+        HIP_TRY(c, sync_streams(c));  // (a batch in flight may still write the old buffers)
+        v.valid = false;
+        dfree(v.depth); dfree(v.img); dfree(v.tensor); dfree(v.minmax);
+        HIP_TRY(c, hipMalloc((void **)&v.depth, (size_t)count * npix * 4));
+        HIP_TRY(c, hipMalloc((void **)&v.img, ((size_t)count * npix * 3 + 15) & ~(size_t)15));
+        HIP_TRY(c, hipMalloc((void **)&v.tensor, (size_t)count * npix * 10));
+        HIP_TRY(c, hipMalloc((void **)&v.minmax, (size_t)count * 8));
+        v.cap = count;
+    }
+    if (!v.acc) {
+        const size_t nparts = (size_t)((c->W + 31) / 32) * ((c->H + 31) / 32);
+        HIP_TRY(c, hipMalloc((void **)&v.acc, npix * 16));
+        HIP_TRY(c, hipMalloc((void **)&v.mask, npix));
+        HIP_TRY(c, hipMalloc((void **)&v.part_min, nparts * 4));
+        HIP_TRY(c, hipMalloc((void **)&v.part_max, nparts * 4));
+    }
+    if (with_filter && v.lv_levels != c->prm.levels) {
+        for (int i = 1; i <= 8; ++i) dfree(v.lv[i]);
+        v.lv_levels = 0;
+        for (int i = 1, w = c->W / 2, h = c->H / 2; i <= c->prm.levels; ++i, w /= 2, h /= 2)
+            HIP_TRY(c, hipMalloc((void **)&v.lv[i], sizeof(float) * (size_t)w * h));
+        v.lv_levels = c->prm.levels;
+    }
+    if (!v.tab_host) {
+        HIP_TRY(c, hipHostMalloc(&v.tab_host, rtr::view_tab_bytes(), hipHostMallocDefault));
+        HIP_TRY(c, hipMalloc(&v.tab_dev, rtr::view_tab_bytes()));
+        HIP_TRY(c, hipEventCreateWithFlags(&v.tab_copied, hipEventDisableTiming));
+    }
+    if (!views_binned(c)) return ensure_soa(c);
+    if (int rc = views_mapped_word(c, &v.err_host, &v.err_dev)) return rc;
+    if (int rc = views_mapped_word(c, &v.entries_host, &v.entries_dev)) return rc;
+    // pools: the single frame's adaptive rule over the densest frame OR view seen, worst case after an overflow
+    const uint64_t worst = pool_worst_cap(c);
+    const uint64_t e = __atomic_load_n(v.entries_host, __ATOMIC_RELAXED);
+    if (e > v.entries_max) v.entries_max = e;
+    const uint64_t emax = v.entries_max > c->entries_max ? v.entries_max : c->entries_max;
+    const uint64_t floor_ = c->n / 2 > (1ull << 20) ? c->n / 2 : (1ull << 20);
+    for (int k = 0; k < count; ++k) {
+        auto &f = v.fs[k];
+        if (int rc = alloc_store(c, f, c->stream)) return rc;
+        const uint64_t have = f.pool_n == c->n ? f.dyn_cap : 0;
+        uint64_t want = (c->opt_pool_worst || v.pool_worst) ? worst
+                        : (have >= 4 * emax && have >= floor_ ? have : (8 * emax > floor_ ? 8 * emax : floor_));
+        if (want > worst) want = worst;
+        if (!(f.dyn && f.pool_n == c->n && f.dyn_cap >= want)) {
+            HIP_TRY(c, sync_streams(c));
+            dfree(f.dyn);
+            f.dyn_cap = want;
+            f.pool_n = c->n;
+            HIP_TRY(c, hipMalloc((void **)&f.dyn, f.dyn_cap * sizeof(uint64_t)));
+        }
+        rtr::StoreConsts want_c{};
+        want_c.depth = v.depth + (size_t)k * npix;
+        want_c.acc = v.acc;
+        want_c.dyn = f.dyn; want_c.dyn_cap = f.dyn_cap;
+        if (c->opt_debug_dyn_cap >= 0 && (uint64_t)c->opt_debug_dyn_cap < want_c.dyn_cap) want_c.dyn_cap = (uint64_t)c->opt_debug_dyn_cap;
+        want_c.err_host = v.err_dev;
+        want_c.entries_host = v.entries_dev;
+        want_c.heavy = 0xFFFFFFFFu;  // (lean frames split nothing)
+        want_c.slice = (uint32_t)c->opt_slice;
+        if (int rc = upload_consts(c, f, c->stream, want_c)) return rc;
+    }
+    return RTR_OK;
+}
+
+// the frame of view k: tile launch (binned) or the atomic form, then the prefilter, into the view's slices
+static int views_enqueue(rtr_ctx *c, int count, const float *P, int with_filter) {
+    auto &v = c->vw;
+    if (int rc = ensure_views(c, count, with_filter)) return rc;
+    const size_t npix = (size_t)c->W * c->H;
+    const bool binned = views_binned(c);
+    const bool pyr_fused = binned && with_filter && c->prm.levels == 4;
+    if (binned) {
+        rtr::Proj proj[RTR_MAX_VIEWS];
+        rtr::TileStore st[RTR_MAX_VIEWS];
+        for (int k = 0; k < count; ++k) {
+            auto &t = v.fs[k].store;
+            t.fill_shift = c->opt_fill_shift >= 0 ? c->opt_fill_shift : 1;
+            t.seq = (t.seq + 1u) & 0xFFFFFFu;
+            if (t.seq == 0u) {  // the 24-bit stamp wrapped: forget every directory entry once
+                HIP_TRY(c, hipMemsetAsync(rtr::ts_dir(t), 0, (size_t)v.fs[k].nst * rtr::kDirK * sizeof(unsigned long long), c->stream));
+                t.seq = 1u;
+            }
+            proj[k] = make_proj(P + 16 * k);
+            st[k] = t;
+        }
+        if (count == 1) {  // (one view: the single frame's lean point kernel -- the table and the view loops cost ~15 us)
+            Timed tm(c, RTR_K_MIN_DEPTH, c->stream, true);
+            rtr::launch_project_bin(c->stream, cloud_of(c), proj[0], c->W, c->H, st[0], c->opt_cull ? c->bounds : nullptr,
+                                    2 | (c->opt_lane_test ? 0 : 4) | 8 | (c->opt_chunk_test ? 0 : 16), c->opt_phases, 0,
+                                    tm.a, tm.b);
+        } else {
+            if (v.tab_pending) HIP_TRY(c, hipEventSynchronize(v.tab_copied));  // (the table's last copy has been read)
+            {
+                Timed tm(c, RTR_K_MIN_DEPTH, c->stream, true);
+                HIP_TRY(c, rtr::launch_project_bin_views(c->stream, cloud_of(c), proj, st, count, c->W, c->H, v.tab_host,
+                                                         v.tab_dev, c->opt_lane_test ? 0 : 4, c->opt_phases, tm.a, tm.b));
+            }
+            HIP_TRY(c, hipEventRecord(v.tab_copied, c->stream));
+            v.tab_pending = true;
+        }
+        if (int rc = launch_check(c, "views point kernel")) return rc;
+    }
+    for (int k = 0; k < count; ++k) {
+        uint32_t *depth = v.depth + (size_t)k * npix;
+        uint8_t *img = v.img + (size_t)k * npix * 3;
+        rtr::FilterLevels L{};
+        if (with_filter) {
+            L.levels = c->prm.levels;
+            L.lv[0] = reinterpret_cast<float *>(depth);
+            L.w[0] = c->W; L.h[0] = c->H;
+            for (int i = 1; i <= L.levels; ++i) L.lv[i] = v.lv[i], L.w[i] = L.w[i - 1] / 2, L.h[i] = L.h[i - 1] / 2;
+        }
+        if (binned) {
+            rtr::TilePyr pyr{};
+            pyr.enable = pyr_fused ? 1 : 0;
+            if (pyr.enable) {
+                pyr.L = L;
+                pyr.n_eff_rows = (uint32_t)((c->H >> 4) << 4);
+                pyr.part_min = v.part_min;
+                pyr.part_max = v.part_max;
+            }
+            v.parity[k] ^= 1;
+            // (bit 64, as for the single frame: the first batch of entries before the counters when the tiles are expected
+            // full -- by the entry count of the last view whose statistics are complete)
+            int lean_bits = 8 | (c->opt_lean_identity ? 32 : 0);
+            const uint64_t e_last = __atomic_load_n(v.entries_host, __ATOMIC_RELAXED);
+            if (c->opt_lean_early > 0 || (c->opt_lean_early < 0 && e_last >= 1024ull * (uint64_t)rtr::tile_count(c->W, c->H)))
+                lean_bits |= 64;
+            Timed t(c, RTR_K_TILE);
+            rtr::launch_tile(c->stream, 0, c->W, c->H, v.fs[k].store, c->prm.depth_window, depth, v.acc, img,
+                             lean_bits | (v.parity[k] << 4), pyr.enable ? &pyr : nullptr);
+        } else {
+            const rtr::Proj pk = make_proj(P + 16 * k);
+            { Timed t(c, RTR_K_CLEAR); rtr::launch_clear(c->stream, depth, v.acc, npix); }
+            { Timed t(c, RTR_K_MIN_DEPTH); rtr::launch_min_depth(c->stream, cloud_of(c), pk, c->W, c->H, depth); }
+            { Timed t(c, RTR_K_ACCUMULATE); rtr::launch_accumulate(c->stream, cloud_of(c), pk, c->W, c->H, depth, v.acc, c->prm.depth_window); }
+            { Timed t(c, RTR_K_RESOLVE); rtr::launch_resolve(c->stream, v.acc, img, npix); }
+        }
+        if (with_filter) {
+            Timed t(c, RTR_K_FILTER);
+            rtr::launch_filter(c->stream, L, depth, img, v.mask, v.tensor + (size_t)k * npix * 5, v.minmax + 2 * k,
+                               v.part_min, v.part_max, c->W, c->H, c->prm.filter_strength, c->prm.gradient_threshold,
+                               pyr_fused ? rtr::tile_count(c->W, c->H) : 0);
+        }
+        if (int rc = launch_check(c, "views frame")) return rc;
+    }
+    return RTR_OK;
+}
+
+// after a synchronisation: the views' tile-store errors.  again (out, may be null): the last batch overflowed the
+// adaptive pools, which are worst-case sized from now on -- render it again
+static int views_check(rtr_ctx *c, bool *again) {
+    if (again) *again = false;
+    auto &v = c->vw;
+    if (!v.err_host) return RTR_OK;
+    const uint32_t e = __atomic_exchange_n(v.err_host, 0u, __ATOMIC_ACQUIRE);
+    if (e == 0u) return RTR_OK;
+    if (e == 2u && c->opt_debug_dyn_cap < 0 && !v.pool_worst && v.valid && again) {
+        v.pool_worst = true;
+        *again = true;
+        return RTR_OK;
+    }
+    v.valid = false;
+    return fail(c, RTR_ERR_INTERNAL, "tile store error 0x%x in a batch of views -- entries were dropped, the views are "
+                "incomplete: render the batch again", e);
+}
+
+static int views_download(rtr_ctx *c, const void *p, void *host, size_t b) {
+    HIP_TRY(c, sync_streams(c));
+    bool again = false;
+    int rc = views_check(c, &again);
+    if (!rc && again) {
+        if ((rc = views_enqueue(c, c->vw.count, c->vw.P, c->vw.with_filter))) return rc;
+        HIP_TRY(c, sync_streams(c));
+        if ((rc = views_check(c, nullptr))) return rc;
+    }
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(host, p, b, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, sync_streams(c));
+    return RTR_OK;
+}
+
+int rtr_render_views(rtr_ctx *c, int count, const float *P, int with_filter) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, count >= 1 && count <= RTR_MAX_VIEWS, "count must be in 1..RTR_MAX_VIEWS");
+    NEED(c, P != nullptr, "P is NULL");
+    NEED(c, c->cap > 0, "no cloud has been uploaded");
+    NEED(c, c->W > 0 && c->H > 0, "rtr_set_resolution has not been called");
+    NEED(c, (c->n + 255) / 256 < (1ull << 24), "rtr_render_views: more than 2^32 - 256 points");
+    DevGuard g(c->device);
+    if (with_filter) {  // the prefilter's conditions (ensure_pyramid), before anything changes
+        const int L = c->prm.levels;
+        if (L < 1 || L > 8) return fail(c, RTR_ERR_UNSUPPORTED, "levels must be in 1..8");
+        if ((c->W % (1 << L)) != 0 || (c->H >> L) < 1)
+            return fail(c, RTR_ERR_UNSUPPORTED, "prefilter needs W %% 2^levels == 0 and H >= 2^levels (got %dx%d, levels %d)",
+                        c->W, c->H, L);
+    }
+    auto &v = c->vw;
+    v.valid = false;
+    if (int rc = views_enqueue(c, count, P, with_filter)) return rc;
+    memcpy(v.P, P, sizeof(float) * 16 * (size_t)count);
+    v.count = count;
+    v.with_filter = with_filter;
+    v.valid = true;
+    return RTR_OK;
+}
+
 // ---- buffers -----------------------------------------------------------------------
 
 int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
     if (!c) return RTR_ERR_INVALID;
     NEED(c, ptr != nullptr, "dev_ptr is NULL");
-    if (which != RTR_BUF_MINMAX)
+    if (which != RTR_BUF_MINMAX && which != RTR_BUF_VIEW_MINMAX)
         if (int rc = check_frame(c)) return rc;
     size_t npix = (size_t)c->W * c->H, b = 0;
     void *p = nullptr;
@@ -2015,6 +2326,15 @@ int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
         case RTR_BUF_VISIBLE:
             NEED(c, c->pp_vis != nullptr && c->pp_vis_current, "RTR_BUF_VISIBLE: no rtr_point_pass with RTR_POINTS_VISIBLE for the resident cloud yet");
             p = c->pp_vis; b = (size_t)((c->n + 31) / 32) * 4; break;
+        case RTR_BUF_VIEW_DEPTH: case RTR_BUF_VIEW_IMAGE: case RTR_BUF_VIEW_TENSOR: case RTR_BUF_VIEW_MINMAX: {
+            NEED(c, c->vw.valid, "RTR_BUF_VIEW_*: no rtr_render_views at this resolution for the resident cloud yet");
+            const size_t k = (size_t)c->vw.count;
+            if (which == RTR_BUF_VIEW_DEPTH) p = c->vw.depth, b = k * npix * 4;
+            else if (which == RTR_BUF_VIEW_IMAGE) p = c->vw.img, b = k * npix * 3;
+            else if (which == RTR_BUF_VIEW_TENSOR) p = c->vw.tensor, b = k * npix * 10;
+            else p = c->vw.minmax, b = k * 8;
+            break;
+        }
         default: return fail(c, RTR_ERR_INVALID, "unknown buffer id %d", which);
     }
     *ptr = p;
@@ -2030,6 +2350,7 @@ int rtr_download_buffer(rtr_ctx *c, int which, void *host, size_t bytes) {
     if (rc) return rc;
     NEED(c, bytes == b, "size mismatch");
     DevGuard g(c->device);
+    if (which >= RTR_BUF_VIEW_DEPTH && which <= RTR_BUF_VIEW_MINMAX) return views_download(c, p, host, b);
     HIP_TRY(c, hipMemcpyAsync(host, p, b, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, sync_streams(c));
     bool retry = false;

@@ -250,6 +250,15 @@ int storage_tile_count(int W, int H);  // 32x16 storage tiles
 void launch_project_bin(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, const TileStore &S,
                         const float *bounds, int clear_split, int phases, int xp = 0, hipEvent_t ev_start = nullptr,
                         hipEvent_t ev_stop = nullptr);  // ev_*: time stamps taken by the dispatch itself (timing on)
+// rtr_render_views: ONE point-kernel launch serves `count` (<= kMaxViews) poses -- view v's in-frustum points go to the tile
+// store S[v], each of them a LEAN frame (see ts_off_order) for launch_tile.  tab_host: view_tab_bytes() of host memory
+// (pinned: it is copied to tab_dev, the same size of device memory, on the stream, and must not change before the copy
+// is done); flags bit 2: no lane test (option "lane_test" = 0)
+constexpr int kMaxViews = 8;
+size_t view_tab_bytes();
+hipError_t launch_project_bin_views(hipStream_t s, const Cloud &c, const Proj *P, const TileStore *S, int count, int W, int H,
+                              void *tab_host, void *tab_dev, int flags, int phases, hipEvent_t ev_start = nullptr,
+                              hipEvent_t ev_stop = nullptr);
 void launch_chunk_bounds(hipStream_t s, const Cloud &c, float *bounds, float *spread);  // 6 floats (+ 1) per 256 points
 // packing (see PackedXyz): pack_measure fills hdr[2 nchunks] (bases, widths, block offsets by an exclusive
 // scan) and *total_planes (device; in 32-byte units); pack_write fills the blocks; pack_verify counts the points whose decoded

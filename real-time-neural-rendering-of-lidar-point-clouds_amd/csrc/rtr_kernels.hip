@@ -1034,17 +1034,39 @@ static LaneTest lane_test_consts(const Proj &P, int W, int H, const float absmax
     return t;
 }
 
+// SEVERAL VIEWS (MV, rtr_render_views).  One launch streams the cloud once for up to kMaxViews poses: the pose-free work
+// -- the header stream, the decode of the bit-packed coordinates, the colour loads -- is done once per chunk, the pose
+// work per view that keeps the chunk.  The poses, their lane-test constants and their tile stores are a table in device
+// memory (ViewTab: ~1.6 KB, neither kernel arguments nor scalar registers could hold eight of each); `bounds` carries
+// its address.  A view's matrix is loaded into the vector registers `mv` and its store into `S` where the view is
+// served.  Packed clouds: every header is tested against each view's five half-spaces (the chunk test, whatever option
+// "chunk_test" says: it is conservative); a chunk survives if some view keeps it, and the views that keep it travel in
+// the top byte of its slot's chunk word (chunks < 2^24).  The lane test then runs per surviving view on the one decoded
+// point per lane, the B streams are decoded once, and each remaining view projects and appends the chunk.  fp32 SoA
+// clouds: each quad is loaded once and goes through the lane test and the append of every view.  Batches are always
+// LEAN frames (no epilogue; see ts_off_order): the tile launch of each view reads its stream counters itself.
+struct ViewTab {
+    Proj P[kMaxViews];
+    LaneTest lt[kMaxViews];
+    TileStore S[kMaxViews];
+    const float *spread;  // lane spreads of an unpacked cloud (or null)
+    int count;
+};
+
 // CTEST (packed, !CULL only): the chunk test of option "chunk_test" -- its own instance, so that the round-4 loop
 // (chunk_test = 0) keeps its own register allocation
-template <bool CULL, bool GROUPS, bool PACKED, bool CTEST = false>
-__global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void k_project_bin(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
+template <bool CULL, bool GROUPS, bool PACKED, bool CTEST = false, bool MV = false>
+// (MV: four waves per SIMD -- at five the view loops spilled 96 bytes per lane to scratch, whose reloads drain the ring)
+__global__ __launch_bounds__(kBlock, (PACKED && !CULL && !MV) ? RTR_T1_WAVES : 4) void k_project_bin(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
                                                         const float4 *__restrict__ z4,
                                                         const uint4 *__restrict__ rgba4, uint32_t n4, Proj P, int W,
                                                         int H, TileStore S, const float *__restrict__ bounds,
                                                         int clear_split, uint32_t cblock, int xp, LaneTest lt) {
     (void)xp;
-    // (!CULL: `bounds` carries the chunks' lane spreads of an unpacked cloud, or null; the packed form has them in its headers)
-    const float *const spread = CULL ? nullptr : bounds;
+    // (!CULL: `bounds` carries the chunks' lane spreads of an unpacked cloud, or null; the packed form has them in its headers;
+    // MV: the view table, which holds them)
+    const ViewTab *const vt = MV ? reinterpret_cast<const ViewTab *>(bounds) : nullptr;
+    const float *const spread = CULL ? nullptr : (MV ? vt->spread : bounds);
     const bool lane_test = (clear_split & 4) == 0;
     const uint4 *const pk_hdr = reinterpret_cast<const uint4 *>(x4);
     const uint32_t *const pk_planes = reinterpret_cast<const uint32_t *>(y4);    // the A streams
@@ -1053,7 +1075,7 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
     const float hiW = f_add(fW, 0.25f), hiH = f_add(fH, 0.25f);
     const int lane = threadIdx.x & 63;
     const uint32_t stx = (uint32_t)(W + 31) >> 5;  // storage tiles per row (tile_geom)
-    uint32_t *const fill = ts_fill(S);
+    uint32_t *fill = ts_fill(S);  // (MV: the served view's)
     // (a context holds < 2^32 points: quad and chunk indices are 32-bit, which keeps scalar registers free)
     // Chunk order: a chunk is 256 consecutive points (one quad per lane); round r of the grid stride
     // is the window of NW consecutive chunks r NW .. r NW + NW - 1, chunk r NW + w going to wave w.
@@ -1122,6 +1144,23 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
     // scratch, and its reload's vmcnt(0) drained the ring on every chunk)
     float nzfront = -lt.zfront;
     if constexpr (!PACKED) asm volatile("" : "+v"(nzfront));
+    // MV: serve view v (wave-uniform) from here on -- its matrix, lane-test constants and tile store
+    auto use_view = [&](uint32_t v) {
+        if constexpr (MV) {
+            S = vt->S[v];
+            fill = ts_fill(S);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) {
+                mv[k] = vt->P[v].m[k];
+                asm volatile("" : "+v"(mv[k]));
+            }
+            lt = vt->lt[v];
+            nzfront = -lt.zfront;
+            if constexpr (!PACKED) asm volatile("" : "+v"(nzfront));
+        } else {
+            (void)v;
+        }
+    };
 #define RTR_M(k) mv[k]
     auto project_rows = [&](const float4 &X, const float4 &Y, const float4 &Z, Rows &r) {
         const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
@@ -1391,7 +1430,8 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
         typedef u32x4_l __attribute__((address_space(3))) lds_u32x4;
         // one chunk out of its slot: the lane test on its A streams, then (a candidate) the long path.  g0 / g1: its header
         // words, c: its chunk (< nchunks)
-        auto chunk_body = [&](const lds_u32 *slot, const u32x4_l &g0, const u32x4_l &g1, uint32_t c) {
+        // (MV: vmask = the views that kept the chunk's header box)
+        auto chunk_body = [&](const lds_u32 *slot, const u32x4_l &g0, const u32x4_l &g1, uint32_t c, uint32_t vmask) {
             const uint32_t ww = (uint32_t)__builtin_amdgcn_readfirstlane((int)g0.w);
             const uint32_t bx = g0.x, by = g0.y, bz = g0.z;  // (vector registers: they are only ever OR-ed into values)
             const uint32_t wx = ww & 63u, wy = (ww >> 6) & 63u, wz = (ww >> 12) & 63u;
@@ -1429,7 +1469,18 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
                 const float x0 = value0(raw.a[0].d[0], raw.a[0].d[1], px, wx, bx);
                 const float y0 = value0(raw.a[1].d[0], raw.a[1].d[1], py, wy, by);
                 const float z0 = value0(raw.a[2].d[0], raw.a[2].d[1], pz, wz, bz);
-                cand = lane_maybe(x0, y0, z0, __uint_as_float(sp_c), true);
+                if constexpr (MV) {
+                    uint32_t kept = 0u;
+                    for (uint32_t m = vmask; m; m &= m - 1u) {
+                        const uint32_t v = (uint32_t)__builtin_ctz(m);
+                        use_view(v);
+                        if (lane_maybe(x0, y0, z0, __uint_as_float(sp_c), true)) kept |= 1u << v;
+                    }
+                    vmask = kept;
+                    cand = kept != 0u;
+                } else {
+                    cand = lane_maybe(x0, y0, z0, __uint_as_float(sp_c), true);
+                }
             }
             if (!cand) return;
             uint32_t i_c = c * 64u + (uint32_t)lane;
@@ -1456,7 +1507,15 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
                     for (int a = 0; a < 3; ++a) asm volatile("" : "+v"(raw_b.a[a].d[0]), "+v"(raw_b.a[a].d[1]), "+v"(raw_b.a[a].d[2]), "+v"(raw_b.a[a].d[3]));
                 }
                 unpack_chunk(raw, raw_b, ww, sbx, sby, sbz, X, Y, Z, lane);
-                project_rows(X, Y, Z, r);
+                if constexpr (!MV) project_rows(X, Y, Z, r);
+            }
+            if constexpr (MV) {  // the decoded chunk, once per view that is left
+                for (uint32_t m = vmask; m; m &= m - 1u) {
+                    use_view((uint32_t)__builtin_ctz(m));
+                    project_rows(X, Y, Z, r);
+                    do_quad(i_c, live_c, r);
+                }
+                return;
             }
 #ifdef RTR_EXPERIMENT
             if (RTR_XP(256)) {  // ... + decode + the three matrix rows
@@ -1492,7 +1551,20 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
                 const uint32_t c = chunk_of(qb + (uint32_t)lane);
                 bool keep = c < nchunks;
                 float lo[3], hi[3];
-                if (keep && chunk_box(cur0.x, cur0.y, cur0.z, cur0.w, lo, hi)) {
+                uint32_t vm = MV ? (1u << vt->count) - 1u : 0u;  // (MV: the views that keep the chunk; no box: all of them)
+                if (MV && keep && chunk_box(cur0.x, cur0.y, cur0.z, cur0.w, lo, hi)) {
+                    vm = 0u;
+                    for (int v = 0; v < vt->count; ++v) {
+                        float m[12];
+#pragma unroll
+                        for (int k = 0; k < 12; ++k) {
+                            m[k] = vt->P[v].m[k];
+                            asm volatile("" : "+v"(m[k]));
+                        }
+                        if (!box_outside(frustum_planes(m, fW, fH), lo, hi)) vm |= 1u << v;
+                    }
+                    keep = vm != 0u;
+                } else if (!MV && keep && chunk_box(cur0.x, cur0.y, cur0.z, cur0.w, lo, hi)) {
                     // (the planes from the matrix in vector registers, once per batch: the barrier keeps the compiler
                     // from holding forty of them through the loop)
                     float m[12];
@@ -1503,7 +1575,7 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
                     }
                     keep = !box_outside(frustum_planes(m, fW, fH), lo, hi);
                 }
-                cur1.w = c;
+                cur1.w = MV ? (c | vm << 24) : c;
                 // (every header word is consumed HERE, where the batch is tested: a word whose load is still pending when
                 // the survivor's header is written would make the compiler wait for it there -- with a vmcnt(0), which
                 // drains the ring's requests on every survivor)
@@ -1543,9 +1615,9 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
                 const lds_u32 *const hs = (const lds_u32 *)(uintptr_t)(rhdr_lds + 32u * (k & (uint32_t)kRing));
                 const u32x4_l g0 = *reinterpret_cast<const lds_u32x4 *>(hs);
                 const u32x4_l g1 = *reinterpret_cast<const lds_u32x4 *>(hs + 4);
-                const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)g1.w);
-                if (c >= nchunks) break;  // (wave-uniform) past the wave's last survivor
-                chunk_body(slot, g0, g1, c);
+                const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)g1.w);
+                if (MV ? cw == ~0u : cw >= nchunks) break;  // (wave-uniform) past the wave's last survivor
+                chunk_body(slot, g0, g1, MV ? (cw & 0xFFFFFFu) : cw, cw >> 24);
             }
         } else {
             // (option chunk_test = 0: every chunk of the wave through the ring, the loop of round 4)
@@ -1576,7 +1648,7 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
                 const uint32_t c = c_use;
                 c_use = next_chunk(c_use);
                 if (c >= nchunks) continue;  // (wave-uniform) past the wave's last chunk
-                chunk_body(slot, g0, g1, c);
+                chunk_body(slot, g0, g1, c, 0u);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the requests past the wave's last chunk: into LDS, before it is left)
@@ -1607,6 +1679,25 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
             }
         };
         fetch(0);
+        if constexpr (MV) {
+            for (uint32_t q = 0; q < R; ++q) {
+                Rows r;
+                const bool have_c = have, live_c = live;
+                const uint32_t i_c = i < n4 ? i : n4 - 1u;
+                const float4 Xc = X, Yc = Y, Zc = Z;  // (the quad is served to every view; the next one is on its way)
+                const uint32_t spc = spb;
+                fetch(q + 1);
+                if (!have_c) continue;
+                for (int v = 0; v < vt->count; ++v) {
+                    use_view((uint32_t)v);
+                    bool cand = true;
+                    if (lane_test && spread && spc < 0x7F000000u) cand = lane_maybe(Xc.x, Yc.x, Zc.x, __uint_as_float(spc), live_c);
+                    if (!cand) continue;
+                    project_rows(Xc, Yc, Zc, r);
+                    do_quad(i_c, live_c, r);
+                }
+            }
+        } else
         for (uint32_t q = 0; q < R; ++q) {
             Rows r;
             const bool have_c = have, live_c = live;
@@ -1674,10 +1765,11 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL) ? RTR_T1_WAVES : 4) void 
         }
     }
 #endif
-    if (clear_split & 8) {
+    if (MV || (clear_split & 8)) {
         // a LEAN frame (lean_frame_end): no ticket, no epilogue -- the tile kernel's workgroups read the stream counters
-        // themselves.  Only the colour-chunk statistic leaves, one fire-and-forget add per wave that has any.
-        if (lane == 0 && n_colour) atomicAdd(ts_sub_colour(S, wave & (uint32_t)(kSubTickets - 1)), (unsigned long long)n_colour);
+        // themselves.  Only the colour-chunk statistic leaves, one fire-and-forget add per wave that has any (not for a
+        // batch of views: its chunks are not one frame's).
+        if (!MV && lane == 0 && n_colour) atomicAdd(ts_sub_colour(S, wave & (uint32_t)(kSubTickets - 1)), (unsigned long long)n_colour);
         return;
     }
     // every claim of this workgroup has returned (its value was used); the workgroup that takes the
@@ -2696,6 +2788,61 @@ void launch_project_bin(hipStream_t s, const Cloud &c, const Proj &P, int W, int
         if (packed && ctest) RTR_T1(false, true, true, true); else if (packed) RTR_T1(false, true, true, false); else RTR_T1(false, true, false, false);
     }
 #undef RTR_T1
+}
+
+size_t view_tab_bytes() { return sizeof(ViewTab); }
+
+hipError_t launch_project_bin_views(hipStream_t s, const Cloud &c, const Proj *P, const TileStore *S, int count, int W, int H,
+                              void *tab_host, void *tab_dev, int flags, int phases, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    if (count < 1 || count > kMaxViews) return hipErrorInvalidValue;
+    uint64_t n4 = (c.n + 3) / 4;
+    if (n4 == 0) return hipSuccess;  // (lean frames: the stream counters are zero and stay so)
+    ViewTab &t = *static_cast<ViewTab *>(tab_host);
+    t = ViewTab{};
+    for (int v = 0; v < count; ++v) {
+        t.P[v] = P[v];
+        t.lt[v] = lane_test_consts(P[v], W, H, c.absmax);
+        t.S[v] = S[v];
+    }
+    const bool packed = c.pk.hdr != nullptr;
+    t.spread = packed ? nullptr : c.spread;
+    t.count = count;
+    if (hipError_t e = hipMemcpyAsync(tab_dev, &t, sizeof t, hipMemcpyHostToDevice, s)) return e;
+    const float4 *x = packed ? (const float4 *)c.pk.hdr : (const float4 *)c.x;
+    const float4 *y = packed ? (const float4 *)c.pk.planes : (const float4 *)c.y;
+    const float4 *z = packed ? (const float4 *)c.pk.planes_b : (const float4 *)c.z;
+    const uint4 *col = (const uint4 *)c.rgba;
+    const int clear_split = 8 | 2 | (flags & 4);  // lean, never split; bit 2: no lane test
+    const float *tab = static_cast<const float *>(tab_dev);
+    // (the grid: what is resident at once, as for the single view -- asked of the runtime once per kernel and device)
+    int dev_now = 0;
+    if (hipGetDevice(&dev_now) != hipSuccess || dev_now < 0 || dev_now >= kGridCacheDevices) dev_now = kGridCacheDevices;
+#define RTR_T1V(GROUPS, PACKED)                                                                                              \
+    do {                                                                                                                     \
+        static int cached_grid[kGridCacheDevices] = {0};                                                                     \
+        auto kernel = k_project_bin<false, GROUPS, PACKED, PACKED, true>;                                                    \
+        int g = dev_now < kGridCacheDevices ? __atomic_load_n(&cached_grid[dev_now], __ATOMIC_RELAXED) : 0;                  \
+        if (g == 0) {                                                                                                        \
+            int per_cu = 0, cus = 0;                                                                                         \
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0) != hipSuccess ||                    \
+                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_now < kGridCacheDevices ? dev_now : 0) != hipSuccess || \
+                per_cu < 1 || cus < 1)                                                                                       \
+                g = kDefaultPointGrid;                                                                                       \
+            else                                                                                                             \
+                g = cus * (per_cu < 4 ? per_cu : (PACKED && per_cu >= 5 ? 5 : 4));                                           \
+            if (dev_now < kGridCacheDevices) __atomic_store_n(&cached_grid[dev_now], g, __ATOMIC_RELAXED);                   \
+        }                                                                                                                    \
+        const dim3 grid(point_grid(n4, c.grid == kDefaultPointGrid ? g : c.grid));                                           \
+        hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, ev_start, ev_stop, 0, x, y, z, col, (uint32_t)n4, P[0], W, H, \
+                              S[0], tab, clear_split, (uint32_t)phases, 0, t.lt[0]);                                         \
+    } while (0)
+    if (c.incoherent) {
+        if (packed) RTR_T1V(false, true); else RTR_T1V(false, false);
+    } else {
+        if (packed) RTR_T1V(true, true); else RTR_T1V(true, false);
+    }
+#undef RTR_T1V
+    return hipGetLastError();
 }
 
 // bounding box of every 256-point chunk (the unit one wave of T1 handles per iteration):

@@ -176,6 +176,16 @@ class Projector:
         P = self._P(P)
         self._chk(self._lib.rtr_render(self._ctx, _vp(P), 1 if with_filter else 0))
 
+    # -- several views (rtr.h section 6c)
+    def render_views(self, Ps, with_filter=False):
+        """Renders K <= MAX_VIEWS poses (Ps: [K,4,4] or [K,16]) in one pass over the cloud into the BUF_VIEW_*
+        buffers ([K, ...] shapes); view v equals render(Ps[v], with_filter).  Asynchronous like render."""
+        Ps = np.ascontiguousarray(Ps, dtype=np.float32)
+        if Ps.ndim not in (2, 3) or Ps.reshape(Ps.shape[0], -1).shape[1] != 16:
+            raise ValueError("Ps must have shape [K,4,4] or [K,16]")
+        Ps = Ps.reshape(-1, 16)
+        self._chk(self._lib.rtr_render_views(self._ctx, Ps.shape[0], _vp(Ps), 1 if with_filter else 0))
+
     # -- point pass (rtr.h section 6b)
     def point_pass(self, P, ids=True, visible=True):
         """Per-pixel point IDs (BUF_POINT_ID: upload index, NO_POINT for none) and / or the per-point visibility
@@ -214,11 +224,20 @@ class Projector:
             L.BUF_MASK: (np.uint8, "|u1", lambda w, h: (h, w)),
             L.BUF_MINMAX: (np.uint32, "<u4", lambda w, h: (2,)),
             L.BUF_POINT_ID: (np.uint32, "<u4", lambda w, h: (h, w)),
-            L.BUF_VISIBLE: (np.uint32, "<u4", lambda w, h, n: ((n + 31) // 32,))}  # (by the point count, not W / H)
+            L.BUF_VISIBLE: (np.uint32, "<u4", lambda w, h, n: ((n + 31) // 32,)),  # (by the point count, not W / H)
+            # (the last batch of views: by its count K)
+            L.BUF_VIEW_DEPTH: (np.uint32, "<u4", lambda w, h, k: (k, h, w)),
+            L.BUF_VIEW_IMAGE: (np.uint8, "|u1", lambda w, h, k: (k, h, w, 3)),
+            L.BUF_VIEW_TENSOR: (np.uint16, "<f2", lambda w, h, k: (k, 5, h, w)),
+            L.BUF_VIEW_MINMAX: (np.uint32, "<u4", lambda w, h, k: (k, 2))}
 
     def _shape(self, which):
         shp = self._BUF[which][2]
-        return shp(self.W, self.H, self.num_points) if which == L.BUF_VISIBLE else shp(self.W, self.H)
+        if which == L.BUF_VISIBLE:
+            return shp(self.W, self.H, self.num_points)
+        if L.BUF_VIEW_DEPTH <= which <= L.BUF_VIEW_MINMAX:
+            return shp(self.W, self.H, self.get_option("views"))
+        return shp(self.W, self.H)
 
     def device_buffer(self, which, typestr=None):
         ptr, nbytes = C.c_void_p(), C.c_size_t()
@@ -396,6 +415,46 @@ class ProjectCloud:
                 color[...] = img.cpu().numpy()
             if depth is not None:
                 depth[...] = self._p.download(L.BUF_DEPTH).view(np.float32)  # :485
+        return 1
+
+    def computeFullViews(self, calibration, extrinsics_list, colors, depths):
+        """computeFull for K = len(extrinsics_list) <= MAX_VIEWS poses at once: one pass over the cloud, the model run
+        ONCE on the [K,5,H,W] fp16 batch tensor (zero copy).  colors[v] / depths[v] (any may be None) receive view v's
+        colour and prefiltered depth, as computeFull would for extrinsics_list[v].  Returns 1."""
+        import torch
+        if self.model is None:
+            raise L.RtrError(L.RTR_ERR_INVALID, "No model: computeFullViews needs modelFilename or set_model()")
+        K = len(extrinsics_list)
+        if len(colors) != K or len(depths) != K:
+            raise ValueError("colors and depths need one entry (or None) per extrinsics matrix")
+        W, H = calibration.getWidth(), calibration.getHeight()
+        for v in range(K):
+            for name, arr, shape, dt in (("color", colors[v], (H, W, 3), np.uint8), ("depth", depths[v], (H, W), np.float32)):
+                if arr is not None and (arr.dtype != dt or arr.shape != shape or not arr.flags.c_contiguous):
+                    raise ValueError("%s[%d] must be a C-contiguous %s array of shape %s" % (name, v, dt, shape))
+        dev = torch.device("cuda", self._device)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if self._bound_stream != stream:
+                self._p.set_stream(stream)
+                self._bound_stream = stream
+            self._p.set_resolution(W, H)
+            Kc = calibration.getIntrinsicsMatrix()
+            Ps = np.stack([compose_projection(Kc, E) for E in extrinsics_list])
+            self._p.render_views(Ps, True)
+            # (a batch that overflowed the adaptive extent pools is rendered again here, before the model reads it)
+            self._p.synchronize()
+            inp = torch.as_tensor(self._p.device_buffer(L.BUF_VIEW_TENSOR), device=dev)  # zero copy, [K,5,H,W]
+            with torch.no_grad():
+                out = self.model(inp)
+            need_depth = any(d is not None for d in depths)
+            dall = self._p.download(L.BUF_VIEW_DEPTH).view(np.float32) if need_depth else None
+            for v in range(K):
+                if colors[v] is not None:
+                    o = out[v].permute(1, 2, 0).contiguous()
+                    colors[v][...] = (o.float() * 255.0).round().clamp(0, 255).to(torch.uint8).cpu().numpy()
+                if depths[v] is not None:
+                    depths[v][...] = dall[v]
         return 1
 
     def _point_pass(self, calibration, extrinsics, filtered, ids, visible):
