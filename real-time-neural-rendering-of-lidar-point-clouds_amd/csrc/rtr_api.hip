@@ -37,12 +37,6 @@ struct rtr_ctx {
     int opt_chunk_test = 1;     // T1 tests packed chunks on their header boxes first (option "chunk_test")
     int opt_keep_soa = 0;       // 1: the fp32 SoA arrays stay resident beside the packed form (option "keep_soa")
     int opt_pool_worst = 0;     // 1: the extent pool is always sized for the worst case, 2 n entries (option "pool_worst_case")
-    bool pool_worst = false;    // ... for this cloud: a frame overflowed the adaptive pool, or the peers map it
-    uint32_t *entries_host = nullptr, *entries_dev = nullptr;  // mapped host word: entries of the last frame whose statistics are complete
-    uint64_t entries_max = 0;   // the most entries a completed frame of this cloud has had
-    float last_P[16] = {0};     // the last whole frame (rtr_render): what a synchronising call repeats when it learns that
-    int last_filter = 0;        // the adaptive extent pool was too small for it
-    bool last_valid = false;
     int opt_lean = 1;           // whole single-GPU frames without split tiles end T1 without its epilogue (option "lean")
     int opt_lean_identity = 1;  // lean frames: tile workgroup b takes tile b when the whole launch is resident (option "lean_identity")
     int opt_lean_early = -1;    // lean frames: first batch of entries requested before the stream counters are known: 0 never,
@@ -55,18 +49,9 @@ struct rtr_ctx {
     uint64_t pk_bytes = 0;          // headers + planes
     int opt_pack = 1;               // 0 never, 1 when it saves >= 1/8 of the coordinate stream, 2 always + verified after packing
 
-    // frame buffers
-    int W = 0, H = 0;
-    uint32_t *depth = nullptr, *acc = nullptr, *minmax = nullptr;
-    uint8_t *img = nullptr, *mask = nullptr;
-    uint32_t *part_min = nullptr, *part_max = nullptr;  // per-tile min / max partials of the prefilter
-    uint16_t *tensor = nullptr;
-    rtr::FilterLevels lv{};
-    int lv_levels = 0;  // levels the pyramid was allocated for
+    int W = 0, H = 0;  // resolution
 
     // tile-binned pipeline: the tile store T1 appends to and T4 reads (rtr_kernels.h)
-    // (two sets: with option "overlap" T1 of frame k+1 fills one set on the front stream while the
-    // tail of frame k still reads the other)
     struct FrontSet {
         rtr::TileStore store{};
         uint64_t pool_n = 0;        // point count the dynamic extent pool was sized for
@@ -76,9 +61,31 @@ struct rtr_ctx {
         uint64_t dyn_cap = 0;
         hipEvent_t binned = nullptr, consumed = nullptr;  // T1 done (front stream) / T4 done (tail stream)
         bool consumed_valid = false;
-    } fs[2];
-    int cur = 0;
-    FrontSet &F() { return fs[cur]; }
+        int parity = 0;             // lean-frame parity of a view's store (the single frame keeps lean_parity)
+    };
+
+    // What a set of frames renders into: the single frame (rtr_render, the phase calls; with option "overlap" T1 of
+    // frame k+1 fills its second set on the front stream while the tail of frame k still reads the other) or a batch
+    // of views (rtr_render_views, one set per view).  depth / img / tensor hold `cap` frames (alloc_target); the
+    // accumulators, prefilter mask, min / max partials and pyramid levels are scratch that the frames take in turn.
+    // Stores are allocated per resolution and pools per cloud by the frames that use them; the minmax words and the
+    // mapped words live as long as the context.
+    struct Target {
+        int cap = 0;
+        uint32_t *depth = nullptr, *acc = nullptr, *part_min = nullptr, *part_max = nullptr;
+        uint8_t *img = nullptr, *mask = nullptr;
+        uint16_t *tensor = nullptr;
+        uint32_t *minmax = nullptr;  // 2 words per frame, RTR_MAX_VIEWS frames
+        float *lv[9] = {nullptr};    // pyramid levels 1..lv_levels (level 0 is a frame's depth)
+        int lv_levels = 0;
+        FrontSet fs[RTR_MAX_VIEWS];
+        int cur = 0;                 // the set of the last frame (the single frame alternates with option "overlap")
+        uint32_t *err_host = nullptr, *err_dev = nullptr;  // mapped word: tile-store error bits of frames since it was last read
+        uint32_t *entries_host = nullptr, *entries_dev = nullptr;  // mapped word: entries of the last frame whose statistics are complete
+        uint64_t entries_max = 0;    // the most entries a completed frame of this cloud has had
+        bool pool_worst = false;     // the pools are worst-case sized for this cloud: a frame overflowed them, or the peers map them
+    } frame, views;
+    FrontSet &F() { return frame.fs[frame.cur]; }
     int opt_overlap = 0;        // whole-frame renders run T1 on `front`, everything else on `stream`
     int opt_tail_cus = 0;       // CUs per XCD reserved for the tail stream when overlapping (0 = no CU masks)
     hipStream_t front = nullptr;
@@ -94,8 +101,6 @@ struct rtr_ctx {
     int opt_p2p_timeout_ms = 2000;   // peer-to-peer flag barriers give up after this long (option "p2p_timeout_ms")
     int opt_fill_shift = -1;         // spacing of the stream counters, 4 << value bytes; -1: by the frames seen (see "fill_shift")
     int opt_debug_dyn_cap = -1;      // test aid: cap the dynamic extent pool at this many entries (-1: off)
-    uint32_t *err_host = nullptr;    // mapped host word: tile-store error bits of frames since it was last read
-    uint32_t *err_dev = nullptr;     // ... as the device sees it (StoreConsts::err_host)
     // whole frames launch k_tile_split (an empty launch costs ~5 us) only while tiles above the split threshold have
     // been seen: T1's epilogue stores their number here (mapped host word, read without a sync -- it describes the
     // last frame whose T1 has COMPLETED, the host may be frames ahead), and the launch stays on for kSplitCooldown
@@ -118,13 +123,6 @@ struct rtr_ctx {
     uint32_t *pp_ids = nullptr, *pp_vis = nullptr;
     uint64_t pp_vis_words = 0;
     bool pp_vis_current = false;  // the mask was computed for the resident cloud
-    // a point pass read the frame that a synchronising call may have to render again (the adaptive extent pool
-    // overflowed): queued right after that frame -> repeated with it; otherwise its outputs are marked incomplete
-    bool pp_after_last = false;   // queued after the last whole frame (rtr_render), nothing rendered since
-    bool pp_since_sync = false;   // queued, and not yet known to have read a complete frame
-    bool pp_invalid = false;      // its outputs came from a frame the tile store reported incomplete
-    float pp_P[16] = {0};
-    int pp_what = 0;
     hipEvent_t pp_done = nullptr;  // recorded behind the last point pass
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
     int opt_grid = rtr::kDefaultPointGrid;  // workgroups of the point kernels
@@ -178,39 +176,37 @@ struct rtr_ctx {
     double total_ms[RTR_K_COUNT] = {0};
     uint64_t launches[RTR_K_COUNT] = {0};
 
-    // the frame queued into each async slot, for rtr_wait to render again: `stale` = it was queued before the adaptive
-    // extent pool grew (check_store_error), so it may have lost entries; `cloud` = cloud_seq when it was queued
-    struct SlotFrame {
-        float P[16] = {0};
-        int with_filter = 0;
-        bool stale = false;
-        uint64_t cloud = 0;
-    } slot_frame[RTR_ASYNC_SLOTS];
     uint64_t cloud_seq = 0;  // +1 per upload / generation (alloc_cloud)
 
-    // several views (rtr_render_views): one tile store and extent pool per view, allocated on first use up to the largest
-    // count seen (stores per resolution, pools per cloud); frame buffers [count_cap] x the single frame's; scratch that
-    // the views of a batch take in turn (accumulators, prefilter mask, pyramid levels, min / max partials)
-    struct Views {
-        rtr_ctx::FrontSet fs[RTR_MAX_VIEWS];
-        int parity[RTR_MAX_VIEWS] = {0};  // lean-frame parity of each view's store
-        int cap = 0;                      // views the frame buffers hold
-        uint32_t *depth = nullptr, *minmax = nullptr, *acc = nullptr, *part_min = nullptr, *part_max = nullptr;
-        uint8_t *img = nullptr, *mask = nullptr;
-        uint16_t *tensor = nullptr;
-        float *lv[9] = {nullptr};
-        int lv_levels = 0;
-        void *tab_host = nullptr, *tab_dev = nullptr;  // rtr::launch_project_bin_views' table (pinned / device)
-        hipEvent_t tab_copied = nullptr;                // ... the last copy of tab_host has been read
-        bool tab_pending = false;
-        uint32_t *err_host = nullptr, *err_dev = nullptr;          // mapped words of the views' stores (StoreConsts)
-        uint32_t *entries_host = nullptr, *entries_dev = nullptr;
-        uint64_t entries_max = 0;
-        bool pool_worst = false;  // a batch overflowed the adaptive pools: worst-case sized for this cloud
-        float P[RTR_MAX_VIEWS * 16] = {0};  // the last batch, what a synchronising call repeats after an overflow
-        int count = 0, with_filter = 0;
-        bool valid = false;
-    } vw;
+    // rtr::launch_project_bin_views' table (pinned / device); `copied`: the last copy of `host` has been read
+    struct ViewTab {
+        void *host = nullptr, *dev = nullptr;
+        hipEvent_t copied = nullptr;
+        bool pending = false;
+    } vtab;
+
+    // What a synchronising call renders again when it learns that the adaptive extent pool was too small (repair)
+    struct Journal {
+        struct Frames {
+            float P[RTR_MAX_VIEWS * 16] = {0};
+            int count = 0, filter = 0;
+        };
+        Frames frame;  // the last whole frame (rtr_render): count 0 or 1
+        Frames views;  // the last batch of views (rtr_render_views); count 0: none, or it is incomplete
+        struct Pass {  // the last point pass
+            float P[16] = {0};
+            int what = 0;
+            bool behind = false;     // queued right behind the last whole frame, nothing rendered since: repeated with it
+            bool unchecked = false;  // queued, and not yet known to have read a complete frame
+            bool invalid = false;    // its outputs came from a frame the tile store reported incomplete
+        } pass;
+        struct Slot {  // the frame queued into each async slot; `stale`: queued before the pool grew (rtr_wait repeats it)
+            float P[16] = {0};
+            int filter = 0;
+            bool stale = false;
+            uint64_t cloud = 0;  // cloud_seq when it was queued
+        } slot[RTR_ASYNC_SLOTS];
+    } jr;
 };
 
 static thread_local std::string g_create_err;
@@ -295,58 +291,92 @@ void free_host_out(rtr_ctx *c) {
     }
 }
 
+hipError_t sync_streams(rtr_ctx *c);
+
+// One zeroed word of pinned host memory that the device writes through its mapping (error bits, statistics)
+hipError_t mapped_word(uint32_t **host, uint32_t **dev) {
+    hipError_t e = hipHostMalloc((void **)host, sizeof(uint32_t), hipHostMallocMapped);
+    if (e != hipSuccess) {
+        *host = nullptr;
+        return e;
+    }
+    **host = 0u;
+    void *d = nullptr;
+    e = hipHostGetDevicePointer(&d, *host, 0);
+    *dev = static_cast<uint32_t *>(d);
+    if (e != hipSuccess) {
+        (void)hipHostFree(*host);
+        *host = nullptr;
+    }
+    return e;
+}
+
+void free_target(rtr_ctx::Target &t) {  // the frame buffers and pyramid levels (the stores, pools and words stay)
+    dfree(t.depth); dfree(t.acc); dfree(t.img); dfree(t.mask); dfree(t.part_min); dfree(t.part_max); dfree(t.tensor);
+    for (auto &l : t.lv) dfree(l);
+    t.lv_levels = 0;
+    t.cap = 0;
+}
+
+// Frame buffers for `count` frames at the current resolution, all or nothing: after a failure the target holds none
+int alloc_target(rtr_ctx *c, rtr_ctx::Target &t, int count) {
+    free_target(t);
+    const size_t npix = (size_t)c->W * c->H, n = (size_t)count * npix;
+    const size_t nparts = (size_t)((c->W + 31) / 32) * ((c->H + 31) / 32);
+    hipError_t e = hipMalloc((void **)&t.depth, n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&t.img, (n * 3 + 15) & ~(size_t)15);
+    if (e == hipSuccess) e = hipMalloc((void **)&t.tensor, n * 5 * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&t.acc, npix * 16);
+    if (e == hipSuccess) e = hipMalloc((void **)&t.mask, npix);
+    if (e == hipSuccess) e = hipMalloc((void **)&t.part_min, nparts * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&t.part_max, nparts * 4);
+    if (e != hipSuccess) {
+        free_target(t);
+        return fail(c, RTR_ERR_HIP, "hipMalloc of the frame buffers (%d x %dx%d) failed: %s", count, c->W, c->H,
+                    hipGetErrorString(e));
+    }
+    t.cap = count;
+    return RTR_OK;
+}
+
 void free_frame(rtr_ctx *c) {
     c->list_valid = false;
     c->split_cooldown = kSplitCooldown;  // (a new resolution: nothing is known about its frames)
     free_host_out(c);
     p2p_release(c);
-    dfree(c->depth); dfree(c->acc); dfree(c->img); dfree(c->mask); dfree(c->part_min); dfree(c->part_max); dfree(c->tensor);
     dfree(c->pp_ids);
-    for (int i = 1; i <= 8; ++i) dfree(c->lv.lv[i]);
-    for (auto &f : c->fs) {
-        dfree(f.store.ext0); dfree(f.store.meta);
-        f.nst = f.ntiles = 0;
-        f.consts = rtr::StoreConsts{};
+    for (auto *t : {&c->frame, &c->views}) {
+        free_target(*t);
+        for (auto &f : t->fs) {
+            dfree(f.store.ext0); dfree(f.store.meta);
+            f.nst = f.ntiles = 0;
+            f.consts = rtr::StoreConsts{};
+        }
     }
-    c->lv.lv[0] = nullptr;
     c->W = c->H = 0;
-    c->lv_levels = 0;
-    auto &v = c->vw;
-    for (auto &f : v.fs) {
-        dfree(f.store.ext0); dfree(f.store.meta);
-        f.nst = f.ntiles = 0;
-        f.consts = rtr::StoreConsts{};
-    }
-    dfree(v.depth); dfree(v.minmax); dfree(v.acc); dfree(v.part_min); dfree(v.part_max); dfree(v.img); dfree(v.mask);
-    dfree(v.tensor);
-    for (int i = 1; i <= 8; ++i) dfree(v.lv[i]);
-    v.lv_levels = 0;
-    v.cap = 0;
-    v.valid = false;
+    c->jr.views.count = 0;
+}
+
+void reset_pool_sizing(rtr_ctx::Target &t) {  // a new cloud: the adaptive extent pools start over
+    t.pool_worst = false;
+    t.entries_max = 0;
+    if (t.entries_host) *t.entries_host = 0u;
 }
 
 void free_lists(rtr_ctx *c) {  // the dynamic extent pools (sized by the point count)
     if (c->p2p.open || c->p2p.red) p2p_release(c);  // (the peers map this rank's pool: they must re-open after a new cloud)
-    for (auto &f : c->fs) {
-        dfree(f.dyn);
-        f.dyn_cap = 0;
-        f.pool_n = 0;
-    }
+    for (auto *t : {&c->frame, &c->views})
+        for (auto &f : t->fs) {
+            dfree(f.dyn);
+            f.dyn_cap = 0;
+            f.pool_n = 0;
+        }
     c->list_valid = false;
     c->split_cooldown = kSplitCooldown;  // (a new cloud)
-    c->pool_worst = false;
-    c->entries_max = 0;
-    if (c->entries_host) *c->entries_host = 0u;
-    c->last_valid = false;
-    for (auto &f : c->vw.fs) {
-        dfree(f.dyn);
-        f.dyn_cap = 0;
-        f.pool_n = 0;
-    }
-    c->vw.pool_worst = false;
-    c->vw.entries_max = 0;
-    if (c->vw.entries_host) *c->vw.entries_host = 0u;
-    c->vw.valid = false;
+    reset_pool_sizing(c->frame);
+    reset_pool_sizing(c->views);
+    c->jr.frame.count = 0;
+    c->jr.views.count = 0;
 }
 
 void free_pack(rtr_ctx *c) {
@@ -364,59 +394,76 @@ void free_cloud(rtr_ctx *c) {
     c->n = c->cap = 0;
 }
 
-// Per-resolution part of the tile store: a static 32 KB extent, a stream length, an extent directory
-// per 32x16 storage tile, and the tile kernel's work list.  s: the stream T1 will run on.
-int alloc_store(rtr_ctx *c, rtr_ctx::FrontSet &f, hipStream_t s) {
+// Tile store of frame k of a target, s: the stream T1 will run on.  Per resolution: a static 32 KB extent, a stream
+// length, an extent directory per 32x16 storage tile, and the tile kernel's work list.  Then the header constants:
+// the buffers T1's last workgroup resets for split tiles / writes the occupancy bitmap to, the dynamic extent pool,
+// the mapped words, the split parameters (uploaded only when one of them changes).
+int ensure_store(rtr_ctx *c, rtr_ctx::Target &t, rtr_ctx::FrontSet &f, int k, hipStream_t s) {
+    const bool single = &t == &c->frame;
     const int nt = rtr::tile_count(c->W, c->H), nst = rtr::storage_tile_count(c->W, c->H);
-    auto &t = f.store;
-    if (!(t.ext0 && f.nst == nst && f.ntiles == nt)) {
-        dfree(t.ext0); dfree(t.meta);
+    auto &st = f.store;
+    if (!(st.ext0 && f.nst == nst && f.ntiles == nt)) {
+        if (single) c->list_valid = false;
+        dfree(st.ext0); dfree(st.meta);
         f.nst = f.ntiles = 0;
         f.consts = rtr::StoreConsts{};
         const size_t meta_bytes = rtr::ts_meta_words(nst, nt) * sizeof(uint32_t);
         // (+ 16 entries of slack: the tile kernel's sweeps read a few entries past the piece they are masking)
-        HIP_TRY(c, hipMalloc((void **)&t.ext0, ((size_t)nst * rtr::kS0 + 16) * sizeof(uint64_t)));
-        HIP_TRY(c, hipMalloc((void **)&t.meta, meta_bytes));
-        HIP_TRY(c, hipMemsetAsync(t.meta, 0, meta_bytes, s));  // stream lengths 0, directory stamps 0 (never current)
-        t.seq = 0;
-        t.nst = f.nst = nst;
-        t.ntiles = f.ntiles = nt;
+        HIP_TRY(c, hipMalloc((void **)&st.ext0, ((size_t)nst * rtr::kS0 + 16) * sizeof(uint64_t)));
+        HIP_TRY(c, hipMalloc((void **)&st.meta, meta_bytes));
+        HIP_TRY(c, hipMemsetAsync(st.meta, 0, meta_bytes, s));  // stream lengths 0, directory stamps 0 (never current)
+        st.seq = 0;
+        st.nst = f.nst = nst;
+        st.ntiles = f.ntiles = nt;
         {   // launch order of the tile kernel: identity until a frame has been rendered
             std::vector<uint32_t> ident((size_t)nt);
             for (int i = 0; i < nt; ++i) ident[(size_t)i] = (uint32_t)i;
-            HIP_TRY(c, hipMemcpyAsync(rtr::ts_perm(t), ident.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(rtr::ts_order(t, 0), ident.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(rtr::ts_order(t, 1), ident.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(rtr::ts_perm(st), ident.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(rtr::ts_order(st, 0), ident.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(rtr::ts_order(st, 1), ident.data(), (size_t)nt * 4, hipMemcpyHostToDevice, s));
             HIP_TRY(c, hipStreamSynchronize(s));  // `ident` goes out of scope
         }
     }
-    return RTR_OK;
-}
-int upload_consts(rtr_ctx *c, rtr_ctx::FrontSet &f, hipStream_t s, const rtr::StoreConsts &want) {
-    if (memcmp(&want, &f.consts, sizeof want) != 0) {
-        f.consts = want;
-        HIP_TRY(c, hipMemcpyAsync(rtr::ts_hdr(f.store) + rtr::kHdrConsts, &f.consts, sizeof f.consts, hipMemcpyHostToDevice, s));
-    }
-    return RTR_OK;
-}
-int ensure_tiles(rtr_ctx *c, hipStream_t s) {
-    auto &f = c->F();
-    if (!(f.store.ext0 && f.nst == rtr::storage_tile_count(c->W, c->H) && f.ntiles == rtr::tile_count(c->W, c->H))) {
-        c->list_valid = false;
-        if (int rc = alloc_store(c, f, s)) return rc;
-    }
-    // header constants: the buffers T1's last workgroup resets for split tiles / writes the occupancy
-    // bitmap to, the dynamic extent pool, the split parameters (uploaded only when one of them changes)
     rtr::StoreConsts want{};
-    want.depth = c->depth; want.acc = c->acc; want.occ = c->p2p.open ? c->p2p.occ : nullptr;
+    want.depth = t.depth + (size_t)k * c->W * c->H; want.acc = t.acc; want.occ = c->p2p.open ? c->p2p.occ : nullptr;
     want.dyn = f.dyn; want.dyn_cap = f.dyn_cap;
     if (c->opt_debug_dyn_cap >= 0 && (uint64_t)c->opt_debug_dyn_cap < want.dyn_cap) want.dyn_cap = (uint64_t)c->opt_debug_dyn_cap;
-    want.err_host = c->err_dev;
-    want.split_host = c->split_dev;
-    want.entries_host = c->entries_dev;
-    want.heavy = c->opt_heavy > 0 ? (uint32_t)c->opt_heavy : 0xFFFFFFFFu;
+    want.err_host = t.err_dev;
+    want.split_host = single ? c->split_dev : nullptr;
+    want.entries_host = t.entries_dev;
+    want.heavy = single && c->opt_heavy > 0 ? (uint32_t)c->opt_heavy : 0xFFFFFFFFu;  // (views are lean frames: nothing is split)
     want.slice = (uint32_t)c->opt_slice;
-    return upload_consts(c, f, s, want);
+    if (memcmp(&want, &f.consts, sizeof want) != 0) {
+        f.consts = want;
+        HIP_TRY(c, hipMemcpyAsync(rtr::ts_hdr(st) + rtr::kHdrConsts, &f.consts, sizeof f.consts, hipMemcpyHostToDevice, s));
+    }
+    return RTR_OK;
+}
+
+// the store's next 24-bit frame stamp; when it wraps every directory entry is forgotten once
+int next_seq(rtr_ctx *c, rtr_ctx::FrontSet &f, hipStream_t s) {
+    auto &t = f.store;
+    t.seq = (t.seq + 1u) & 0xFFFFFFu;
+    if (t.seq == 0u) {
+        HIP_TRY(c, hipMemsetAsync(rtr::ts_dir(t), 0, (size_t)f.nst * rtr::kDirK * sizeof(unsigned long long), s));
+        t.seq = 1u;
+    }
+    return RTR_OK;
+}
+
+int t1_flags(const rtr_ctx *c, bool clear_split, bool no_split, bool lean) {  // rtr::launch_project_bin's flag word
+    return (clear_split ? 1 : 0) | (no_split ? 2 : 0) | (c->opt_lane_test ? 0 : 4) | (lean ? 8 : 0) | (c->opt_chunk_test ? 0 : 16);
+}
+
+// Tile-launch bits of a lean frame (tile_body): bit 5 = no launch order when the launch is resident at once; bit 6 =
+// the first batch of entries before the counters, when the tiles are expected full: the entry count of the target's
+// last frame whose statistics are complete -- a mapped word, no sync -- is at least half a batch, 1024 entries, per tile
+int lean_bits(const rtr_ctx *c, const rtr_ctx::Target &t) {
+    int bits = 8 | (c->opt_lean_identity ? 32 : 0);
+    const uint64_t e_last = __atomic_load_n(t.entries_host, __ATOMIC_RELAXED);
+    if (c->opt_lean_early > 0 || (c->opt_lean_early < 0 && e_last >= 1024ull * (uint64_t)rtr::tile_count(c->W, c->H)))
+        bits |= 64;
+    return bits;
 }
 
 // The dynamic extents of one frame sum to less than twice its entries (every extent doubles its stream,
@@ -426,32 +473,30 @@ int ensure_tiles(rtr_ctx *c, hipStream_t s) {
 // without a sync), at least n / 2 and 2^20 -- 4 B per point (n / 4 re-allocated in the middle of BASELINE C2's frames:
 // a sync, a free and a malloc cost more than the memory is worth).  A frame whose entries jump past that (the camera suddenly
 // sees four times more of the cloud than ever before) overflows the pool, reports it (tile-store error 2), and the next
-// synchronising call grows the pool to the worst case and renders the frame again (finish_sync) -- the caller never
+// synchronising call grows the pool to the worst case and renders the frame again (repair) -- the caller never
 // sees it, unless it consumes frames on the stream without ever synchronising: option "pool_worst_case" is for that.
-hipError_t sync_streams(rtr_ctx *c);
+// other_max: entries of the densest frame seen elsewhere that count too (the views': the single frame's).
 uint64_t pool_worst_cap(const rtr_ctx *c) { return 2 * c->n + 64; }
-uint64_t pool_want_cap(rtr_ctx *c, uint64_t have) {
+uint64_t pool_want_cap(rtr_ctx *c, rtr_ctx::Target &t, uint64_t have, uint64_t other_max) {
     const uint64_t worst = pool_worst_cap(c);
-    if (c->opt_pool_worst || c->pool_worst || c->p2p.open) return worst;
-    if (c->entries_host) {
-        const uint64_t e = __atomic_load_n(c->entries_host, __ATOMIC_RELAXED);
-        if (e > c->entries_max) c->entries_max = e;
-    }
+    if (c->opt_pool_worst || t.pool_worst || c->p2p.open) return worst;
+    const uint64_t e = __atomic_load_n(t.entries_host, __ATOMIC_RELAXED);
+    if (e > t.entries_max) t.entries_max = e;
+    const uint64_t emax = t.entries_max > other_max ? t.entries_max : other_max;
     uint64_t floor_ = c->n / 2 > (1ull << 20) ? c->n / 2 : (1ull << 20);
     // (hysteresis: grown to 8 x when the head-room over the densest frame seen falls under 4 x)
-    uint64_t want = have >= 4 * c->entries_max && have >= floor_ ? have : (8 * c->entries_max > floor_ ? 8 * c->entries_max : floor_);
+    uint64_t want = have >= 4 * emax && have >= floor_ ? have : (8 * emax > floor_ ? 8 * emax : floor_);
     return want < worst ? want : worst;
 }
-int ensure_lists(rtr_ctx *c) {
-    auto &f = c->F();
-    const uint64_t want = pool_want_cap(c, f.pool_n == c->n ? f.dyn_cap : 0);
+int ensure_pool(rtr_ctx *c, rtr_ctx::Target &t, rtr_ctx::FrontSet &f, uint64_t other_max) {
+    const uint64_t want = pool_want_cap(c, t, f.pool_n == c->n ? f.dyn_cap : 0, other_max);
     if (f.dyn && f.pool_n == c->n && f.dyn_cap >= want) return RTR_OK;
-    // (the peers map the pool that was EXPORTED -- set 0's: export / open again after a new cloud.  The second set's
-    // pool, first allocated by a frame with option "overlap", is nobody else's business)
-    if (&f == &c->fs[0] && (c->p2p.open || c->p2p.red)) p2p_release(c);
+    // (the peers map the pool that was EXPORTED -- the single frame's set 0: export / open again after a new cloud.
+    // The second set's pool, first allocated by a frame with option "overlap", is nobody else's business)
+    if (&f == &c->frame.fs[0] && (c->p2p.open || c->p2p.red)) p2p_release(c);
     HIP_TRY(c, sync_streams(c));  // (frames in flight may still read the old pool)
     dfree(f.dyn);
-    c->list_valid = false;
+    if (&t == &c->frame) c->list_valid = false;
     f.dyn_cap = want;
     f.pool_n = c->n;
     HIP_TRY(c, hipMalloc((void **)&f.dyn, f.dyn_cap * sizeof(uint64_t)));
@@ -498,14 +543,12 @@ int alloc_cloud(rtr_ctx *c, uint64_t n) {
     }
     if (n != c->n) {  // (the adaptive extent pool starts over; the peers of a sharded frame must map the new one)
         if (c->p2p.open || c->p2p.red) p2p_release(c);
-        c->pool_worst = false;
-        c->entries_max = 0;
-        if (c->entries_host) *c->entries_host = 0u;
+        reset_pool_sizing(c->frame);
     }
     c->n = n;
     ++c->cloud_seq;
     c->list_valid = false;
-    c->last_valid = false;
+    c->jr.frame.count = 0;
     c->pp_vis_current = false;
     c->split_cooldown = kSplitCooldown;  // (a new cloud: nothing is known about its frames)
     return RTR_OK;
@@ -558,39 +601,6 @@ hipError_t sync_streams(rtr_ctx *c) {
     return hipStreamSynchronize(c->stream);
 }
 
-// Tile-store errors (entries dropped by T1: an extent that never appeared, an exhausted extent pool) reach the
-// host through a mapped word that T1's epilogue writes; every call that has just synchronised reports and
-// clears it -- a wrong frame is never returned as RTR_OK.
-// retry (out): the only error is an overflow of the ADAPTIVE extent pool (ensure_lists) -- the pool is worst-case sized
-// from now on and the caller renders the frame again instead of failing.
-int check_store_error(rtr_ctx *c, bool *retry = nullptr) {
-    if (retry) *retry = false;
-    if (!c->err_host) return RTR_OK;
-    const uint32_t e = __atomic_exchange_n(c->err_host, 0u, __ATOMIC_ACQUIRE);
-    if (c->pp_since_sync) {  // (a point pass has read a frame: complete unless this word says otherwise)
-        if (e != 0u) c->pp_invalid = true;  // (finish_sync_rerender repeats it when it followed the frame repeated there)
-        if (e != 0u || hipEventQuery(c->pp_done) == hipSuccess) c->pp_since_sync = false;
-    }
-    if (e == 0u) return RTR_OK;
-    if (e == 2u && c->opt_debug_dyn_cap < 0 && c->F().dyn_cap < pool_worst_cap(c)) {
-        c->pool_worst = true;  // (ensure_lists re-allocates before the next T1)
-        for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)  // (every frame still on its way to a slot was queued before the growth: rtr_wait repeats it)
-            if (c->ho[k].busy) c->slot_frame[k].stale = true;
-        if (retry) {
-            *retry = true;
-            return RTR_OK;
-        }
-        return fail(c, RTR_ERR_INTERNAL, "tile store error 0x2: the extent pool, sized by the frames seen so far, was too small "
-                    "for a frame rendered since the last synchronising call -- entries were dropped; the pool is worst-case "
-                    "sized from now on: render the frame again (option pool_worst_case = 1 sizes it so from the start)");
-    }
-    return fail(c, RTR_ERR_INTERNAL, "tile store error 0x%x: %s%s%s%s-- entries were dropped, frames rendered since the last "
-                "synchronising call are incomplete", e, (e & 1u) ? "a stream extent never appeared " : "",
-                (e & 2u) ? "the dynamic extent pool overflowed " : "",
-                (e & 4u) ? "a contested tile of a sharded frame had more stream pieces than its table holds " : "",
-                (e & 8u) ? "the split tiles' second phase gave up waiting for the first " : "");
-}
-
 // after the last reader of the active list / bin set has been queued on the tail stream
 void mark_consumed(rtr_ctx *c) {
     if (!c->front) return;
@@ -624,25 +634,53 @@ int launch_check(rtr_ctx *c, const char *what) {
     return RTR_OK;
 }
 
-int ensure_pyramid(rtr_ctx *c) {
+// The prefilter's conditions, checked before anything changes
+int check_prefilter(rtr_ctx *c) {
     const int L = c->prm.levels;
     if (L < 1 || L > 8) return fail(c, RTR_ERR_UNSUPPORTED, "levels must be in 1..8");
     if ((c->W % (1 << L)) != 0 || (c->H >> L) < 1)
         return fail(c, RTR_ERR_UNSUPPORTED,
                     "prefilter needs W %% 2^levels == 0 and H >= 2^levels (got %dx%d, levels %d): the reference's "
                     "pyramid strides are only defined then (project_cloud.cu:39,336-362)", c->W, c->H, L);
-    if (c->lv_levels == L) return RTR_OK;
-    for (int i = 1; i <= 8; ++i) dfree(c->lv.lv[i]);
-    c->lv.levels = L;
-    c->lv.lv[0] = reinterpret_cast<float *>(c->depth);
-    c->lv.w[0] = c->W; c->lv.h[0] = c->H;
-    for (int i = 1; i <= L; ++i) {
-        c->lv.w[i] = c->lv.w[i - 1] / 2;
-        c->lv.h[i] = c->lv.h[i - 1] / 2;
-        HIP_TRY(c, hipMalloc((void **)&c->lv.lv[i], sizeof(float) * (size_t)c->lv.w[i] * c->lv.h[i]));
-    }
-    c->lv_levels = L;
     return RTR_OK;
+}
+
+int ensure_levels(rtr_ctx *c, rtr_ctx::Target &t) {  // the pyramid levels 1..levels a target's frames take in turn
+    const int L = c->prm.levels;
+    if (t.lv_levels == L) return RTR_OK;
+    for (auto &l : t.lv) dfree(l);
+    t.lv_levels = 0;
+    for (int i = 1, w = c->W / 2, h = c->H / 2; i <= L; ++i, w /= 2, h /= 2)
+        HIP_TRY(c, hipMalloc((void **)&t.lv[i], sizeof(float) * (size_t)w * h));
+    t.lv_levels = L;
+    return RTR_OK;
+}
+
+int ensure_pyramid(rtr_ctx *c) {
+    if (int rc = check_prefilter(c)) return rc;
+    return ensure_levels(c, c->frame);
+}
+
+rtr::FilterLevels levels_of(const rtr_ctx *c, const rtr_ctx::Target &t, int k) {  // frame k's pyramid
+    rtr::FilterLevels L{};
+    L.levels = t.lv_levels;
+    L.lv[0] = reinterpret_cast<float *>(t.depth + (size_t)k * c->W * c->H);
+    L.w[0] = c->W; L.h[0] = c->H;
+    for (int i = 1; i <= L.levels; ++i) L.lv[i] = t.lv[i], L.w[i] = L.w[i - 1] / 2, L.h[i] = L.h[i - 1] / 2;
+    return L;
+}
+
+// what a tile launch needs to emit frame k's prefilter pyramid and min / max partials (when `enable`)
+rtr::TilePyr tile_pyr(const rtr_ctx *c, const rtr_ctx::Target &t, int k, bool enable) {
+    rtr::TilePyr pyr{};
+    pyr.enable = enable ? 1 : 0;
+    if (enable) {
+        pyr.L = levels_of(c, t, k);
+        pyr.n_eff_rows = (uint32_t)((c->H >> 4) << 4);
+        pyr.part_min = t.part_min;
+        pyr.part_max = t.part_max;
+    }
+    return pyr;
 }
 
 }  // namespace
@@ -690,37 +728,17 @@ int rtr_create(rtr_ctx **out, int device) {
         return rc;
     }
     c->stream = c->own_stream;
-    e = hipMalloc((void **)&c->minmax, 2 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->err_host, sizeof(uint32_t), hipHostMallocMapped);
-    if (e == hipSuccess) {
-        *c->err_host = 0u;
-        void *d = nullptr;
-        e = hipHostGetDevicePointer(&d, c->err_host, 0);
-        c->err_dev = static_cast<uint32_t *>(d);
-    }
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->split_host, sizeof(uint32_t), hipHostMallocMapped);
-    if (e == hipSuccess) {
-        *c->split_host = 0u;
-        void *d = nullptr;
-        e = hipHostGetDevicePointer(&d, c->split_host, 0);
-        c->split_dev = static_cast<uint32_t *>(d);
-        c->split_cooldown = kSplitCooldown;
-    }
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->entries_host, sizeof(uint32_t), hipHostMallocMapped);
-    if (e == hipSuccess) {
-        *c->entries_host = 0u;
-        void *d = nullptr;
-        e = hipHostGetDevicePointer(&d, c->entries_host, 0);
-        c->entries_dev = static_cast<uint32_t *>(d);
+    c->split_cooldown = kSplitCooldown;
+    // (the minmax words serve RTR_BUF_MINMAX before any resolution is set)
+    e = mapped_word(&c->split_host, &c->split_dev);
+    for (auto *t : {&c->frame, &c->views}) {
+        if (e == hipSuccess) e = hipMalloc((void **)&t->minmax, RTR_MAX_VIEWS * 2 * sizeof(uint32_t));
+        if (e == hipSuccess) e = mapped_word(&t->err_host, &t->err_dev);
+        if (e == hipSuccess) e = mapped_word(&t->entries_host, &t->entries_dev);
     }
     if (e != hipSuccess) {
         int rc = fail(nullptr, RTR_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
-        if (c->minmax) (void)hipFree(c->minmax);
-        if (c->err_host) (void)hipHostFree(c->err_host);
-        if (c->split_host) (void)hipHostFree(c->split_host);
-        if (c->entries_host) (void)hipHostFree(c->entries_host);
-        (void)hipStreamDestroy(c->own_stream);
-        delete c;
+        (void)rtr_destroy(c);
         return rc;
     }
     *out = c;
@@ -736,16 +754,16 @@ int rtr_destroy(rtr_ctx *c) {
     for (auto &p : c->pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     free_frame(c);
     free_cloud(c);
-    dfree(c->minmax);
+    for (auto *t : {&c->frame, &c->views}) {
+        dfree(t->minmax);
+        if (t->err_host) (void)hipHostFree(t->err_host);
+        if (t->entries_host) (void)hipHostFree(t->entries_host);
+    }
     if (c->p2p.status_host) (void)hipHostFree(c->p2p.status_host);
     if (c->split_host) (void)hipHostFree(c->split_host);
-    if (c->err_host) (void)hipHostFree(c->err_host);
-    if (c->entries_host) (void)hipHostFree(c->entries_host);
-    if (c->vw.err_host) (void)hipHostFree(c->vw.err_host);
-    if (c->vw.entries_host) (void)hipHostFree(c->vw.entries_host);
-    if (c->vw.tab_host) (void)hipHostFree(c->vw.tab_host);
-    dfree(c->vw.tab_dev);
-    if (c->vw.tab_copied) (void)hipEventDestroy(c->vw.tab_copied);
+    if (c->vtab.host) (void)hipHostFree(c->vtab.host);
+    dfree(c->vtab.dev);
+    if (c->vtab.copied) (void)hipEventDestroy(c->vtab.copied);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->pp_done) (void)hipEventDestroy(c->pp_done);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -779,7 +797,7 @@ static int set_overlap(rtr_ctx *c, bool on) {
         if (c->front) (void)hipStreamDestroy(c->front);
         if (c->masked_tail) (void)hipStreamDestroy(c->masked_tail);
         c->front = c->masked_tail = nullptr;
-        for (auto &f : c->fs) {
+        for (auto &f : c->frame.fs) {
             if (f.binned) (void)hipEventDestroy(f.binned);
             if (f.consumed) (void)hipEventDestroy(f.consumed);
             f.binned = f.consumed = nullptr;
@@ -812,7 +830,8 @@ static int set_overlap(rtr_ctx *c, bool on) {
     } else {
         HIP_TRY(c, hipStreamCreateWithFlags(&c->front, hipStreamNonBlocking));
     }
-    for (auto &f : c->fs) {
+    for (int k = 0; k < 2; ++k) {  // (the single frame's two sets)
+        auto &f = c->frame.fs[k];
         hipError_t e = hipEventCreateWithFlags(&f.binned, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&f.consumed, hipEventDisableTiming);
         if (e != hipSuccess) {
@@ -984,24 +1003,21 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "p2p_open")) *value = c->p2p.open ? 1 : 0;  // the peers' buffers are mapped (rtr_p2p_open)
     else if (!strcmp(key, "keep_soa")) *value = c->opt_keep_soa;
     else if (!strcmp(key, "pool_worst_case")) *value = c->opt_pool_worst;
-    else if (!strcmp(key, "views")) *value = c->vw.valid ? c->vw.count : 0;  // views of the last rtr_render_views
+    else if (!strcmp(key, "views")) *value = c->jr.views.count;  // views of the last rtr_render_views
     else if (!strcmp(key, "resident_millibytes_per_point")) {
         // device memory this context holds for the cloud and its frames, per point: coordinates (fp32 SoA and / or packed
         // form), colours, chunk boxes and lane spreads, tile stores and extent pools, frame buffers
         const uint64_t nchunks = ((c->cap / 4) + 63) / 64;
         uint64_t b = (c->x ? 12 * c->cap : 0) + (c->rgba ? 4 * c->cap : 0) + nchunks * 28 + (c->pk_hdr ? c->pk_bytes + 64 : 0) +
                      (c->perm ? 4 * c->cap : 0);
-        for (const auto &f : c->fs) {
-            b += f.dyn ? f.dyn_cap * 8 : 0;
-            b += f.store.ext0 ? ((uint64_t)f.nst * rtr::kS0 + 16) * 8 + rtr::ts_meta_words(f.nst, f.ntiles) * 4 : 0;
-        }
         const uint64_t npix = (uint64_t)c->W * c->H;
-        b += c->depth ? npix * (4 + 16 + 3 + 1 + 10) : 0;
-        for (const auto &f : c->vw.fs) {  // (several views: their stores, pools and frame buffers)
-            b += f.dyn ? f.dyn_cap * 8 : 0;
-            b += f.store.ext0 ? ((uint64_t)f.nst * rtr::kS0 + 16) * 8 + rtr::ts_meta_words(f.nst, f.ntiles) * 4 : 0;
+        for (const auto *t : {&c->frame, &c->views}) {
+            for (const auto &f : t->fs) {
+                b += f.dyn ? f.dyn_cap * 8 : 0;
+                b += f.store.ext0 ? ((uint64_t)f.nst * rtr::kS0 + 16) * 8 + rtr::ts_meta_words(f.nst, f.ntiles) * 4 : 0;
+            }
+            b += t->cap ? npix * (16 + 1 + (uint64_t)t->cap * (4 + 3 + 10)) : 0;
         }
-        b += c->vw.cap ? npix * (16 + 1 + (uint64_t)c->vw.cap * (4 + 3 + 10)) : 0;
         *value = c->n ? (int)((b * 1000) / c->n > 0x7FFFFFFFull ? 0x7FFFFFFF : (b * 1000) / c->n) : 0;
     }
     else if (!strcmp(key, "pack")) *value = c->opt_pack;
@@ -1022,7 +1038,7 @@ int rtr_stream_probe(rtr_ctx *c, const float P[16]) {
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
     if (int rc = ensure_soa(c)) return rc;
-    { Timed t(c, RTR_K_PROBE); rtr::launch_stream_probe(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->minmax, c->opt_probe); }
+    { Timed t(c, RTR_K_PROBE); rtr::launch_stream_probe(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->frame.minmax, c->opt_probe); }
     return launch_check(c, "stream_probe");
 }
 
@@ -1050,43 +1066,106 @@ int rtr_reset_stream(rtr_ctx *c) {
     return switch_stream(c, c->masked_tail ? c->masked_tail : c->own_stream);
 }
 
-// After a synchronisation: tile-store errors.  When the adaptive extent pool overflowed and the last frame was a whole
-// one (rtr_render and what is built on it), that frame is rendered again with the grown pool -- the device buffers hold
-// the right frame when the call returns.
-static int finish_sync_rerender(rtr_ctx *c) {
-    float P[16], Q[16];
-    memcpy(P, c->last_P, sizeof P);
-    memcpy(Q, c->pp_P, sizeof Q);
-    const bool pass = c->pp_after_last;  // (a point pass queued behind that frame is repeated with it)
-    const int what = c->pp_what;
-    int rc = rtr_render(c, P, c->last_filter);
-    if (!rc && pass) rc = rtr_point_pass(c, Q, what);
-    return rc;
-}
-static int finish_sync(rtr_ctx *c) {
-    bool retry = false;
-    int rc = check_store_error(c, c->last_valid ? &retry : nullptr);
-    if (rc || !retry) return rc;
-    if ((rc = finish_sync_rerender(c))) return rc;
-    HIP_TRY(c, sync_streams(c));
-    return check_store_error(c);
+// A device-to-host copy of a frame's results: queued again behind a repaired frame
+struct Copy { void *host; const void *dev; size_t bytes; };
+static hipError_t queue_copies(rtr_ctx *c, const Copy *cp, int n) {
+    for (int i = 0; i < n; ++i)
+        if (cp[i].host) {
+            const hipError_t e = hipMemcpyAsync(cp[i].host, cp[i].dev, cp[i].bytes, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
 }
 
-static int views_check(rtr_ctx *c, bool *again);
+static int queue_slot(rtr_ctx *c, const float P[16], int slot, int with_filter);
 static int views_enqueue(rtr_ctx *c, int count, const float *P, int with_filter);
+
+// After a synchronisation: the tile-store errors of target t.  They (entries dropped by T1: an extent that never
+// appeared, an exhausted extent pool) reach the host through a mapped word that T1's epilogue writes; every call that
+// has just synchronised reports and clears it -- a wrong frame is never returned as RTR_OK.  When the only error is an
+// overflow of the ADAPTIVE extent pool (ensure_pool), the pool is worst-case sized from now on (and every frame still
+// on its way to an async slot is marked stale: it was queued before the growth), and what the journal recorded for t
+// is rendered again, once: with `slots` (rtr_wait) every stale slot in slot order, then the last whole frame and the
+// point pass queued behind it -- or the last batch of views.  `own` (rtr_project): that frame instead of the
+// journal's, whatever form it took.  `copies` are queued again behind them; one more synchronisation and check
+// follow, without another try.
+static int repair(rtr_ctx *c, rtr_ctx::Target &t, bool slots = false, const Copy *copies = nullptr, int ncopies = 0,
+                  const rtr_ctx::Journal::Frames *own = nullptr) {
+    auto &j = c->jr;
+    const bool single = &t == &c->frame;
+    const bool was_worst = t.pool_worst;  // (rtr_wait reads the word twice before it repeats anything)
+    bool retry = false;
+    auto check = [&](bool may_retry) -> int {
+        const uint32_t e = __atomic_exchange_n(t.err_host, 0u, __ATOMIC_ACQUIRE);
+        if (single && j.pass.unchecked) {  // (a point pass has read a frame: complete unless this word says otherwise)
+            if (e != 0u) j.pass.invalid = true;  // (repeated below when it followed the frame repeated there)
+            if (e != 0u || hipEventQuery(c->pp_done) == hipSuccess) j.pass.unchecked = false;
+        }
+        if (e == 0u) return RTR_OK;
+        const bool grow = e == 2u && c->opt_debug_dyn_cap < 0 && !was_worst && t.fs[t.cur].dyn_cap < pool_worst_cap(c);
+        if (grow && (single || may_retry)) {  // (the views' pools grow only with a batch to render again)
+            t.pool_worst = true;  // (ensure_pool re-allocates before the next T1)
+            for (int k = 0; single && k < RTR_ASYNC_SLOTS; ++k)
+                if (c->ho[k].busy) j.slot[k].stale = true;
+            if (may_retry) {
+                retry = true;
+                return RTR_OK;
+            }
+        }
+        if (!single) {
+            j.views.count = 0;
+            return fail(c, RTR_ERR_INTERNAL, "tile store error 0x%x in a batch of views -- entries were dropped, the views are "
+                        "incomplete: render the batch again", e);
+        }
+        if (grow)
+            return fail(c, RTR_ERR_INTERNAL, "tile store error 0x2: the extent pool, sized by the frames seen so far, was too "
+                        "small for a frame rendered since the last synchronising call -- entries were dropped; the pool is "
+                        "worst-case sized from now on: render the frame again (option pool_worst_case = 1 sizes it so from "
+                        "the start)");
+        return fail(c, RTR_ERR_INTERNAL, "tile store error 0x%x: %s%s%s%s-- entries were dropped, frames rendered since the last "
+                    "synchronising call are incomplete", e, (e & 1u) ? "a stream extent never appeared " : "",
+                    (e & 2u) ? "the dynamic extent pool overflowed " : "",
+                    (e & 4u) ? "a contested tile of a sharded frame had more stream pieces than its table holds " : "",
+                    (e & 8u) ? "the split tiles' second phase gave up waiting for the first " : "");
+    };
+    if (int rc = check(single ? own || j.frame.count > 0 || slots : j.views.count > 0)) return rc;
+    bool stale = false;
+    for (int k = 0; slots && k < RTR_ASYNC_SLOTS; ++k) stale |= c->ho[k].busy && j.slot[k].stale;
+    if (!retry && !stale) return RTR_OK;
+    if (slots) {  // (rtr_wait has waited for its slots only: what was queued behind them is finished and checked too)
+        HIP_TRY(c, sync_streams(c));
+        if (int rc = check(true)) return rc;
+    }
+    if (single) {
+        const auto frame = own ? *own : j.frame;  // (the slots' frames below replace the record)
+        const auto pass = j.pass;
+        for (int k = 0; slots && k < RTR_ASYNC_SLOTS; ++k) {
+            const auto f = j.slot[k];
+            if (!c->ho[k].busy || !f.stale) continue;
+            if (f.cloud != c->cloud_seq)
+                return fail(c, RTR_ERR_INTERNAL, "rtr_wait: the frame of slot %d lost entries in an overflowing extent pool "
+                            "and the cloud has been replaced since: it cannot be rendered again", k);
+            if (int rc = queue_slot(c, f.P, k, f.filter)) return rc;
+        }
+        if (frame.count) {
+            if (int rc = rtr_render(c, frame.P, frame.filter)) return rc;
+            if (pass.behind)
+                if (int rc = rtr_point_pass(c, pass.P, pass.what)) return rc;
+        }
+    } else if (int rc = views_enqueue(c, j.views.count, j.views.P, j.views.filter)) {
+        return rc;
+    }
+    HIP_TRY(c, queue_copies(c, copies, ncopies));
+    HIP_TRY(c, sync_streams(c));
+    return check(false);
+}
+
 int rtr_synchronize(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
-    int rc = finish_sync(c);
-    bool again = false;
-    if (!rc) rc = views_check(c, &again);
-    if (!rc && again) {  // (a batch overflowed the adaptive pools: rendered again with worst-case ones)
-        if ((rc = views_enqueue(c, c->vw.count, c->vw.P, c->vw.with_filter))) return rc;
-        HIP_TRY(c, sync_streams(c));
-        rc = views_check(c, nullptr);
-    }
-    return rc;
+    if (int rc = repair(c, c->frame)) return rc;
+    return repair(c, c->views);
 }
 
 // ---- cloud -------------------------------------------------------------------------
@@ -1337,16 +1416,11 @@ int rtr_set_resolution(rtr_ctx *c, int W, int H) {
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
     free_frame(c);
-    size_t npix = (size_t)W * H;
-    HIP_TRY(c, hipMalloc((void **)&c->depth, npix * 4));
-    HIP_TRY(c, hipMalloc((void **)&c->acc, npix * 16));
-    HIP_TRY(c, hipMalloc((void **)&c->img, (npix * 3 + 15) & ~(size_t)15));
-    HIP_TRY(c, hipMalloc((void **)&c->mask, npix));
-    size_t nparts = (size_t)((W + 31) / 32) * ((H + 31) / 32);
-    HIP_TRY(c, hipMalloc((void **)&c->part_min, nparts * 4));
-    HIP_TRY(c, hipMalloc((void **)&c->part_max, nparts * 4));
-    HIP_TRY(c, hipMalloc((void **)&c->tensor, npix * 5 * sizeof(uint16_t)));
     c->W = W; c->H = H;
+    if (int rc = alloc_target(c, c->frame, 1)) {
+        c->W = c->H = 0;
+        return rc;
+    }
     return RTR_OK;
 }
 
@@ -1356,7 +1430,7 @@ int rtr_clear(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
-    { Timed t(c, RTR_K_CLEAR); rtr::launch_clear(c->stream, c->depth, c->acc, (size_t)c->W * c->H); }
+    { Timed t(c, RTR_K_CLEAR); rtr::launch_clear(c->stream, c->frame.depth, c->frame.acc, (size_t)c->W * c->H); }
     return launch_check(c, "clear");
 }
 
@@ -1379,28 +1453,23 @@ static int bin_points(rtr_ctx *c, const float P[16], bool overlapped, bool clear
     c->p2p.occ_from_scan = false;
     hipStream_t s1 = c->stream;
     if (overlapped) {
-        c->cur ^= 1;
+        c->frame.cur ^= 1;
         s1 = c->front;
         if (c->F().consumed_valid) HIP_TRY(c, hipStreamWaitEvent(c->front, c->F().consumed, 0));
     }
-    if (int rc = ensure_lists(c)) return rc;
-    if (int rc = ensure_tiles(c, s1)) return rc;
+    if (int rc = ensure_pool(c, c->frame, c->F(), 0)) return rc;
+    if (int rc = ensure_store(c, c->frame, c->F(), 0, s1)) return rc;
     auto &t = c->F().store;
     // (automatic: 8 bytes apart -- fewer cache lines for T1's epilogue to read and reset: -2 us on C3, -2.5 us on C2 --
     // unless tiles above the split threshold have been seen lately, where the claims of all waves queue on a dozen
     // counters and those want lines of their own; any spacing can follow any other, the counters are zero between frames)
     const bool heavy_seen = c->split_cooldown > 0 || __atomic_load_n(c->split_host, __ATOMIC_RELAXED) != 0u;
     t.fill_shift = c->opt_fill_shift >= 0 ? c->opt_fill_shift : (heavy_seen ? 4 : 1);
-    t.seq = (t.seq + 1u) & 0xFFFFFFu;
-    if (t.seq == 0u) {  // the 24-bit stamp wrapped: forget every directory entry once
-        HIP_TRY(c, hipMemsetAsync(rtr::ts_dir(t), 0, (size_t)c->F().nst * rtr::kDirK * sizeof(unsigned long long), s1));
-        t.seq = 1u;
-    }
+    if (int rc = next_seq(c, c->F(), s1)) return rc;
     {
         Timed tm(c, RTR_K_MIN_DEPTH, s1, true);
         rtr::launch_project_bin(s1, cloud_of(c), make_proj(P), c->W, c->H, t, c->opt_cull ? c->bounds : nullptr,
-                                (clear_split ? 1 : 0) | (no_split ? 2 : 0) | (c->opt_lane_test ? 0 : 4) | (lean ? 8 : 0) | (c->opt_chunk_test ? 0 : 16),
-                                c->opt_phases, c->opt_xp, tm.a, tm.b);
+                                t1_flags(c, clear_split, no_split, lean), c->opt_phases, c->opt_xp, tm.a, tm.b);
         c->p2p.occ_from_scan = c->p2p.open;
     }
     if (overlapped) {
@@ -1418,20 +1487,20 @@ int rtr_min_depth_pass(rtr_ctx *c, const float P[16]) {
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
     c->list_valid = false;
-    c->last_valid = false;
+    c->jr.frame.count = 0;
     if (use_tiles(c)) {
         // (the phase calls' frames are consumed on the stream -- a sharded frame is reduced before anything synchronises
         // -- and no synchronising call can render them again: the extent pool is sized for the worst case at once)
-        c->pool_worst = true;
+        c->frame.pool_worst = true;
         if (int rc = bin_points(c, P, false, c->p2p.whole_frame)) return rc;
         Timed t(c, RTR_K_TILE);
-        rtr::launch_tile(c->stream, 1, c->W, c->H, c->F().store, c->prm.depth_window, c->depth, c->acc, c->img,
+        rtr::launch_tile(c->stream, 1, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, c->frame.img,
                          (c->p2p.whole_frame ? 6 : 0) | (c->lean_parity << 4), nullptr);  // 2: only writer, 4: tiles without entries are not written
         mark_consumed(c);
     } else {
         if (int rc = ensure_soa(c)) return rc;
         Timed t(c, RTR_K_MIN_DEPTH);
-        rtr::launch_min_depth(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->depth);
+        rtr::launch_min_depth(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->frame.depth);
     }
     return launch_check(c, "min_depth_pass");
 }
@@ -1449,14 +1518,7 @@ int rtr_accumulate_pass(rtr_ctx *c, const float P[16]) {
     if (use_bins) {
         // inside rtr_p2p_render with the default pyramid depth the tile kernel also emits the prefilter's
         // levels and min / max partials from the GLOBAL depth tile it has just loaded
-        rtr::TilePyr pyr{};
-        pyr.enable = (c->p2p.whole_frame && c->p2p.pyramid_done) ? 1 : 0;
-        if (pyr.enable) {
-            pyr.L = c->lv;
-            pyr.n_eff_rows = (uint32_t)((c->H >> 4) << 4);
-            pyr.part_min = c->part_min;
-            pyr.part_max = c->part_max;
-        }
+        const rtr::TilePyr pyr = tile_pyr(c, c->frame, 0, c->p2p.whole_frame && c->p2p.pyramid_done);
         rtr::Sliced dsl{};
         if (c->p2p.whole_frame && c->p2p.depth_peers) {  // MIN over the occupying ranks' local depth, tile by tile
             dsl.src = c->p2p.depth;
@@ -1470,13 +1532,13 @@ int rtr_accumulate_pass(rtr_ctx *c, const float P[16]) {
         }
         c->p2p.depth_sliced = c->p2p.depth_peers = false;
         Timed t(c, RTR_K_TILE);
-        rtr::launch_tile(c->stream, 2, c->W, c->H, c->F().store, c->prm.depth_window, c->depth, c->acc, c->img,
+        rtr::launch_tile(c->stream, 2, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, c->frame.img,
                          c->p2p.whole_frame ? 6 : 0, pyr.enable ? &pyr : nullptr, (dsl.chunk || dsl.peers) ? &dsl : nullptr);
         mark_consumed(c);
     } else {
         if (int rc = ensure_soa(c)) return rc;
         Timed t(c, RTR_K_ACCUMULATE);
-        rtr::launch_accumulate(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->depth, c->acc, c->prm.depth_window);
+        rtr::launch_accumulate(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->frame.depth, c->frame.acc, c->prm.depth_window);
     }
     return launch_check(c, "accumulate_pass");
 }
@@ -1485,7 +1547,7 @@ int rtr_resolve(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
-    { Timed t(c, RTR_K_RESOLVE); rtr::launch_resolve(c->stream, c->acc, c->img, (size_t)c->W * c->H); }
+    { Timed t(c, RTR_K_RESOLVE); rtr::launch_resolve(c->stream, c->frame.acc, c->frame.img, (size_t)c->W * c->H); }
     return launch_check(c, "resolve");
 }
 
@@ -1496,8 +1558,8 @@ int rtr_resolve_range(rtr_ctx *c, const void *acc_dev, uint64_t first_pixel, uin
     NEED(c, first_pixel % 4 == 0 && first_pixel + count <= npix, "bad pixel range (first must be a multiple of 4)");
     if (count == 0) return RTR_OK;
     DevGuard g(c->device);
-    const uint32_t *src = acc_dev ? static_cast<const uint32_t *>(acc_dev) : c->acc + first_pixel * 4;
-    { Timed t(c, RTR_K_RESOLVE); rtr::launch_resolve(c->stream, src, c->img + first_pixel * 3, (size_t)count); }
+    const uint32_t *src = acc_dev ? static_cast<const uint32_t *>(acc_dev) : c->frame.acc + first_pixel * 4;
+    { Timed t(c, RTR_K_RESOLVE); rtr::launch_resolve(c->stream, src, c->frame.img + first_pixel * 3, (size_t)count); }
     return launch_check(c, "resolve_range");
 }
 
@@ -1508,7 +1570,7 @@ static int filter_impl(rtr_ctx *c, int pyramid_parts, const rtr::Sliced *img_sli
     if (int rc = ensure_pyramid(c)) return rc;
     {
         Timed t(c, RTR_K_FILTER);
-        rtr::launch_filter(c->stream, c->lv, c->depth, c->img, c->mask, c->tensor, c->minmax, c->part_min, c->part_max,
+        rtr::launch_filter(c->stream, levels_of(c, c->frame, 0), c->frame.depth, c->frame.img, c->frame.mask, c->frame.tensor, c->frame.minmax, c->frame.part_min, c->frame.part_max,
                            c->W, c->H, c->prm.filter_strength, c->prm.gradient_threshold, pyramid_parts, img_slices,
                            depth_src);
     }
@@ -1526,12 +1588,13 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
     if (!c) return RTR_ERR_INVALID;
     NEED(c, P != nullptr, "P is NULL");
     if (int rc = check_frame(c)) return rc;
-    c->pp_after_last = false;
+    c->jr.pass.behind = false;
     if (with_filter) {  // fail before touching the frame buffers
         DevGuard g(c->device);
         if (int rc = ensure_pyramid(c)) return rc;
     }
     int rc;
+    bool fused = false;  // the tile launch has emitted the prefilter's pyramid
     if (use_tiles(c)) {  // one launch does clear + min + accumulate + resolve per tile
         DevGuard g(c->device);
         // (T1 beside the previous frame's tail must not touch the frame buffers: the split tiles' pixels are then
@@ -1551,47 +1614,30 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
             c->lean_parity ^= 1;
             c->last_lean = true;
         }
-        if (overlapped && split_launch) rtr::launch_reset_split(c->stream, c->W, c->H, c->F().store, c->depth, c->acc);
+        if (overlapped && split_launch) rtr::launch_reset_split(c->stream, c->W, c->H, c->F().store, c->frame.depth, c->frame.acc);
         // with the default four levels the tile kernel also emits the prefilter's pyramid and
         // min / max partials (F1) while the finished depth tile is still in LDS
-        rtr::TilePyr pyr{};
-        pyr.enable = (with_filter && c->prm.levels == 4) ? 1 : 0;
-        if (pyr.enable) {
-            pyr.L = c->lv;
-            pyr.n_eff_rows = (uint32_t)((c->H >> 4) << 4);
-            pyr.part_min = c->part_min;
-            pyr.part_max = c->part_max;
-        }
+        fused = with_filter && c->prm.levels == 4;
+        const rtr::TilePyr pyr = tile_pyr(c, c->frame, 0, fused);
         {
             Timed t(c, RTR_K_TILE);
-            // (lean frames, tile_body: bit 5 = no launch order when the launch is resident at once; bit 6 = the first batch
-            // of entries before the counters, when the tiles are expected full: the last frame's entry count -- a mapped
-            // word, no sync -- is at least half a batch, 1024 entries, per tile)
-            int lean_bits = 0;
-            if (lean) {
-                lean_bits = 8 | (c->opt_lean_identity ? 32 : 0);
-                const uint64_t e_last = c->entries_host ? __atomic_load_n(c->entries_host, __ATOMIC_RELAXED) : 0u;
-                if (c->opt_lean_early > 0 || (c->opt_lean_early < 0 && e_last >= 1024ull * (uint64_t)rtr::tile_count(c->W, c->H)))
-                    lean_bits |= 64;
-            }
-            rtr::launch_tile(c->stream, 0, c->W, c->H, c->F().store, c->prm.depth_window, c->depth, c->acc, c->img,
-                             c->opt_keep_accum | lean_bits | (c->lean_parity << 4), pyr.enable ? &pyr : nullptr);
+            rtr::launch_tile(c->stream, 0, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, c->frame.img,
+                             c->opt_keep_accum | (lean ? lean_bits(c, c->frame) : 0) | (c->lean_parity << 4), fused ? &pyr : nullptr);
             if (lean) c->list_valid = false;  // (the tile launch has consumed and reset the stream counters)
             // tiles heavier than option "split_threshold" are split over several workgroups: a second launch takes
             // the minimum over each slice (they meet in the depth buffer), then -- behind a barrier over its 256
             // workgroups -- accumulates the slices against that minimum, and the last slice of each tile resolves it
             // (no work item on ordinary frames: its workgroups leave at once)
             if (split_launch)  // (skipped while no frame has had a tile above the threshold: see rtr_ctx::split_host)
-                rtr::launch_tile(c->stream, 3, c->W, c->H, c->F().store, c->prm.depth_window, c->depth, c->acc, c->img,
-                                 c->opt_keep_accum, pyr.enable ? &pyr : nullptr);
+                rtr::launch_tile(c->stream, 3, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, c->frame.img,
+                                 c->opt_keep_accum, fused ? &pyr : nullptr);
         }
         mark_consumed(c);
         if ((rc = launch_check(c, "tile frame"))) return rc;
-        memcpy(c->last_P, P, sizeof c->last_P);  // (what a synchronising call repeats if the adaptive pool overflowed)
-        c->last_filter = with_filter;
-        c->last_valid = true;
-        if (with_filter) return filter_impl(c, pyr.enable ? rtr::tile_count(c->W, c->H) : 0);
-        return RTR_OK;
+        auto &rec = c->jr.frame;  // (what a synchronising call repeats if the adaptive pool overflowed)
+        memcpy(rec.P, P, sizeof(float) * 16);
+        rec.filter = with_filter;
+        rec.count = 1;
     } else {
         c->force_atomic = true;  // the phase calls below must not take the binned form either
         rc = rtr_clear(c);
@@ -1601,25 +1647,24 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
         c->force_atomic = false;
         if (rc) return rc;
     }
-    if (with_filter && (rc = rtr_filter(c))) return rc;
+    if (with_filter) return filter_impl(c, fused ? rtr::tile_count(c->W, c->H) : 0);
     return RTR_OK;
 }
 
 static int frame_to_host(rtr_ctx *c, const float P[16], uint8_t *host_img, float *host_depth, int with_filter) {
     if (!c) return RTR_ERR_INVALID;
     if (!host_img && !host_depth) return fail(c, RTR_ERR_NO_OUTPUT, "both outputs are NULL (project_cloud.cu:270-273)");
-    for (int attempt = 0;; ++attempt) {  // (a second time only after the adaptive extent pool overflowed: check_store_error)
-        int rc = rtr_render(c, P, with_filter);
-        if (rc) return rc;
-        DevGuard g(c->device);
-        size_t npix = (size_t)c->W * c->H;
-        if (host_depth) HIP_TRY(c, hipMemcpyAsync(host_depth, c->depth, npix * 4, hipMemcpyDeviceToHost, c->stream));
-        if (host_img) HIP_TRY(c, hipMemcpyAsync(host_img, c->img, npix * 3, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, sync_streams(c));
-        bool retry = false;
-        rc = check_store_error(c, attempt == 0 ? &retry : nullptr);
-        if (rc || !retry) return rc;
-    }
+    if (int rc = rtr_render(c, P, with_filter)) return rc;
+    DevGuard g(c->device);
+    const size_t npix = (size_t)c->W * c->H;
+    const Copy copies[2] = {{host_depth, c->frame.depth, npix * 4}, {host_img, c->frame.img, npix * 3}};
+    HIP_TRY(c, queue_copies(c, copies, 2));
+    HIP_TRY(c, sync_streams(c));
+    rtr_ctx::Journal::Frames own;  // (after an overflow of the adaptive pool: this frame again, once)
+    memcpy(own.P, P, sizeof(float) * 16);
+    own.count = 1;
+    own.filter = with_filter;
+    return repair(c, c->frame, false, copies, 2, &own);
 }
 
 int rtr_project(rtr_ctx *c, const float P[16], uint8_t *host_img, float *host_depth) {
@@ -1667,15 +1712,15 @@ static int queue_slot(rtr_ctx *c, const float P[16], int slot, int with_filter) 
     if (h.busy) HIP_TRY(c, hipStreamWaitEvent(c->stream, h.done, 0));
     if (int rc = rtr_render(c, P, with_filter)) return rc;
     const size_t npix = (size_t)c->W * c->H;
-    HIP_TRY(c, hipMemcpyAsync(h.ddepth, c->depth, npix * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(h.dimg, c->img, npix * 3, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h.ddepth, c->frame.depth, npix * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h.dimg, c->frame.img, npix * 3, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(h.snap, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, h.snap, 0));
     rtr::launch_copy_to_host(c->copy_stream, h.ddepth, h.depth_map, npix * 4, h.dimg, h.img_map, npix * 3);
     HIP_TRY(c, hipEventRecord(h.done, c->copy_stream));
-    auto &f = c->slot_frame[slot];
+    auto &f = c->jr.slot[slot];
     memcpy(f.P, P, sizeof f.P);
-    f.with_filter = with_filter;
+    f.filter = with_filter;
     f.stale = false;
     f.cloud = c->cloud_seq;
     h.busy = true;
@@ -1692,55 +1737,19 @@ int rtr_project_async(rtr_ctx *c, const float P[16], int slot, int with_filter) 
     return queue_slot(c, P, slot, with_filter);
 }
 
-// The adaptive extent pool overflowed in a frame queued before some slot's frame was complete (check_store_error marked
-// those slots stale): every stale slot is rendered again with the grown pool, in slot order, and so is the last whole
-// frame, which the device buffers hold.  Everything queued so far is finished first and its error word read: those
-// frames are the ones being repeated.
-static int repair_slots(rtr_ctx *c) {
-    HIP_TRY(c, sync_streams(c));
-    bool retry = false;
-    if (int rc = check_store_error(c, &retry)) return rc;
-    const bool last = c->last_valid, pass = c->pp_after_last;  // (the slots' frames below replace them)
-    const int last_filter = c->last_filter;
-    float last_P[16];
-    memcpy(last_P, c->last_P, sizeof last_P);
-    for (int k = 0; k < RTR_ASYNC_SLOTS; ++k) {
-        const auto &f = c->slot_frame[k];
-        if (!c->ho[k].busy || !f.stale) continue;
-        if (f.cloud != c->cloud_seq)
-            return fail(c, RTR_ERR_INTERNAL, "rtr_wait: the frame of slot %d lost entries in an overflowing extent pool and "
-                        "the cloud has been replaced since: it cannot be rendered again", k);
-        float P[16];
-        memcpy(P, f.P, sizeof P);
-        if (int rc = queue_slot(c, P, k, f.with_filter)) return rc;
-    }
-    if (!last) return RTR_OK;
-    memcpy(c->last_P, last_P, sizeof last_P);
-    c->last_filter = last_filter;
-    c->pp_after_last = pass;
-    return finish_sync_rerender(c);
-}
-
 int rtr_wait(rtr_ctx *c, int slot) {
     if (!c) return RTR_ERR_INVALID;
     NEED(c, slot >= -1 && slot < RTR_ASYNC_SLOTS, "slot out of range (-1: every slot)");
     DevGuard g(c->device);
-    for (int attempt = 0;; ++attempt) {
-        for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
-            if ((slot < 0 || k == slot) && c->ho[k].busy) HIP_TRY(c, hipEventSynchronize(c->ho[k].done));
-        bool retry = false;
-        int rc = check_store_error(c, attempt == 0 ? &retry : nullptr);
-        bool stale = false;
-        for (int k = 0; k < RTR_ASYNC_SLOTS; ++k) stale |= c->ho[k].busy && c->slot_frame[k].stale;
-        if (!rc && (retry || stale) && attempt == 0) {  // (once: the pool is worst-case sized from now on)
-            if ((rc = repair_slots(c))) return rc;
-            continue;
-        }
-        if (!rc && retry) rc = fail(c, RTR_ERR_INTERNAL, "rtr_wait: the extent pool overflowed again");
-        for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
-            if (slot < 0 || k == slot) c->ho[k].busy = false;
-        return rc;
-    }
+    for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
+        if ((slot < 0 || k == slot) && c->ho[k].busy) HIP_TRY(c, hipEventSynchronize(c->ho[k].done));
+    const int rc = repair(c, c->frame, true);  // (after an overflow: the stale slots, then the last whole frame)
+    // (a slot repeated there has queued its copies again, on the copy stream: they are finished before it is free)
+    for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
+        if ((slot < 0 || k == slot) && c->ho[k].busy) HIP_TRY(c, hipEventSynchronize(c->ho[k].done));
+    for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
+        if (slot < 0 || k == slot) c->ho[k].busy = false;
+    return rc;
 }
 
 int rtr_project_filtered(rtr_ctx *c, const float P[16], uint8_t *host_img, float *host_depth) {
@@ -1761,13 +1770,7 @@ static int p2p_alloc(rtr_ctx *c) {  // this rank's exchange buffers (per resolut
         HIP_TRY(c, hipMemsetAsync(q.flags, 0, 4096, c->stream));
         HIP_TRY(c, sync_streams(c));
     }
-    if (!q.status_host) {
-        HIP_TRY(c, hipHostMalloc((void **)&q.status_host, sizeof(uint32_t), hipHostMallocMapped));
-        *q.status_host = 0;
-        void *d = nullptr;
-        HIP_TRY(c, hipHostGetDevicePointer(&d, q.status_host, 0));
-        q.status_dev = static_cast<uint32_t *>(d);
-    }
+    if (!q.status_host) HIP_TRY(c, mapped_word(&q.status_host, &q.status_dev));
     return RTR_OK;
 }
 
@@ -1781,14 +1784,14 @@ int rtr_p2p_export(rtr_ctx *c, rtr_p2p_handles *mine) {
     HIP_TRY(c, sync_streams(c));
     // (the owner-computes form reads the peers' tile stores: allocate this rank's now -- it is sized by the cloud, for
     // the worst case: a pool the peers have mapped must never move)
-    c->cur = 0;
-    c->pool_worst = true;
-    if (int rc = ensure_lists(c)) return rc;
-    if (int rc = ensure_tiles(c, c->stream)) return rc;
+    c->frame.cur = 0;
+    c->frame.pool_worst = true;
+    if (int rc = ensure_pool(c, c->frame, c->F(), 0)) return rc;
+    if (int rc = ensure_store(c, c->frame, c->F(), 0, c->stream)) return rc;
     if (int rc = p2p_alloc(c)) return rc;
     HIP_TRY(c, sync_streams(c));
     memset(mine, 0, sizeof *mine);
-    void *bufs[9] = {c->depth, c->acc, c->p2p.ximg, c->p2p.red, c->p2p.flags, c->p2p.occ,
+    void *bufs[9] = {c->frame.depth, c->frame.acc, c->p2p.ximg, c->p2p.red, c->p2p.flags, c->p2p.occ,
                      c->F().store.meta, c->F().store.ext0, c->F().dyn};
     unsigned char *dst[9] = {mine->depth, mine->accum, mine->image, mine->reduced, mine->flags, mine->tiles,
                              mine->store_meta, mine->store_ext0, mine->store_dyn};
@@ -1812,7 +1815,7 @@ int rtr_p2p_open(rtr_ctx *c, int rank, int world, const rtr_p2p_handles *all) {
     NEED(c, !q.open, "already open (rtr_p2p_close first)");
     NEED(c, c->F().store.meta && c->F().store.ext0 && c->F().dyn, "the tile store changed since rtr_p2p_export (export again)");
     rtr::PeerSet *sets[9] = {&q.depth, &q.accum, &q.image, &q.reduced, &q.flags_of, &q.occ_of, &q.meta_of, &q.ext0_of, &q.dyn_of};
-    void *own[9] = {c->depth, c->acc, q.ximg, q.red, q.flags, q.occ, c->F().store.meta, c->F().store.ext0, c->F().dyn};
+    void *own[9] = {c->frame.depth, c->frame.acc, q.ximg, q.red, q.flags, q.occ, c->F().store.meta, c->F().store.ext0, c->F().dyn};
     for (int r = 0; r < world; ++r) {
         const unsigned char *src[9] = {all[r].depth, all[r].accum, all[r].image, all[r].reduced, all[r].flags, all[r].tiles,
                                        all[r].store_meta, all[r].store_ext0, all[r].store_dyn};
@@ -1896,7 +1899,7 @@ int rtr_p2p_min_depth(rtr_ctx *c) {
     if (q.whole_frame)
         q.depth_sliced = true;  // the accumulate launch reads the slices tile by tile and stores the result
     else
-        rtr::launch_p2p_gather(c->stream, q.reduced, c->depth, s.chunk * 4, npix * 4, -1);
+        rtr::launch_p2p_gather(c->stream, q.reduced, c->frame.depth, s.chunk * 4, npix * 4, -1);
     return launch_check(c, "p2p_min_depth");
 }
 
@@ -1916,7 +1919,7 @@ int rtr_p2p_sum_resolve(rtr_ctx *c) {
     if (q.whole_frame && q.pyramid_done)
         q.image_sliced = true;  // the fused prefilter reads the slices itself and writes RTR_BUF_IMAGE
     else
-        rtr::launch_p2p_gather(c->stream, q.image, c->img, s.chunk * 3, nbytes, -1);
+        rtr::launch_p2p_gather(c->stream, q.image, c->frame.img, s.chunk * 3, nbytes, -1);
     return launch_check(c, "p2p_sum_resolve");
 }
 
@@ -1968,7 +1971,7 @@ int rtr_p2p_render(rtr_ctx *c, const float P[16], int with_filter) {
     q.whole_frame = q.pyramid_done = q.depth_sliced = q.depth_peers = q.image_sliced = q.depth_in_red = false;
     if (!rc && from_red && !fused) {
         DevGuard g(c->device);
-        HIP_TRY(c, hipMemcpyAsync(c->depth, q.red, (size_t)c->W * c->H * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->frame.depth, q.red, (size_t)c->W * c->H * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     }
     if (!rc && with_filter) rc = filter_impl(c, parts, isl.chunk ? &isl : nullptr, (from_red && fused) ? q.red : nullptr);
     return rc;
@@ -1998,14 +2001,7 @@ int rtr_p2p_render_owned(rtr_ctx *c, const float P[16], int with_filter, int fra
     const unsigned long long ticks = 100000ull * (unsigned long long)c->opt_p2p_timeout_ms;
     // every rank's stream lengths and occupancy bitmap are final (and gathered into local memory)
     rtr::launch_p2p_sync_gather(c->stream, q.flags, q.flags_of, q.rank, q.world, ++q.seq, q.status_dev, ticks, q.occ_of, q.occ_all);
-    rtr::TilePyr pyr{};
-    pyr.enable = (mine && fused) ? 1 : 0;
-    if (pyr.enable) {
-        pyr.L = c->lv;
-        pyr.n_eff_rows = (uint32_t)((c->H >> 4) << 4);
-        pyr.part_min = c->part_min;
-        pyr.part_max = c->part_max;
-    }
+    const rtr::TilePyr pyr = tile_pyr(c, c->frame, 0, mine && fused);
     rtr::Sliced dsl{};
     dsl.occ_all = q.occ_all;
     dsl.peers = q.world;
@@ -2013,14 +2009,14 @@ int rtr_p2p_render_owned(rtr_ctx *c, const float P[16], int with_filter, int fra
     dsl.tab = q.tab;
     {   // the frame's owner writes its tiles where the frame ends up; everybody else into the buffers the owner reads
         Timed t(c, RTR_K_TILE);
-        rtr::launch_tile(c->stream, 4, c->W, c->H, c->F().store, c->prm.depth_window, c->depth, c->acc, mine ? c->img : q.ximg,
+        rtr::launch_tile(c->stream, 4, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, mine ? c->frame.img : q.ximg,
                          c->opt_keep_accum, pyr.enable ? &pyr : nullptr, &dsl);
     }
     mark_consumed(c);
     p2p_barrier(c);  // every tile of the frame is final on the rank that produced it; nobody reads a tile store any more
     if (int rc = launch_check(c, "owned tile frame")) return rc;
     if (!mine) return RTR_OK;
-    rtr::launch_p2p_collect(c->stream, c->W, c->H, q.tab, q.occ_all, q.world, q.rank, c->depth, c->img, pyr.enable ? &pyr : nullptr);
+    rtr::launch_p2p_collect(c->stream, c->W, c->H, q.tab, q.occ_all, q.world, q.rank, c->frame.depth, c->frame.img, pyr.enable ? &pyr : nullptr);
     if (int rc = launch_check(c, "collect")) return rc;
     if (with_filter) return filter_impl(c, pyr.enable ? rtr::tile_count(c->W, c->H) : 0);
     return RTR_OK;
@@ -2056,15 +2052,16 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
     const uint32_t *perm = c->reordered ? c->perm : nullptr;
     if (ids) HIP_TRY(c, hipMemsetAsync(ids, 0xFF, npix * 4, c->stream));
     if (vis && (perm || words == 0)) HIP_TRY(c, hipMemsetAsync(vis, 0, c->pp_vis_words * 4, c->stream));
-    rtr::launch_point_pass(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->depth, c->prm.depth_window, ids, vis, perm);
+    rtr::launch_point_pass(c->stream, cloud_of(c), make_proj(P), c->W, c->H, c->frame.depth, c->prm.depth_window, ids, vis, perm);
     if (int rc = launch_check(c, "point_pass")) return rc;
     HIP_TRY(c, hipEventRecord(c->pp_done, c->stream));
     if (vis) c->pp_vis_current = true;
-    memcpy(c->pp_P, P, sizeof c->pp_P);
-    c->pp_what = what;
-    c->pp_after_last = c->last_valid;  // (what a synchronising call repeats with the frame: finish_sync_rerender)
-    c->pp_since_sync = true;
-    c->pp_invalid = false;
+    auto &pass = c->jr.pass;  // (what a synchronising call repeats with the frame: repair)
+    memcpy(pass.P, P, sizeof pass.P);
+    pass.what = what;
+    pass.behind = c->jr.frame.count > 0;
+    pass.unchecked = true;
+    pass.invalid = false;
     return RTR_OK;
 }
 
@@ -2072,20 +2069,11 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
 // rtr_render_views (rtr.h, section 6c).  Binned batches: ONE point-kernel launch appends every view's points to that
 // view's tile store (rtr::launch_project_bin_views), then per view a lean tile launch (and the prefilter) writes the
 // view's slices of the batch buffers.  Every other form loops over the atomic form into the same slices.  Neither
-// touches the single frame's buffers, its tile stores, last_P or the asynchronous slots.
+// touches the single frame's target, its journal entries or the asynchronous slots.
 // The views' extent pools are adaptive like the single frame's (sized by the densest frame or view seen); a batch that
-// overflows one reports it through its own mapped word, and the next synchronising call (rtr_synchronize, a download
-// of RTR_BUF_VIEW_*) sizes every view's pool for the worst case -- 16 B per point and view -- and repeats the batch.
-
-static int views_mapped_word(rtr_ctx *c, uint32_t **host, uint32_t **dev) {
-    if (*host) return RTR_OK;
-    HIP_TRY(c, hipHostMalloc((void **)host, sizeof(uint32_t), hipHostMallocMapped));
-    **host = 0u;
-    void *d = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer(&d, *host, 0));
-    *dev = static_cast<uint32_t *>(d);
-    return RTR_OK;
-}
+// overflows one reports it through the views' own mapped word, and the next synchronising call (rtr_synchronize, a
+// download of RTR_BUF_VIEW_*) sizes every view's pool for the worst case -- 16 B per point and view -- and repeats the
+// batch (repair).
 
 static bool views_binned(const rtr_ctx *c) {  // the binned form serves batches; the rest loop over the atomic form
     return c->opt_mode == 1 && rtr::tile_count(c->W, c->H) <= 4096 && !c->p2p.open && !c->opt_overlap;
@@ -2093,77 +2081,32 @@ static bool views_binned(const rtr_ctx *c) {  // the binned form serves batches;
 
 // buffers, scratch and (binned) tile stores / pools for `count` views at this resolution and cloud
 static int ensure_views(rtr_ctx *c, int count, int with_filter) {
-    auto &v = c->vw;
-    const size_t npix = (size_t)c->W * c->H;
+    auto &v = c->views;
     if (count > v.cap) {
         HIP_TRY(c, sync_streams(c));  // (a batch in flight may still write the old buffers)
-        v.valid = false;
-        dfree(v.depth); dfree(v.img); dfree(v.tensor); dfree(v.minmax);
-        HIP_TRY(c, hipMalloc((void **)&v.depth, (size_t)count * npix * 4));
-        HIP_TRY(c, hipMalloc((void **)&v.img, ((size_t)count * npix * 3 + 15) & ~(size_t)15));
-        HIP_TRY(c, hipMalloc((void **)&v.tensor, (size_t)count * npix * 10));
-        HIP_TRY(c, hipMalloc((void **)&v.minmax, (size_t)count * 8));
-        v.cap = count;
+        c->jr.views.count = 0;
+        if (int rc = alloc_target(c, v, count)) return rc;
     }
-    if (!v.acc) {
-        const size_t nparts = (size_t)((c->W + 31) / 32) * ((c->H + 31) / 32);
-        HIP_TRY(c, hipMalloc((void **)&v.acc, npix * 16));
-        HIP_TRY(c, hipMalloc((void **)&v.mask, npix));
-        HIP_TRY(c, hipMalloc((void **)&v.part_min, nparts * 4));
-        HIP_TRY(c, hipMalloc((void **)&v.part_max, nparts * 4));
-    }
-    if (with_filter && v.lv_levels != c->prm.levels) {
-        for (int i = 1; i <= 8; ++i) dfree(v.lv[i]);
-        v.lv_levels = 0;
-        for (int i = 1, w = c->W / 2, h = c->H / 2; i <= c->prm.levels; ++i, w /= 2, h /= 2)
-            HIP_TRY(c, hipMalloc((void **)&v.lv[i], sizeof(float) * (size_t)w * h));
-        v.lv_levels = c->prm.levels;
-    }
-    if (!v.tab_host) {
-        HIP_TRY(c, hipHostMalloc(&v.tab_host, rtr::view_tab_bytes(), hipHostMallocDefault));
-        HIP_TRY(c, hipMalloc(&v.tab_dev, rtr::view_tab_bytes()));
-        HIP_TRY(c, hipEventCreateWithFlags(&v.tab_copied, hipEventDisableTiming));
+    if (with_filter)
+        if (int rc = ensure_levels(c, v)) return rc;
+    auto &tab = c->vtab;
+    if (!tab.host) {
+        HIP_TRY(c, hipHostMalloc(&tab.host, rtr::view_tab_bytes(), hipHostMallocDefault));
+        HIP_TRY(c, hipMalloc(&tab.dev, rtr::view_tab_bytes()));
+        HIP_TRY(c, hipEventCreateWithFlags(&tab.copied, hipEventDisableTiming));
     }
     if (!views_binned(c)) return ensure_soa(c);
-    if (int rc = views_mapped_word(c, &v.err_host, &v.err_dev)) return rc;
-    if (int rc = views_mapped_word(c, &v.entries_host, &v.entries_dev)) return rc;
-    // pools: the single frame's adaptive rule over the densest frame OR view seen, worst case after an overflow
-    const uint64_t worst = pool_worst_cap(c);
-    const uint64_t e = __atomic_load_n(v.entries_host, __ATOMIC_RELAXED);
-    if (e > v.entries_max) v.entries_max = e;
-    const uint64_t emax = v.entries_max > c->entries_max ? v.entries_max : c->entries_max;
-    const uint64_t floor_ = c->n / 2 > (1ull << 20) ? c->n / 2 : (1ull << 20);
     for (int k = 0; k < count; ++k) {
-        auto &f = v.fs[k];
-        if (int rc = alloc_store(c, f, c->stream)) return rc;
-        const uint64_t have = f.pool_n == c->n ? f.dyn_cap : 0;
-        uint64_t want = (c->opt_pool_worst || v.pool_worst) ? worst
-                        : (have >= 4 * emax && have >= floor_ ? have : (8 * emax > floor_ ? 8 * emax : floor_));
-        if (want > worst) want = worst;
-        if (!(f.dyn && f.pool_n == c->n && f.dyn_cap >= want)) {
-            HIP_TRY(c, sync_streams(c));
-            dfree(f.dyn);
-            f.dyn_cap = want;
-            f.pool_n = c->n;
-            HIP_TRY(c, hipMalloc((void **)&f.dyn, f.dyn_cap * sizeof(uint64_t)));
-        }
-        rtr::StoreConsts want_c{};
-        want_c.depth = v.depth + (size_t)k * npix;
-        want_c.acc = v.acc;
-        want_c.dyn = f.dyn; want_c.dyn_cap = f.dyn_cap;
-        if (c->opt_debug_dyn_cap >= 0 && (uint64_t)c->opt_debug_dyn_cap < want_c.dyn_cap) want_c.dyn_cap = (uint64_t)c->opt_debug_dyn_cap;
-        want_c.err_host = v.err_dev;
-        want_c.entries_host = v.entries_dev;
-        want_c.heavy = 0xFFFFFFFFu;  // (lean frames split nothing)
-        want_c.slice = (uint32_t)c->opt_slice;
-        if (int rc = upload_consts(c, f, c->stream, want_c)) return rc;
+        // (pools: the single frame's adaptive rule over the densest frame OR view seen)
+        if (int rc = ensure_pool(c, v, v.fs[k], c->frame.entries_max)) return rc;
+        if (int rc = ensure_store(c, v, v.fs[k], k, c->stream)) return rc;
     }
     return RTR_OK;
 }
 
 // the frame of view k: tile launch (binned) or the atomic form, then the prefilter, into the view's slices
 static int views_enqueue(rtr_ctx *c, int count, const float *P, int with_filter) {
-    auto &v = c->vw;
+    auto &v = c->views;
     if (int rc = ensure_views(c, count, with_filter)) return rc;
     const size_t npix = (size_t)c->W * c->H;
     const bool binned = views_binned(c);
@@ -2172,62 +2115,37 @@ static int views_enqueue(rtr_ctx *c, int count, const float *P, int with_filter)
         rtr::Proj proj[RTR_MAX_VIEWS];
         rtr::TileStore st[RTR_MAX_VIEWS];
         for (int k = 0; k < count; ++k) {
-            auto &t = v.fs[k].store;
-            t.fill_shift = c->opt_fill_shift >= 0 ? c->opt_fill_shift : 1;
-            t.seq = (t.seq + 1u) & 0xFFFFFFu;
-            if (t.seq == 0u) {  // the 24-bit stamp wrapped: forget every directory entry once
-                HIP_TRY(c, hipMemsetAsync(rtr::ts_dir(t), 0, (size_t)v.fs[k].nst * rtr::kDirK * sizeof(unsigned long long), c->stream));
-                t.seq = 1u;
-            }
+            v.fs[k].store.fill_shift = c->opt_fill_shift >= 0 ? c->opt_fill_shift : 1;
+            if (int rc = next_seq(c, v.fs[k], c->stream)) return rc;
             proj[k] = make_proj(P + 16 * k);
-            st[k] = t;
+            st[k] = v.fs[k].store;
         }
         if (count == 1) {  // (one view: the single frame's lean point kernel -- the table and the view loops cost ~15 us)
             Timed tm(c, RTR_K_MIN_DEPTH, c->stream, true);
             rtr::launch_project_bin(c->stream, cloud_of(c), proj[0], c->W, c->H, st[0], c->opt_cull ? c->bounds : nullptr,
-                                    2 | (c->opt_lane_test ? 0 : 4) | 8 | (c->opt_chunk_test ? 0 : 16), c->opt_phases, 0,
-                                    tm.a, tm.b);
+                                    t1_flags(c, false, true, true), c->opt_phases, 0, tm.a, tm.b);
         } else {
-            if (v.tab_pending) HIP_TRY(c, hipEventSynchronize(v.tab_copied));  // (the table's last copy has been read)
+            auto &tab = c->vtab;
+            if (tab.pending) HIP_TRY(c, hipEventSynchronize(tab.copied));  // (the table's last copy has been read)
             {
                 Timed tm(c, RTR_K_MIN_DEPTH, c->stream, true);
-                HIP_TRY(c, rtr::launch_project_bin_views(c->stream, cloud_of(c), proj, st, count, c->W, c->H, v.tab_host,
-                                                         v.tab_dev, c->opt_lane_test ? 0 : 4, c->opt_phases, tm.a, tm.b));
+                HIP_TRY(c, rtr::launch_project_bin_views(c->stream, cloud_of(c), proj, st, count, c->W, c->H, tab.host,
+                                                         tab.dev, c->opt_lane_test ? 0 : 4, c->opt_phases, tm.a, tm.b));
             }
-            HIP_TRY(c, hipEventRecord(v.tab_copied, c->stream));
-            v.tab_pending = true;
+            HIP_TRY(c, hipEventRecord(tab.copied, c->stream));
+            tab.pending = true;
         }
         if (int rc = launch_check(c, "views point kernel")) return rc;
     }
     for (int k = 0; k < count; ++k) {
         uint32_t *depth = v.depth + (size_t)k * npix;
         uint8_t *img = v.img + (size_t)k * npix * 3;
-        rtr::FilterLevels L{};
-        if (with_filter) {
-            L.levels = c->prm.levels;
-            L.lv[0] = reinterpret_cast<float *>(depth);
-            L.w[0] = c->W; L.h[0] = c->H;
-            for (int i = 1; i <= L.levels; ++i) L.lv[i] = v.lv[i], L.w[i] = L.w[i - 1] / 2, L.h[i] = L.h[i - 1] / 2;
-        }
         if (binned) {
-            rtr::TilePyr pyr{};
-            pyr.enable = pyr_fused ? 1 : 0;
-            if (pyr.enable) {
-                pyr.L = L;
-                pyr.n_eff_rows = (uint32_t)((c->H >> 4) << 4);
-                pyr.part_min = v.part_min;
-                pyr.part_max = v.part_max;
-            }
-            v.parity[k] ^= 1;
-            // (bit 64, as for the single frame: the first batch of entries before the counters when the tiles are expected
-            // full -- by the entry count of the last view whose statistics are complete)
-            int lean_bits = 8 | (c->opt_lean_identity ? 32 : 0);
-            const uint64_t e_last = __atomic_load_n(v.entries_host, __ATOMIC_RELAXED);
-            if (c->opt_lean_early > 0 || (c->opt_lean_early < 0 && e_last >= 1024ull * (uint64_t)rtr::tile_count(c->W, c->H)))
-                lean_bits |= 64;
+            const rtr::TilePyr pyr = tile_pyr(c, v, k, pyr_fused);
+            v.fs[k].parity ^= 1;
             Timed t(c, RTR_K_TILE);
             rtr::launch_tile(c->stream, 0, c->W, c->H, v.fs[k].store, c->prm.depth_window, depth, v.acc, img,
-                             lean_bits | (v.parity[k] << 4), pyr.enable ? &pyr : nullptr);
+                             lean_bits(c, v) | (v.fs[k].parity << 4), pyr_fused ? &pyr : nullptr);
         } else {
             const rtr::Proj pk = make_proj(P + 16 * k);
             { Timed t(c, RTR_K_CLEAR); rtr::launch_clear(c->stream, depth, v.acc, npix); }
@@ -2237,45 +2155,12 @@ static int views_enqueue(rtr_ctx *c, int count, const float *P, int with_filter)
         }
         if (with_filter) {
             Timed t(c, RTR_K_FILTER);
-            rtr::launch_filter(c->stream, L, depth, img, v.mask, v.tensor + (size_t)k * npix * 5, v.minmax + 2 * k,
+            rtr::launch_filter(c->stream, levels_of(c, v, k), depth, img, v.mask, v.tensor + (size_t)k * npix * 5, v.minmax + 2 * k,
                                v.part_min, v.part_max, c->W, c->H, c->prm.filter_strength, c->prm.gradient_threshold,
                                pyr_fused ? rtr::tile_count(c->W, c->H) : 0);
         }
         if (int rc = launch_check(c, "views frame")) return rc;
     }
-    return RTR_OK;
-}
-
-// after a synchronisation: the views' tile-store errors.  again (out, may be null): the last batch overflowed the
-// adaptive pools, which are worst-case sized from now on -- render it again
-static int views_check(rtr_ctx *c, bool *again) {
-    if (again) *again = false;
-    auto &v = c->vw;
-    if (!v.err_host) return RTR_OK;
-    const uint32_t e = __atomic_exchange_n(v.err_host, 0u, __ATOMIC_ACQUIRE);
-    if (e == 0u) return RTR_OK;
-    if (e == 2u && c->opt_debug_dyn_cap < 0 && !v.pool_worst && v.valid && again) {
-        v.pool_worst = true;
-        *again = true;
-        return RTR_OK;
-    }
-    v.valid = false;
-    return fail(c, RTR_ERR_INTERNAL, "tile store error 0x%x in a batch of views -- entries were dropped, the views are "
-                "incomplete: render the batch again", e);
-}
-
-static int views_download(rtr_ctx *c, const void *p, void *host, size_t b) {
-    HIP_TRY(c, sync_streams(c));
-    bool again = false;
-    int rc = views_check(c, &again);
-    if (!rc && again) {
-        if ((rc = views_enqueue(c, c->vw.count, c->vw.P, c->vw.with_filter))) return rc;
-        HIP_TRY(c, sync_streams(c));
-        if ((rc = views_check(c, nullptr))) return rc;
-    }
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(host, p, b, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, sync_streams(c));
     return RTR_OK;
 }
 
@@ -2287,20 +2172,14 @@ int rtr_render_views(rtr_ctx *c, int count, const float *P, int with_filter) {
     NEED(c, c->W > 0 && c->H > 0, "rtr_set_resolution has not been called");
     NEED(c, (c->n + 255) / 256 < (1ull << 24), "rtr_render_views: more than 2^32 - 256 points");
     DevGuard g(c->device);
-    if (with_filter) {  // the prefilter's conditions (ensure_pyramid), before anything changes
-        const int L = c->prm.levels;
-        if (L < 1 || L > 8) return fail(c, RTR_ERR_UNSUPPORTED, "levels must be in 1..8");
-        if ((c->W % (1 << L)) != 0 || (c->H >> L) < 1)
-            return fail(c, RTR_ERR_UNSUPPORTED, "prefilter needs W %% 2^levels == 0 and H >= 2^levels (got %dx%d, levels %d)",
-                        c->W, c->H, L);
-    }
-    auto &v = c->vw;
-    v.valid = false;
+    if (with_filter)  // (before anything changes)
+        if (int rc = check_prefilter(c)) return rc;
+    auto &rec = c->jr.views;
+    rec.count = 0;
     if (int rc = views_enqueue(c, count, P, with_filter)) return rc;
-    memcpy(v.P, P, sizeof(float) * 16 * (size_t)count);
-    v.count = count;
-    v.with_filter = with_filter;
-    v.valid = true;
+    memcpy(rec.P, P, sizeof(float) * 16 * (size_t)count);
+    rec.filter = with_filter;
+    rec.count = count;
     return RTR_OK;
 }
 
@@ -2314,12 +2193,12 @@ int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
     size_t npix = (size_t)c->W * c->H, b = 0;
     void *p = nullptr;
     switch (which) {
-        case RTR_BUF_DEPTH: p = c->depth; b = npix * 4; break;
-        case RTR_BUF_ACCUM: p = c->acc; b = npix * 16; break;
-        case RTR_BUF_IMAGE: p = c->img; b = npix * 3; break;
-        case RTR_BUF_TENSOR: p = c->tensor; b = npix * 10; break;
-        case RTR_BUF_MASK: p = c->mask; b = npix; break;
-        case RTR_BUF_MINMAX: p = c->minmax; b = 8; break;
+        case RTR_BUF_DEPTH: p = c->frame.depth; b = npix * 4; break;
+        case RTR_BUF_ACCUM: p = c->frame.acc; b = npix * 16; break;
+        case RTR_BUF_IMAGE: p = c->frame.img; b = npix * 3; break;
+        case RTR_BUF_TENSOR: p = c->frame.tensor; b = npix * 10; break;
+        case RTR_BUF_MASK: p = c->frame.mask; b = npix; break;
+        case RTR_BUF_MINMAX: p = c->frame.minmax; b = 8; break;
         case RTR_BUF_POINT_ID:
             NEED(c, c->pp_ids != nullptr, "RTR_BUF_POINT_ID: no rtr_point_pass with RTR_POINTS_IDS at this resolution yet");
             p = c->pp_ids; b = npix * 4; break;
@@ -2327,12 +2206,12 @@ int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
             NEED(c, c->pp_vis != nullptr && c->pp_vis_current, "RTR_BUF_VISIBLE: no rtr_point_pass with RTR_POINTS_VISIBLE for the resident cloud yet");
             p = c->pp_vis; b = (size_t)((c->n + 31) / 32) * 4; break;
         case RTR_BUF_VIEW_DEPTH: case RTR_BUF_VIEW_IMAGE: case RTR_BUF_VIEW_TENSOR: case RTR_BUF_VIEW_MINMAX: {
-            NEED(c, c->vw.valid, "RTR_BUF_VIEW_*: no rtr_render_views at this resolution for the resident cloud yet");
-            const size_t k = (size_t)c->vw.count;
-            if (which == RTR_BUF_VIEW_DEPTH) p = c->vw.depth, b = k * npix * 4;
-            else if (which == RTR_BUF_VIEW_IMAGE) p = c->vw.img, b = k * npix * 3;
-            else if (which == RTR_BUF_VIEW_TENSOR) p = c->vw.tensor, b = k * npix * 10;
-            else p = c->vw.minmax, b = k * 8;
+            NEED(c, c->jr.views.count > 0, "RTR_BUF_VIEW_*: no rtr_render_views at this resolution for the resident cloud yet");
+            const size_t k = (size_t)c->jr.views.count;
+            if (which == RTR_BUF_VIEW_DEPTH) p = c->views.depth, b = k * npix * 4;
+            else if (which == RTR_BUF_VIEW_IMAGE) p = c->views.img, b = k * npix * 3;
+            else if (which == RTR_BUF_VIEW_TENSOR) p = c->views.tensor, b = k * npix * 10;
+            else p = c->views.minmax, b = k * 8;
             break;
         }
         default: return fail(c, RTR_ERR_INVALID, "unknown buffer id %d", which);
@@ -2350,18 +2229,19 @@ int rtr_download_buffer(rtr_ctx *c, int which, void *host, size_t bytes) {
     if (rc) return rc;
     NEED(c, bytes == b, "size mismatch");
     DevGuard g(c->device);
-    if (which >= RTR_BUF_VIEW_DEPTH && which <= RTR_BUF_VIEW_MINMAX) return views_download(c, p, host, b);
-    HIP_TRY(c, hipMemcpyAsync(host, p, b, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, sync_streams(c));
-    bool retry = false;
-    rc = check_store_error(c, c->last_valid ? &retry : nullptr);
-    if (!rc && retry) {  // (the adaptive extent pool overflowed: the frame -- and a point pass behind it -- again, then the copy)
-        if ((rc = finish_sync_rerender(c))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(host, p, b, hipMemcpyDeviceToHost, c->stream));
+    const Copy copy{host, p, b};
+    if (which >= RTR_BUF_VIEW_DEPTH && which <= RTR_BUF_VIEW_MINMAX) {  // (a batch: checked -- and repaired -- before the copy)
         HIP_TRY(c, sync_streams(c));
-        rc = check_store_error(c);
+        if ((rc = repair(c, c->views))) return rc;
+        HIP_TRY(c, queue_copies(c, &copy, 1));
+        HIP_TRY(c, sync_streams(c));
+        return RTR_OK;
     }
-    if (!rc && (which == RTR_BUF_POINT_ID || which == RTR_BUF_VISIBLE) && c->pp_invalid)
+    HIP_TRY(c, queue_copies(c, &copy, 1));
+    HIP_TRY(c, sync_streams(c));
+    // (after an overflow of the adaptive pool: the frame and a point pass behind it again, then the copy)
+    rc = repair(c, c->frame, false, &copy, 1);
+    if (!rc && (which == RTR_BUF_POINT_ID || which == RTR_BUF_VISIBLE) && c->jr.pass.invalid)
         rc = fail(c, RTR_ERR_INTERNAL, "the last rtr_point_pass read a frame the tile store reported incomplete (the adaptive "
                   "extent pool overflowed and a later frame was rendered before a synchronising call): render the frame and "
                   "run the point pass again");
