@@ -385,6 +385,32 @@ int rtr_point_pass(rtr_ctx *ctx, const float P[16], int what);
 #define RTR_MAX_VIEWS 8
 int rtr_render_views(rtr_ctx *ctx, int count, const float *P, int with_filter);
 
+/* ---- 6d. clip planes: leave part of the cloud out of every frame ------------------------------------
+ * Up to RTR_MAX_CLIP_PLANES world-space half-spaces, each {a, b, c, d} (planes: count x 4 floats).  A point (x, y, z)
+ * of the uploaded cloud -- the coordinates as uploaded: packing and the Morton sort do not change them -- is kept iff
+ * for every plane
+ *     ((a*x + b*y) + c*z) + d >= 0
+ * with every product and sum rounded to fp32 on its own (no FMA; NaN is not >= 0): numpy float32 arithmetic in that
+ * order is an exact reference.  For the unit-normal planes of an axis-aligned box -- {1,0,0,-lo.x}, {-1,0,0,hi.x}, and
+ * the same in y and z -- the test is exactly lo <= p <= hi per axis, points on the faces included.
+ * A point that is not kept acts as if it were absent from the cloud in every output: depth, accumulators, image,
+ * prefilter mask / tensor / min-max, RTR_BUF_POINT_ID never names it, its RTR_BUF_VISIBLE bit is 0, and the frame
+ * statistics and the adaptive extent pool's sizing never count it.  Every call that renders honours them: rtr_project
+ * (_filtered), rtr_render, rtr_project_async, the phase calls, rtr_point_pass, rtr_render_views (the planes are shared
+ * by every view) and rtr_p2p_render(_owned) -- a sharded frame uses each rank's own planes, so the caller sets the same
+ * ones on every rank.  rtr_stream_probe ignores them.  Chunks that lie outside a plane are rejected on their boxes
+ * before their coordinates are read, so a crop costs less than the whole frame.
+ * The planes are context state like rtr_params: a call uses the planes in force when it is issued, and a frame that a
+ * synchronising call renders again (an overflow of the adaptive pool, an async slot that rtr_wait repeats) comes out
+ * with the planes it was issued with.  count = 0 (the default) clears them; frames are then exactly as without this
+ * section.
+ * Errors: count outside 0..RTR_MAX_CLIP_PLANES, planes NULL with count > 0, a non-finite coefficient or a = b = c = 0
+ * -> RTR_ERR_INVALID, nothing changed.  rtr_get_clip_planes writes the count and count x 4 floats (room for
+ * RTR_MAX_CLIP_PLANES x 4; planes may be NULL while none are set). */
+#define RTR_MAX_CLIP_PLANES 8
+int rtr_set_clip_planes(rtr_ctx *ctx, int count, const float *planes);
+int rtr_get_clip_planes(rtr_ctx *ctx, int *count, float *planes);
+
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {
     RTR_K_CLEAR = 0, RTR_K_MIN_DEPTH = 1, RTR_K_ACCUMULATE = 2, RTR_K_RESOLVE = 3, RTR_K_FILTER = 4,

@@ -18,7 +18,8 @@
 //
 // Beyond the reference: computePointIds / visible_points (rtr.h section 6b) name the points a frame shows, by their
 // index in the grid's flattened vertex order (the order the constructor uploads); construct with point_ids = true
-// when the library may sort the cloud (its default upload policy does for unordered clouds).
+// when the library may sort the cloud (its default upload policy does for unordered clouds).  setClipPlanes /
+// setClipBox / clearClip (rtr.h section 6d) leave part of the cloud out of every later frame.
 //
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
@@ -173,6 +174,31 @@ public:
         return p;
     }
     rtr_ctx* context() const { return ctx_; }
+
+    // Clip planes (rtr.h section 6d): every later frame leaves out the points outside any of `count` (<= 8) world-space
+    // half-spaces {a, b, c, d} (planes: count x 4 floats) -- kept iff ((a x + b y) + c z) + d >= 0 in fp32 for each.
+    void setClipPlanes(const float* planes, int count) { check(ctx_, rtr_set_clip_planes(ctx_, count, planes)); }
+    // Keeps only the points inside the box lo <= q <= hi, q = M p (M: 4x4 row-major world -> box; null: the world axes,
+    // where the test is exactly lo <= p <= hi per axis, faces included).  With M the six planes are computed in double
+    // and rounded to float once; those float planes define what is kept.
+    void setClipBox(const float lo[3], const float hi[3], const double* M = nullptr) {
+        float pl[6][4] = {};
+        for (int k = 0; k < 3; ++k) {
+            if (!M) {
+                pl[2 * k][k] = 1.f, pl[2 * k][3] = -lo[k];
+                pl[2 * k + 1][k] = -1.f, pl[2 * k + 1][3] = hi[k];
+                continue;
+            }
+            for (int j = 0; j < 3; ++j) {
+                pl[2 * k][j] = (float)M[4 * k + j];
+                pl[2 * k + 1][j] = (float)-M[4 * k + j];
+            }
+            pl[2 * k][3] = (float)(M[4 * k + 3] - (double)lo[k]);
+            pl[2 * k + 1][3] = (float)((double)hi[k] - M[4 * k + 3]);
+        }
+        setClipPlanes(&pl[0][0], 6);
+    }
+    void clearClip() { check(ctx_, rtr_set_clip_planes(ctx_, 0, nullptr)); }
 
     // Renders the frame (computeRGBD / computeFilteredRGBD without host copies) and returns, per pixel (row-major
     // H x W), the vertex index of the point it shows, -1 for none (empty or prefiltered-away pixels).

@@ -60,6 +60,43 @@ def compose_projection(K, E):
     return P.reshape(16)
 
 
+def clip_box_planes(lo, hi, M=None):
+    """The six clip planes (float32 (6, 4): rtr_set_clip_planes) that keep the points inside a box.  Without M the box
+    is lo <= p <= hi in world coordinates (lo, hi rounded to float32): planes {1,0,0,-lo.x}, {-1,0,0,hi.x}, ... and y, z,
+    whose float32 test is exactly that comparison per axis, points on the faces kept.  With M (4x4 world -> box
+    coordinates q = M[:3,:3] p + M[:3,3]) the box is lo <= q <= hi: planes (M[k,:3], M[k,3] - lo[k]) and
+    (-M[k,:3], hi[k] - M[k,3]), computed in float64 and rounded to float32 once -- those float32 planes, not the real
+    box, define what is kept."""
+    lo = np.asarray(lo, dtype=np.float64).reshape(3)
+    hi = np.asarray(hi, dtype=np.float64).reshape(3)
+    out = np.zeros((6, 4), np.float32)
+    if M is None:
+        lo32, hi32 = lo.astype(np.float32), hi.astype(np.float32)
+        for k in range(3):
+            out[2 * k, k], out[2 * k, 3] = np.float32(1), -lo32[k]
+            out[2 * k + 1, k], out[2 * k + 1, 3] = np.float32(-1), hi32[k]
+        return out
+    M = np.asarray(M, dtype=np.float64).reshape(4, 4)
+    for k in range(3):
+        out[2 * k, :3] = M[k, :3]
+        out[2 * k, 3] = M[k, 3] - lo[k]
+        out[2 * k + 1, :3] = -M[k, :3]
+        out[2 * k + 1, 3] = hi[k] - M[k, 3]
+    return out
+
+
+def clip_keep(planes, xyz):
+    """The exact reference of the clip test (rtr.h section 6d) in numpy float32: bool per point of xyz ([n, >= 3])."""
+    planes = np.asarray(planes, dtype=np.float32).reshape(-1, 4)
+    p = np.asarray(xyz)
+    x, y, z = (np.ascontiguousarray(p[:, k], dtype=np.float32) for k in range(3))
+    keep = np.ones(len(p), bool)
+    with np.errstate(all="ignore"):
+        for a, b, c, d in planes:
+            keep &= (((a * x + b * y) + c * z) + d) >= np.float32(0)
+    return keep
+
+
 def benchmark_calibration(width, height):
     """OPENCV pinhole, zero distortion, fx = fy = 0.8 W, cx = W/2, cy = H/2."""
     return CameraCalibration.pinhole(0.8 * width, 0.8 * width, width / 2.0, height / 2.0, width, height)

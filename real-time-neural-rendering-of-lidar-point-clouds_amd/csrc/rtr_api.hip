@@ -50,6 +50,7 @@ struct rtr_ctx {
     int opt_pack = 1;               // 0 never, 1 when it saves >= 1/8 of the coordinate stream, 2 always + verified after packing
 
     int W = 0, H = 0;  // resolution
+    rtr::Clip clip{};  // the user's clip planes (rtr_set_clip_planes; count 0: none): every point kernel of a frame honours them
 
     // tile-binned pipeline: the tile store T1 appends to and T4 reads (rtr_kernels.h)
     struct FrontSet {
@@ -190,6 +191,7 @@ struct rtr_ctx {
         struct Frames {
             float P[RTR_MAX_VIEWS * 16] = {0};
             int count = 0, filter = 0;
+            rtr::Clip clip{};  // the clip planes the frames were issued with
         };
         Frames frame;  // the last whole frame (rtr_render): count 0 or 1
         Frames views;  // the last batch of views (rtr_render_views); count 0: none, or it is incomplete
@@ -199,12 +201,14 @@ struct rtr_ctx {
             bool behind = false;     // queued right behind the last whole frame, nothing rendered since: repeated with it
             bool unchecked = false;  // queued, and not yet known to have read a complete frame
             bool invalid = false;    // its outputs came from a frame the tile store reported incomplete
+            rtr::Clip clip{};
         } pass;
         struct Slot {  // the frame queued into each async slot; `stale`: queued before the pool grew (rtr_wait repeats it)
             float P[16] = {0};
             int filter = 0;
             bool stale = false;
             uint64_t cloud = 0;  // cloud_seq when it was queued
+            rtr::Clip clip{};
         } slot[RTR_ASYNC_SLOTS];
     } jr;
 };
@@ -565,7 +569,8 @@ rtr::Cloud cloud_of(const rtr_ctx *c) {
     // cloud measures ~1.0; the reference loader's 0.25 m blocks in hash-map order, unordered inside, measure 0.28 for a
     // 10 m room and must keep the wave-level claim groups: 0.33 ms instead of 0.66 ms per frame without them)
     return rtr::Cloud{c->x, c->y, c->z, c->rgba, c->n, c->opt_grid, (!c->reordered && c->order_ratio > 0.5f) ? 1 : 0,
-                      rtr::PackedXyz{c->pk_hdr, c->pk_planes, c->pk_planes_b}, c->spread, {c->absmax[0], c->absmax[1], c->absmax[2]}};
+                      rtr::PackedXyz{c->pk_hdr, c->pk_planes, c->pk_planes_b}, c->spread, {c->absmax[0], c->absmax[1], c->absmax[2]},
+                      c->clip};
 }
 
 struct Timed {  // brackets one phase with hipEvents on the stream it is launched on
@@ -1032,6 +1037,35 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     return RTR_OK;
 }
 
+// ---- clip planes (rtr.h, section 6d) ------------------------------------------------
+int rtr_set_clip_planes(rtr_ctx *c, int count, const float *planes) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, count >= 0 && count <= RTR_MAX_CLIP_PLANES, "clip planes: count outside 0..RTR_MAX_CLIP_PLANES");
+    NEED(c, count == 0 || planes != nullptr, "clip planes: planes is NULL");
+    rtr::Clip next{};
+    for (int j = 0; j < count; ++j) {
+        for (int k = 0; k < 4; ++k) {
+            NEED(c, std::isfinite(planes[4 * j + k]), "clip planes: a coefficient is not finite");
+            next.p[j][k] = planes[4 * j + k];
+        }
+        NEED(c, next.p[j][0] != 0.f || next.p[j][1] != 0.f || next.p[j][2] != 0.f, "clip planes: a = b = c = 0");
+    }
+    next.count = count;
+    if (memcmp(&next, &c->clip, sizeof next) != 0) c->list_valid = false;  // (bins of other planes serve no later pass)
+    c->clip = next;
+    return RTR_OK;
+}
+
+int rtr_get_clip_planes(rtr_ctx *c, int *count, float *planes) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, count != nullptr, "count is NULL");
+    NEED(c, c->clip.count == 0 || planes != nullptr, "planes is NULL");
+    *count = c->clip.count;
+    for (int j = 0; j < c->clip.count; ++j)
+        for (int k = 0; k < 4; ++k) planes[4 * j + k] = c->clip.p[j][k];
+    return RTR_OK;
+}
+
 int rtr_stream_probe(rtr_ctx *c, const float P[16]) {
     if (!c) return RTR_ERR_INVALID;
     NEED(c, P != nullptr, "P is NULL");
@@ -1136,6 +1170,12 @@ static int repair(rtr_ctx *c, rtr_ctx::Target &t, bool slots = false, const Copy
         HIP_TRY(c, sync_streams(c));
         if (int rc = check(true)) return rc;
     }
+    // (every frame goes again with the clip planes it was issued with; the context's own come back afterwards)
+    struct ClipScope {
+        rtr_ctx *c;
+        rtr::Clip keep;
+        ~ClipScope() { c->clip = keep; }
+    } clip_scope{c, c->clip};
     if (single) {
         const auto frame = own ? *own : j.frame;  // (the slots' frames below replace the record)
         const auto pass = j.pass;
@@ -1145,15 +1185,19 @@ static int repair(rtr_ctx *c, rtr_ctx::Target &t, bool slots = false, const Copy
             if (f.cloud != c->cloud_seq)
                 return fail(c, RTR_ERR_INTERNAL, "rtr_wait: the frame of slot %d lost entries in an overflowing extent pool "
                             "and the cloud has been replaced since: it cannot be rendered again", k);
+            c->clip = f.clip;
             if (int rc = queue_slot(c, f.P, k, f.filter)) return rc;
         }
         if (frame.count) {
+            c->clip = frame.clip;
             if (int rc = rtr_render(c, frame.P, frame.filter)) return rc;
+            c->clip = pass.clip;
             if (pass.behind)
                 if (int rc = rtr_point_pass(c, pass.P, pass.what)) return rc;
         }
-    } else if (int rc = views_enqueue(c, j.views.count, j.views.P, j.views.filter)) {
-        return rc;
+    } else {
+        c->clip = j.views.clip;
+        if (int rc = views_enqueue(c, j.views.count, j.views.P, j.views.filter)) return rc;
     }
     HIP_TRY(c, queue_copies(c, copies, ncopies));
     HIP_TRY(c, sync_streams(c));
@@ -1638,6 +1682,7 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
         memcpy(rec.P, P, sizeof(float) * 16);
         rec.filter = with_filter;
         rec.count = 1;
+        rec.clip = c->clip;
     } else {
         c->force_atomic = true;  // the phase calls below must not take the binned form either
         rc = rtr_clear(c);
@@ -1664,6 +1709,7 @@ static int frame_to_host(rtr_ctx *c, const float P[16], uint8_t *host_img, float
     memcpy(own.P, P, sizeof(float) * 16);
     own.count = 1;
     own.filter = with_filter;
+    own.clip = c->clip;
     return repair(c, c->frame, false, copies, 2, &own);
 }
 
@@ -1723,6 +1769,7 @@ static int queue_slot(rtr_ctx *c, const float P[16], int slot, int with_filter) 
     f.filter = with_filter;
     f.stale = false;
     f.cloud = c->cloud_seq;
+    f.clip = c->clip;
     h.busy = true;
     return RTR_OK;
 }
@@ -2062,6 +2109,7 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
     pass.behind = c->jr.frame.count > 0;
     pass.unchecked = true;
     pass.invalid = false;
+    pass.clip = c->clip;
     return RTR_OK;
 }
 
@@ -2180,6 +2228,7 @@ int rtr_render_views(rtr_ctx *c, int count, const float *P, int with_filter) {
     memcpy(rec.P, P, sizeof(float) * 16 * (size_t)count);
     rec.filter = with_filter;
     rec.count = count;
+    rec.clip = c->clip;
     return RTR_OK;
 }
 

@@ -65,4 +65,51 @@ RTR_HD bool chunk_box(uint32_t bx, uint32_t by, uint32_t bz, uint32_t widths, fl
     return ok;
 }
 
+// ---- user clip planes (rtr_set_clip_planes) ----------------------------------------------------------------------
+// A point (x, y, z) of the uploaded cloud is kept iff ((a x + b y) + c z) + d >= 0 for every plane {a, b, c, d}, each
+// product and sum rounded to fp32 on its own (no FMA: this header is compiled with -ffp-contract=off everywhere).  NaN
+// is not >= 0.  For the unit normals of an axis-aligned box ({1, 0, 0, -lo}, {-1, 0, 0, hi}, ...) this is exactly
+// lo <= x <= hi: 0 x y and 0 x z are +-0, the sums x + +-0 are x (or +0 for x = -0, which still compares as 0), and
+// x - lo rounds to >= 0 exactly when x >= lo (round-to-nearest is monotonic and x - lo = 0 only for x = lo).
+// Passed BY VALUE to the point kernels (like Proj); count = 0 never reaches a kernel.
+constexpr int kMaxClipPlanes = 8;
+struct Clip {
+    float p[kMaxClipPlanes][4];
+    int count;
+};
+RTR_HD bool clip_keep(const Clip &c, float x, float y, float z) {
+    bool keep = true;
+    for (int j = 0; j < c.count; ++j) {
+        const float a = c.p[j][0] * x, b = c.p[j][1] * y, s = a + b, cz = c.p[j][2] * z, t = s + cz, v = t + c.p[j][3];
+        keep = keep && (v >= 0.f);
+    }
+    return keep;
+}
+// The box [lo, hi] lies entirely on the wrong side of one clip plane: no point in it can pass clip_keep.  Same form as
+// box_outside -- the largest value of a.p + d over the box, v, against a slack of 1e-4 x the magnitude of its terms, m,
+// plus 2^-126 for products that leave the normal range.  Why no box holding a point p that clip_keep keeps is rejected
+// (u = 2^-24, T = |a x| + |b y| + |c z| + |d| of the plane at p, all <= m's real value M):
+//   - the point test: each of its three products errs by <= u |term| + 2^-150 (2^-150: a product in the subnormal range;
+//     sums carry no absolute error there) and each of its three sums by <= u |partial sum|, so its real value
+//     a.p + d >= computed - 3.01 u T - 3 x 2^-150 >= -3.01 u M - 2^-148 (computed >= 0);
+//   - the box arithmetic: its products round the real ones monotonically, so max(fl(a lo), fl(a hi)) >= fl(a p_k) >=
+//     a p_k - u |a p_k| - 2^-150; the three sums of those maxima err by <= 3.01 u M more, hence
+//     v >= a.p + d - 4.02 u M - 2^-148 >= -7.1 u M - 2^-147 (~ -4.3e-7 M), and the computed m is >= M (1 - 7.1 u);
+//   - rejection needs v < -1e-4 m - 2^-126, more than 200 times that distance: it never happens.
+// NaN (0 x inf, a NaN coefficient) compares false and an infinite box end makes m infinite: neither is ever rejected.
+RTR_HD bool clip_box_outside(const Clip &c, const float lo[3], const float hi[3]) {
+    bool culled = false;
+    for (int j = 0; j < c.count; ++j) {
+        float v = c.p[j][3], m = __builtin_fabsf(c.p[j][3]);
+        for (int k = 0; k < 3; ++k) {
+            const float t0 = c.p[j][k] * lo[k], t1 = c.p[j][k] * hi[k];
+            v += t0 > t1 ? t0 : t1;
+            const float e0 = __builtin_fabsf(lo[k]), e1 = __builtin_fabsf(hi[k]);
+            m += __builtin_fabsf(c.p[j][k]) * (e0 > e1 ? e0 : e1);
+        }
+        culled = culled || (v < -1e-4f * m - 0x1p-126f);
+    }
+    return culled;
+}
+
 }  // namespace rtr

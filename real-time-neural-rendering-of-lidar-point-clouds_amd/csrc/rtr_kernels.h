@@ -56,6 +56,7 @@ struct Cloud {
     // k_project_bin, "lane test").  null: no lane test.  absmax: largest finite |x|, |y|, |z| of the cloud.
     const float *spread;
     float absmax[3];
+    Clip clip;  // the user's clip planes (rtr_set_clip_planes; count 0: none): the point kernels launch their CLIP forms
 };
 
 struct FilterLevels {

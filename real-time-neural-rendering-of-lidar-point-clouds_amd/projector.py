@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .camera import compose_projection
+from .camera import clip_box_planes, compose_projection
 
 
 def _vp(a):
@@ -185,6 +185,29 @@ class Projector:
             raise ValueError("Ps must have shape [K,4,4] or [K,16]")
         Ps = Ps.reshape(-1, 16)
         self._chk(self._lib.rtr_render_views(self._ctx, Ps.shape[0], _vp(Ps), 1 if with_filter else 0))
+
+    # -- clip planes (rtr.h section 6d)
+    def set_clip_planes(self, planes):
+        """Leaves out of every later frame the points outside any of up to MAX_CLIP_PLANES world-space half-spaces:
+        planes is a (k, 4) array of {a, b, c, d} (rounded to float32), a point is kept iff ((a x + b y) + c z) + d >= 0
+        in float32 for each of them.  None or an empty array clears them."""
+        if planes is None:
+            self._chk(self._lib.rtr_set_clip_planes(self._ctx, 0, None))
+            return
+        planes = np.ascontiguousarray(planes, dtype=np.float32)
+        if planes.size == 0:
+            self._chk(self._lib.rtr_set_clip_planes(self._ctx, 0, None))
+            return
+        if planes.ndim != 2 or planes.shape[1] != 4:
+            raise ValueError("planes must have shape (k, 4)")
+        self._chk(self._lib.rtr_set_clip_planes(self._ctx, planes.shape[0], _vp(planes)))
+
+    def clip_planes(self):
+        """The clip planes in force: float32 (k, 4), k = 0 when there are none."""
+        out = np.zeros((L.MAX_CLIP_PLANES, 4), np.float32)
+        k = C.c_int32()
+        self._chk(self._lib.rtr_get_clip_planes(self._ctx, C.byref(k), _vp(out)))
+        return out[:k.value].copy()
 
     # -- point pass (rtr.h section 6b)
     def point_pass(self, P, ids=True, visible=True):
@@ -374,6 +397,20 @@ class ProjectCloud:
         fn = self._p._lib.rtr_project_filtered if filtered else self._p._lib.rtr_project
         self._p._chk(fn(self._p._ctx, _vp(P), _vp(color), _vp(depth)))
         return 1
+
+    def setClipPlanes(self, planes):
+        """Every later frame leaves out the points outside the world-space half-spaces `planes` ((k, 4), k <= 8, see
+        Projector.set_clip_planes); None or empty clears them."""
+        self._p.set_clip_planes(planes)
+
+    def setClipBox(self, lo, hi, M=None):
+        """Keeps only the points inside the box lo <= q <= hi, q = M p (M: 4x4 world -> box; None: the world axes,
+        where the test is exactly lo <= p <= hi per axis, faces included).  See camera.clip_box_planes."""
+        self._p.set_clip_planes(clip_box_planes(lo, hi, M))
+
+    def clearClip(self):
+        """No clip planes: the whole cloud again."""
+        self._p.set_clip_planes(None)
 
     def computeRGBD(self, calibration, extrinsics, color, depth):
         """project_cloud.cu:268-312.  extrinsics = world->camera 4x4 (main.cpp:96)."""
