@@ -180,7 +180,8 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *  "xp": only in RTR_EXPERIMENT builds (make experiment): switches parts of the point kernel off for
  *          timing attribution -- frames are WRONG while it is non-zero; the shipped library rejects it.
  *  "probe_variant": measurement aid of tools/probe_variants.py (selects the rtr_stream_probe kernel).
- *  rtr_get_option("views") reads the view count of the last rtr_render_views batch (section 6c; 0: none current). */
+ *  rtr_get_option("views") reads the view count of the last rtr_render_views batch (section 6c; 0: none current).
+ *  rtr_get_option("point_keep") reads 1 while a keep mask is set (section 6e). */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
 /* Reads an option back; also "p2p_open" (see "p2p_timeout_ms"), "reordered" (1: the resident cloud was sorted by the library),
  * "order_ratio_ppm" (mean chunk-box diagonal / cloud diagonal as uploaded, in millionths), "packed" and
@@ -333,7 +334,8 @@ typedef enum {
     RTR_BUF_VIEW_DEPTH = 8,   /* u32 [count, H, W]                                                       */
     RTR_BUF_VIEW_IMAGE = 9,   /* u8  [count, H, W, 3]                                                    */
     RTR_BUF_VIEW_TENSOR = 10, /* f16 [count, 5, H, W]  one contiguous batch tensor                       */
-    RTR_BUF_VIEW_MINMAX = 11  /* u32 [count, 2]                                                          */
+    RTR_BUF_VIEW_MINMAX = 11, /* u32 [count, 2]                                                          */
+    RTR_BUF_POINT_KEEP = 12   /* u32 [(n + 31) / 32]  the keep mask in force (section 6e), upload order, bits past n clear */
 } rtr_buffer;
 int rtr_device_buffer(rtr_ctx *ctx, int which, void **dev_ptr, size_t *bytes);
 /* Synchronous device->host copy of one buffer (bytes must equal its size). */
@@ -410,6 +412,31 @@ int rtr_render_views(rtr_ctx *ctx, int count, const float *P, int with_filter);
 #define RTR_MAX_CLIP_PLANES 8
 int rtr_set_clip_planes(rtr_ctx *ctx, int count, const float *planes);
 int rtr_get_clip_planes(rtr_ctx *ctx, int *count, float *planes);
+
+/* ---- 6e. keep mask: hide any set of points from every frame ---------------------------------------------------------
+ * words: (n + 31) / 32 u32 in upload order -- bit i % 32 of word i / 32 set = point i is kept: the layout of
+ * RTR_BUF_VISIBLE, so a point pass's output can be fed straight back.  Host memory or device memory of the context's
+ * device (copied; the caller may reuse it at once).  words == NULL with nwords == 0 clears the mask.  Bits past n are
+ * ignored and read back as 0 (RTR_BUF_POINT_KEEP; rtr_get_option("point_keep") reads 1 while a mask is set).
+ * Indices are the point pass's: the index in the rtr_upload_points array, or i - first for rtr_generate_synthetic.  A
+ * cloud sorted by the library needs option "point_ids" = 1 (the mask goes through its permutation; rtr_reorder_points
+ * keeps the mask in force and refuses to sort a masked cloud without point_ids).
+ * A hidden point acts as if it were absent from the cloud in every output, exactly as a clipped point (section 6d):
+ * depth, accumulators, image, prefilter mask / tensor / min-max, RTR_BUF_POINT_ID never names it, its RTR_BUF_VISIBLE
+ * bit is 0, and the frame statistics and the adaptive extent pool's sizing never count it.  Every call that renders
+ * honours it: rtr_project(_filtered), rtr_render, rtr_project_async, the phase calls, rtr_point_pass,
+ * rtr_render_views (shared by every view) and rtr_p2p_render(_owned) -- each rank its own mask, in its own rank-local
+ * indices.  rtr_stream_probe and rtr_download_points ignore it.  With clip planes a point is drawn iff the mask AND
+ * every plane keep it.  Chunks of 256 resident points that the mask hides entirely are rejected before their
+ * coordinates are read.
+ * Ordering: the call first completes every frame, pass, view batch and async slot issued before it, as rtr_synchronize
+ * does (frames that overflowed the adaptive pool are rendered again with the mask they were issued with); if that
+ * fails it returns the error and the old mask stays.  A new cloud (rtr_upload_points, rtr_generate_synthetic) clears it.
+ * Memory: while a mask is set, 2 bits per point (upload-order and resident-order copies) + 1 byte per 256 points; none
+ * without one.
+ * Errors: no cloud, nwords != (n + 31) / 32, words NULL with nwords > 0, a sorted cloud without point_ids
+ * -> RTR_ERR_INVALID, nothing changed. */
+int rtr_set_point_keep(rtr_ctx *ctx, const uint32_t *words, uint64_t nwords);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

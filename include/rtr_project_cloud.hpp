@@ -19,7 +19,8 @@
 // Beyond the reference: computePointIds / visible_points (rtr.h section 6b) name the points a frame shows, by their
 // index in the grid's flattened vertex order (the order the constructor uploads); construct with point_ids = true
 // when the library may sort the cloud (its default upload policy does for unordered clouds).  setClipPlanes /
-// setClipBox / clearClip (rtr.h section 6d) leave part of the cloud out of every later frame.
+// setClipBox / clearClip (rtr.h section 6d) leave part of the cloud out of every later frame; setPointKeep / hidePoints /
+// clearPointKeep (section 6e) hide any set of vertices, by the same indices (point_ids = true when the cloud may be sorted).
 //
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
@@ -199,6 +200,33 @@ public:
         setClipPlanes(&pl[0][0], 6);
     }
     void clearClip() { check(ctx_, rtr_set_clip_planes(ctx_, 0, nullptr)); }
+
+    // Keep mask (rtr.h section 6e): every later frame leaves out the vertices whose flag is 0 (keep: one flag per vertex,
+    // in the order the constructor uploads -- the indices of computePointIds / visible_points).
+    void setPointKeep(const std::vector<uint8_t>& keep) {
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        if (keep.size() != n) throw std::invalid_argument("setPointKeep: one flag per vertex");
+        std::vector<uint32_t> words((size_t)((n + 31) / 32), 0u);
+        for (size_t i = 0; i < keep.size(); ++i)
+            if (keep[i]) words[i / 32] |= 1u << (i % 32);
+        check(ctx_, rtr_set_point_keep(ctx_, words.data(), words.size()));
+    }
+    // Hides the vertices `indices` as well, on top of the mask in force (none: every vertex kept).
+    void hidePoints(const std::vector<uint64_t>& indices) {
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        std::vector<uint32_t> words((size_t)((n + 31) / 32), 0xFFFFFFFFu);
+        int set = 0;
+        check(ctx_, rtr_get_option(ctx_, "point_keep", &set));
+        if (set) check(ctx_, rtr_download_buffer(ctx_, RTR_BUF_POINT_KEEP, words.data(), words.size() * 4));
+        for (uint64_t i : indices) {
+            if (i >= n) throw std::out_of_range("hidePoints: index past the vertex count");
+            words[(size_t)(i / 32)] &= ~(1u << (i % 32));
+        }
+        check(ctx_, rtr_set_point_keep(ctx_, words.data(), words.size()));
+    }
+    void clearPointKeep() { check(ctx_, rtr_set_point_keep(ctx_, nullptr, 0)); }
 
     // Renders the frame (computeRGBD / computeFilteredRGBD without host copies) and returns, per pixel (row-major
     // H x W), the vertex index of the point it shows, -1 for none (empty or prefiltered-away pixels).

@@ -118,6 +118,10 @@ struct rtr_ctx {
     bool reordered = false;     // the resident cloud was sorted by the library
     int opt_point_ids = 0;      // 1: a sorted cloud keeps its upload order as a resident permutation (option "point_ids")
     uint32_t *perm = nullptr;   // [cap] upload index of every resident point (only while `reordered`)
+    // the keep mask (rtr_set_point_keep; keep_up null: none): the caller's upload-order words, and the resident-order
+    // copy with its chunk summary the point kernels read (rtr::Keep).  Cleared with every new cloud
+    uint32_t *keep_up = nullptr, *keep_res = nullptr;
+    uint8_t *keep_sum = nullptr;
 
     // point pass (rtr_point_pass): per-pixel point IDs [H*W] (per resolution) and the visibility mask (8 words per
     // 256-point chunk; (n + 31) / 32 of them are the buffer)
@@ -207,6 +211,7 @@ struct rtr_ctx {
             float P[16] = {0};
             int filter = 0;
             bool stale = false;
+            bool sealed = false;  // finished and checked by rtr_set_point_keep: no later overflow makes it stale
             uint64_t cloud = 0;  // cloud_seq when it was queued
             rtr::Clip clip{};
         } slot[RTR_ASYNC_SLOTS];
@@ -389,7 +394,12 @@ void free_pack(rtr_ctx *c) {
     c->pk_bytes = 0;
 }
 
+void free_keep(rtr_ctx *c) {
+    dfree(c->keep_up); dfree(c->keep_res); dfree(c->keep_sum);
+}
+
 void free_cloud(rtr_ctx *c) {
+    free_keep(c);
     dfree(c->x); dfree(c->y); dfree(c->z); dfree(c->rgba); dfree(c->bounds); dfree(c->spread); dfree(c->perm);
     dfree(c->pp_vis);
     c->pp_vis_words = 0;
@@ -549,6 +559,7 @@ int alloc_cloud(rtr_ctx *c, uint64_t n) {
         if (c->p2p.open || c->p2p.red) p2p_release(c);
         reset_pool_sizing(c->frame);
     }
+    free_keep(c);  // (a new cloud: no mask)
     c->n = n;
     ++c->cloud_seq;
     c->list_valid = false;
@@ -570,7 +581,7 @@ rtr::Cloud cloud_of(const rtr_ctx *c) {
     // 10 m room and must keep the wave-level claim groups: 0.33 ms instead of 0.66 ms per frame without them)
     return rtr::Cloud{c->x, c->y, c->z, c->rgba, c->n, c->opt_grid, (!c->reordered && c->order_ratio > 0.5f) ? 1 : 0,
                       rtr::PackedXyz{c->pk_hdr, c->pk_planes, c->pk_planes_b}, c->spread, {c->absmax[0], c->absmax[1], c->absmax[2]},
-                      c->clip};
+                      c->clip, rtr::Keep{c->keep_up ? c->keep_res : nullptr, c->keep_sum}};
 }
 
 struct Timed {  // brackets one phase with hipEvents on the stream it is launched on
@@ -995,7 +1006,8 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     NEED(c, key != nullptr && value != nullptr, "key / value is NULL");
     if (!strcmp(key, "mode")) *value = c->opt_mode;
     else if (!strcmp(key, "auto_reorder")) *value = c->opt_auto_reorder;
-    else if (!strcmp(key, "reordered")) *value = c->reordered ? 1 : 0;  // the resident cloud was sorted by the library
+    else if (!strcmp(key, "reordered")) *value = c->reordered ? 1 : 0;
+    else if (!strcmp(key, "point_keep")) *value = c->keep_up ? 1 : 0;  // a keep mask is set (rtr_set_point_keep)  // the resident cloud was sorted by the library
     else if (!strcmp(key, "order_ratio_ppm")) *value = (int)(c->order_ratio * 1e6f);  // chunk / cloud diagonal as uploaded
     else if (!strcmp(key, "cull")) *value = c->opt_cull;
     else if (!strcmp(key, "point_ids")) *value = c->opt_point_ids;
@@ -1014,7 +1026,7 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
         // form), colours, chunk boxes and lane spreads, tile stores and extent pools, frame buffers
         const uint64_t nchunks = ((c->cap / 4) + 63) / 64;
         uint64_t b = (c->x ? 12 * c->cap : 0) + (c->rgba ? 4 * c->cap : 0) + nchunks * 28 + (c->pk_hdr ? c->pk_bytes + 64 : 0) +
-                     (c->perm ? 4 * c->cap : 0);
+                     (c->perm ? 4 * c->cap : 0) + (c->keep_up ? (c->n + 31) / 32 * 4 + nchunks * 33 + 4 : 0);
         const uint64_t npix = (uint64_t)c->W * c->H;
         for (const auto *t : {&c->frame, &c->views}) {
             for (const auto &f : t->fs) {
@@ -1140,7 +1152,7 @@ static int repair(rtr_ctx *c, rtr_ctx::Target &t, bool slots = false, const Copy
         if (grow && (single || may_retry)) {  // (the views' pools grow only with a batch to render again)
             t.pool_worst = true;  // (ensure_pool re-allocates before the next T1)
             for (int k = 0; single && k < RTR_ASYNC_SLOTS; ++k)
-                if (c->ho[k].busy) j.slot[k].stale = true;
+                if (c->ho[k].busy && !j.slot[k].sealed) j.slot[k].stale = true;
             if (may_retry) {
                 retry = true;
                 return RTR_OK;
@@ -1210,6 +1222,63 @@ int rtr_synchronize(rtr_ctx *c) {
     HIP_TRY(c, sync_streams(c));
     if (int rc = repair(c, c->frame)) return rc;
     return repair(c, c->views);
+}
+
+// ---- keep mask (rtr.h, section 6e) ----------------------------------------------------
+// Everything issued before is finished and checked first, as rtr_synchronize does, and also the async slots' frames a
+// repair repeats (with the mask they were issued with): no journal entry then needs a copy of the mask.  The slots stay
+// busy for rtr_wait, sealed: a later overflow does not make them stale.
+static int complete_all(rtr_ctx *c) {
+    HIP_TRY(c, sync_streams(c));
+    if (int rc = repair(c, c->frame, true)) return rc;
+    for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
+        if (c->ho[k].busy) HIP_TRY(c, hipEventSynchronize(c->ho[k].done));
+    if (int rc = repair(c, c->views)) return rc;
+    for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
+        if (c->ho[k].busy) c->jr.slot[k].sealed = true;
+    return RTR_OK;
+}
+
+int rtr_set_point_keep(rtr_ctx *c, const uint32_t *words, uint64_t nwords) {
+    if (!c) return RTR_ERR_INVALID;
+    const bool clear = words == nullptr && nwords == 0;
+    NEED(c, clear || c->n > 0, "rtr_set_point_keep: no cloud");
+    NEED(c, words != nullptr || nwords == 0, "rtr_set_point_keep: words is NULL");
+    if (!clear && nwords != (c->n + 31) / 32)
+        return fail(c, RTR_ERR_INVALID, "rtr_set_point_keep: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
+    NEED(c, clear || !c->reordered || c->perm,
+         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be mapped: set "
+         "point_ids = 1 before the upload (or upload with auto_reorder = 0)");
+    DevGuard g(c->device);
+    if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the mask they were issued with)
+    if (clear) {
+        if (c->keep_up) c->list_valid = false;
+        free_keep(c);
+        return RTR_OK;
+    }
+    const uint64_t nchunks = (c->n + 255) / 256;
+    struct Buf {  // freed on every exit path unless taken
+        void *p = nullptr;
+        ~Buf() { if (p) (void)hipFree(p); }
+    } up, res, sum;
+    HIP_TRY(c, hipMalloc(&up.p, nwords * 4));
+    // (the caller's words, host or device memory, into a new buffer: a failed copy leaves the old mask in force)
+    HIP_TRY(c, hipMemcpyAsync(up.p, words, nwords * 4, hipMemcpyDefault, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!c->keep_res) {
+        HIP_TRY(c, hipMalloc(&res.p, nchunks * 32));
+        HIP_TRY(c, hipMalloc(&sum.p, (nchunks + 3) & ~3ull));  // (read as whole dwords)
+    }
+    uint32_t *const kres = c->keep_res ? c->keep_res : (uint32_t *)res.p;
+    uint8_t *const ksum = c->keep_sum ? c->keep_sum : (uint8_t *)sum.p;
+    rtr::launch_keep_build(c->stream, (uint32_t *)up.p, c->reordered ? c->perm : nullptr, c->n, kres, ksum);
+    HIP_TRY(c, sync_streams(c));
+    if (int rc = launch_check(c, "keep mask")) return rc;
+    dfree(c->keep_up);
+    c->keep_up = (uint32_t *)up.p, up.p = nullptr;
+    if (res.p) c->keep_res = (uint32_t *)res.p, c->keep_sum = (uint8_t *)sum.p, res.p = sum.p = nullptr;
+    c->list_valid = false;  // (bins of another mask serve no later pass)
+    return RTR_OK;
 }
 
 // ---- cloud -------------------------------------------------------------------------
@@ -1368,6 +1437,9 @@ int rtr_generate_synthetic(rtr_ctx *c, int scene, uint64_t seed, uint64_t first,
 int rtr_reorder_points(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
     DevGuard g(c->device);
+    NEED(c, !c->keep_up || (c->opt_point_ids && (!c->reordered || c->perm)),
+         "the cloud has a keep mask (rtr_set_point_keep), which a sort without option point_ids = 1 would lose: set "
+         "point_ids = 1 before the upload, or clear the mask first");
     HIP_TRY(c, sync_streams(c));
     c->list_valid = false;
     c->pp_vis_current = false;
@@ -1385,6 +1457,7 @@ int rtr_reorder_points(rtr_ctx *c) {
     c->reordered = true;
     free_pack(c);
     rtr::launch_chunk_bounds(c->stream, cloud_of(c), c->bounds, c->spread);
+    if (c->keep_up) rtr::launch_keep_build(c->stream, c->keep_up, c->perm, c->n, c->keep_res, c->keep_sum);  // (the mask follows)
     HIP_TRY(c, sync_streams(c));
     if (int rc = launch_check(c, "reorder")) return rc;
     if (int rc = pack_cloud(c)) return rc;
@@ -1768,6 +1841,7 @@ static int queue_slot(rtr_ctx *c, const float P[16], int slot, int with_filter) 
     memcpy(f.P, P, sizeof f.P);
     f.filter = with_filter;
     f.stale = false;
+    f.sealed = false;
     f.cloud = c->cloud_seq;
     f.clip = c->clip;
     h.busy = true;
@@ -2237,7 +2311,7 @@ int rtr_render_views(rtr_ctx *c, int count, const float *P, int with_filter) {
 int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
     if (!c) return RTR_ERR_INVALID;
     NEED(c, ptr != nullptr, "dev_ptr is NULL");
-    if (which != RTR_BUF_MINMAX && which != RTR_BUF_VIEW_MINMAX)
+    if (which != RTR_BUF_MINMAX && which != RTR_BUF_VIEW_MINMAX && which != RTR_BUF_POINT_KEEP)
         if (int rc = check_frame(c)) return rc;
     size_t npix = (size_t)c->W * c->H, b = 0;
     void *p = nullptr;
@@ -2263,6 +2337,9 @@ int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
             else p = c->views.minmax, b = k * 8;
             break;
         }
+        case RTR_BUF_POINT_KEEP:
+            NEED(c, c->keep_up != nullptr, "RTR_BUF_POINT_KEEP: no keep mask is set (rtr_set_point_keep)");
+            p = c->keep_up; b = (size_t)((c->n + 31) / 32) * 4; break;
         default: return fail(c, RTR_ERR_INVALID, "unknown buffer id %d", which);
     }
     *ptr = p;

@@ -112,4 +112,30 @@ RTR_HD bool clip_box_outside(const Clip &c, const float lo[3], const float hi[3]
     return culled;
 }
 
+// ---- per-point keep mask (rtr_set_point_keep) --------------------------------------------------------------------
+// The mask in RESIDENT order: bit r % 32 of words[r / 32] set = resident point r is kept; a 256-point chunk c owns
+// words[8 c .. 8 c + 7], and lane l of the wave that holds the chunk (its points 4 l .. 4 l + 3) finds its four bits at
+// (l % 8) * 4 .. + 3 of the chunk's word l / 8 (keep_lane_bits).  sum[c] summarises the chunk's points below n: all of
+// them hidden (the chunk is rejected with the box tests, before its coordinates are read), all kept (the mask is never
+// read for it) or some of each.  Bits at or past n are 0 and do not count.
+// Passed BY VALUE to the point kernels (like Clip); words = null never reaches a kernel.
+constexpr uint8_t kKeepSome = 0, kKeepNone = 1, kKeepAll = 2;
+struct Keep {
+    const uint32_t *words;  // [8 x chunks] resident order
+    const uint8_t *sum;     // [chunks] kKeepSome / kKeepNone / kKeepAll
+};
+RTR_HD uint32_t keep_lane_bits(uint32_t word, uint32_t lane) { return (word >> ((lane & 7u) * 4u)) & 15u; }
+// the summary of one chunk from its eight words; `valid` = its points below n (1..256)
+RTR_HD uint8_t keep_chunk_state(const uint32_t w[8], uint32_t valid) {
+    bool any = false, all = true;
+    for (uint32_t j = 0; j < 8; ++j) {
+        const uint32_t bits = valid >= 32u * (j + 1u) ? 32u : (valid > 32u * j ? valid - 32u * j : 0u);
+        if (bits == 0u) break;
+        const uint32_t m = bits == 32u ? 0xFFFFFFFFu : (1u << bits) - 1u;
+        any = any || (w[j] & m) != 0u;
+        all = all && (w[j] & m) == m;
+    }
+    return !any ? kKeepNone : (all ? kKeepAll : kKeepSome);
+}
+
 }  // namespace rtr

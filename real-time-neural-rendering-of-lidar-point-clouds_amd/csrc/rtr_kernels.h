@@ -57,6 +57,7 @@ struct Cloud {
     const float *spread;
     float absmax[3];
     Clip clip;  // the user's clip planes (rtr_set_clip_planes; count 0: none): the point kernels launch their CLIP forms
+    Keep keep;  // the user's keep mask in resident order (rtr_set_point_keep; words null: none): the KEEP forms
 };
 
 struct FilterLevels {
@@ -334,5 +335,9 @@ void launch_pad_nan(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba,
 void launch_point_pass(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, const uint32_t *depth, float window,
                        uint32_t *ids, uint32_t *vis, const uint32_t *perm);
 void launch_iota(hipStream_t s, uint32_t *out, uint64_t n);  // out[i] = i
+// rtr_set_point_keep / a sort: the resident-order keep mask and its chunk summary (Keep) from the upload-order mask
+// `up` ((n + 31) / 32 words; perm: resident index -> upload index, null while the cloud is in upload order).  Also
+// clears the bits of `up` at or past n.  res: 8 words per chunk, sum: a byte per chunk.
+void launch_keep_build(hipStream_t s, uint32_t *up, const uint32_t *perm, uint64_t n, uint32_t *res, uint8_t *sum);
 
 }  // namespace rtr

@@ -103,6 +103,29 @@ __device__ __forceinline__ uint32_t ld_fresh(const uint32_t *p) {  // sc1: bypas
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- the keep mask (rtr_set_point_keep; Keep in rtr_chunk_box.h) ----
+// Both reads are SCALAR loads (through the constant address space; the mask never changes while a kernel runs): they
+// count on lgkmcnt, so they neither wait for nor hold up the vector loads in flight -- T1's LDS ring of the packed
+// form, the prefetched next quad of the fp32 one.  c: a wave-uniform chunk.
+typedef const __attribute__((address_space(4))) uint32_t *keep_cptr;
+__device__ __forceinline__ uint32_t keep_state(const Keep &kp, uint32_t c) {  // kKeepSome / kKeepNone / kKeepAll
+    const uint32_t w = *((keep_cptr)(const void *)kp.sum + (c >> 2));
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)((w >> ((c & 3u) * 8u)) & 0xFFu));
+}
+// the lane's four bits of chunk c (points 4 l .. 4 l + 3: bit k = point 4 l + k kept): the chunk's eight words in one
+// scalar load, the lane's word picked from them
+__device__ __forceinline__ uint32_t keep_bits(const Keep &kp, uint32_t c, uint32_t lane) {
+    const keep_cptr p = (keep_cptr)(const void *)kp.words + 8u * c;
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = p[j];
+    const uint32_t q = lane >> 3;
+    uint32_t v = w[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) v = q == (uint32_t)j ? w[j] : v;
+    return keep_lane_bits(v, lane);
+}
+
 static int point_grid(uint64_t n4, int grid) {
     uint64_t blocks = (n4 + kBlock - 1) / kBlock;
     uint64_t cap = grid < 1 ? 1 : (uint64_t)grid;
@@ -178,10 +201,12 @@ __device__ __forceinline__ void wave_acc(uint32_t *__restrict__ acc, int pix, bo
 // points read a dummy pixel) so their latencies overlap.
 // CLIP (rtr_set_clip_planes; its own kernels, so that the frames without planes keep their code): a point that
 // clip_keep drops is culled right next to project_point, as if it were not in the cloud.
-template <bool CLIP>
+// KEEP (rtr_set_point_keep; k_min_depth_keep, which also takes the planes, count 0 included): a wave's 64 quads are one
+// chunk -- rejected on its summary before its coordinates are read, else its hidden points culled like clipped ones.
+template <bool CLIP, bool KEEP = false>
 __device__ __forceinline__ void min_depth_body(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
                                                const float4 *__restrict__ z4, uint64_t n4, const Proj &P, int W, int H,
-                                               uint32_t *__restrict__ depth, const Clip &cl) {
+                                               uint32_t *__restrict__ depth, const Clip &cl, const Keep &kp = Keep{}) {
     const float fW = (float)W, fH = (float)H;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
     const int lane = threadIdx.x & 63;
@@ -189,8 +214,20 @@ __device__ __forceinline__ void min_depth_body(const float4 *__restrict__ x4, co
     // shuffles across all 64 lanes); lanes past the end re-read the wave's first quad, masked out
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i - (uint64_t)lane < n4; i += stride) {
         const bool live = i < n4;
+        uint32_t kb = 15u;
+        if constexpr (KEEP) {
+            const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)((i - (uint64_t)lane) >> 6));
+            const uint32_t st = keep_state(kp, c);
+            if (st == kKeepNone) continue;  // (wave-uniform)
+            if (st != kKeepAll) kb = keep_bits(kp, c, (uint32_t)lane);
+        }
         Quad q = project_quad<CLIP>(x4, y4, z4, live ? i : i - (uint64_t)lane, P, W, H, fW, fH, cl);
         if (!live) q.pix[0] = q.pix[1] = q.pix[2] = q.pix[3] = -1;
+        if constexpr (KEEP) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (!((kb >> k) & 1u)) q.pix[k] = -1;
+        }
         bool any = (q.pix[0] & q.pix[1] & q.pix[2] & q.pix[3]) >= 0;  // some sign bit clear
         if (__ballot(any) == 0ull) continue;                          // wave-uniform skip
         uint32_t cur[4];
@@ -213,11 +250,19 @@ __global__ __launch_bounds__(kBlock) void k_min_depth_clip(const float4 *__restr
                                                            uint32_t *__restrict__ depth, Clip cl) {
     min_depth_body<true>(x4, y4, z4, n4, P, W, H, depth, cl);
 }
+__global__ __launch_bounds__(kBlock) void k_min_depth_keep(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
+                                                           const float4 *__restrict__ z4, uint64_t n4, Proj P, int W, int H,
+                                                           uint32_t *__restrict__ depth, Clip cl, Keep kp) {
+    min_depth_body<true, true>(x4, y4, z4, n4, P, W, H, depth, cl, kp);
+}
 
 void launch_min_depth(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, uint32_t *depth) {
     uint64_t n4 = (c.n + 3) / 4;
     if (n4 == 0) return;
-    if (c.clip.count > 0)
+    if (c.keep.words)
+        hipLaunchKernelGGL(k_min_depth_keep, dim3(point_grid(n4, c.grid)), dim3(kBlock), 0, s, (const float4 *)c.x,
+                           (const float4 *)c.y, (const float4 *)c.z, n4, P, W, H, depth, c.clip, c.keep);
+    else if (c.clip.count > 0)
         hipLaunchKernelGGL(k_min_depth_clip, dim3(point_grid(n4, c.grid)), dim3(kBlock), 0, s, (const float4 *)c.x,
                            (const float4 *)c.y, (const float4 *)c.z, n4, P, W, H, depth, c.clip);
     else
@@ -237,18 +282,30 @@ __device__ __forceinline__ void acc_add(uint32_t *__restrict__ acc, int pix, uin
     atomicAdd(a + 1, (unsigned long long)((c >> 16) & 0xFFu) | (1ull << 32));
 }
 
-template <bool CLIP>
+template <bool CLIP, bool KEEP = false>
 __device__ __forceinline__ void accumulate_body(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
                                                 const float4 *__restrict__ z4, const uint32_t *__restrict__ rgba, uint64_t n4,
                                                 const Proj &P, int W, int H, const uint32_t *__restrict__ depth,
-                                                uint32_t *__restrict__ acc, float window, const Clip &cl) {
+                                                uint32_t *__restrict__ acc, float window, const Clip &cl, const Keep &kp = Keep{}) {
     const float fW = (float)W, fH = (float)H;
     const int lane = threadIdx.x & 63;
     uint64_t stride = (uint64_t)gridDim.x * kBlock;
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i - (uint64_t)lane < n4; i += stride) {
         const bool live = i < n4;  // wave-uniform trip count, see k_min_depth
+        uint32_t kb = 15u;
+        if constexpr (KEEP) {  // (see min_depth_body)
+            const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)((i - (uint64_t)lane) >> 6));
+            const uint32_t st = keep_state(kp, c);
+            if (st == kKeepNone) continue;
+            if (st != kKeepAll) kb = keep_bits(kp, c, (uint32_t)lane);
+        }
         Quad q = project_quad<CLIP>(x4, y4, z4, live ? i : i - (uint64_t)lane, P, W, H, fW, fH, cl);
         if (!live) q.pix[0] = q.pix[1] = q.pix[2] = q.pix[3] = -1;
+        if constexpr (KEEP) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (!((kb >> k) & 1u)) q.pix[k] = -1;
+        }
         bool any = (q.pix[0] & q.pix[1] & q.pix[2] & q.pix[3]) >= 0;
         if (__ballot(any) == 0ull) continue;
         uint32_t m[4];
@@ -280,12 +337,22 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_clip(const float4 *__rest
                                                             uint32_t *__restrict__ acc, float window, Clip cl) {
     accumulate_body<true>(x4, y4, z4, rgba, n4, P, W, H, depth, acc, window, cl);
 }
+__global__ __launch_bounds__(kBlock) void k_accumulate_keep(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
+                                                            const float4 *__restrict__ z4,
+                                                            const uint32_t *__restrict__ rgba, uint64_t n4, Proj P, int W,
+                                                            int H, const uint32_t *__restrict__ depth,
+                                                            uint32_t *__restrict__ acc, float window, Clip cl, Keep kp) {
+    accumulate_body<true, true>(x4, y4, z4, rgba, n4, P, W, H, depth, acc, window, cl, kp);
+}
 
 void launch_accumulate(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, const uint32_t *depth,
                        uint32_t *acc, float window) {
     uint64_t n4 = (c.n + 3) / 4;
     if (n4 == 0) return;
-    if (c.clip.count > 0)
+    if (c.keep.words)
+        hipLaunchKernelGGL(k_accumulate_keep, dim3(point_grid(n4, c.grid)), dim3(kBlock), 0, s, (const float4 *)c.x,
+                           (const float4 *)c.y, (const float4 *)c.z, c.rgba, n4, P, W, H, depth, acc, window, c.clip, c.keep);
+    else if (c.clip.count > 0)
         hipLaunchKernelGGL(k_accumulate_clip, dim3(point_grid(n4, c.grid)), dim3(kBlock), 0, s, (const float4 *)c.x,
                            (const float4 *)c.y, (const float4 *)c.z, c.rgba, n4, P, W, H, depth, acc, window, c.clip);
     else
@@ -1109,8 +1176,10 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL && !MV) ? RTR_T1_WAVES : 4
                                                         const uint4 *__restrict__ rgba4, uint32_t n4, Proj P, int W,
                                                         int H, TileStore S, const float *__restrict__ bounds,
                                                         int clear_split, uint32_t cblock, int xp, LaneTest lt) {
-    constexpr bool CLIP = false;
+    constexpr bool CLIP = false, KEEP = false;
     const Clip clip{};
+    const Keep kmask{};
+    (void)kmask;
 #include "rtr_t1_body.inc"
 }
 template <bool CULL, bool GROUPS, bool PACKED, bool CTEST = false, bool MV = false>
@@ -1119,7 +1188,22 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL && !MV) ? RTR_T1_WAVES : 4
                                                         const uint4 *__restrict__ rgba4, uint32_t n4, Proj P, int W,
                                                         int H, TileStore S, const float *__restrict__ bounds,
                                                         int clear_split, uint32_t cblock, int xp, LaneTest lt, Clip clip) {
-    constexpr bool CLIP = true;
+    constexpr bool CLIP = true, KEEP = false;
+    const Keep kmask{};
+    (void)kmask;
+#include "rtr_t1_body.inc"
+}
+// KEEP (rtr_set_point_keep): k_project_bin_keep, the clip instance (planes: count 0 included) plus the keep mask -- a
+// chunk that the mask hides entirely is rejected with the box tests (on its summary byte: before its coordinates are
+// read), and on the exact path the points the conservative test and the planes have left lose the hidden ones (their
+// bits from one scalar load of the chunk's eight words, for chunks that are only partly hidden)
+template <bool CULL, bool GROUPS, bool PACKED, bool CTEST = false, bool MV = false>
+__global__ __launch_bounds__(kBlock, (PACKED && !CULL && !MV) ? RTR_T1_WAVES : 4) void k_project_bin_keep(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
+                                                        const float4 *__restrict__ z4,
+                                                        const uint4 *__restrict__ rgba4, uint32_t n4, Proj P, int W,
+                                                        int H, TileStore S, const float *__restrict__ bounds,
+                                                        int clear_split, uint32_t cblock, int xp, LaneTest lt, Clip clip, Keep kmask) {
+    constexpr bool CLIP = true, KEEP = true;
 #include "rtr_t1_body.inc"
 }
 
@@ -2085,6 +2169,14 @@ void launch_project_bin(hipStream_t s, const Cloud &c, const Proj &P, int W, int
     };
 #define RTR_T1(CULL, GROUPS, PACKED, CTEST)                                                                                   \
     do {                                                                                                                      \
+        if (c.keep.words) {                                                                                                   \
+            static int cached_grid[kGridCacheDevices] = {0};                                                                  \
+            const dim3 grid(point_grid(n4, c.grid == kDefaultPointGrid ? default_grid(k_project_bin_keep<CULL, GROUPS, PACKED, CTEST>, cached_grid) : c.grid)); \
+            hipExtLaunchKernelGGL((k_project_bin_keep<CULL, GROUPS, PACKED, CTEST>), grid, block, 0, s, ev_start, ev_stop, 0, x, y, z, col, \
+                                  (uint32_t)n4, P, W, H, S, CULL ? bounds : (packed ? nullptr : c.spread), clear_split,      \
+                                  (uint32_t)phases, xp, lt, c.clip, c.keep);                                                  \
+            break;                                                                                                            \
+        }                                                                                                                     \
         if (c.clip.count > 0) {                                                                                               \
             static int cached_grid[kGridCacheDevices] = {0};                                                                  \
             const dim3 grid(point_grid(n4, c.grid == kDefaultPointGrid ? default_grid(k_project_bin_clip<CULL, GROUPS, PACKED, CTEST>, cached_grid) : c.grid)); \
@@ -2156,7 +2248,13 @@ hipError_t launch_project_bin_views(hipStream_t s, const Cloud &c, const Proj *P
         hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, ev_start, ev_stop, 0, x, y, z, col, (uint32_t)n4, P[0], W, H, \
                               S[0], tab, clear_split, (uint32_t)phases, 0, t.lt[0] __VA_ARGS__);                             \
     } while (0)
-    if (c.clip.count > 0) {  // (the planes are shared by every view: a kernel argument of the clip instances)
+    if (c.keep.words) {  // (the mask, like the planes, is shared by every view)
+        if (c.incoherent) {
+            if (packed) RTR_T1V(k_project_bin_keep, false, true, , c.clip, c.keep); else RTR_T1V(k_project_bin_keep, false, false, , c.clip, c.keep);
+        } else {
+            if (packed) RTR_T1V(k_project_bin_keep, true, true, , c.clip, c.keep); else RTR_T1V(k_project_bin_keep, true, false, , c.clip, c.keep);
+        }
+    } else if (c.clip.count > 0) {  // (the planes are shared by every view: a kernel argument of the clip instances)
         if (c.incoherent) {
             if (packed) RTR_T1V(k_project_bin_clip, false, true, , c.clip); else RTR_T1V(k_project_bin_clip, false, false, , c.clip);
         } else {
@@ -3534,10 +3632,10 @@ __device__ __forceinline__ uint32_t spread_nibbles(uint32_t b) {  // bit m of th
     x = (x | (x << 3)) & 0x11111111u;
     return x;
 }
-template <bool PERM, bool CLIP>
+template <bool PERM, bool CLIP, bool KEEP = false>
 __device__ __forceinline__ void point_pass_chunk(const PointPassArgs &a, const Proj &P, int W, int H, float fW, float fH,
                                                  uint64_t c, const float4 &X, const float4 &Y, const float4 &Z, int lane,
-                                                 const Clip &clip) {
+                                                 const Clip &clip, uint32_t kb = 15u) {
     const uint64_t i0 = c * 256u + 4u * (uint64_t)lane;
     const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
     int pix[4];
@@ -3547,6 +3645,7 @@ __device__ __forceinline__ void point_pass_chunk(const PointPassArgs &a, const P
         pix[k] = project_point(P, xs[k], ys[k], zs[k], W, H, fW, fH, d[k]);
         if (i0 + k >= a.n) pix[k] = -1;
         if (CLIP && !clip_keep(clip, xs[k], ys[k], zs[k])) pix[k] = -1;  // (a clipped point is neither named nor visible)
+        if (KEEP && !((kb >> k) & 1u)) pix[k] = -1;                         // (nor is a hidden one)
     }
     uint32_t m[4];
 #pragma unroll
@@ -3583,8 +3682,11 @@ __device__ __forceinline__ void point_pass_chunk(const PointPassArgs &a, const P
 }
 // CLIP: k_point_pass_clip, the frame's clip planes -- the header test also rejects chunks outside them, and clipped points
 // are masked like those past n
-template <bool PACKED, bool PERM, bool CLIP>
-__device__ __forceinline__ void point_pass_body(const PointPassArgs &a, const Proj &P, int W, int H, const Clip &clip) {
+// KEEP: k_point_pass_keep, the planes and the keep mask -- a chunk the mask hides entirely is rejected before its
+// coordinates are read (its visibility words are zero), the hidden points of a partly hidden one are masked like clipped ones
+template <bool PACKED, bool PERM, bool CLIP, bool KEEP = false>
+__device__ __forceinline__ void point_pass_body(const PointPassArgs &a, const Proj &P, int W, int H, const Clip &clip,
+                                                const Keep &kp = Keep{}) {
     const float fW = (float)W, fH = (float)H;
     const int lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
@@ -3592,9 +3694,18 @@ __device__ __forceinline__ void point_pass_body(const PointPassArgs &a, const Pr
     const uint64_t n4 = (a.n + 3) / 4, nchunks = (n4 + 63) / 64;
     if (!PACKED) {
         for (uint64_t c = wave; c < nchunks; c += nwaves) {  // (wave-uniform)
+            uint32_t kb = 15u;
+            if constexpr (KEEP) {
+                const uint32_t st = keep_state(kp, (uint32_t)c);
+                if (st == kKeepNone) {
+                    if (!PERM && a.vis && lane < 8) a.vis[8 * c + lane] = 0u;  // (no point of it is visible)
+                    continue;
+                }
+                if (st != kKeepAll) kb = keep_bits(kp, (uint32_t)c, (uint32_t)lane);
+            }
             const uint64_t i = c * 64u + (uint64_t)lane, ic = i < n4 ? i : n4 - 1u;
             const float4 X = ld_stream(a.x4 + ic), Y = ld_stream(a.y4 + ic), Z = ld_stream(a.z4 + ic);
-            point_pass_chunk<PERM, CLIP>(a, P, W, H, fW, fH, c, X, Y, Z, lane, clip);
+            point_pass_chunk<PERM, CLIP, KEEP>(a, P, W, H, fW, fH, c, X, Y, Z, lane, clip, kb);
         }
         return;
     }
@@ -3607,6 +3718,7 @@ __device__ __forceinline__ void point_pass_body(const PointPassArgs &a, const Pr
             const uint4 h0 = a.pk.hdr[2 * chunk];
             float lo[3], hi[3];
             keep = !(chunk_box(h0.x, h0.y, h0.z, h0.w, lo, hi) && (box_outside(fpl, lo, hi) || (CLIP && clip_box_outside(clip, lo, hi))));
+            if constexpr (KEEP) keep = keep && kp.sum[chunk] != kKeepNone;
         }
         if (!PERM && a.vis && valid && !keep) {  // (no point of a rejected chunk is visible)
             uint4 *w = reinterpret_cast<uint4 *>(a.vis + 8 * chunk);
@@ -3623,7 +3735,10 @@ __device__ __forceinline__ void point_pass_body(const PointPassArgs &a, const Pr
             const ChunkRaw raw = load_chunk_b(a.pk.planes_b, h0, h1, lane);
             float4 X, Y, Z;
             unpack_chunk(raw_a, raw, h0.w, h0.x, h0.y, h0.z, X, Y, Z, lane);
-            point_pass_chunk<PERM, CLIP>(a, P, W, H, fW, fH, cc, X, Y, Z, lane, clip);
+            uint32_t kb = 15u;
+            if constexpr (KEEP)
+                if (keep_state(kp, (uint32_t)cc) != kKeepAll) kb = keep_bits(kp, (uint32_t)cc, (uint32_t)lane);
+            point_pass_chunk<PERM, CLIP, KEEP>(a, P, W, H, fW, fH, cc, X, Y, Z, lane, clip, kb);
         }
     }
 }
@@ -3636,6 +3751,10 @@ template <bool PACKED, bool PERM>
 __global__ __launch_bounds__(kBlock) void k_point_pass_clip(PointPassArgs a, Proj P, int W, int H, Clip clip) {
     point_pass_body<PACKED, PERM, true>(a, P, W, H, clip);
 }
+template <bool PACKED, bool PERM>
+__global__ __launch_bounds__(kBlock) void k_point_pass_keep(PointPassArgs a, Proj P, int W, int H, Clip clip, Keep kp) {
+    point_pass_body<PACKED, PERM, true, true>(a, P, W, H, clip, kp);
+}
 
 void launch_point_pass(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, const uint32_t *depth, float window,
                        uint32_t *ids, uint32_t *vis, const uint32_t *perm) {
@@ -3645,7 +3764,12 @@ void launch_point_pass(hipStream_t s, const Cloud &c, const Proj &P, int W, int 
     const bool packed = c.pk.hdr != nullptr;
     const uint64_t blocks = (nchunks + 3) / 4;  // (up to 8 waves per CU, every chunk dealt round robin)
     const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048)), block(kBlock);
-    if (c.clip.count > 0) {
+    if (c.keep.words) {
+        if (packed && perm) hipLaunchKernelGGL((k_point_pass_keep<true, true>), grid, block, 0, s, a, P, W, H, c.clip, c.keep);
+        else if (packed) hipLaunchKernelGGL((k_point_pass_keep<true, false>), grid, block, 0, s, a, P, W, H, c.clip, c.keep);
+        else if (perm) hipLaunchKernelGGL((k_point_pass_keep<false, true>), grid, block, 0, s, a, P, W, H, c.clip, c.keep);
+        else hipLaunchKernelGGL((k_point_pass_keep<false, false>), grid, block, 0, s, a, P, W, H, c.clip, c.keep);
+    } else if (c.clip.count > 0) {
         if (packed && perm) hipLaunchKernelGGL((k_point_pass_clip<true, true>), grid, block, 0, s, a, P, W, H, c.clip);
         else if (packed) hipLaunchKernelGGL((k_point_pass_clip<true, false>), grid, block, 0, s, a, P, W, H, c.clip);
         else if (perm) hipLaunchKernelGGL((k_point_pass_clip<false, true>), grid, block, 0, s, a, P, W, H, c.clip);
@@ -3666,6 +3790,49 @@ void launch_iota(hipStream_t s, uint32_t *out, uint64_t n) {
     if (n == 0) return;
     const uint64_t blocks = (n + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(k_iota, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, out, n);
+}
+
+// The keep mask in resident order (rtr_set_point_keep, after a sort): one wave per 256-point chunk, lane l gathers the
+// bits of its points 4 l .. 4 l + 3 from the upload-order mask (through perm when the cloud is sorted), the four ballots
+// are interleaved into the chunk's eight words as in the point pass, and lane 0 writes the chunk's summary
+// (keep_chunk_state: the same rule on the ballots).  Points at or past n are hidden and do not count.
+__global__ __launch_bounds__(kBlock) void k_keep_build(const uint32_t *__restrict__ up, const uint32_t *__restrict__ perm,
+                                                       uint64_t n, uint32_t *__restrict__ res, uint8_t *__restrict__ sum) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t nchunks = (n + 255) / 256;
+    for (uint64_t c = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+        bool kept[4], valid[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint64_t r = c * 256u + 4u * (uint64_t)lane + (uint64_t)k;
+            valid[k] = r < n;
+            const uint64_t u = valid[k] ? (perm ? (uint64_t)perm[r] : r) : 0u;
+            kept[k] = valid[k] && ((up[u >> 5] >> (u & 31u)) & 1u);
+        }
+        unsigned long long b[4], v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b[k] = __ballot(kept[k]), v[k] = __ballot(valid[k]);
+        if (lane < 8) {
+            const int sh = 8 * lane;
+            res[8 * c + lane] = spread_nibbles((uint32_t)(b[0] >> sh)) | (spread_nibbles((uint32_t)(b[1] >> sh)) << 1) |
+                                (spread_nibbles((uint32_t)(b[2] >> sh)) << 2) | (spread_nibbles((uint32_t)(b[3] >> sh)) << 3);
+        }
+        if (lane == 0) {
+            const bool none = (b[0] | b[1] | b[2] | b[3]) == 0ull;
+            const bool all = b[0] == v[0] && b[1] == v[1] && b[2] == v[2] && b[3] == v[3];
+            sum[c] = none ? kKeepNone : (all ? kKeepAll : kKeepSome);
+        }
+    }
+}
+// the bits of the upload-order mask at or past n read back as 0 (after every wave of k_keep_build has read it)
+__global__ void k_keep_tail(uint32_t *up, uint64_t n) {
+    if (n % 32u) up[n / 32u] &= (1u << (n % 32u)) - 1u;
+}
+void launch_keep_build(hipStream_t s, uint32_t *up, const uint32_t *perm, uint64_t n, uint32_t *res, uint8_t *sum) {
+    if (n == 0) return;
+    const uint64_t blocks = ((n + 255) / 256 + 3) / 4;  // (a wave per chunk)
+    hipLaunchKernelGGL(k_keep_build, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, up, perm, n, res, sum);
+    hipLaunchKernelGGL(k_keep_tail, dim3(1), dim3(1), 0, s, up, n);
 }
 
 }  // namespace rtr

@@ -1,6 +1,6 @@
-// rtr_t1_body.inc -- the body of T1 (k_project_bin and k_project_bin_clip in rtr_kernels.hip, which include it with
-// CLIP and `clip` defined): one text for both kernels, compiled in each as if written there, so that the kernels without
-// clip planes keep exactly the code they had.
+// rtr_t1_body.inc -- the body of T1 (k_project_bin, k_project_bin_clip and k_project_bin_keep in rtr_kernels.hip, which
+// include it with CLIP, `clip`, KEEP and `kmask` defined): one text for the three kernels, compiled in each as if written
+// there, so that the kernels without clip planes or a keep mask keep exactly the code they had.
     (void)xp;
     // (!CULL: `bounds` carries the chunks' lane spreads of an unpacked cloud, or null; the packed form has them in its headers;
     // MV: the view table, which holds them)
@@ -120,6 +120,10 @@
         return __ballot(front && !out) != 0ull;
     };
     uint32_t n_colour = 0;  // chunks of this wave whose colours were loaded (frame statistics)
+    // (KEEP: the keep summary of the chunk do_quad serves, a scalar the paths below load when they take up the chunk, so
+    // that its latency is not on the exact path)
+    uint32_t kst = kKeepAll;
+    (void)kst;
     // (Skipping the per-point conservative test below for chunks that have been through the lane test -- inside a stretch
     // of the cloud that lies in the frustum nearly every point passes it -- was measured: 135-142 us against 122-124.  A
     // chunk near the camera plane stays a candidate of the lane test, whose margin step needs r.z > zsafe, and it is this
@@ -161,6 +165,21 @@
                 any = any || maybe[k];
             }
             if (__ballot(any) == 0ull) return;
+        }
+        if constexpr (KEEP) {  // the keep mask, on what is left: the lane's four bits of a chunk that is partly hidden
+            // (the lane test before this point looked at the lane's first point whether it is hidden or not: its bound
+            // holds for the other three all the same, so it stays conservative)
+            if (kst != kKeepAll) {
+                const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(i >> 6));  // (lane 0 is always live)
+                const uint32_t kb = keep_bits(kmask, c, (uint32_t)lane);
+                any = false;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    maybe[k] = maybe[k] && ((kb >> k) & 1u);
+                    any = any || maybe[k];
+                }
+                if (__ballot(any) == 0ull) return;
+            }
         }
         bool in[4];
         uint32_t st[4], pix[4];
@@ -381,6 +400,12 @@
         // words, c: its chunk (< nchunks)
         // (MV: vmask = the views that kept the chunk's header box)
         auto chunk_body = [&](const lds_u32 *slot, const u32x4_l &g0, const u32x4_l &g1, uint32_t c, uint32_t vmask) {
+            // (KEEP: the chunk's summary -- the chunk test of one view has brought it with the chunk word and rejected
+            // the hidden chunks before the ring; the ring of chunk_test = 0 brings every chunk: a hidden one goes here)
+            if constexpr (KEEP && (MV || !CTEST)) {
+                kst = keep_state(kmask, c);
+                if (!CTEST && kst == kKeepNone) return;
+            }
             const uint32_t ww = (uint32_t)__builtin_amdgcn_readfirstlane((int)g0.w);
             const uint32_t bx = g0.x, by = g0.y, bz = g0.z;  // (vector registers: they are only ever OR-ed into values)
             const uint32_t wx = ww & 63u, wy = (ww >> 6) & 63u, wz = (ww >> 12) & 63u;
@@ -488,6 +513,7 @@
             // the A array's first bytes), so "data k has landed" is vmcnt(kRing) with no drain in the prologue; the
             // header loads (the compiler's) only ever add requests behind it, which makes that count conservative.
             uint4 cur0, cur1;  // lane l: the header of position qb + l of the current batch
+            uint32_t ksum = 0u;  // (KEEP) lane l: its chunk's keep summary
             uint32_t qb = 0;
             unsigned long long pmask = 0ull;  // survivors of the current batch not requested yet
             auto load_batch = [&](uint32_t q0, uint4 &h0, uint4 &h1) {
@@ -495,6 +521,7 @@
                 const uint32_t cc = c < nchunks ? c : nchunks - 1u;
                 h0 = pk_hdr[2 * (size_t)cc];
                 h1 = pk_hdr[2 * (size_t)cc + 1];
+                if constexpr (KEEP) ksum = kmask.sum[cc];
             };
             auto test_batch = [&]() {
                 const uint32_t c = chunk_of(qb + (uint32_t)lane);
@@ -526,7 +553,9 @@
                     keep = !box_outside(frustum_planes(m, fW, fH), lo, hi);
                     if (CLIP) keep = keep && !clip_box_outside(clip, lo, hi);
                 }
-                cur1.w = MV ? (c | vm << 24) : c;
+                if constexpr (KEEP) keep = keep && ksum != kKeepNone;  // (a chunk the mask hides entirely: never requested)
+                // (KEEP, one view: the chunk's summary travels in the top two bits of its chunk word, chunks < 2^25)
+                cur1.w = MV ? (c | vm << 24) : (KEEP ? (c | ksum << 30) : c);
                 // (every header word is consumed HERE, where the batch is tested: a word whose load is still pending when
                 // the survivor's header is written would make the compiler wait for it there -- with a vmcnt(0), which
                 // drains the ring's requests on every survivor)
@@ -567,6 +596,12 @@
                 const u32x4_l g0 = *reinterpret_cast<const lds_u32x4 *>(hs);
                 const u32x4_l g1 = *reinterpret_cast<const lds_u32x4 *>(hs + 4);
                 const uint32_t cw = (uint32_t)__builtin_amdgcn_readfirstlane((int)g1.w);
+                if constexpr (KEEP && !MV) {
+                    if ((cw & 0x3FFFFFFFu) >= nchunks) break;  // (wave-uniform) past the wave's last survivor
+                    kst = cw >> 30;
+                    chunk_body(slot, g0, g1, cw & 0x3FFFFFFFu, 0u);
+                    continue;
+                }
                 if (MV ? cw == ~0u : cw >= nchunks) break;  // (wave-uniform) past the wave's last survivor
                 chunk_body(slot, g0, g1, MV ? (cw & 0xFFFFFFu) : cw, cw >> 24);
             }
@@ -614,11 +649,15 @@
         // flight, which is what keeps HBM busy with only 4 waves per SIMD.  Lanes past the end of the cloud
         // re-read its last quad and are masked (`live`).
         float4 X = make_float4(0.f, 0.f, 0.f, 0.f), Y = X, Z = X;
-        uint32_t i = 0, spb = 0x7F800000u;
+        uint32_t i = 0, spb = 0x7F800000u, kst_f = kKeepAll;
         bool have = false, live = false;
         auto fetch = [&](uint32_t q) {
             const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)(q < R ? chunk_of(q) : nchunks));
             have = c < nchunks;  // wave-uniform
+            if constexpr (KEEP) {  // (a chunk the mask hides entirely: its coordinates are never read)
+                kst_f = have ? keep_state(kmask, c) : kKeepAll;
+                if (kst_f == kKeepNone) have = false;
+            }
             if (have) {
                 i = c * 64u + (uint32_t)lane;
                 live = i < n4;
@@ -637,6 +676,7 @@
                 const uint32_t i_c = i < n4 ? i : n4 - 1u;
                 const float4 Xc = X, Yc = Y, Zc = Z;  // (the quad is served to every view; the next one is on its way)
                 const uint32_t spc = spb;
+                if constexpr (KEEP) kst = kst_f;
                 fetch(q + 1);
                 if (!have_c) continue;
                 for (int v = 0; v < vt->count; ++v) {
@@ -657,6 +697,7 @@
             if (have_c && lane_test && spread && spb < 0x7F000000u)
                 cand = lane_maybe(X.x, Y.x, Z.x, __uint_as_float(spb), live_c);  // (the lane test: one point per lane)
             if (cand) project_rows(X, Y, Z, r);
+            if constexpr (KEEP) kst = kst_f;
             fetch(q + 1);
             if (cand) do_quad(i_c, live_c, r);
         }
@@ -674,6 +715,7 @@
                 const float lo[3] = {b[0], b[1], b[2]}, hi[3] = {b[3], b[4], b[5]};
                 keep = !box_outside(fpl, lo, hi);  // NaN / inf boxes compare false: never culled
                 if (CLIP) keep = keep && !clip_box_outside(clip, lo, hi);
+                if constexpr (KEEP) keep = keep && kmask.sum[chunk] != kKeepNone;
             }
             unsigned long long mask = __ballot(keep);
             while (mask) {
@@ -681,6 +723,7 @@
                 mask &= mask - 1;
                 const uint32_t i = chunk_of(g0 + (uint32_t)l) * 64u + (uint32_t)lane;
                 const bool live = i < n4;  // (lanes past the end of the cloud re-read its last quad, masked)
+                if constexpr (KEEP) kst = keep_state(kmask, (uint32_t)__builtin_amdgcn_readfirstlane((int)(i >> 6)));
                 const uint32_t ic = live ? i : n4 - 1u;
                 float4 X, Y, Z;
                 if (PACKED) {

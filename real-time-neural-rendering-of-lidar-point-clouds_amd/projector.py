@@ -209,6 +209,55 @@ class Projector:
         self._chk(self._lib.rtr_get_clip_planes(self._ctx, C.byref(k), _vp(out)))
         return out[:k.value].copy()
 
+    # -- keep mask (rtr.h section 6e)
+    def set_point_keep(self, keep):
+        """Hides from every later frame the points whose keep bit is clear, by their upload index (the point pass's).
+        keep: None (clears the mask), a bool array of length n, a uint32 word array of (n + 31) // 32 words (bit i % 32
+        of word i // 32: point i is kept -- the layout of BUF_VISIBLE), or device memory holding such words: a torch
+        tensor on the context's device, an object with __cuda_array_interface__ (device_buffer(BUF_VISIBLE) included)
+        or an integer device pointer.  A bool torch tensor is packed on the host.  A cloud the library may sort needs
+        option point_ids = 1."""
+        if keep is None:
+            self._chk(self._lib.rtr_set_point_keep(self._ctx, None, 0))
+            return
+        nwords = (self.num_points + 31) // 32
+        if isinstance(keep, int):
+            self._chk(self._lib.rtr_set_point_keep(self._ctx, C.c_void_p(keep), nwords))
+            return
+        if hasattr(keep, "__cuda_array_interface__") and not hasattr(keep, "data_ptr"):
+            self._chk(self._lib.rtr_set_point_keep(self._ctx, C.c_void_p(keep.__cuda_array_interface__["data"][0]),
+                                                   nwords))
+            return
+        if hasattr(keep, "data_ptr"):  # a torch tensor
+            if keep.dtype.is_floating_point:
+                raise ValueError("keep must be bool or 32-bit words")
+            if keep.is_cuda and str(keep.dtype) != "torch.bool":
+                import torch
+                keep = keep.contiguous()
+                torch.cuda.current_stream(keep.device).synchronize()  # (the words may still be on their way)
+                if keep.numel() * keep.element_size() != 4 * nwords:
+                    raise ValueError("keep must hold (n + 31) // 32 32-bit words")
+                self._chk(self._lib.rtr_set_point_keep(self._ctx, C.c_void_p(keep.data_ptr()), nwords))
+                return
+            keep = keep.cpu().numpy()
+        keep = np.asarray(keep)
+        if keep.dtype == bool:
+            if keep.shape != (self.num_points,):
+                raise ValueError("a bool keep mask must have shape (n,) = (%d,)" % self.num_points)
+            words = np.packbits(np.concatenate([keep, np.zeros(32 * nwords - keep.size, bool)]),
+                                bitorder="little").view("<u4")
+        else:
+            words = keep.astype("<u4", copy=False)
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        self._chk(self._lib.rtr_set_point_keep(self._ctx, _vp(words), words.size))
+
+    def point_keep(self):
+        """The keep mask in force as a bool array over the uploaded points, or None when none is set."""
+        if not self.get_option("point_keep"):
+            return None
+        words = self.download(L.BUF_POINT_KEEP)
+        return np.unpackbits(words.astype("<u4").view(np.uint8), bitorder="little")[:self.num_points].astype(bool)
+
     # -- point pass (rtr.h section 6b)
     def point_pass(self, P, ids=True, visible=True):
         """Per-pixel point IDs (BUF_POINT_ID: upload index, NO_POINT for none) and / or the per-point visibility
@@ -252,11 +301,12 @@ class Projector:
             L.BUF_VIEW_DEPTH: (np.uint32, "<u4", lambda w, h, k: (k, h, w)),
             L.BUF_VIEW_IMAGE: (np.uint8, "|u1", lambda w, h, k: (k, h, w, 3)),
             L.BUF_VIEW_TENSOR: (np.uint16, "<f2", lambda w, h, k: (k, 5, h, w)),
-            L.BUF_VIEW_MINMAX: (np.uint32, "<u4", lambda w, h, k: (k, 2))}
+            L.BUF_VIEW_MINMAX: (np.uint32, "<u4", lambda w, h, k: (k, 2)),
+            L.BUF_POINT_KEEP: (np.uint32, "<u4", lambda w, h, n: ((n + 31) // 32,))}
 
     def _shape(self, which):
         shp = self._BUF[which][2]
-        if which == L.BUF_VISIBLE:
+        if which in (L.BUF_VISIBLE, L.BUF_POINT_KEEP):
             return shp(self.W, self.H, self.num_points)
         if L.BUF_VIEW_DEPTH <= which <= L.BUF_VIEW_MINMAX:
             return shp(self.W, self.H, self.get_option("views"))
@@ -411,6 +461,24 @@ class ProjectCloud:
     def clearClip(self):
         """No clip planes: the whole cloud again."""
         self._p.set_clip_planes(None)
+
+    def setPointKeep(self, keep):
+        """Every later frame leaves out the points whose keep bit is clear: a bool array over the uploaded vertices,
+        uint32 words in the layout of visible_points' source (BUF_VISIBLE), or device memory holding them (see
+        Projector.set_point_keep).  Needs point_ids=True when the cloud may be sorted."""
+        self._p.set_point_keep(keep)
+
+    def hidePoints(self, indices):
+        """Hides the uploaded vertices `indices` as well, on top of the mask in force (none: every point kept)."""
+        keep = self._p.point_keep()
+        if keep is None:
+            keep = np.ones(self._p.num_points, bool)
+        keep[np.asarray(indices, dtype=np.int64)] = False
+        self._p.set_point_keep(keep)
+
+    def clearPointKeep(self):
+        """No keep mask: every point again."""
+        self._p.set_point_keep(None)
 
     def computeRGBD(self, calibration, extrinsics, color, depth):
         """project_cloud.cu:268-312.  extrinsics = world->camera 4x4 (main.cpp:96)."""
