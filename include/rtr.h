@@ -216,6 +216,51 @@ int rtr_num_points(const rtr_ctx *ctx, uint64_t *n);
  * option "auto_reorder"). */
 int rtr_download_points(rtr_ctx *ctx, float *xyzw, uint8_t *rgba, uint64_t first, uint64_t count);
 
+/* ---- 2b. appending points to the resident cloud ------------------------------------------------------------------
+ * Adds m points from HOST memory behind the resident cloud without uploading it again (one scan of a survey, one
+ * piece of a growing capture per call).  Arguments, strides and channel order are those of rtr_upload_points.
+ *
+ * Indices: the m points get upload indices n .. n + m - 1, n the count before the call -- the indices of the point
+ * pass (RTR_BUF_POINT_ID, RTR_BUF_VISIBLE) and of the keep mask.  Points of rtr_generate_synthetic keep their
+ * i - first indices.  m = 0 returns RTR_OK and changes nothing; on a context without points the call is
+ * rtr_upload_points.
+ *
+ * Equivalence: a cloud built by rtr_upload_points(A), then rtr_append_points(B1) .. rtr_append_points(Bk) renders bit
+ * for bit what one rtr_upload_points(A ++ B1 ++ .. ++ Bk) renders with the same options, params, clip planes and
+ * resolution: the host outputs of rtr_project(_filtered) / rtr_project_async, RTR_BUF_DEPTH, _ACCUM, _IMAGE, _TENSOR,
+ * _MASK, _MINMAX, RTR_BUF_POINT_ID and _VISIBLE (whenever the point pass is allowed on both clouds), RTR_BUF_VIEW_*, the
+ * phase calls and rtr_frame_stats words [2] and [3].  What depends on the resident order may differ:
+ * rtr_download_points' order, the option read-backs "reordered", "order_ratio_ppm", "packed_millibytes_per_point",
+ * "resident_millibytes_per_point", and the chunk-counting words of rtr_frame_stats.
+ *
+ * Resident order: points already resident never move; the block goes behind them (its first points may complete the
+ * cloud's last partial 256-point chunk).  Option "auto_reorder" applies to the BLOCK by itself: 0 appends it as given,
+ * 1 Morton-sorts it on its own, 2 (default) sorts it when m >= 65536 and its own chunk measure (mean chunk diagonal
+ * over block diagonal) is above 2 (256 / m)^(1/3).  A block sort makes "reordered" read 1, so the point pass then
+ * needs option "point_ids" = 1, which extends the resident permutation.  The block is NOT sorted when that would lose
+ * the upload order a keep mask in force needs (cloud in upload order, "point_ids" = 0, mask set: the rule of
+ * rtr_reorder_points); this costs speed only.
+ *
+ * Form: a packed cloud stays packed (the new chunks are packed losslessly, and verified with "pack" = 2), an unpacked
+ * one stays unpacked; "keep_soa" is honoured.  A keep mask in force is extended and the new points are KEPT:
+ * RTR_BUF_POINT_KEEP and the nwords of rtr_set_point_keep grow to (n + m + 31) / 32.
+ *
+ * Ordering: like rtr_set_point_keep, the call first completes every frame, pass, view batch and async slot issued
+ * before it (rtr_synchronize); frames that overflowed the adaptive extent pool are rendered again with the cloud they
+ * were issued with -- if that fails, the call returns the error and the cloud is unchanged.
+ *
+ * Side effects, as after an upload: an open peer-to-peer exchange is closed ("p2p_open" reads 0; every rank exports
+ * and opens again), the adaptive extent pools are sized for the new n by the next frame, RTR_BUF_VISIBLE by the next
+ * point pass.
+ *
+ * Errors (RTR_ERR_INVALID, nothing changes): the argument checks of rtr_upload_points, n + m >= 2^32.  A failed
+ * allocation leaves the cloud as it was too: every new buffer is allocated before anything is committed.
+ *
+ * Cost: kernel work proportional to m, plus O(n / 256) passes over per-chunk arrays and, when the resident arrays'
+ * capacity (1/8 head-room) is exceeded, one device-to-device copy of them. */
+int rtr_append_points(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, const uint8_t *rgb,
+                      size_t rgb_stride_bytes, size_t m);
+
 /* ---- 3. camera (project_cloud.cu:318, project_cloud.h:50-59) -------------------- */
 /* P = K4 * E in fp32, row-major, exactly as the reference composes it with glm:
  * K row-major 3x3 intrinsics, E row-major 4x4 world->camera, both double. */

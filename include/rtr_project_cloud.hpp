@@ -21,6 +21,9 @@
 // when the library may sort the cloud (its default upload policy does for unordered clouds).  setClipPlanes /
 // setClipBox / clearClip (rtr.h section 6d) leave part of the cloud out of every later frame; setPointKeep / hidePoints /
 // clearPointKeep (section 6e) hide any set of vertices, by the same indices (point_ids = true when the cloud may be sorted).
+// appendPoints (section 2b) adds a grid (one registered scan) or raw float4 / uchar4 arrays behind the resident cloud
+// without uploading it again; the indices of computePointIds, visible_points and hidePoints continue across appends --
+// the appended vertices follow every vertex given so far, in the same flattened order.
 //
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
@@ -73,6 +76,25 @@ public:
 #ifdef RTR_WITH_TORCH
         load_model(device);
 #endif
+    }
+    // Appends a grid, flattened like the constructor (rtr.h section 2b)
+    template <class Grid>
+    void appendPoints(const Grid& grid) {
+        std::vector<float> xyzw;
+        std::vector<uint8_t> rgba;
+        for (const auto& pair : grid) {
+            for (const auto& p : pair.second.positions) {
+                xyzw.push_back(p.x); xyzw.push_back(p.y); xyzw.push_back(p.z); xyzw.push_back(1.0f);
+            }
+            for (const auto& c : pair.second.colors) {
+                rgba.push_back(c[0]); rgba.push_back(c[1]); rgba.push_back(c[2]); rgba.push_back(255);
+            }
+        }
+        appendPoints(xyzw.data(), 16, rgba.data(), 4, xyzw.size() / 4);
+    }
+    // Appends m points from host memory, strides as in rtr_upload_points (16 / 4: float4 / uchar4, 12 / 3: tight)
+    void appendPoints(const float* xyz, size_t xyz_stride_bytes, const uint8_t* rgb, size_t rgb_stride_bytes, size_t m) {
+        check(ctx_, rtr_append_points(ctx_, xyz, xyz_stride_bytes, rgb, rgb_stride_bytes, m));
     }
     ProjectCloud(const ProjectCloud&) = delete;  // owns device buffers (the reference forgets this)
     ProjectCloud& operator=(const ProjectCloud&) = delete;

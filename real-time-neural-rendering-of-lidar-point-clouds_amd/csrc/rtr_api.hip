@@ -47,6 +47,8 @@ struct rtr_ctx {
     uint4 *pk_hdr = nullptr;        // rtr::PackedXyz of the resident cloud (option "pack"); null: not in use
     uint32_t *pk_planes = nullptr, *pk_planes_b = nullptr;  // (one allocation: A streams, then B streams)
     uint64_t pk_bytes = 0;          // headers + planes
+    uint64_t pk_units = 0, pk_units_cap = 0;  // 32-byte units of the planes in use / allocated (rtr_append_points grows them)
+    uint64_t pk_hdr_chunks = 0;     // chunks the header array holds (+ the zero pair behind them)
     int opt_pack = 1;               // 0 never, 1 when it saves >= 1/8 of the coordinate stream, 2 always + verified after packing
 
     int W = 0, H = 0;  // resolution
@@ -392,6 +394,7 @@ void free_pack(rtr_ctx *c) {
     dfree(c->pk_hdr); dfree(c->pk_planes);
     c->pk_planes_b = nullptr;
     c->pk_bytes = 0;
+    c->pk_units = c->pk_units_cap = c->pk_hdr_chunks = 0;
 }
 
 void free_keep(rtr_ctx *c) {
@@ -1025,7 +1028,8 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
         // device memory this context holds for the cloud and its frames, per point: coordinates (fp32 SoA and / or packed
         // form), colours, chunk boxes and lane spreads, tile stores and extent pools, frame buffers
         const uint64_t nchunks = ((c->cap / 4) + 63) / 64;
-        uint64_t b = (c->x ? 12 * c->cap : 0) + (c->rgba ? 4 * c->cap : 0) + nchunks * 28 + (c->pk_hdr ? c->pk_bytes + 64 : 0) +
+        uint64_t b = (c->x ? 12 * c->cap : 0) + (c->rgba ? 4 * c->cap : 0) + nchunks * 28 +
+                     (c->pk_hdr ? c->pk_bytes + (c->pk_units_cap - c->pk_units) * 32 + 64 : 0) +
                      (c->perm ? 4 * c->cap : 0) + (c->keep_up ? (c->n + 31) / 32 * 4 + nchunks * 33 + 4 : 0);
         const uint64_t npix = (uint64_t)c->W * c->H;
         for (const auto *t : {&c->frame, &c->views}) {
@@ -1224,6 +1228,30 @@ int rtr_synchronize(rtr_ctx *c) {
     return repair(c, c->views);
 }
 
+}  // extern "C"
+
+namespace {
+struct AppendBufs {  // rtr_append_points' buffers: freed on every exit path unless taken
+    std::vector<void *> p;
+    ~AppendBufs() { for (void *q : p) if (q) (void)hipFree(q); }
+    template <class T> hipError_t get(T **out, size_t bytes) {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes ? bytes : 4);
+        if (e == hipSuccess) p.push_back(q);
+        *out = static_cast<T *>(q);
+        return e;
+    }
+    template <class T> void swap_in(T *&field, T *next) {  // a resident array replaced: the old one goes with the scratch
+        if (field == next) return;
+        p.push_back((void *)field);
+        for (auto &x : p) if (x == (void *)next) x = nullptr;
+        field = next;
+    }
+};
+}  // namespace
+
+extern "C" {
+
 // ---- keep mask (rtr.h, section 6e) ----------------------------------------------------
 // Everything issued before is finished and checked first, as rtr_synchronize does, and also the async slots' frames a
 // repair repeats (with the mask they were issued with): no journal entry then needs a copy of the mask.  The slots stay
@@ -1345,6 +1373,8 @@ static int pack_cloud(rtr_ctx *c) {
     c->pk_planes = planes;
     c->pk_planes_b = planes + b_dw;
     c->pk_bytes = bytes;
+    c->pk_units = c->pk_units_cap = host[0];
+    c->pk_hdr_chunks = nchunks;
     return RTR_OK;
 }
 
@@ -1431,6 +1461,252 @@ int rtr_generate_synthetic(rtr_ctx *c, int scene, uint64_t seed, uint64_t first,
     if (!c->pk_hdr)
         if (int rc2 = pack_cloud(c)) return rc2;
     drop_soa(c);
+    return RTR_OK;
+}
+
+// ---- appending (rtr.h, section 2b) ----------------------------------------------------
+// The block goes behind the resident points.  Its first points may complete the last partial 256-point chunk c0, so the
+// per-chunk state from c0 on is rebuilt over a WINDOW: fp32 SoA arrays holding chunk c0's resident points (copied, or
+// decoded from the packed form when the SoA arrays are not resident) followed by the block.  The upload's kernels run
+// on the window in their range forms (rtr_kernels.h): chunk boxes and lane spreads, packed headers (the scan continues
+// from chunk c0's block offset) and blocks, the keep mask's resident words and summaries.  Every buffer that may fail
+// to allocate is allocated before the first resident byte changes; the arrays grow with 1/8 head-room.
+static uint64_t grown(uint64_t have, uint64_t need) {
+    if (need <= have) return have;
+    const uint64_t g = have + have / 8;
+    return g > need ? g : need;
+}
+
+int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rgb, size_t rs, size_t m) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, m == 0 || (xyz && rgb), "xyz / rgb is NULL");
+    NEED(c, xs >= 12 && xs % 4 == 0, "xyz_stride_bytes must be >= 12 and a multiple of 4");
+    NEED(c, rs >= 3, "rgb_stride_bytes must be >= 3");
+    NEED(c, m < (1ull << 32) && c->n + m < (1ull << 32),
+         "too many points for one context (point indices are 32-bit): shard the cloud");
+    if (m == 0) return RTR_OK;
+    if (c->n == 0) return rtr_upload_points(c, xyz, xs, rgb, rs, m);
+    DevGuard g(c->device);
+    if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
+    drop_soa(c);  // (SoA arrays decoded for a call in between are not kept: the window decodes what it needs)
+    hipStream_t s = c->stream;
+    const uint64_t n0 = c->n, n1 = n0 + m, c0 = n0 / 256, r = n0 - c0 * 256;
+    const uint64_t nch0 = (n0 + 255) / 256, nch1 = (n1 + 255) / 256, wch = nch1 - c0;
+    const uint64_t wn = r + m, wpad = (wn + 3) & ~3ull, m4 = (m + 3) & ~3ull, n1pad = (n1 + 3) & ~3ull;
+    AppendBufs buf;
+
+    // the block: host -> device in pieces, AoS -> SoA (b*), NaN-padded to a multiple of 4
+    float *bx, *by, *bz, *wx, *wy, *wz;
+    uint32_t *bc, *bperm = nullptr;
+    HIP_TRY(c, buf.get(&bx, m4 * 4)); HIP_TRY(c, buf.get(&by, m4 * 4)); HIP_TRY(c, buf.get(&bz, m4 * 4));
+    HIP_TRY(c, buf.get(&bc, m4 * 4));
+    {
+        const uint64_t chunk = 1ull << 24, sm = m < chunk ? m : chunk;
+        uint8_t *sx, *sc;
+        HIP_TRY(c, buf.get(&sx, sm * xs));
+        HIP_TRY(c, buf.get(&sc, sm * rs));
+        for (uint64_t off = 0; off < m; off += chunk) {
+            const uint64_t cnt = (m - off) < chunk ? (m - off) : chunk;
+            HIP_TRY(c, hipMemcpyAsync(sx, (const uint8_t *)xyz + off * xs, cnt * xs, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(sc, rgb + off * rs, cnt * rs, hipMemcpyHostToDevice, s));
+            rtr::launch_aos_to_soa(s, sx, xs, sc, rs, cnt, bx + off, by + off, bz + off, bc + off);
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+        rtr::launch_pad_nan(s, bx, by, bz, bc, m, m4);
+        if (int rc = launch_check(c, "aos_to_soa")) return rc;
+    }
+
+    // option "auto_reorder" on the block alone (auto_reorder's rule), never losing the order a keep mask needs
+    rtr::Cloud wcl = cloud_of(c);
+    wcl.rgba = nullptr;
+    wcl.pk = rtr::PackedXyz{nullptr, nullptr, nullptr};
+    wcl.keep = rtr::Keep{nullptr, nullptr};
+    bool sort = c->opt_auto_reorder == 1;
+    if (c->opt_auto_reorder == 2 && m >= (1u << 16)) {
+        float *bb, ratio = 0.f, am[3];
+        HIP_TRY(c, buf.get(&bb, ((m + 255) / 256) * 6 * sizeof(float)));
+        wcl.x = bx, wcl.y = by, wcl.z = bz, wcl.n = m, wcl.spread = nullptr;
+        rtr::launch_chunk_bounds(s, wcl, bb, nullptr);
+        const int e = rtr::order_quality(s, bb, m, &ratio, am);
+        if (e != 0) return fail(c, RTR_ERR_HIP, "block order measure failed: %s", hipGetErrorString((hipError_t)e));
+        sort = ratio > 2.0f * cbrtf(256.0f / (float)m);
+    }
+    sort = sort && m >= 2 && !(c->keep_up && !c->reordered && !c->opt_point_ids);
+    const bool reordered1 = c->reordered || sort;
+    const bool with_perm = c->reordered ? c->perm != nullptr : (sort && c->opt_point_ids);
+    if (with_perm) {  // upload indices of the block: n0 .. n1 - 1, sorted with it
+        HIP_TRY(c, buf.get(&bperm, m * 4));
+        rtr::launch_iota(s, bperm, m, n0);
+    }
+    if (sort) {
+        const int e = rtr::reorder_morton(s, bx, by, bz, bc, m, bperm);
+        if (e != 0) return fail(c, RTR_ERR_HIP, "block sort failed: %s", hipGetErrorString((hipError_t)e));
+    }
+
+    // the window: chunk c0's resident points, then the block; its chunk boxes and lane spreads
+    HIP_TRY(c, buf.get(&wx, wpad * 4)); HIP_TRY(c, buf.get(&wy, wpad * 4)); HIP_TRY(c, buf.get(&wz, wpad * 4));
+    if (r) {
+        if (c->x) {
+            HIP_TRY(c, hipMemcpyAsync(wx, c->x + c0 * 256, r * 4, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(wy, c->y + c0 * 256, r * 4, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(wz, c->z + c0 * 256, r * 4, hipMemcpyDeviceToDevice, s));
+        } else {  // (packed form only: chunk c0 alone is decoded, bit for bit; it writes whole quads, the block follows)
+            rtr::unpack_to_soa(s, rtr::PackedXyz{c->pk_hdr + 2 * c0, c->pk_planes, c->pk_planes_b}, r, wx, wy, wz);
+        }
+    }
+    HIP_TRY(c, hipMemcpyAsync(wx + r, bx, m * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(wy + r, by, m * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(wz + r, bz, m * 4, hipMemcpyDeviceToDevice, s));
+    rtr::launch_pad_nan(s, wx, wy, wz, nullptr, wn, wpad);
+    float *wb, *wsp;
+    HIP_TRY(c, buf.get(&wb, wch * 6 * sizeof(float)));
+    HIP_TRY(c, buf.get(&wsp, wch * sizeof(float)));
+    wcl.x = wx, wcl.y = wy, wcl.z = wz, wcl.n = wn, wcl.spread = wsp;
+    rtr::launch_chunk_bounds(s, wcl, wb, wsp);
+
+    // packed: the window's headers, the scan continued from chunk c0's block offset
+    const bool packed = c->pk_hdr != nullptr;
+    uint4 *whdr = nullptr;
+    uint64_t *tot = nullptr, first_unit = c->pk_units, units1 = 0;
+    if (packed) {
+        if (c0 < nch0) {
+            uint4 h1;
+            HIP_TRY(c, hipMemcpyAsync(&h1, c->pk_hdr + 2 * c0 + 1, sizeof h1, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            first_unit = ((uint64_t)h1.y << 32) | h1.x;
+        }
+        uint32_t *cnt;
+        HIP_TRY(c, buf.get(&whdr, wch * 2 * sizeof(uint4)));
+        HIP_TRY(c, buf.get(&cnt, wch * sizeof(uint32_t)));
+        HIP_TRY(c, buf.get(&tot, 2 * sizeof(uint64_t)));
+        HIP_TRY(c, hipMemsetAsync(tot, 0, 2 * sizeof(uint64_t), s));
+        rtr::pack_measure(s, wcl, whdr, cnt, tot, first_unit);
+        HIP_TRY(c, hipMemcpyAsync(&units1, tot, sizeof units1, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = launch_check(c, "append window")) return rc;
+
+    // every buffer the commit needs, before anything resident changes
+    const uint64_t cap1 = (grown(c->cap, n1pad) + 3) & ~3ull, cch1 = (cap1 / 4 + 63) / 64;
+    const bool regrow = cap1 > c->cap;
+    float *x1 = c->x, *y1 = c->y, *z1 = c->z, *bounds1 = c->bounds, *spread1 = c->spread;
+    uint32_t *rgba1 = c->rgba, *perm1 = with_perm ? c->perm : nullptr;
+    if (regrow) {
+        HIP_TRY(c, buf.get(&rgba1, cap1 * 4));
+        HIP_TRY(c, buf.get(&bounds1, cch1 * 6 * sizeof(float)));
+        HIP_TRY(c, buf.get(&spread1, cch1 * sizeof(float)));
+        if (c->x) {
+            HIP_TRY(c, buf.get(&x1, cap1 * 4)); HIP_TRY(c, buf.get(&y1, cap1 * 4)); HIP_TRY(c, buf.get(&z1, cap1 * 4));
+        }
+    }
+    if (with_perm && (regrow || !c->perm)) HIP_TRY(c, buf.get(&perm1, cap1 * 4));
+    uint4 *hdr1 = c->pk_hdr;
+    uint32_t *planes1 = c->pk_planes, *planes1_b = c->pk_planes_b;
+    uint64_t hch1 = c->pk_hdr_chunks, ucap1 = c->pk_units_cap;
+    if (packed && nch1 > c->pk_hdr_chunks) {
+        hch1 = grown(c->pk_hdr_chunks, nch1);
+        HIP_TRY(c, buf.get(&hdr1, (hch1 + 1) * 2 * sizeof(uint4)));  // (+ one zero header: read in pairs)
+    }
+    if (packed && units1 > c->pk_units_cap) {
+        ucap1 = grown(c->pk_units_cap, units1);
+        HIP_TRY(c, buf.get(&planes1, rtr::pack_total_dwords(ucap1) * 4));
+        planes1_b = planes1 + rtr::pack_b_dwords(ucap1);
+    }
+    uint32_t *up1 = nullptr, *res1 = nullptr;
+    uint8_t *sum1 = nullptr;
+    if (c->keep_up) {
+        HIP_TRY(c, buf.get(&up1, (n1 + 31) / 32 * 4));
+        HIP_TRY(c, buf.get(&res1, nch1 * 32));
+        HIP_TRY(c, buf.get(&sum1, (nch1 + 3) & ~3ull));  // (read as whole dwords)
+    }
+
+    // commit: the resident prefix into grown arrays, then the window's chunks from c0 on
+    auto d2d = [&](void *dst, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    };
+    if (regrow) {
+        HIP_TRY(c, d2d(rgba1, c->rgba, n0 * 4));
+        HIP_TRY(c, d2d(bounds1, c->bounds, c0 * 6 * sizeof(float)));
+        HIP_TRY(c, d2d(spread1, c->spread, c0 * sizeof(float)));
+        if (c->x) {
+            HIP_TRY(c, d2d(x1, c->x, c0 * 256 * 4)); HIP_TRY(c, d2d(y1, c->y, c0 * 256 * 4)); HIP_TRY(c, d2d(z1, c->z, c0 * 256 * 4));
+        }
+    }
+    HIP_TRY(c, d2d(rgba1 + n0, bc, m * 4));
+    if (n1pad > n1) HIP_TRY(c, hipMemsetAsync(rgba1 + n1, 0, (n1pad - n1) * 4, s));
+    if (x1) {
+        HIP_TRY(c, d2d(x1 + c0 * 256, wx, wpad * 4)); HIP_TRY(c, d2d(y1 + c0 * 256, wy, wpad * 4));
+        HIP_TRY(c, d2d(z1 + c0 * 256, wz, wpad * 4));
+    }
+    HIP_TRY(c, d2d(bounds1 + 6 * c0, wb, wch * 6 * sizeof(float)));
+    HIP_TRY(c, d2d(spread1 + c0, wsp, wch * sizeof(float)));
+    if (with_perm) {
+        if (perm1 != c->perm) {
+            if (c->perm) HIP_TRY(c, d2d(perm1, c->perm, n0 * 4));
+            else rtr::launch_iota(s, perm1, n0);  // (the cloud was in upload order until this block's sort)
+        }
+        HIP_TRY(c, d2d(perm1 + n0, bperm, m * 4));
+    }
+    if (packed) {
+        if (hdr1 != c->pk_hdr) HIP_TRY(c, d2d(hdr1, c->pk_hdr, c0 * 2 * sizeof(uint4)));
+        HIP_TRY(c, d2d(hdr1 + 2 * c0, whdr, wch * 2 * sizeof(uint4)));
+        HIP_TRY(c, hipMemsetAsync(hdr1 + 2 * nch1, 0, 2 * sizeof(uint4), s));
+        if (planes1 != c->pk_planes) {  // (the A region grows, so the B region moves)
+            HIP_TRY(c, d2d(planes1, c->pk_planes, first_unit * 2 * 4));
+            HIP_TRY(c, d2d(planes1_b, c->pk_planes_b, first_unit * 6 * 4));
+        }
+        rtr::pack_write(s, wcl, hdr1 + 2 * c0, planes1, planes1_b);
+        // (the spare bytes behind both streams read as zero, as after an upload: the last lanes' loads run into them)
+        HIP_TRY(c, hipMemsetAsync(planes1 + units1 * 2, 0, (rtr::pack_b_dwords(units1) - units1 * 2) * 4, s));
+        HIP_TRY(c, hipMemsetAsync(planes1_b + units1 * 6, 0, 64, s));
+        if (c->opt_pack == 2) rtr::pack_verify(s, wcl, hdr1 + 2 * c0, planes1, planes1_b, tot + 1);
+    }
+    if (c->keep_up) {  // (the new points kept; resident words and summaries from chunk c0 on)
+        HIP_TRY(c, d2d(up1, c->keep_up, (n0 + 31) / 32 * 4));
+        rtr::launch_keep_append(s, up1, n0, n1);
+        HIP_TRY(c, d2d(res1, c->keep_res, c0 * 32));
+        HIP_TRY(c, d2d(sum1, c->keep_sum, c0));
+        rtr::launch_keep_build(s, up1, reordered1 ? perm1 : nullptr, n1, res1, sum1, c0);
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = launch_check(c, "append")) return rc;
+
+    // the new state
+    buf.swap_in(c->rgba, rgba1); buf.swap_in(c->bounds, bounds1); buf.swap_in(c->spread, spread1);
+    buf.swap_in(c->x, x1); buf.swap_in(c->y, y1); buf.swap_in(c->z, z1);
+    if (with_perm) buf.swap_in(c->perm, perm1);
+    c->cap = cap1;
+    if (packed) {
+        buf.swap_in(c->pk_hdr, hdr1); buf.swap_in(c->pk_planes, planes1);
+        c->pk_planes_b = planes1_b;
+        c->pk_units = units1, c->pk_units_cap = ucap1, c->pk_hdr_chunks = hch1;
+        c->pk_bytes = units1 * 32 + nch1 * 32;
+    }
+    if (c->keep_up) { buf.swap_in(c->keep_up, up1); buf.swap_in(c->keep_res, res1); buf.swap_in(c->keep_sum, sum1); }
+    c->n = n1;
+    c->reordered = reordered1;
+    ++c->cloud_seq;
+    c->list_valid = false;
+    c->jr.frame.count = 0;
+    c->jr.views.count = 0;
+    c->pp_vis_current = false;
+    c->split_cooldown = kSplitCooldown;
+    if (c->p2p.open || c->p2p.red) p2p_release(c);  // (the peers map pools sized for the old cloud)
+    reset_pool_sizing(c->frame);
+    reset_pool_sizing(c->views);
+    {   // order measure and absmax over every chunk box: the lane test's margin steps and the incoherent form read them
+        float ratio = 0.f;
+        if (rtr::order_quality(s, c->bounds, n1, &ratio, c->absmax) != 0) {
+            (void)hipGetLastError();
+            c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();
+        }
+        c->order_ratio = n1 >= (1u << 16) ? ratio : 0.f;
+    }
+    if (packed && c->opt_pack == 2) {
+        uint64_t bad = 0;
+        HIP_TRY(c, hipMemcpy(&bad, tot + 1, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad) return fail(c, RTR_ERR_HIP, "pack: %llu appended points decode to other coordinates", (unsigned long long)bad);
+    }
     return RTR_OK;
 }
 

@@ -261,14 +261,22 @@ size_t view_tab_bytes();
 hipError_t launch_project_bin_views(hipStream_t s, const Cloud &c, const Proj *P, const TileStore *S, int count, int W, int H,
                               void *tab_host, void *tab_dev, int flags, int phases, hipEvent_t ev_start = nullptr,
                               hipEvent_t ev_stop = nullptr);
-void launch_chunk_bounds(hipStream_t s, const Cloud &c, float *bounds, float *spread);  // 6 floats (+ 1) per 256 points
+// 6 floats (+ 1) per 256 points; from chunk c0 on (rtr_append_points): c's arrays start at point 256 c0, c.n counts from
+// there, bounds + 6 c0, spread + c0
+void launch_chunk_bounds(hipStream_t s, const Cloud &c, float *bounds, float *spread);
 // packing (see PackedXyz): pack_measure fills hdr[2 nchunks] (bases, widths, block offsets by an exclusive
 // scan) and *total_planes (device; in 32-byte units); pack_write fills the blocks; pack_verify counts the points whose decoded
 // coordinates differ from the raw ones (must be 0) into *mismatches (device).  nchunks = ceil(ceil(n / 4) / 64).
-void pack_measure(hipStream_t s, const Cloud &c, uint4 *hdr, uint32_t *chunk_planes, uint64_t *total_planes);  // (c.spread -> hdr[2 c + 1].z)
+// Range form (rtr_append_points): `c` is the cloud from chunk c0 on (its arrays start at point 256 c0, c.spread at
+// spread + c0, c.n counts from there) and hdr = the headers from chunk c0 on; the scan starts at first_unit, chunk c0's
+// block offset, and *total_planes ends as the units of chunks [0, c1).  Every kernel then gives exactly what the
+// whole-cloud launch gives for those chunks: a chunk only reads its own 256 points.
+void pack_measure(hipStream_t s, const Cloud &c, uint4 *hdr, uint32_t *chunk_planes, uint64_t *total_planes,
+                  uint64_t first_unit = 0);  // (c.spread -> hdr[2 c + 1].z)
 void pack_write(hipStream_t s, const Cloud &c, const uint4 *hdr, uint32_t *planes, uint32_t *planes_b);
 void pack_verify(hipStream_t s, const Cloud &c, const uint4 *hdr, const uint32_t *planes, const uint32_t *planes_b, uint64_t *mismatches);
 // x, y, z (padded to a multiple of 4 points) back from the packed form, bit for bit
+// (pk.hdr + 2 c0 and n - 256 c0 points: chunks c0.. alone -- the headers' block offsets are absolute)
 void unpack_to_soa(hipStream_t s, const PackedXyz &pk, uint64_t n, float *x, float *y, float *z);
 // rtr_reorder.hip; perm (may be null) is permuted with the points (option "point_ids": upload index per resident point)
 int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n, uint32_t *perm = nullptr);
@@ -326,7 +334,7 @@ void launch_soa_to_aos(hipStream_t s, const float *x, const float *y, const floa
                        uint64_t count, float *xyzw, uint8_t *rgba_out);
 // (a, b: device buffers padded to 16 bytes; ha, hb: device pointers of mapped pinned host buffers, padded likewise)
 void launch_copy_to_host(hipStream_t s, const void *a, void *ha, size_t bytes_a, const void *b, void *hb, size_t bytes_b);
-void launch_pad_nan(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n, uint64_t n_pad);
+void launch_pad_nan(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n, uint64_t n_pad);  // (rgba may be null)
 // rtr_point_pass: streams the RESIDENT coordinates once (packed: chunks rejected on their header boxes, survivors
 // decoded; else the fp32 SoA) and, for the frame `depth` holds, atomicMin's the upload index of every point whose
 // depth bits are its pixel's into ids[H*W] (cleared to 0xFFFFFFFF by the caller) and sets the bit of every point the
@@ -334,10 +342,14 @@ void launch_pad_nan(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba,
 // the caller clears it and the bits go through perm[resident index] = upload index).  ids / vis may be null.
 void launch_point_pass(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, const uint32_t *depth, float window,
                        uint32_t *ids, uint32_t *vis, const uint32_t *perm);
-void launch_iota(hipStream_t s, uint32_t *out, uint64_t n);  // out[i] = i
+void launch_iota(hipStream_t s, uint32_t *out, uint64_t n, uint64_t first = 0);  // out[i] = first + i
 // rtr_set_point_keep / a sort: the resident-order keep mask and its chunk summary (Keep) from the upload-order mask
 // `up` ((n + 31) / 32 words; perm: resident index -> upload index, null while the cloud is in upload order).  Also
-// clears the bits of `up` at or past n.  res: 8 words per chunk, sum: a byte per chunk.
-void launch_keep_build(hipStream_t s, uint32_t *up, const uint32_t *perm, uint64_t n, uint32_t *res, uint8_t *sum);
+// clears the bits of `up` at or past n.  res: 8 words per chunk, sum: a byte per chunk.  c0 > 0: only chunks [c0, ..)
+// are built (rtr_append_points: the earlier ones hold no new point)
+void launch_keep_build(hipStream_t s, uint32_t *up, const uint32_t *perm, uint64_t n, uint32_t *res, uint8_t *sum,
+                       uint64_t c0 = 0);
+// rtr_append_points: the upload-order mask of n0 points grown to n1, the new points kept (bits [n0, n1) set)
+void launch_keep_append(hipStream_t s, uint32_t *up, uint64_t n0, uint64_t n1);
 
 }  // namespace rtr

@@ -2368,9 +2368,9 @@ __global__ __launch_bounds__(kBlock) void k_pack_measure(const uint4 *__restrict
 // exclusive scan of the chunks' plane counts -> hdr[2 c + 1]; one workgroup (a one-off at upload: ~1 ms per 1e8 points)
 __global__ __launch_bounds__(512) void k_pack_scan(const uint32_t *__restrict__ chunk_planes, uint64_t nchunks,
                                                    uint4 *__restrict__ hdr, uint64_t *__restrict__ total_planes,
-                                                   const float *__restrict__ spread) {
+                                                   const float *__restrict__ spread, uint64_t carry0) {
     __shared__ uint32_t s_w[8];
-    uint64_t carry = 0;
+    uint64_t carry = carry0;
     for (uint64_t c0 = 0; c0 < nchunks; c0 += 512) {
         const uint64_t c = c0 + threadIdx.x;
         const uint32_t v = c < nchunks ? chunk_planes[c] : 0u;
@@ -2488,12 +2488,14 @@ static unsigned pack_grid(uint64_t n4) {
     const uint64_t blocks = ((n4 + 63) / 64 + 3) / 4;
     return (unsigned)(blocks < 8192 ? (blocks ? blocks : 1) : 8192);
 }
-void pack_measure(hipStream_t s, const Cloud &c, uint4 *hdr, uint32_t *chunk_planes, uint64_t *total_planes) {
+void pack_measure(hipStream_t s, const Cloud &c, uint4 *hdr, uint32_t *chunk_planes, uint64_t *total_planes,
+                  uint64_t first_unit) {
     const uint64_t n4 = (c.n + 3) / 4;
     if (n4 == 0) return;
     hipLaunchKernelGGL(k_pack_measure, dim3(pack_grid(n4)), dim3(kBlock), 0, s, (const uint4 *)c.x, (const uint4 *)c.y,
                        (const uint4 *)c.z, n4, hdr, chunk_planes);
-    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(512), 0, s, chunk_planes, (n4 + 63) / 64, hdr, total_planes, c.spread);
+    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(512), 0, s, chunk_planes, (n4 + 63) / 64, hdr, total_planes, c.spread,
+                       first_unit);
 }
 void pack_write(hipStream_t s, const Cloud &c, const uint4 *hdr, uint32_t *planes, uint32_t *planes_b) {
     const uint64_t n4 = (c.n + 3) / 4;
@@ -3573,7 +3575,7 @@ __global__ void k_pad_nan(float *x, float *y, float *z, uint32_t *rgba, uint64_t
         x[t] = q;
         y[t] = q;
         z[t] = q;
-        rgba[t] = 0;
+        if (rgba) rgba[t] = 0;
     }
 }
 
@@ -3783,13 +3785,13 @@ void launch_point_pass(hipStream_t s, const Cloud &c, const Proj &P, int W, int 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_iota(uint32_t *__restrict__ out, uint64_t n) {
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) out[i] = (uint32_t)i;
+__global__ __launch_bounds__(kBlock) void k_iota(uint32_t *__restrict__ out, uint64_t n, uint64_t first) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) out[i] = (uint32_t)(first + i);
 }
-void launch_iota(hipStream_t s, uint32_t *out, uint64_t n) {
+void launch_iota(hipStream_t s, uint32_t *out, uint64_t n, uint64_t first) {
     if (n == 0) return;
     const uint64_t blocks = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_iota, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, out, n);
+    hipLaunchKernelGGL(k_iota, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, out, n, first);
 }
 
 // The keep mask in resident order (rtr_set_point_keep, after a sort): one wave per 256-point chunk, lane l gathers the
@@ -3797,10 +3799,11 @@ void launch_iota(hipStream_t s, uint32_t *out, uint64_t n) {
 // are interleaved into the chunk's eight words as in the point pass, and lane 0 writes the chunk's summary
 // (keep_chunk_state: the same rule on the ballots).  Points at or past n are hidden and do not count.
 __global__ __launch_bounds__(kBlock) void k_keep_build(const uint32_t *__restrict__ up, const uint32_t *__restrict__ perm,
-                                                       uint64_t n, uint32_t *__restrict__ res, uint8_t *__restrict__ sum) {
+                                                       uint64_t n, uint32_t *__restrict__ res, uint8_t *__restrict__ sum,
+                                                       uint64_t c0) {
     const int lane = threadIdx.x & 63;
     const uint64_t nchunks = (n + 255) / 256;
-    for (uint64_t c = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+    for (uint64_t c = c0 + (((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6); c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
         bool kept[4], valid[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -3828,11 +3831,30 @@ __global__ __launch_bounds__(kBlock) void k_keep_build(const uint32_t *__restric
 __global__ void k_keep_tail(uint32_t *up, uint64_t n) {
     if (n % 32u) up[n / 32u] &= (1u << (n % 32u)) - 1u;
 }
-void launch_keep_build(hipStream_t s, uint32_t *up, const uint32_t *perm, uint64_t n, uint32_t *res, uint8_t *sum) {
-    if (n == 0) return;
-    const uint64_t blocks = ((n + 255) / 256 + 3) / 4;  // (a wave per chunk)
-    hipLaunchKernelGGL(k_keep_build, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, up, perm, n, res, sum);
+void launch_keep_build(hipStream_t s, uint32_t *up, const uint32_t *perm, uint64_t n, uint32_t *res, uint8_t *sum,
+                       uint64_t c0) {
+    const uint64_t nchunks = (n + 255) / 256;
+    if (c0 >= nchunks) return;
+    const uint64_t blocks = (nchunks - c0 + 3) / 4;  // (a wave per chunk)
+    hipLaunchKernelGGL(k_keep_build, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, up, perm, n, res, sum, c0);
     hipLaunchKernelGGL(k_keep_tail, dim3(1), dim3(1), 0, s, up, n);
+}
+
+// rtr_append_points: the upload-order mask of a cloud of n0 points, grown to n1, keeps the new points -- the bits
+// [n0, n1) are set.  Word n0 / 32 keeps its bits below n0 (the ones at or past n0 are clear, k_keep_tail); the words
+// behind it are written whole.
+__global__ __launch_bounds__(kBlock) void k_keep_append(uint32_t *__restrict__ up, uint64_t n0, uint64_t n1) {
+    const uint64_t w0 = n0 / 32u, w1 = (n1 + 31u) / 32u;
+    for (uint64_t w = w0 + (uint64_t)blockIdx.x * kBlock + threadIdx.x; w < w1; w += (uint64_t)gridDim.x * kBlock) {
+        const uint64_t lo = w * 32u > n0 ? w * 32u : n0, hi = w * 32u + 32u < n1 ? w * 32u + 32u : n1;  // bits [lo, hi)
+        const uint32_t bits = (uint32_t)((((1ull << (hi - lo)) - 1ull) << (lo - w * 32u)));
+        up[w] = (w == w0 && (n0 % 32u) ? up[w] : 0u) | bits;
+    }
+}
+void launch_keep_append(hipStream_t s, uint32_t *up, uint64_t n0, uint64_t n1) {
+    if (n1 <= n0) return;
+    const uint64_t words = (n1 + 31) / 32 - n0 / 32, blocks = (words + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_keep_append, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, up, n0, n1);
 }
 
 }  // namespace rtr

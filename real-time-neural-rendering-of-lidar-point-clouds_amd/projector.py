@@ -108,6 +108,18 @@ class Projector:
         self._chk(self._lib.rtr_upload_points(self._ctx, _vp(xyz), xyz.shape[1] * 4, _vp(rgb), rgb.shape[1],
                                               xyz.shape[0]))
 
+    def append_points(self, xyz, rgb):
+        """Adds points behind the resident cloud without uploading it again (include/rtr.h section 2b): the shapes and
+        dtypes of upload_points; the new points get upload indices n .. n + m - 1.  Frames equal, bit for bit, those of
+        one upload of everything appended so far."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if xyz.ndim != 2 or xyz.shape[1] not in (3, 4) or rgb.ndim != 2 or rgb.shape[1] not in (3, 4) \
+                or rgb.shape[0] != xyz.shape[0]:
+            raise ValueError("xyz must be [n,3|4] float32 and rgb [n,3|4] uint8 with equal n")
+        self._chk(self._lib.rtr_append_points(self._ctx, _vp(xyz), xyz.shape[1] * 4, _vp(rgb), rgb.shape[1],
+                                              xyz.shape[0]))
+
     def generate_synthetic(self, scene, seed, first, count, total):
         sc = L.SCENES[scene] if isinstance(scene, str) else int(scene)
         self._chk(self._lib.rtr_generate_synthetic(self._ctx, sc, seed, first, count, total))
@@ -430,6 +442,16 @@ class ProjectCloud:
         """The reference constructor's argument: a block grid (project_cloud.cu:189-206);
         `grid` is a formats.Grid (CloudReader::loadCloud's result, cloudreader.cpp:180-216)."""
         return cls(grid.vertex_positions(), grid.vertex_colors(), modelFilename, device)
+
+    def appendPoints(self, vertices, colors):
+        """Appends points (the constructor's arrays: float4 / uchar4 or tight xyz / rgb) to the resident cloud without
+        uploading it again.  computePointIds, visible_points and hidePoints indices continue across appends: the new
+        points follow every point given so far."""
+        self._p.append_points(vertices, colors)
+
+    def appendGrid(self, grid):
+        """appendPoints of a formats.Grid, flattened like from_grid (one registered scan per call)."""
+        self._p.append_points(grid.vertex_positions(), grid.vertex_colors())
 
     @property
     def projector(self):
