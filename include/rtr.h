@@ -261,6 +261,43 @@ int rtr_download_points(rtr_ctx *ctx, float *xyzw, uint8_t *rgba, uint64_t first
 int rtr_append_points(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, const uint8_t *rgb,
                       size_t rgb_stride_bytes, size_t m);
 
+/* ---- 2c. removing points from the resident cloud ------------------------------------------------------------------
+ * Takes points out of the resident cloud and gives their memory back (a bad scan, outliers, passers-by; the last append
+ * again).  keep_words: (n + 31) / 32 words in UPLOAD order, bit i % 32 of word i / 32 set = point i stays -- the layout
+ * of rtr_set_point_keep and RTR_BUF_VISIBLE, so RTR_BUF_POINT_KEEP or a point pass's visibility can be passed as they
+ * are.  Host memory or device memory of the context's device; the words are copied, the caller may reuse them when the
+ * call returns.  Bits past n are ignored.
+ *
+ * Indices: the survivors keep their relative upload order and are renumbered 0 .. n' - 1: survivor i gets the number
+ * of kept points with an upload index below i.  This applies to the point pass (RTR_BUF_POINT_ID, _VISIBLE), to the
+ * keep mask and to later appends, which continue at n'.
+ *
+ * Equivalence: rtr_upload_points(A), then rtr_remove_points(keep), renders bit for bit what one
+ * rtr_upload_points(A[keep]) renders with the same options, params, clip planes and resolution -- the outputs section 2b
+ * lists, with what depends on the resident order excepted as there; and so across any sequence of uploads, appends and
+ * removals.
+ *
+ * Resident order: a stable compaction; points never change their relative order (a sorted cloud stays sorted and is
+ * not sorted again).  The 256-point chunks before the first one that loses a point are untouched; the ones from there
+ * on are rebuilt.  A packed cloud stays packed ("pack" = 2 verifies the rebuilt chunks), an unpacked one unpacked;
+ * "keep_soa" is honoured.  The permutation of "point_ids" is compacted and renumbered.  A keep mask in force is
+ * compacted onto the survivors: RTR_BUF_POINT_KEEP then reads old[keep] and the nwords of rtr_set_point_keep shrink.
+ * Device arrays holding more than 1/8 head-room over the survivors are reallocated to that size.
+ *
+ * Ordering and side effects as for rtr_append_points: the call first completes everything issued before it (async slots
+ * come out with the old cloud); then an open peer-to-peer exchange is closed, the adaptive extent pools are sized again
+ * by the next frame and RTR_BUF_VISIBLE by the next point pass.  A mask that keeps every point changes nothing (the
+ * exchange stays open); one that keeps none leaves the context of an upload of 0 points, without a keep mask.
+ *
+ * Errors (RTR_ERR_INVALID, nothing changes): no cloud, nwords != (n + 31) / 32, keep_words NULL, a cloud the library
+ * sorted without option "point_ids" = 1 (upload indices cannot be mapped).  A failed allocation leaves the cloud as it
+ * was too: every new buffer is allocated before anything is committed.
+ *
+ * Cost: a pass over the keep bits of every resident point (through the permutation when sorted), kernel work
+ * proportional to the points from the first chunk that loses one, and O(n / 256) passes over per-chunk arrays; removing
+ * a tail costs about what appending it did. */
+int rtr_remove_points(rtr_ctx *ctx, const uint32_t *keep_words, uint64_t nwords);
+
 /* ---- 3. camera (project_cloud.cu:318, project_cloud.h:50-59) -------------------- */
 /* P = K4 * E in fp32, row-major, exactly as the reference composes it with glm:
  * K row-major 3x3 intrinsics, E row-major 4x4 world->camera, both double. */

@@ -24,6 +24,8 @@
 // appendPoints (section 2b) adds a grid (one registered scan) or raw float4 / uchar4 arrays behind the resident cloud
 // without uploading it again; the indices of computePointIds, visible_points and hidePoints continue across appends --
 // the appended vertices follow every vertex given so far, in the same flattened order.
+// removePoints (section 2c) takes vertices out for good and renumbers the rest; commitPointKeep removes what the keep
+// mask in force hides.
 //
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
@@ -249,6 +251,31 @@ public:
         check(ctx_, rtr_set_point_keep(ctx_, words.data(), words.size()));
     }
     void clearPointKeep() { check(ctx_, rtr_set_point_keep(ctx_, nullptr, 0)); }
+    // Removal (rtr.h section 2c): takes the vertices `indices` out of the resident cloud for good, giving their memory
+    // back; the others keep their order and are renumbered 0 .. n' - 1 (the indices of computePointIds, visible_points,
+    // hidePoints and later appends).
+    void removePoints(const std::vector<uint64_t>& indices) {
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        std::vector<uint32_t> words((size_t)((n + 31) / 32), 0xFFFFFFFFu);
+        for (uint64_t i : indices) {
+            if (i >= n) throw std::out_of_range("removePoints: index past the vertex count");
+            words[(size_t)(i / 32)] &= ~(1u << (i % 32));
+        }
+        check(ctx_, rtr_remove_points(ctx_, words.data(), words.size()));
+    }
+    // Removes the vertices the keep mask in force hides, then clears the mask (frames unchanged; nothing without a mask).
+    void commitPointKeep() {
+        int set = 0;
+        check(ctx_, rtr_get_option(ctx_, "point_keep", &set));
+        if (!set) return;
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        std::vector<uint32_t> words((size_t)((n + 31) / 32), 0u);
+        check(ctx_, rtr_download_buffer(ctx_, RTR_BUF_POINT_KEEP, words.data(), words.size() * 4));
+        check(ctx_, rtr_remove_points(ctx_, words.data(), words.size()));
+        check(ctx_, rtr_set_point_keep(ctx_, nullptr, 0));
+    }
 
     // Renders the frame (computeRGBD / computeFilteredRGBD without host copies) and returns, per pixel (row-major
     // H x W), the vertex index of the point it shows, -1 for none (empty or prefiltered-away pixels).

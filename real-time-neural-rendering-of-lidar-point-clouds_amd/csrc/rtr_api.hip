@@ -8,6 +8,7 @@
 // per frame), and the camera matrix travels as a kernel argument.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1231,7 +1232,7 @@ int rtr_synchronize(rtr_ctx *c) {
 }  // extern "C"
 
 namespace {
-struct AppendBufs {  // rtr_append_points' buffers: freed on every exit path unless taken
+struct AppendBufs {  // rtr_append_points' / rtr_remove_points' buffers: freed on every exit path unless taken
     std::vector<void *> p;
     ~AppendBufs() { for (void *q : p) if (q) (void)hipFree(q); }
     template <class T> hipError_t get(T **out, size_t bytes) {
@@ -1706,6 +1707,237 @@ int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
         uint64_t bad = 0;
         HIP_TRY(c, hipMemcpy(&bad, tot + 1, sizeof bad, hipMemcpyDeviceToHost));
         if (bad) return fail(c, RTR_ERR_HIP, "pack: %llu appended points decode to other coordinates", (unsigned long long)bad);
+    }
+    return RTR_OK;
+}
+
+// ---- removing (rtr.h, section 2c) -------------------------------------------------------------------------------
+// A stable compaction of the resident order.  One wave per chunk counts its survivors (through perm when the cloud is
+// sorted) and names the first chunk c0 that loses a point; chunks before it stay where they are.  The survivors of the
+// chunks from c0 on are compacted into a WINDOW (fp32 SoA, colours, renumbered upload indices) that then takes
+// rtr_append_points' commit path: chunk boxes and lane spreads, packed headers (the scan continues from chunk c0's block
+// offset) and blocks, the keep mask's resident words and summaries.  Every buffer is allocated before the first resident
+// byte changes; arrays that would hold more than 1/8 head-room over the survivors are reallocated to that size.
+static uint64_t fitted(uint64_t have, uint64_t need) {  // capacity after a removal: `have` unless it wastes > 1/8
+    const uint64_t fit = need + need / 8;
+    return need > have ? fit : (have > fit ? fit : have);
+}
+
+int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, c->n > 0, "rtr_remove_points: no cloud");
+    NEED(c, keep_words != nullptr, "rtr_remove_points: keep_words is NULL");
+    if (nwords != (c->n + 31) / 32)
+        return fail(c, RTR_ERR_INVALID, "rtr_remove_points: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
+    NEED(c, !c->reordered || c->perm,
+         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be mapped: set "
+         "point_ids = 1 before the upload (or upload with auto_reorder = 0)");
+    DevGuard g(c->device);
+    if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
+    drop_soa(c);
+    hipStream_t s = c->stream;
+    const uint64_t n0 = c->n, nch0 = (n0 + 255) / 256;
+    const uint32_t *perm0 = c->reordered ? c->perm : nullptr;
+    AppendBufs buf;
+
+    // the caller's words (host or device memory), survivors per chunk, their exclusive scan, the first chunk losing one
+    uint32_t *kw, *cnt, *dst, *scr;
+    uint64_t *tot;
+    HIP_TRY(c, buf.get(&kw, nwords * 4));
+    HIP_TRY(c, buf.get(&cnt, nch0 * 4));
+    HIP_TRY(c, buf.get(&dst, nch0 * 4));
+    const uint64_t scr_words = std::max(rtr::scan_scratch_words(nch0), rtr::scan_scratch_words(nwords));
+    HIP_TRY(c, buf.get(&scr, scr_words * 4));
+    HIP_TRY(c, buf.get(&tot, 4 * sizeof(uint64_t)));  // first loss, survivors, kept words' total, pack mismatches
+    HIP_TRY(c, hipMemcpyAsync(kw, keep_words, nwords * 4, hipMemcpyDefault, s));
+    HIP_TRY(c, hipMemsetAsync(tot, 0xFF, sizeof(uint64_t), s));
+    HIP_TRY(c, hipMemsetAsync(tot + 1, 0, 3 * sizeof(uint64_t), s));
+    rtr::launch_remove_count(s, kw, perm0, n0, cnt, tot);
+    rtr::launch_scan_u32(s, cnt, nch0, 0, dst, scr, tot + 1);
+    uint64_t head[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(head, tot, sizeof head, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = launch_check(c, "remove count")) return rc;
+    const uint64_t n1 = head[1], c0 = head[0] < nch0 ? head[0] : nch0;
+    if (n1 == n0) return RTR_OK;  // (every point stays: nothing changes)
+    if (n1 == 0) {  // (no point stays: the context of an upload of 0 points)
+        // (its 4-point arrays are allocated before the cloud is freed: a failed allocation leaves the cloud as it was;
+        // the upload then finds them and allocates nothing)
+        float *ex, *ey, *ez, *eb, *esp;
+        uint32_t *ec;
+        HIP_TRY(c, buf.get(&ex, 16)); HIP_TRY(c, buf.get(&ey, 16)); HIP_TRY(c, buf.get(&ez, 16));
+        HIP_TRY(c, buf.get(&ec, 16)); HIP_TRY(c, buf.get(&eb, 6 * sizeof(float))); HIP_TRY(c, buf.get(&esp, sizeof(float)));
+        free_cloud(c);
+        buf.swap_in(c->x, ex); buf.swap_in(c->y, ey); buf.swap_in(c->z, ez); buf.swap_in(c->rgba, ec);
+        buf.swap_in(c->bounds, eb); buf.swap_in(c->spread, esp);
+        c->cap = 4;
+        const float nx[4] = {0.f, 0.f, 0.f, 1.f};
+        const uint8_t nc[4] = {0, 0, 0, 255};
+        return rtr_upload_points(c, nx, 16, nc, 4, 0);
+    }
+
+    // the window: the survivors of chunks c0.., compacted (renumbered upload indices when the permutation is kept)
+    const uint64_t wn = n1 - 256 * c0, wpad = (wn + 3) & ~3ull, wch = (wn + 255) / 256, nch1 = c0 + wch;
+    const uint64_t n1pad = (n1 + 3) & ~3ull;
+    const bool with_perm = perm0 != nullptr;
+    uint32_t *wscan = nullptr, *wrgba, *wperm = nullptr;
+    float *wx, *wy, *wz;
+    if (with_perm || c->keep_up) {
+        HIP_TRY(c, buf.get(&wscan, nwords * 4));
+        rtr::launch_scan_u32(s, kw, nwords, n0, wscan, scr, tot + 2);
+    }
+    HIP_TRY(c, buf.get(&wx, wpad * 4)); HIP_TRY(c, buf.get(&wy, wpad * 4)); HIP_TRY(c, buf.get(&wz, wpad * 4));
+    HIP_TRY(c, buf.get(&wrgba, wpad * 4));
+    if (with_perm) HIP_TRY(c, buf.get(&wperm, wpad * 4));
+    rtr::Cloud cl = cloud_of(c);
+    rtr::launch_remove_compact(s, cl, perm0, kw, wscan, dst, c0, wx, wy, wz, wrgba, wperm);
+    rtr::launch_pad_nan(s, wx, wy, wz, wrgba, wn, wpad);
+    float *wb, *wsp;
+    HIP_TRY(c, buf.get(&wb, wch * 6 * sizeof(float)));
+    HIP_TRY(c, buf.get(&wsp, wch * sizeof(float)));
+    rtr::Cloud wcl = cl;
+    wcl.rgba = nullptr;
+    wcl.pk = rtr::PackedXyz{nullptr, nullptr, nullptr};
+    wcl.keep = rtr::Keep{nullptr, nullptr};
+    wcl.x = wx, wcl.y = wy, wcl.z = wz, wcl.n = wn, wcl.spread = wsp;
+    rtr::launch_chunk_bounds(s, wcl, wb, wsp);
+
+    // packed: the window's headers, the scan continued from chunk c0's block offset
+    const bool packed = c->pk_hdr != nullptr;
+    uint4 *whdr = nullptr;
+    uint64_t first_unit = 0, units1 = 0;
+    if (packed) {
+        uint4 h1;
+        HIP_TRY(c, hipMemcpyAsync(&h1, c->pk_hdr + 2 * c0 + 1, sizeof h1, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        first_unit = ((uint64_t)h1.y << 32) | h1.x;
+        units1 = first_unit;  // (an empty window -- only whole trailing chunks removed -- adds no unit)
+        if (wn) {
+            HIP_TRY(c, buf.get(&whdr, wch * 2 * sizeof(uint4)));
+            rtr::pack_measure(s, wcl, whdr, cnt, tot + 1, first_unit);  // (cnt is free again; tot[1] ends as the units)
+            HIP_TRY(c, hipMemcpyAsync(&units1, tot + 1, sizeof units1, hipMemcpyDeviceToHost, s));
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = launch_check(c, "remove window")) return rc;
+
+    // every buffer the commit needs, before anything resident changes
+    const uint64_t cap1 = (fitted(c->cap, n1pad) + 3) & ~3ull, cch1 = (cap1 / 4 + 63) / 64;
+    const bool realloc = cap1 != c->cap;
+    float *x1 = c->x, *y1 = c->y, *z1 = c->z, *bounds1 = c->bounds, *spread1 = c->spread;
+    uint32_t *rgba1 = c->rgba, *perm1 = with_perm ? c->perm : nullptr;
+    if (realloc) {
+        HIP_TRY(c, buf.get(&rgba1, cap1 * 4));
+        HIP_TRY(c, buf.get(&bounds1, cch1 * 6 * sizeof(float)));
+        HIP_TRY(c, buf.get(&spread1, cch1 * sizeof(float)));
+        if (c->x) {
+            HIP_TRY(c, buf.get(&x1, cap1 * 4)); HIP_TRY(c, buf.get(&y1, cap1 * 4)); HIP_TRY(c, buf.get(&z1, cap1 * 4));
+        }
+        if (with_perm) HIP_TRY(c, buf.get(&perm1, cap1 * 4));
+    }
+    uint4 *hdr1 = c->pk_hdr;
+    uint32_t *planes1 = c->pk_planes, *planes1_b = c->pk_planes_b;
+    uint64_t hch1 = c->pk_hdr_chunks, ucap1 = c->pk_units_cap;
+    if (packed) {  // (merged chunks may span wider boxes: the planes can grow)
+        hch1 = fitted(c->pk_hdr_chunks, nch1);
+        if (hch1 != c->pk_hdr_chunks) HIP_TRY(c, buf.get(&hdr1, (hch1 + 1) * 2 * sizeof(uint4)));  // (+ one zero pair)
+        ucap1 = fitted(c->pk_units_cap, units1);
+        if (ucap1 != c->pk_units_cap) {
+            HIP_TRY(c, buf.get(&planes1, rtr::pack_total_dwords(ucap1) * 4));
+            planes1_b = planes1 + rtr::pack_b_dwords(ucap1);
+        }
+    }
+    uint32_t *up1 = nullptr, *res1 = nullptr;
+    uint8_t *sum1 = nullptr;
+    if (c->keep_up) {
+        HIP_TRY(c, buf.get(&up1, (n1 + 31) / 32 * 4));
+        HIP_TRY(c, buf.get(&res1, nch1 * 32));
+        HIP_TRY(c, buf.get(&sum1, (nch1 + 3) & ~3ull));  // (read as whole dwords)
+    }
+
+    // commit: the kept prefix into reallocated arrays, then the window's chunks from c0 on
+    auto d2d = [&](void *dst_, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(dst_, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+    };
+    const uint64_t p0 = 256 * c0;  // (the untouched prefix: whole chunks)
+    if (realloc) {
+        HIP_TRY(c, d2d(rgba1, c->rgba, p0 * 4));
+        HIP_TRY(c, d2d(bounds1, c->bounds, c0 * 6 * sizeof(float)));
+        HIP_TRY(c, d2d(spread1, c->spread, c0 * sizeof(float)));
+        if (c->x) {
+            HIP_TRY(c, d2d(x1, c->x, p0 * 4)); HIP_TRY(c, d2d(y1, c->y, p0 * 4)); HIP_TRY(c, d2d(z1, c->z, p0 * 4));
+        }
+        if (with_perm) HIP_TRY(c, d2d(perm1, c->perm, p0 * 4));
+    }
+    HIP_TRY(c, d2d(rgba1 + p0, wrgba, wpad * 4));
+    if (x1) {
+        HIP_TRY(c, d2d(x1 + p0, wx, wpad * 4)); HIP_TRY(c, d2d(y1 + p0, wy, wpad * 4)); HIP_TRY(c, d2d(z1 + p0, wz, wpad * 4));
+    }
+    HIP_TRY(c, d2d(bounds1 + 6 * c0, wb, wch * 6 * sizeof(float)));
+    HIP_TRY(c, d2d(spread1 + c0, wsp, wch * sizeof(float)));
+    if (with_perm) HIP_TRY(c, d2d(perm1 + p0, wperm, wn * 4));
+    if (packed) {
+        if (hdr1 != c->pk_hdr) HIP_TRY(c, d2d(hdr1, c->pk_hdr, c0 * 2 * sizeof(uint4)));
+        HIP_TRY(c, d2d(hdr1 + 2 * c0, whdr, wch * 2 * sizeof(uint4)));
+        HIP_TRY(c, hipMemsetAsync(hdr1 + 2 * nch1, 0, 2 * sizeof(uint4), s));
+        if (planes1 != c->pk_planes) {  // (the A region's size changes, so the B region moves)
+            HIP_TRY(c, d2d(planes1, c->pk_planes, first_unit * 2 * 4));
+            HIP_TRY(c, d2d(planes1_b, c->pk_planes_b, first_unit * 6 * 4));
+        }
+        rtr::pack_write(s, wcl, hdr1 + 2 * c0, planes1, planes1_b);
+        // (the spare bytes behind both streams read as zero, as after an upload: the last lanes' loads run into them)
+        HIP_TRY(c, hipMemsetAsync(planes1 + units1 * 2, 0, (rtr::pack_b_dwords(units1) - units1 * 2) * 4, s));
+        HIP_TRY(c, hipMemsetAsync(planes1_b + units1 * 6, 0, 64, s));
+        if (c->opt_pack == 2) rtr::pack_verify(s, wcl, hdr1 + 2 * c0, planes1, planes1_b, tot + 3);
+    }
+    if (c->keep_up) {  // (old[keep] in upload order; resident words and summaries from chunk c0 on)
+        HIP_TRY(c, hipMemsetAsync(up1, 0, (n1 + 31) / 32 * 4, s));
+        rtr::launch_remove_mask(s, kw, wscan, c->keep_up, n0, up1);
+        HIP_TRY(c, d2d(res1, c->keep_res, c0 * 32));
+        HIP_TRY(c, d2d(sum1, c->keep_sum, c0));
+        rtr::launch_keep_build(s, up1, with_perm ? perm1 : nullptr, n1, res1, sum1, c0);
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = launch_check(c, "remove")) return rc;
+
+    // the new state
+    buf.swap_in(c->rgba, rgba1); buf.swap_in(c->bounds, bounds1); buf.swap_in(c->spread, spread1);
+    buf.swap_in(c->x, x1); buf.swap_in(c->y, y1); buf.swap_in(c->z, z1);
+    if (with_perm) buf.swap_in(c->perm, perm1);
+    c->cap = cap1;
+    if (packed) {
+        buf.swap_in(c->pk_hdr, hdr1); buf.swap_in(c->pk_planes, planes1);
+        c->pk_planes_b = planes1_b;
+        c->pk_units = units1, c->pk_units_cap = ucap1, c->pk_hdr_chunks = hch1;
+        c->pk_bytes = units1 * 32 + nch1 * 32;
+    }
+    if (c->keep_up) { buf.swap_in(c->keep_up, up1); buf.swap_in(c->keep_res, res1); buf.swap_in(c->keep_sum, sum1); }
+    if (c->pp_vis && c->pp_vis_words > ((n1 + 31) / 32 > 8 ? (n1 + 31) / 32 : 8)) {  // (sized again by the next point pass)
+        dfree(c->pp_vis);
+        c->pp_vis_words = 0;
+    }
+    c->n = n1;
+    ++c->cloud_seq;
+    c->list_valid = false;
+    c->jr.frame.count = 0;
+    c->jr.views.count = 0;
+    c->pp_vis_current = false;
+    c->split_cooldown = kSplitCooldown;
+    if (c->p2p.open || c->p2p.red) p2p_release(c);  // (the peers map pools sized for the old cloud)
+    reset_pool_sizing(c->frame);
+    reset_pool_sizing(c->views);
+    {   // order measure and absmax over every chunk box: the lane test's margin steps and the incoherent form read them
+        float ratio = 0.f;
+        if (rtr::order_quality(s, c->bounds, n1, &ratio, c->absmax) != 0) {
+            (void)hipGetLastError();
+            c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();
+        }
+        c->order_ratio = n1 >= (1u << 16) ? ratio : 0.f;
+    }
+    if (packed && c->opt_pack == 2) {
+        uint64_t bad = 0;
+        HIP_TRY(c, hipMemcpy(&bad, tot + 3, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad) return fail(c, RTR_ERR_HIP, "pack: %llu points of the rebuilt chunks decode to other coordinates", (unsigned long long)bad);
     }
     return RTR_OK;
 }

@@ -352,4 +352,22 @@ void launch_keep_build(hipStream_t s, uint32_t *up, const uint32_t *perm, uint64
 // rtr_append_points: the upload-order mask of n0 points grown to n1, the new points kept (bits [n0, n1) set)
 void launch_keep_append(hipStream_t s, uint32_t *up, uint64_t n0, uint64_t n1);
 
+// rtr_remove_points (section 2c): keep = the upload-order keep words of the n resident points (bits at or past n are
+// ignored), perm = resident index -> upload index (null while the cloud is in upload order).
+// remove_count: cnt[c] = the survivors of chunk c, *first_loss (device, set to ~0 by the caller) = the first chunk that
+// loses a point.
+void launch_remove_count(hipStream_t s, const uint32_t *keep, const uint32_t *perm, uint64_t n, uint32_t *cnt, uint64_t *first_loss);
+// out[i] = the exclusive sum of in[0 .. i) -- popc_bits > 0: of the popcounts of words holding popc_bits bits -- and
+// *total (device) = the sum of all; scratch: scan_scratch_words(count) words
+uint64_t scan_scratch_words(uint64_t count);
+void launch_scan_u32(hipStream_t s, const uint32_t *in, uint64_t count, uint64_t popc_bits, uint32_t *out, uint32_t *scratch,
+                     uint64_t *total);
+// the survivors of chunks c0.. (c: the resident cloud; its fp32 SoA when c.x is set, else its packed form) into the
+// window: x / y / z / rgba (and the renumbered upload indices, wperm non-null: perm non-null, wscan = the exclusive
+// popcount scan of keep) from dst[c] - 256 c0 on, dst = the exclusive scan of cnt
+void launch_remove_compact(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *keep, const uint32_t *wscan,
+                           const uint32_t *dst, uint64_t c0, float *wx, float *wy, float *wz, uint32_t *wrgba, uint32_t *wperm);
+// the upload-order mask `up` of n points compacted onto the survivors: up1 (zeroed by the caller) gets old[keep]
+void launch_remove_mask(hipStream_t s, const uint32_t *keep, const uint32_t *wscan, const uint32_t *up, uint64_t n, uint32_t *up1);
+
 }  // namespace rtr

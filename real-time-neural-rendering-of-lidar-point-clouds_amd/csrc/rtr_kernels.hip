@@ -6,6 +6,7 @@
 // divide / sqrt.  Nothing here is GEMM-shaped: the path is an HBM-bound stream plus
 // a scatter, so the work goes into coalescing, atomic traffic and launch count.
 #include "rtr_kernels.h"
+#include "rtr_remove_index.h"
 
 #include <hip/hip_ext.h>
 #include <hip/hip_fp16.h>
@@ -3855,6 +3856,206 @@ void launch_keep_append(hipStream_t s, uint32_t *up, uint64_t n0, uint64_t n1) {
     if (n1 <= n0) return;
     const uint64_t words = (n1 + 31) / 32 - n0 / 32, blocks = (words + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(k_keep_append, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, up, n0, n1);
+}
+
+
+// ---- rtr_remove_points (rtr.h section 2c) ------------------------------------------------------------------------
+// A stable compaction of the resident order.  keep: the caller's upload-order words (bits at or past n ignored), perm:
+// resident index -> upload index (null while the cloud is in upload order).  Lane l of the wave that holds chunk c
+// gathers the keep bits of its points 4 l .. 4 l + 3, as k_keep_build does; the four ballots give the chunk's survivor
+// count and every survivor's slot in it (rtr_remove_index.h).
+__device__ __forceinline__ void remove_gather(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ perm, uint64_t n,
+                                              uint64_t c, int lane, uint32_t u[4], bool kept[4], bool valid[4]) {
+    const uint64_t r0 = c * 256u + 4u * (uint64_t)lane;
+    if (perm && r0 < n) {  // (perm holds whole quads: its arrays are padded to a multiple of 4 points)
+        const uint4 q = *reinterpret_cast<const uint4 *>(perm + r0);
+        u[0] = q.x, u[1] = q.y, u[2] = q.z, u[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) u[k] = (uint32_t)(r0 + k);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        valid[k] = r0 + k < n;
+        kept[k] = valid[k] && ((keep[u[k] >> 5] >> (u[k] & 31u)) & 1u);
+    }
+}
+// cnt[c] = the survivors of chunk c; *first_loss = the first chunk that loses a point (the caller sets ~0).  A wave's
+// chunks ascend, so its first loss is its least; the workgroup folds its waves' in LDS and issues one atomic (one per
+// chunk, all on one address, cost 4.4 ms at 1e8 points)
+__global__ __launch_bounds__(kBlock) void k_remove_count(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ perm,
+                                                         uint64_t n, uint32_t *__restrict__ cnt,
+                                                         unsigned long long *__restrict__ first_loss) {
+    __shared__ unsigned long long s_first;
+    const int lane = threadIdx.x & 63;
+    const uint64_t nchunks = (n + 255) / 256;
+    if (threadIdx.x == 0) s_first = ~0ull;
+    __syncthreads();
+    unsigned long long mine = ~0ull;
+    for (uint64_t c = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+        uint32_t u[4];
+        bool kept[4], valid[4];
+        remove_gather(keep, perm, n, c, lane, u, kept, valid);
+        uint32_t s = 0, v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s += __popcll(__ballot(kept[k])), v += __popcll(__ballot(valid[k]));
+        if (lane == 0) cnt[c] = s;
+        if (s != v && mine == ~0ull) mine = c;
+    }
+    if (lane == 0 && mine != ~0ull) atomicMin(&s_first, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_first != ~0ull) atomicMin(first_loss, s_first);
+}
+void launch_remove_count(hipStream_t s, const uint32_t *keep, const uint32_t *perm, uint64_t n, uint32_t *cnt, uint64_t *first_loss) {
+    const uint64_t nchunks = (n + 255) / 256;
+    if (nchunks == 0) return;
+    const uint64_t blocks = (nchunks + 3) / 4;  // (a wave per chunk)
+    hipLaunchKernelGGL(k_remove_count, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, keep, perm, n, cnt,
+                       (unsigned long long *)first_loss);
+}
+
+// Exclusive scan of `count` u32 values (popc_bits > 0: of the popcounts of words holding popc_bits bits, the bits past
+// them ignored) in three launches: tile sums (kScanTile values per workgroup), one workgroup scans the sums, every
+// tile scans itself from its sum's prefix.
+constexpr uint64_t kScanPer = 8, kScanTile = kBlock * kScanPer;
+__device__ __forceinline__ uint32_t scan_value(const uint32_t *__restrict__ in, uint64_t i, uint64_t count, uint64_t popc_bits) {
+    if (i >= count) return 0u;
+    const uint32_t v = in[i];
+    if (!popc_bits) return v;
+    const uint32_t m = (i == popc_bits / 32u && (popc_bits % 32u)) ? (1u << (popc_bits % 32u)) - 1u : 0xFFFFFFFFu;
+    return (uint32_t)__popc(v & m);
+}
+__global__ __launch_bounds__(kBlock) void k_scan_tiles(const uint32_t *__restrict__ in, uint64_t count, uint64_t popc_bits,
+                                                       uint32_t *__restrict__ tile_sum) {
+    __shared__ uint32_t s_w[8];
+    const uint64_t ntiles = (count + kScanTile - 1) / kScanTile;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t i0 = t * kScanTile + threadIdx.x * kScanPer;
+        uint32_t v = 0, tot = 0;
+#pragma unroll
+        for (uint64_t k = 0; k < kScanPer; ++k) v += scan_value(in, i0 + k, count, popc_bits);
+        (void)block_scan(v, s_w, tot);
+        if (threadIdx.x == 0) tile_sum[t] = tot;
+    }
+}
+__global__ __launch_bounds__(512) void k_scan_top(uint32_t *__restrict__ tile_sum, uint64_t ntiles, uint64_t *__restrict__ total) {
+    __shared__ uint32_t s_w[8];
+    uint64_t carry = 0;
+    for (uint64_t t0 = 0; t0 < ntiles; t0 += 512) {
+        const uint64_t t = t0 + threadIdx.x;
+        const uint32_t v = t < ntiles ? tile_sum[t] : 0u;
+        uint32_t tot = 0;
+        const uint32_t incl = block_scan(v, s_w, tot);
+        if (t < ntiles) tile_sum[t] = (uint32_t)(carry + (incl - v));  // (sums of fewer than 2^32 points)
+        carry += tot;
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+__global__ __launch_bounds__(kBlock) void k_scan_apply(const uint32_t *__restrict__ in, uint64_t count, uint64_t popc_bits,
+                                                       const uint32_t *__restrict__ tile_sum, uint32_t *__restrict__ out) {
+    __shared__ uint32_t s_w[8];
+    const uint64_t ntiles = (count + kScanTile - 1) / kScanTile;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t i0 = t * kScanTile + threadIdx.x * kScanPer;
+        uint32_t v[kScanPer], sum = 0, tot = 0;
+#pragma unroll
+        for (uint64_t k = 0; k < kScanPer; ++k) v[k] = scan_value(in, i0 + k, count, popc_bits), sum += v[k];
+        uint32_t run = tile_sum[t] + block_scan(sum, s_w, tot) - sum;
+#pragma unroll
+        for (uint64_t k = 0; k < kScanPer; ++k) {
+            if (i0 + k < count) out[i0 + k] = run;
+            run += v[k];
+        }
+    }
+}
+uint64_t scan_scratch_words(uint64_t count) { return (count + kScanTile - 1) / kScanTile + 1; }
+void launch_scan_u32(hipStream_t s, const uint32_t *in, uint64_t count, uint64_t popc_bits, uint32_t *out, uint32_t *scratch,
+                     uint64_t *total) {
+    const uint64_t ntiles = (count + kScanTile - 1) / kScanTile;
+    const unsigned grid = (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192);
+    if (ntiles) hipLaunchKernelGGL(k_scan_tiles, dim3(grid), dim3(kBlock), 0, s, in, count, popc_bits, scratch);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(512), 0, s, scratch, ntiles, total);
+    if (ntiles) hipLaunchKernelGGL(k_scan_apply, dim3(grid), dim3(kBlock), 0, s, in, count, popc_bits, scratch, out);
+}
+
+// The survivors of chunks c0.. into the window (fp32 SoA, colours, renumbered upload indices when perm is kept): chunk
+// c's go to dst[c] - 256 c0 on, in their order.  Coordinates from the fp32 SoA when resident, else decoded from the
+// packed form (bit for bit); wscan: the exclusive popcount scan of `keep` (renumbering; read only with perm).
+__global__ __launch_bounds__(kBlock) void k_remove_compact(const uint4 *__restrict__ hdr, const uint32_t *__restrict__ planes,
+                                                           const uint32_t *__restrict__ planes_b, const float4 *__restrict__ x4,
+                                                           const float4 *__restrict__ y4, const float4 *__restrict__ z4,
+                                                           const uint4 *__restrict__ rgba4, const uint32_t *__restrict__ perm,
+                                                           const uint32_t *__restrict__ keep, const uint32_t *__restrict__ wscan,
+                                                           const uint32_t *__restrict__ dst, uint64_t n, uint64_t c0,
+                                                           float *__restrict__ wx, float *__restrict__ wy, float *__restrict__ wz,
+                                                           uint32_t *__restrict__ wrgba, uint32_t *__restrict__ wperm) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t nchunks = (n + 255) / 256, n4 = (n + 3) / 4;
+    for (uint64_t c = c0 + (((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6); c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+        uint32_t u[4];
+        bool kept[4], valid[4];
+        remove_gather(keep, perm, n, c, lane, u, kept, valid);
+        unsigned long long b[4];
+        uint32_t below = 0, own = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            b[k] = __ballot(kept[k]);
+            below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b[k], below));
+            own |= kept[k] ? 1u << k : 0u;
+        }
+        if ((b[0] | b[1] | b[2] | b[3]) == 0ull) continue;  // (wave-uniform)
+        const uint64_t i = c * 64 + lane;
+        float4 X, Y, Z;
+        if (x4) {
+            if (i < n4) X = x4[i], Y = y4[i], Z = z4[i];
+        } else {  // (every lane decodes, as k_unpack_soa does: lanes past the end read the spare bytes)
+            const uint4 h0 = hdr[2 * c], h1 = hdr[2 * c + 1];
+            const ChunkRawA raw_a = load_chunk_a(planes, h0, h1, lane);
+            const ChunkRaw raw = load_chunk_b(planes_b, h0, h1, lane);
+            unpack_chunk(raw_a, raw, h0.w, h0.x, h0.y, h0.z, X, Y, Z, lane);
+        }
+        if (!own) continue;  // (i < n4 from here on)
+        const uint4 col = rgba4[i];
+        const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
+        const uint32_t cs[4] = {col.x, col.y, col.z, col.w};
+        const uint64_t base = (uint64_t)dst[c] - 256u * c0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!kept[k]) continue;
+            const uint64_t o = base + remove_slot(below, own, (uint32_t)k);
+            wx[o] = xs[k], wy[o] = ys[k], wz[o] = zs[k], wrgba[o] = cs[k];
+            if (wperm) wperm[o] = remove_rank(wscan[u[k] >> 5], keep[u[k] >> 5], u[k]);
+        }
+    }
+}
+void launch_remove_compact(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *keep, const uint32_t *wscan,
+                           const uint32_t *dst, uint64_t c0, float *wx, float *wy, float *wz, uint32_t *wrgba, uint32_t *wperm) {
+    const uint64_t nchunks = (c.n + 255) / 256;
+    if (c0 >= nchunks) return;
+    const uint64_t blocks = (nchunks - c0 + 3) / 4;
+    hipLaunchKernelGGL(k_remove_compact, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, c.pk.hdr, c.pk.planes,
+                       c.pk.planes_b, (const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, (const uint4 *)c.rgba, perm,
+                       keep, wscan, dst, c.n, c0, wx, wy, wz, wrgba, wperm);
+}
+
+// The upload-order keep mask in force compacted onto the survivors: the mask bits of word w's kept points go to bits
+// wscan[w] .. of up1 (cleared by the caller), in order.
+__global__ __launch_bounds__(kBlock) void k_remove_mask(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ wscan,
+                                                        const uint32_t *__restrict__ up, uint64_t n, uint32_t *__restrict__ up1) {
+    const uint64_t nwords = (n + 31) / 32;
+    for (uint64_t w = (uint64_t)blockIdx.x * kBlock + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t kw = keep[w] & ((w == n / 32u && (n % 32u)) ? (1u << (n % 32u)) - 1u : 0xFFFFFFFFu);
+        const uint32_t bits = remove_extract(up[w], kw);
+        if (!bits) continue;
+        const uint32_t base = wscan[w], sh = base & 31u;
+        atomicOr(&up1[base >> 5], bits << sh);
+        if (sh && (bits >> (32u - sh))) atomicOr(&up1[(base >> 5) + 1], bits >> (32u - sh));
+    }
+}
+void launch_remove_mask(hipStream_t s, const uint32_t *keep, const uint32_t *wscan, const uint32_t *up, uint64_t n, uint32_t *up1) {
+    const uint64_t nwords = (n + 31) / 32, blocks = (nwords + kBlock - 1) / kBlock;
+    if (nwords == 0) return;
+    hipLaunchKernelGGL(k_remove_mask, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, keep, wscan, up, n, up1);
 }
 
 }  // namespace rtr

@@ -120,6 +120,17 @@ class Projector:
         self._chk(self._lib.rtr_append_points(self._ctx, _vp(xyz), xyz.shape[1] * 4, _vp(rgb), rgb.shape[1],
                                               xyz.shape[0]))
 
+    def remove_points(self, keep):
+        """Takes the points whose keep bit is clear out of the resident cloud and gives their memory back
+        (include/rtr.h section 2c).  keep: the forms of set_point_keep except None -- a bool array of length n, uint32
+        words, a torch tensor, an object with __cuda_array_interface__ (device_buffer(BUF_VISIBLE) included) or a device
+        pointer.  The survivors keep their order and are renumbered 0 .. n' - 1; frames equal, bit for bit, those of
+        one upload of the survivors."""
+        if keep is None:
+            raise ValueError("remove_points needs a keep mask (None keeps every point: nothing to remove)")
+        ptr, nwords, _hold = self._keep_words(keep)
+        self._chk(self._lib.rtr_remove_points(self._ctx, ptr, nwords))
+
     def generate_synthetic(self, scene, seed, first, count, total):
         sc = L.SCENES[scene] if isinstance(scene, str) else int(scene)
         self._chk(self._lib.rtr_generate_synthetic(self._ctx, sc, seed, first, count, total))
@@ -232,14 +243,17 @@ class Projector:
         if keep is None:
             self._chk(self._lib.rtr_set_point_keep(self._ctx, None, 0))
             return
+        ptr, nwords, _hold = self._keep_words(keep)
+        self._chk(self._lib.rtr_set_point_keep(self._ctx, ptr, nwords))
+
+    def _keep_words(self, keep):
+        """(pointer, nwords, owner) of a keep argument of set_point_keep / remove_points: device memory is passed as
+        it is, a bool array is packed into upload-order words (owner: the host array, alive while the pointer is used)."""
         nwords = (self.num_points + 31) // 32
         if isinstance(keep, int):
-            self._chk(self._lib.rtr_set_point_keep(self._ctx, C.c_void_p(keep), nwords))
-            return
+            return C.c_void_p(keep), nwords, None
         if hasattr(keep, "__cuda_array_interface__") and not hasattr(keep, "data_ptr"):
-            self._chk(self._lib.rtr_set_point_keep(self._ctx, C.c_void_p(keep.__cuda_array_interface__["data"][0]),
-                                                   nwords))
-            return
+            return C.c_void_p(keep.__cuda_array_interface__["data"][0]), nwords, keep
         if hasattr(keep, "data_ptr"):  # a torch tensor
             if keep.dtype.is_floating_point:
                 raise ValueError("keep must be bool or 32-bit words")
@@ -249,8 +263,7 @@ class Projector:
                 torch.cuda.current_stream(keep.device).synchronize()  # (the words may still be on their way)
                 if keep.numel() * keep.element_size() != 4 * nwords:
                     raise ValueError("keep must hold (n + 31) // 32 32-bit words")
-                self._chk(self._lib.rtr_set_point_keep(self._ctx, C.c_void_p(keep.data_ptr()), nwords))
-                return
+                return C.c_void_p(keep.data_ptr()), nwords, keep
             keep = keep.cpu().numpy()
         keep = np.asarray(keep)
         if keep.dtype == bool:
@@ -261,7 +274,7 @@ class Projector:
         else:
             words = keep.astype("<u4", copy=False)
         words = np.ascontiguousarray(words, dtype=np.uint32)
-        self._chk(self._lib.rtr_set_point_keep(self._ctx, _vp(words), words.size))
+        return _vp(words), words.size, words
 
     def point_keep(self):
         """The keep mask in force as a bool array over the uploaded points, or None when none is set."""
@@ -500,6 +513,28 @@ class ProjectCloud:
 
     def clearPointKeep(self):
         """No keep mask: every point again."""
+        self._p.set_point_keep(None)
+
+    def removePoints(self, indices):
+        """Takes the uploaded vertices `indices` out of the resident cloud for good, giving their memory back; the
+        others keep their order and are renumbered 0 .. n' - 1 (computePointIds, visible_points, hidePoints and later
+        appends use the new indices)."""
+        n = self._p.num_points
+        idx = np.asarray(indices, dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= n):  # (as the C++ facade: no index counted from the end)
+            raise IndexError("removePoints: indices must lie in [0, %d)" % n)
+        keep = np.ones(n, bool)
+        keep[idx] = False
+        self._p.remove_points(keep)
+
+    def commitPointKeep(self):
+        """Removes the vertices the keep mask in force hides (see removePoints), then clears the mask: the frames stay
+        what they were, the hidden vertices no longer cost memory or time.  Nothing happens without a mask."""
+        keep = self._p.point_keep()
+        if keep is None:
+            return
+        if not keep.all():
+            self._p.remove_points(self._p.download(L.BUF_POINT_KEEP))
         self._p.set_point_keep(None)
 
     def computeRGBD(self, calibration, extrinsics, color, depth):
