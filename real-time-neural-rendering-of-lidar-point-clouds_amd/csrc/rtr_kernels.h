@@ -56,8 +56,8 @@ struct Cloud {
     // k_project_bin, "lane test").  null: no lane test.  absmax: largest finite |x|, |y|, |z| of the cloud.
     const float *spread;
     float absmax[3];
-    Clip clip;  // the user's clip planes (rtr_set_clip_planes; count 0: none): the point kernels launch their CLIP forms
-    Keep keep;  // the user's keep mask in resident order (rtr_set_point_keep; words null: none): the KEEP forms
+    Clip clip;  // the user's clip planes (rtr_set_clip_planes; count 0: none): the point kernels take them as Filter pack (Clip)
+    Keep keep;  // the user's keep mask in resident order (rtr_set_point_keep; words null: none): Filter pack (Clip, Keep)
 };
 
 struct FilterLevels {

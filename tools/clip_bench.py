@@ -3,7 +3,7 @@ six legs measured in ONE process, each clipped leg alternated with the no-planes
   (a) no planes; (b) one plane that keeps the whole cloud; (c) an axis box enclosing the whole cloud (6 planes);
   (d) a plane that cuts the in-frustum part about in half; (e) a crop box keeping ~1/8 of the room; (f) an overview
   from above with the ceiling clipped away.
-T1's own time: run under `rocprofv3 --kernel-trace --stats` (k_project_bin vs k_project_bin_clip rows).
+T1's own time: run under `rocprofv3 --kernel-trace --stats` (k_project_bin<...> vs k_project_bin<..., rtr::Clip> rows).
   python tools/clip_bench.py [--steps K] [--rounds R] [--out FILE]"""
 import argparse
 import json

@@ -3,7 +3,7 @@ six legs measured in ONE process, each masked leg alternated with the unmasked l
   (a) no mask; (b) an all-kept mask; (c) 10 % of the points hidden at random; (d) 50 % hidden at random; (e) a
   contiguous half of the RESIDENT order hidden (whole chunks rejected on their summary); (f) the mask fed back from
   RTR_BUF_VISIBLE of another pose (device memory).
-T1's own time: run under `rocprofv3 --kernel-trace --stats` (k_project_bin vs k_project_bin_keep rows).
+T1's own time: run under `rocprofv3 --kernel-trace --stats` (k_project_bin<...> vs k_project_bin<..., rtr::Clip, rtr::Keep> rows).
   python tools/mask_bench.py [--steps K] [--rounds R] [--out FILE]"""
 import argparse
 import json
