@@ -298,6 +298,48 @@ int rtr_append_points(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, c
  * a tail costs about what appending it did. */
 int rtr_remove_points(rtr_ctx *ctx, const uint32_t *keep_words, uint64_t nwords);
 
+/* ---- 2d. moving points of the resident cloud ----------------------------------------------------------------------
+ * Moves resident points by an affine transform where they lie, without uploading the cloud again (a loop closure that
+ * corrects the poses of scans already resident, one re-registered scan, a georeferenced cloud).  M: row-major 3 x 4,
+ * fp32; a selected point (x, y, z) becomes
+ *     x' = ((M[0] x + M[1] y) + M[2] z) + M[3],  y' = ((M[4] x + M[5] y) + M[6] z) + M[7],
+ *     z' = ((M[8] x + M[9] y) + M[10] z) + M[11],
+ * every product and every sum rounded to fp32 on its own (no FMA; the clip planes' contract, section 6d).  There is no
+ * shortcut for special matrices: [I|0] maps -0 to +0, and a point with an infinite coordinate gets NaN in its other
+ * coordinates (0 x inf) -- what the formula gives.
+ *
+ * select_words: (n + 31) / 32 words in UPLOAD order, bit i % 32 of word i / 32 set = point i moves -- the layout of
+ * rtr_remove_points, rtr_set_point_keep and RTR_BUF_VISIBLE.  Host memory or device memory of the context's device; the
+ * words are copied.  Bits past n are ignored.  select_words = NULL with nwords = 0 moves every point, on any cloud; a
+ * selection on a cloud the library sorted needs option "point_ids" = 1.  A selection without a set bit returns RTR_OK
+ * and changes nothing.
+ *
+ * Equivalence: rtr_upload_points(A), then rtr_transform_points(M, sel), renders bit for bit what one
+ * rtr_upload_points(A') renders, A'[i] = M applied to A[i] for the selected i and A[i] for the others, with the same
+ * options, params, clip planes and resolution -- the outputs section 2b lists, with what depends on the resident order
+ * excepted as there; and so across any sequence of uploads, appends, removals and moves.  rtr_download_points returns A'
+ * in the resident order.  Clip planes are world-space: they act on the new coordinates.
+ *
+ * What stays: upload indices, the resident order (no sort: option "auto_reorder" is not applied; rtr_reorder_points
+ * sorts on request), colours, the permutation of "point_ids", the keep mask in force (RTR_BUF_POINT_KEEP reads the same
+ * words).  A packed cloud stays packed (even when packing no longer saves 1/8; "pack" = 2 verifies the rebuilt chunks),
+ * an unpacked one unpacked; "keep_soa" is honoured.  An open peer-to-peer exchange stays open: nothing the peers map is
+ * reallocated; each rank moves its own points by its own upload indices.  Only the 256-point chunks from the first to
+ * the last one holding a selected point are rebuilt; the packed blocks behind them move without being decoded.
+ *
+ * Ordering: like rtr_append_points, the call first completes everything issued before it (async slots come out with the
+ * old cloud); frames that overflowed the adaptive extent pool are rendered again with the old cloud -- if that fails,
+ * the call returns the error and the cloud is unchanged.  Bins of an earlier rtr_min_depth_pass are not reused.
+ *
+ * Errors (RTR_ERR_INVALID, nothing changes): no cloud, M NULL or a non-finite coefficient, nwords != (n + 31) / 32 with a
+ * selection, select_words NULL with nwords > 0, a selection on a sorted cloud without "point_ids" = 1.  A failed
+ * allocation leaves the cloud as it was too: every new buffer is allocated before anything is committed.
+ *
+ * Cost: with a selection, a pass over its bits (through the permutation when sorted); kernel work proportional to the
+ * points of the chunks rebuilt; a device-to-device move of the packed blocks behind them when their size changes; and
+ * O(n / 256) passes over per-chunk arrays. */
+int rtr_transform_points(rtr_ctx *ctx, const float M[12], const uint32_t *select_words, uint64_t nwords);
+
 /* ---- 3. camera (project_cloud.cu:318, project_cloud.h:50-59) -------------------- */
 /* P = K4 * E in fp32, row-major, exactly as the reference composes it with glm:
  * K row-major 3x3 intrinsics, E row-major 4x4 world->camera, both double. */

@@ -25,7 +25,8 @@
 // without uploading it again; the indices of computePointIds, visible_points and hidePoints continue across appends --
 // the appended vertices follow every vertex given so far, in the same flattened order.
 // removePoints (section 2c) takes vertices out for good and renumbers the rest; commitPointKeep removes what the keep
-// mask in force hides.
+// mask in force hides.  transformPoints (section 2d) moves a range of vertices (one re-registered scan) by an affine
+// transform where they lie: indices, order and the keep mask stay.
 //
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
@@ -263,6 +264,29 @@ public:
             words[(size_t)(i / 32)] &= ~(1u << (i % 32));
         }
         check(ctx_, rtr_remove_points(ctx_, words.data(), words.size()));
+    }
+    // Moving (rtr.h section 2d): the vertices [first, first + count) (default: to the last one) move by M, row-major 4 x 4
+    // whose bottom row must be exactly 0 0 0 1 (std::invalid_argument otherwise); its other twelve elements are rounded
+    // to float once.  A range past the vertex count throws std::out_of_range.  The whole cloud moves without a selection
+    // (any cloud, sorted or not); a part of a cloud the library may sort needs point_ids = true.
+    void transformPoints(const double M[16], uint64_t first = 0, uint64_t count = UINT64_MAX) {
+        if (!(M[12] == 0.0 && M[13] == 0.0 && M[14] == 0.0 && M[15] == 1.0))
+            throw std::invalid_argument("transformPoints: the bottom row of M must be exactly 0 0 0 1");
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        if (first > n || (count != UINT64_MAX && count > n - first))
+            throw std::out_of_range("transformPoints: the range exceeds the vertex count");
+        if (count == UINT64_MAX) count = n - first;
+        float m[12];
+        for (int i = 0; i < 12; ++i) m[i] = (float)M[i];
+        if (count == 0) return;
+        if (first == 0 && count == n) {
+            check(ctx_, rtr_transform_points(ctx_, m, nullptr, 0));
+            return;
+        }
+        std::vector<uint32_t> words((size_t)((n + 31) / 32), 0u);
+        for (uint64_t i = first; i < first + count; ++i) words[(size_t)(i / 32)] |= 1u << (i % 32);
+        check(ctx_, rtr_transform_points(ctx_, m, words.data(), words.size()));
     }
     // Removes the vertices the keep mask in force hides, then clears the mask (frames unchanged; nothing without a mask).
     void commitPointKeep() {

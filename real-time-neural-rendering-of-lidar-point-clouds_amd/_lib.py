@@ -24,7 +24,7 @@ SYMBOLS = [
     "rtr_device_count", "rtr_p2p_export", "rtr_p2p_open", "rtr_p2p_close", "rtr_p2p_min_depth", "rtr_p2p_sum_resolve", "rtr_p2p_status",
     "rtr_p2p_render", "rtr_frame_stats", "rtr_get_option", "rtr_host_output_buffers", "rtr_project_async", "rtr_wait",
     "rtr_p2p_render_owned", "rtr_point_pass", "rtr_render_views", "rtr_set_clip_planes", "rtr_get_clip_planes",
-    "rtr_set_point_keep", "rtr_append_points", "rtr_remove_points",
+    "rtr_set_point_keep", "rtr_append_points", "rtr_remove_points", "rtr_transform_points",
 ]
 
 RTR_OK, RTR_ERR_INVALID, RTR_ERR_HIP, RTR_ERR_NO_OUTPUT, RTR_ERR_UNSUPPORTED, RTR_ERR_INTERNAL = 0, -1, -2, -3, -4, -5
@@ -92,6 +92,7 @@ def lib():
     L.rtr_upload_points.argtypes = [vp, vp, sz, vp, sz, sz]
     L.rtr_append_points.argtypes = [vp, vp, sz, vp, sz, sz]
     L.rtr_remove_points.argtypes = [vp, vp, u64]
+    L.rtr_transform_points.argtypes = [vp, vp, vp, u64]
     L.rtr_generate_synthetic.argtypes = [vp, i32, u64, u64, u64, u64]
     L.rtr_num_points.argtypes = [vp, C.POINTER(u64)]
     L.rtr_download_points.argtypes = [vp, vp, vp, u64, u64]

@@ -1942,6 +1942,167 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     return RTR_OK;
 }
 
+// ---- moving points (rtr.h, section 2d) --------------------------------------------------------------------------
+// Points move where they lie: upload indices, the resident order, colours, the permutation and the keep mask stay.  A
+// selection pass names the first and last chunk holding a selected point, c0 and c1 (no pass for "every point"); only
+// chunks c0 .. c1 are rebuilt.  An unpacked cloud is moved in place (its SoA arrays, then the boxes of c0 .. c1).  A packed
+// one gets a WINDOW: chunks c0 .. c1 decoded (read from the SoA arrays with "keep_soa" = 1), the selected points moved,
+// then rtr_append_points' range forms -- chunk boxes and lane spreads, headers (the scan continues from chunk c0's block
+// offset), blocks.  The blocks behind c1 are not decoded: when the window's units differ from the old ones by delta, the
+// tail's A and B blocks move by delta (through a scratch copy, or into fresh planes when the capacity changes; `fitted`)
+// and its headers' offsets with them.  Every buffer is allocated before the first resident byte changes.
+int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_words, uint64_t nwords) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, c->n > 0, "rtr_transform_points: no cloud");
+    NEED(c, M != nullptr, "rtr_transform_points: M is NULL");
+    for (int i = 0; i < 12; ++i) NEED(c, std::isfinite(M[i]), "rtr_transform_points: M has a non-finite coefficient");
+    const bool every = select_words == nullptr && nwords == 0;
+    NEED(c, select_words != nullptr || nwords == 0, "rtr_transform_points: select_words is NULL");
+    if (!every && nwords != (c->n + 31) / 32)
+        return fail(c, RTR_ERR_INVALID, "rtr_transform_points: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
+    NEED(c, every || !c->reordered || c->perm,
+         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be mapped: set "
+         "point_ids = 1 before the upload (or upload with auto_reorder = 0), or move every point (select_words NULL)");
+    DevGuard g(c->device);
+    if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
+    drop_soa(c);  // (SoA arrays decoded for a call in between are not kept: they would hold the old coordinates)
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nch = (n + 255) / 256;
+    const uint32_t *perm0 = c->reordered ? c->perm : nullptr;
+    rtr::Affine A;
+    memcpy(A.m, M, sizeof A.m);
+    AppendBufs buf;
+
+    // the caller's words (host or device memory) and the span of the chunks holding a selected point
+    uint32_t *sel = nullptr;
+    uint64_t *tot;  // span (first, last chunk), window units, pack mismatches
+    HIP_TRY(c, buf.get(&tot, 4 * sizeof(uint64_t)));
+    HIP_TRY(c, hipMemsetAsync(tot, 0, 4 * sizeof(uint64_t), s));
+    uint64_t c0 = 0, c1 = nch - 1;
+    if (!every) {
+        HIP_TRY(c, buf.get(&sel, nwords * 4));
+        HIP_TRY(c, hipMemcpyAsync(sel, select_words, nwords * 4, hipMemcpyDefault, s));
+        HIP_TRY(c, hipMemsetAsync(tot, 0xFF, sizeof(uint64_t), s));
+        rtr::launch_transform_span(s, sel, perm0, n, tot);
+        uint64_t span[2] = {0, 0};
+        HIP_TRY(c, hipMemcpyAsync(span, tot, sizeof span, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (int rc = launch_check(c, "transform span")) return rc;
+        if (span[0] >= nch) return RTR_OK;  // (no point selected: nothing changes)
+        c0 = span[0], c1 = span[1];
+    }
+    const uint64_t p0 = 256 * c0, wn = std::min(n, 256 * (c1 + 1)) - p0, wpad = (wn + 3) & ~3ull, wch = c1 + 1 - c0;
+    const rtr::Cloud cl = cloud_of(c);
+    rtr::Cloud wcl = cl;
+    wcl.rgba = nullptr;
+    wcl.pk = rtr::PackedXyz{nullptr, nullptr, nullptr};
+    wcl.keep = rtr::Keep{nullptr, nullptr};
+    wcl.n = wn;
+    const bool packed = c->pk_hdr != nullptr;
+    if (!packed) {  // (in place: nothing left to allocate)
+        rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, c->x + p0, c->y + p0, c->z + p0, true);
+        wcl.x = c->x + p0, wcl.y = c->y + p0, wcl.z = c->z + p0, wcl.spread = c->spread + c0;
+        rtr::launch_chunk_bounds(s, wcl, c->bounds + 6 * c0, c->spread + c0);
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (int rc = launch_check(c, "transform")) return rc;
+    } else {
+        // the window: chunks c0 .. c1 with the selected points moved, their boxes, lane spreads and headers
+        float *wx, *wy, *wz, *wb, *wsp;
+        HIP_TRY(c, buf.get(&wx, wpad * 4)); HIP_TRY(c, buf.get(&wy, wpad * 4)); HIP_TRY(c, buf.get(&wz, wpad * 4));
+        HIP_TRY(c, buf.get(&wb, wch * 6 * sizeof(float)));
+        HIP_TRY(c, buf.get(&wsp, wch * sizeof(float)));
+        rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, wx, wy, wz, false);
+        wcl.x = wx, wcl.y = wy, wcl.z = wz, wcl.spread = wsp;
+        rtr::launch_chunk_bounds(s, wcl, wb, wsp);
+        uint4 h0, h1 = make_uint4(0, 0, 0, 0);
+        HIP_TRY(c, hipMemcpyAsync(&h0, c->pk_hdr + 2 * c0 + 1, sizeof h0, hipMemcpyDeviceToHost, s));
+        if (c1 + 1 < nch) HIP_TRY(c, hipMemcpyAsync(&h1, c->pk_hdr + 2 * (c1 + 1) + 1, sizeof h1, hipMemcpyDeviceToHost, s));
+        uint4 *whdr;
+        uint32_t *cnt;
+        HIP_TRY(c, buf.get(&whdr, wch * 2 * sizeof(uint4)));
+        HIP_TRY(c, buf.get(&cnt, wch * sizeof(uint32_t)));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const uint64_t first_unit = ((uint64_t)h0.y << 32) | h0.x;
+        const uint64_t old_end = c1 + 1 < nch ? (((uint64_t)h1.y << 32) | h1.x) : c->pk_units;  // (the tail's first unit)
+        rtr::pack_measure(s, wcl, whdr, cnt, tot + 2, first_unit);
+        uint64_t new_end = 0;
+        HIP_TRY(c, hipMemcpyAsync(&new_end, tot + 2, sizeof new_end, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (int rc = launch_check(c, "transform window")) return rc;
+        const int64_t delta = (int64_t)(new_end - old_end);
+        const uint64_t tail = c->pk_units - old_end, units1 = new_end + tail;
+
+        // every buffer the commit needs, before anything resident changes
+        const uint64_t ucap1 = fitted(c->pk_units_cap, units1);
+        uint32_t *planes1 = c->pk_planes, *planes1_b = c->pk_planes_b, *tmp = nullptr;
+        if (ucap1 != c->pk_units_cap) {
+            HIP_TRY(c, buf.get(&planes1, rtr::pack_total_dwords(ucap1) * 4));
+            planes1_b = planes1 + rtr::pack_b_dwords(ucap1);
+        } else if (delta != 0 && tail) {
+            HIP_TRY(c, buf.get(&tmp, tail * 8 * 4));  // (the tail's A blocks, then its B blocks)
+        }
+
+        // commit: the tail's blocks to their new place, the window's headers and blocks, the tail's block offsets
+        auto d2d = [&](void *dst_, const void *src, size_t bytes) {
+            return bytes ? hipMemcpyAsync(dst_, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+        };
+        if (planes1 != c->pk_planes) {  // (fresh planes: the prefix and the tail are copied, nothing overlaps)
+            HIP_TRY(c, d2d(planes1, c->pk_planes, first_unit * 2 * 4));
+            HIP_TRY(c, d2d(planes1_b, c->pk_planes_b, first_unit * 6 * 4));
+            HIP_TRY(c, d2d(planes1 + new_end * 2, c->pk_planes + old_end * 2, tail * 2 * 4));
+            HIP_TRY(c, d2d(planes1_b + new_end * 6, c->pk_planes_b + old_end * 6, tail * 6 * 4));
+        } else if (tmp) {  // (source and destination overlap: through the scratch copy)
+            HIP_TRY(c, d2d(tmp, c->pk_planes + old_end * 2, tail * 2 * 4));
+            HIP_TRY(c, d2d(tmp + tail * 2, c->pk_planes_b + old_end * 6, tail * 6 * 4));
+            HIP_TRY(c, d2d(planes1 + new_end * 2, tmp, tail * 2 * 4));
+            HIP_TRY(c, d2d(planes1_b + new_end * 6, tmp + tail * 2, tail * 6 * 4));
+        }
+        HIP_TRY(c, d2d(c->pk_hdr + 2 * c0, whdr, wch * 2 * sizeof(uint4)));
+        rtr::launch_shift_units(s, c->pk_hdr, c1 + 1, nch, delta);
+        rtr::pack_write(s, wcl, c->pk_hdr + 2 * c0, planes1, planes1_b);
+        // (the spare bytes behind both streams read as zero, as after an upload: the last lanes' loads run into them)
+        HIP_TRY(c, hipMemsetAsync(planes1 + units1 * 2, 0, (rtr::pack_b_dwords(units1) - units1 * 2) * 4, s));
+        HIP_TRY(c, hipMemsetAsync(planes1_b + units1 * 6, 0, 64, s));
+        if (c->opt_pack == 2) rtr::pack_verify(s, wcl, c->pk_hdr + 2 * c0, planes1, planes1_b, tot + 3);
+        HIP_TRY(c, d2d(c->bounds + 6 * c0, wb, wch * 6 * sizeof(float)));
+        HIP_TRY(c, d2d(c->spread + c0, wsp, wch * sizeof(float)));
+        if (c->x) {  // ("keep_soa" = 1: the SoA arrays take the window as well)
+            HIP_TRY(c, d2d(c->x + p0, wx, wpad * 4)); HIP_TRY(c, d2d(c->y + p0, wy, wpad * 4)); HIP_TRY(c, d2d(c->z + p0, wz, wpad * 4));
+        }
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (int rc = launch_check(c, "transform")) return rc;
+        if (planes1 != c->pk_planes) {
+            buf.swap_in(c->pk_planes, planes1);
+            c->pk_planes_b = planes1_b;
+            c->pk_units_cap = ucap1;
+        }
+        c->pk_units = units1;
+        c->pk_bytes = units1 * 32 + nch * 32;
+    }
+
+    // what depends on the coordinates (n-sized state -- stores, pools, the peers' mappings -- stays)
+    ++c->cloud_seq;
+    c->list_valid = false;
+    c->jr.frame.count = 0;
+    c->jr.views.count = 0;
+    c->pp_vis_current = false;
+    c->split_cooldown = kSplitCooldown;
+    {   // order measure and absmax over every chunk box: the lane test's margin steps and the incoherent form read them
+        float ratio = 0.f;
+        if (rtr::order_quality(s, c->bounds, n, &ratio, c->absmax) != 0) {
+            (void)hipGetLastError();
+            c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();
+        }
+        c->order_ratio = n >= (1u << 16) ? ratio : 0.f;
+    }
+    if (packed && c->opt_pack == 2) {
+        uint64_t bad = 0;
+        HIP_TRY(c, hipMemcpy(&bad, tot + 3, sizeof bad, hipMemcpyDeviceToHost));
+        if (bad) return fail(c, RTR_ERR_HIP, "pack: %llu moved points decode to other coordinates", (unsigned long long)bad);
+    }
+    return RTR_OK;
+}
+
 int rtr_reorder_points(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
     DevGuard g(c->device);

@@ -112,6 +112,23 @@ RTR_HD bool clip_box_outside(const Clip &c, const float lo[3], const float hi[3]
     return culled;
 }
 
+// ---- moving resident points (rtr_transform_points) ---------------------------------------------------------------
+// M row-major 3 x 4: a selected point (x, y, z) becomes x' = ((m0 x + m1 y) + m2 z) + m3, y' and z' likewise from rows 1
+// and 2, every product and sum rounded to fp32 on its own (no FMA, as clip_keep).  No shortcut for special matrices:
+// [I|0] maps -0 to +0 (the last sum adds +0) and an infinite coordinate makes the point's other coordinates NaN (0 x inf),
+// exactly what one upload of the moved points computed this way gives.  Passed BY VALUE to the kernel (like Proj).
+struct Affine {
+    float m[12];
+};
+RTR_HD void affine_apply(const Affine &a, float &x, float &y, float &z) {
+    float o[3];
+    for (int r = 0; r < 3; ++r) {
+        const float p = a.m[4 * r] * x, q = a.m[4 * r + 1] * y, s = p + q, t = a.m[4 * r + 2] * z, u = s + t;
+        o[r] = u + a.m[4 * r + 3];
+    }
+    x = o[0], y = o[1], z = o[2];
+}
+
 // ---- per-point keep mask (rtr_set_point_keep) --------------------------------------------------------------------
 // The mask in RESIDENT order: bit r % 32 of words[r / 32] set = resident point r is kept; a 256-point chunk c owns
 // words[8 c .. 8 c + 7], and lane l of the wave that holds the chunk (its points 4 l .. 4 l + 3) finds its four bits at

@@ -370,4 +370,16 @@ void launch_remove_compact(hipStream_t s, const Cloud &c, const uint32_t *perm, 
 // the upload-order mask `up` of n points compacted onto the survivors: up1 (zeroed by the caller) gets old[keep]
 void launch_remove_mask(hipStream_t s, const uint32_t *keep, const uint32_t *wscan, const uint32_t *up, uint64_t n, uint32_t *up1);
 
+// rtr_transform_points (section 2d): sel = the caller's upload-order selection words (bits at or past n ignored; null:
+// every point), perm as for remove.
+// transform_span: span[0] / span[1] (device, set to ~0 / 0 by the caller) = the first / last chunk holding a selected point
+void launch_transform_span(hipStream_t s, const uint32_t *sel, const uint32_t *perm, uint64_t n, uint64_t *span);
+// chunks c0 .. c1 of c (its fp32 SoA when c.x is set, else its packed form) with the selected points moved by M
+// (affine_apply) into wx / wy / wz from point 256 c0 on (the window's arrays index from there), every quad below n;
+// in_place (wx = c.x + 256 c0 ...): only the quads holding a selected point are written
+void launch_transform_window(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *sel, uint64_t c0, uint64_t c1,
+                             const Affine &M, float *wx, float *wy, float *wz, bool in_place);
+// the block offsets hdr[2 c + 1].xy of chunks [c_from, c_to) move by delta units (the blocks behind a rebuilt window moved)
+void launch_shift_units(hipStream_t s, uint4 *hdr, uint64_t c_from, uint64_t c_to, int64_t delta);
+
 }  // namespace rtr

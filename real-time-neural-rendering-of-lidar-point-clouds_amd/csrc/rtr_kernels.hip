@@ -4792,4 +4792,109 @@ void launch_remove_mask(hipStream_t s, const uint32_t *keep, const uint32_t *wsc
     hipLaunchKernelGGL(k_remove_mask, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, keep, wscan, up, n, up1);
 }
 
+// ---- rtr_transform_points (rtr.h section 2d) ---------------------------------------------------------------------
+// sel: the caller's upload-order selection words (null: every point), perm as for remove_gather.  Lane l of the wave that
+// holds chunk c gathers the selection bits of its points 4 l .. 4 l + 3 (remove_gather; bits at or past n do not count).
+__device__ __forceinline__ void transform_gather(const uint32_t *__restrict__ sel, const uint32_t *__restrict__ perm, uint64_t n,
+                                                 uint64_t c, int lane, bool moved[4]) {
+    uint32_t u[4];
+    bool valid[4];
+    if (sel) {
+        remove_gather(sel, perm, n, c, lane, u, moved, valid);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) moved[k] = c * 256u + 4u * (uint64_t)lane + (uint64_t)k < n;
+    }
+}
+// span[0] / span[1] = the first / last chunk holding a selected point (the caller sets ~0 / 0).  A wave's chunks ascend,
+// so its first hit is its least and its last its greatest; the workgroup folds its waves' in LDS and issues one atomic
+// of each kind (k_remove_count: one per chunk on one address costs 4.4 ms at 1e8 points)
+__global__ __launch_bounds__(kBlock) void k_transform_span(const uint32_t *__restrict__ sel, const uint32_t *__restrict__ perm,
+                                                           uint64_t n, unsigned long long *__restrict__ span) {
+    __shared__ unsigned long long s_lo, s_hi;
+    const int lane = threadIdx.x & 63;
+    const uint64_t nchunks = (n + 255) / 256;
+    if (threadIdx.x == 0) s_lo = ~0ull, s_hi = 0ull;
+    __syncthreads();
+    unsigned long long lo = ~0ull, hi = 0ull;
+    for (uint64_t c = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+        bool moved[4];
+        transform_gather(sel, perm, n, c, lane, moved);
+        if (__ballot(moved[0] || moved[1] || moved[2] || moved[3]) != 0ull) {  // (wave-uniform)
+            if (lo == ~0ull) lo = c;
+            hi = c;
+        }
+    }
+    if (lane == 0 && lo != ~0ull) atomicMin(&s_lo, lo), atomicMax(&s_hi, hi);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_lo != ~0ull) atomicMin(&span[0], s_lo), atomicMax(&span[1], s_hi);
+}
+void launch_transform_span(hipStream_t s, const uint32_t *sel, const uint32_t *perm, uint64_t n, uint64_t *span) {
+    const uint64_t nchunks = (n + 255) / 256;
+    if (nchunks == 0) return;
+    const uint64_t blocks = (nchunks + 3) / 4;  // (a wave per chunk)
+    hipLaunchKernelGGL(k_transform_span, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, sel, perm, n,
+                       (unsigned long long *)span);
+}
+
+// Chunks c0 .. c1 with the selected points moved (affine_apply) into the window w* (quad q of the cloud at w*[q - 64 c0]).
+// Coordinates from the fp32 SoA when resident, else decoded from the packed form (bit for bit); unselected points and the
+// NaN pads pass through bit for bit.  in_place: w* are the SoA arrays themselves (from point 256 c0 on) -- the same thread
+// reads and writes a quad, so they are not __restrict__ -- and only quads holding a selected point are stored.
+__global__ __launch_bounds__(kBlock) void k_transform_window(const uint4 *__restrict__ hdr, const uint32_t *__restrict__ planes,
+                                                             const uint32_t *__restrict__ planes_b, const float4 *x4,
+                                                             const float4 *y4, const float4 *z4, const uint32_t *__restrict__ perm,
+                                                             const uint32_t *__restrict__ sel, uint64_t n, uint64_t c0, uint64_t c1,
+                                                             Affine M, int in_place, float4 *wx4, float4 *wy4, float4 *wz4) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t n4 = (n + 3) / 4;
+    for (uint64_t c = c0 + (((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6); c <= c1; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+        bool moved[4];
+        transform_gather(sel, perm, n, c, lane, moved);
+        const bool mine = moved[0] || moved[1] || moved[2] || moved[3];
+        if (in_place && __ballot(mine) == 0ull) continue;  // (wave-uniform)
+        const uint64_t i = c * 64 + lane;
+        float4 X = make_float4(0.f, 0.f, 0.f, 0.f), Y = X, Z = X;
+        if (x4) {
+            if (i < n4) X = x4[i], Y = y4[i], Z = z4[i];
+        } else {  // (every lane decodes, as k_unpack_soa does: lanes past the end read the spare bytes)
+            const uint4 h0 = hdr[2 * c], h1 = hdr[2 * c + 1];
+            const ChunkRawA raw_a = load_chunk_a(planes, h0, h1, lane);
+            const ChunkRaw raw = load_chunk_b(planes_b, h0, h1, lane);
+            unpack_chunk(raw_a, raw, h0.w, h0.x, h0.y, h0.z, X, Y, Z, lane);
+        }
+        if (i >= n4 || (in_place && !mine)) continue;
+        if (moved[0]) affine_apply(M, X.x, Y.x, Z.x);
+        if (moved[1]) affine_apply(M, X.y, Y.y, Z.y);
+        if (moved[2]) affine_apply(M, X.z, Y.z, Z.z);
+        if (moved[3]) affine_apply(M, X.w, Y.w, Z.w);
+        const uint64_t o = i - c0 * 64;
+        wx4[o] = X, wy4[o] = Y, wz4[o] = Z;
+    }
+}
+void launch_transform_window(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *sel, uint64_t c0, uint64_t c1,
+                             const Affine &M, float *wx, float *wy, float *wz, bool in_place) {
+    const uint64_t nchunks = (c.n + 255) / 256;
+    if (c0 > c1 || c1 >= nchunks) return;
+    const uint64_t blocks = (c1 - c0 + 1 + 3) / 4;  // (a wave per chunk)
+    hipLaunchKernelGGL(k_transform_window, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, c.pk.hdr,
+                       c.pk.planes, c.pk.planes_b, (const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, perm, sel,
+                       c.n, c0, c1, M, in_place ? 1 : 0, (float4 *)wx, (float4 *)wy, (float4 *)wz);
+}
+
+__global__ __launch_bounds__(kBlock) void k_shift_units(uint4 *__restrict__ hdr, uint64_t c_from, uint64_t c_to, long long delta) {
+    for (uint64_t c = c_from + (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < c_to; c += (uint64_t)gridDim.x * kBlock) {
+        uint4 h = hdr[2 * c + 1];
+        const uint64_t off = ((((uint64_t)h.y) << 32) | (uint64_t)h.x) + (uint64_t)delta;
+        h.x = (uint32_t)off, h.y = (uint32_t)(off >> 32);
+        hdr[2 * c + 1] = h;
+    }
+}
+void launch_shift_units(hipStream_t s, uint4 *hdr, uint64_t c_from, uint64_t c_to, int64_t delta) {
+    if (c_from >= c_to || delta == 0) return;
+    const uint64_t blocks = (c_to - c_from + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_shift_units, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, hdr, c_from, c_to,
+                       (long long)delta);
+}
+
 }  // namespace rtr

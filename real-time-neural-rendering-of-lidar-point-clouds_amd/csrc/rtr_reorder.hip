@@ -105,9 +105,13 @@ __global__ __launch_bounds__(256) void k_gather_u32(const uint32_t *__restrict__
 
 // How spatially compact the 256-point chunks are: sum of the chunk boxes' diagonals, number of
 // chunks with a finite box, and the cloud's bounding box -- all from the chunk bounds
-// (k_chunk_bounds), i.e. 24 bytes per 256 points.
+// (k_chunk_bounds), i.e. 24 bytes per 256 points.  The diagonals are summed per wave (a fixed
+// assignment of chunks to lanes, a fixed shuffle tree) into part[wave]; the host adds the waves'
+// sums in wave order, so the same boxes always give the same measure (fp32 atomics would add them
+// in arrival order: the last bit, and "order_ratio_ppm", could differ between two uploads).
+constexpr int kOrderMaxGrid = 128;
 __global__ __launch_bounds__(256) void k_order_quality(const float *__restrict__ bounds, uint64_t nchunks,
-                                                       float *__restrict__ sum_diag, uint32_t *__restrict__ finite,
+                                                       float *__restrict__ part, uint32_t *__restrict__ finite,
                                                        uint32_t *__restrict__ bb) {
     float sum = 0.f;
     uint32_t cnt = 0;
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(256) void k_order_quality(const float *__restrict__
         }
     }
     if ((threadIdx.x & 63) == 0) {
-        atomicAdd(sum_diag, sum);
+        part[((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6] = sum;
         atomicAdd(finite, cnt);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -157,20 +161,22 @@ int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, 
     absmax[0] = absmax[1] = absmax[2] = __builtin_inff();
     const uint64_t nchunks = ((n + 3) / 4 + 63) / 64;
     if (nchunks == 0) return 0;
-    struct Out { float sum; uint32_t finite; uint32_t bb[6]; } h, *d = nullptr;
-    const Out init{0.f, 0u, {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u}};
+    struct Out { uint32_t finite; uint32_t bb[6]; float part[kOrderMaxGrid * 4]; } h, *d = nullptr;
+    const Out init{0u, {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u}, {}};
     hipError_t e = hipMalloc((void **)&d, sizeof(Out));
     if (e != hipSuccess) return (int)e;
     e = hipMemcpyAsync(d, &init, sizeof init, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        const unsigned grid = (unsigned)((nchunks + 255) / 256 < 128 ? (nchunks + 255) / 256 : 128);  // (few waves: eight same-address atomics each)
-        hipLaunchKernelGGL(k_order_quality, dim3(grid), dim3(256), 0, s, bounds, nchunks, &d->sum, &d->finite, d->bb);
+        const unsigned grid = (unsigned)((nchunks + 255) / 256 < kOrderMaxGrid ? (nchunks + 255) / 256 : kOrderMaxGrid);  // (few waves: seven same-address atomics each)
+        hipLaunchKernelGGL(k_order_quality, dim3(grid), dim3(256), 0, s, bounds, nchunks, d->part, &d->finite, d->bb);
         e = hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d);
     if (e != hipSuccess) return (int)e;
     if (h.finite == 0 || !(h.bb[0] <= h.bb[3])) return 0;
+    float sum = 0.f;
+    for (int w = 0; w < kOrderMaxGrid * 4; ++w) sum += h.part[w];  // (in wave order; waves that did not run hold 0)
     float ext2 = 0.f;
     for (int k = 0; k < 3; ++k) {
         const float lo = ord2f(h.bb[k]), hi = ord2f(h.bb[3 + k]);
@@ -179,7 +185,7 @@ int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, 
         absmax[k] = fabsf(lo) > fabsf(hi) ? fabsf(lo) : fabsf(hi);
     }
     const float cloud = sqrtf(ext2);
-    if (cloud > 0.f) *ratio = (h.sum / (float)h.finite) / cloud;
+    if (cloud > 0.f) *ratio = (sum / (float)h.finite) / cloud;
     return 0;
 }
 

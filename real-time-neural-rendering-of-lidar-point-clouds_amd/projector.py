@@ -18,6 +18,19 @@ def _vp(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _affine_rows(M):
+    """The 12 float32 coefficients rtr_transform_points takes (row-major 3 x 4) from a (3, 4) or (4, 4) array whose
+    bottom row is exactly 0 0 0 1; every element is rounded to float32 once."""
+    m = np.asarray(M)
+    if m.dtype.kind not in "fiu" or m.shape not in ((3, 4), (4, 4)):
+        raise ValueError("M must be a real (3, 4) or (4, 4) array, got %s %s" % (m.dtype, m.shape))
+    if m.shape == (4, 4):
+        if not (m[3, 0] == 0 and m[3, 1] == 0 and m[3, 2] == 0 and m[3, 3] == 1):
+            raise ValueError("the bottom row of a 4 x 4 M must be exactly (0, 0, 0, 1): only affine transforms")
+        m = m[:3]
+    return np.ascontiguousarray(m.astype(np.float32)).reshape(12)
+
+
 class DeviceBuffer:
     """A context-owned device buffer exposed through __cuda_array_interface__ so that
     torch.as_tensor(buf, device='cuda') aliases it (zero copy) for RCCL collectives."""
@@ -130,6 +143,19 @@ class Projector:
             raise ValueError("remove_points needs a keep mask (None keeps every point: nothing to remove)")
         ptr, nwords, _hold = self._keep_words(keep)
         self._chk(self._lib.rtr_remove_points(self._ctx, ptr, nwords))
+
+    def transform_points(self, M, select=None):
+        """Moves resident points by the affine transform M where they lie (include/rtr.h section 2d): indices, order,
+        colours and the keep mask stay.  M: (3, 4) or (4, 4) (bottom row exactly 0 0 0 1), rounded to float32 once; a
+        selected point p becomes ((M00 x + M01 y) + M02 z) + M03, ... in fp32.  select: None moves every point, else the
+        forms of set_point_keep -- a bool array of length n, uint32 words, device memory -- naming the points that move.
+        Frames equal, bit for bit, those of one upload of the moved cloud."""
+        m = _affine_rows(M)
+        if select is None:
+            self._chk(self._lib.rtr_transform_points(self._ctx, _vp(m), None, 0))
+            return
+        ptr, nwords, _hold = self._keep_words(select)
+        self._chk(self._lib.rtr_transform_points(self._ctx, _vp(m), ptr, nwords))
 
     def generate_synthetic(self, scene, seed, first, count, total):
         sc = L.SCENES[scene] if isinstance(scene, str) else int(scene)
@@ -526,6 +552,25 @@ class ProjectCloud:
         keep = np.ones(n, bool)
         keep[idx] = False
         self._p.remove_points(keep)
+
+    def transformPoints(self, M, first=0, count=None):
+        """Moves the uploaded vertices [first, first + count) (default: to the last one) by the affine transform M, (3, 4)
+        or (4, 4) with bottom row 0 0 0 1 (see Projector.transform_points) -- one re-registered scan.  Indices, order,
+        colours and the keep mask stay; a range past the vertex count raises IndexError."""
+        m = _affine_rows(M)
+        n = self._p.num_points
+        first = int(first)
+        count = n - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > n:  # (as the C++ facade)
+            raise IndexError("transformPoints: the range [%d, %d + %d) must lie in [0, %d)" % (first, first, count, n))
+        if count == 0:
+            return
+        if first == 0 and count == n:  # (every point: no selection, so any cloud, sorted or not)
+            self._p.transform_points(m.reshape(3, 4))
+            return
+        sel = np.zeros(n, bool)
+        sel[first:first + count] = True
+        self._p.transform_points(m.reshape(3, 4), sel)
 
     def commitPointKeep(self):
         """Removes the vertices the keep mask in force hides (see removePoints), then clears the mask: the frames stay

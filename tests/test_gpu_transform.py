@@ -1,0 +1,608 @@
+"""Moving points of the resident cloud on the GPU (include/rtr.h section 2d): rtr_upload_points(A) then
+rtr_transform_points(M, sel) renders bit for bit what one upload of A' renders -- A'[i] = M applied to A[i] for the
+selected i, numpy float32 ((m0 x + m1 y) + m2 z) + m3 -- compared with a second context that uploads A' AND with the
+oracle on A', in every form the cloud and the frame can take; the absmax trap of the lane test, downloads, the packed
+form's sizes, the point pass and the keep mask, clip planes, sequences with appends and removals, the ordering against
+earlier calls, an overflowing extent pool, views and phase calls, the error paths, a full-size cloud and memory."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import pool_overflow_scenes as sc
+
+pytestmark = pytest.mark.gpu
+
+CONFIGS = {"default": {}, "pack0": {"pack": 0}, "pack2": {"pack": 2}, "mode0": {"mode": 0}, "cull": {"cull": 1},
+           "chunk_test0": {"chunk_test": 0}, "lane_test0": {"lane_test": 0}, "overlap": {"overlap": 1},
+           "auto_reorder1": {"auto_reorder": 1}, "keep_soa1": {"keep_soa": 1}, "point_ids1": {"point_ids": 1}}
+SCENES = (("room_shell", 150_001), ("uniform_box", 160_003))  # (a coherent scan, never sorted; hash order: sorted)
+
+
+def _rot(ax, ay, az):
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+def _m(R, t):
+    return np.hstack([np.asarray(R, np.float64), np.asarray(t, np.float64).reshape(3, 1)])
+
+
+TRANSFORMS = {"rigid": _m(_rot(0.02, -0.03, 0.05), [0.3, -0.2, 0.1]),
+              "far": _m(np.eye(3), [1e4, -5e3, 2e3]),
+              "scale_shear": _m([[1000.0, 300.0, 0.0], [0.0, 1000.0, 0.0], [50.0, 0.0, 1000.0]], [0.0, 0.0, 0.0]),
+              "identity": _m(np.eye(3), [0.0, 0.0, 0.0])}
+
+
+def moved(xyzw, M, sel=None):
+    """A': numpy float32, every product and sum rounded on its own; xyzw (n, 4) float32, sel bool or None (all)."""
+    m = np.asarray(M, np.float64)[:3].astype(np.float32)
+    out = np.array(xyzw, np.float32, copy=True)
+    idx = slice(None) if sel is None else sel
+    x, y, z = out[idx, 0].copy(), out[idx, 1].copy(), out[idx, 2].copy()
+    with np.errstate(all="ignore"):
+        for r in range(3):
+            out[idx, r] = ((m[r, 0] * x + m[r, 1] * y) + m[r, 2] * z) + m[r, 3]
+    return out
+
+
+def _new(pkg, options, W, H):
+    p = pkg.Projector(0)
+    for k, v in options.items():
+        p.set_option(k, v)
+    p.set_resolution(W, H)
+    return p
+
+
+def _options(config, scene):
+    o = dict(CONFIGS[config])
+    if scene == "uniform_box" or config == "auto_reorder1":  # (the library sorts these clouds)
+        o["point_ids"] = 1
+    return o
+
+
+def _selections(n, seed):
+    """Selections over the upload indices (None: every point)."""
+    idx = np.arange(n)
+    rng = np.random.default_rng(seed)
+    last = n - n % 256 if n % 256 else n - 256
+    return {"all": None,
+            "random": rng.random(n) < 0.3,
+            "middle": (idx >= n // 3) & (idx < n // 2),
+            "tail": idx >= n - n // 5,
+            "one_chunk": (idx >= 256 * 5) & (idx < 256 * 6),
+            "every_other_chunk": (idx // 256) % 2 == 0,
+            "last_partial_chunk": idx >= last,
+            "empty": np.zeros(n, bool)}
+
+
+def _ref(orc, xyzw, rgba, P, W, H, filtered):
+    r = orc.project(xyzw, rgba, P, W, H)
+    out = {"depth_bits": r["depth_bits"], "img": r["img"]}
+    if filtered:
+        f = orc.filter(r["depth_bits"], r["img"])
+        out.update(depth_bits=f["depth"].view(np.uint32), img=f["img"], tensor=f["tensor"], minmax=f["minmax"])
+    return out
+
+
+def _frame(pkg, p, P, filtered):
+    L = pkg._lib
+    img, depth = p.project(P, filtered=filtered)
+    out = {"depth_bits": depth.view(np.uint32).copy(), "img": img.copy()}
+    if filtered:
+        out["tensor"] = p.download(L.BUF_TENSOR).reshape(5, p.H, p.W)
+        out["minmax"] = p.download(L.BUF_MINMAX)
+    return out
+
+
+def _check(pkg, orc, a, b, xyzw, rgba, P, filtered, what):
+    """a's frame == b's frame == the oracle's on (xyzw, rgba)."""
+    filtered = filtered and a.W % 16 == 0 and a.H >= 16
+    fa = _frame(pkg, a, P, filtered)
+    fb = _frame(pkg, b, P, filtered) if b is not None else None
+    r = _ref(orc, xyzw, rgba, P, a.W, a.H, filtered)
+    for k in ("depth_bits", "img") + (("tensor", "minmax") if filtered else ()):
+        ref = r[k] if k != "minmax" else np.asarray(r[k]).view(np.uint32).reshape(2)
+        assert np.array_equal(fa[k], ref), (k, what)
+        if fb is not None:
+            assert np.array_equal(fa[k], fb[k]), (k, "one-shot", what)
+
+
+def _words(sel):
+    n = sel.size
+    return np.packbits(np.concatenate([sel, np.zeros(-n % 32, bool)]), bitorder="little").view("<u4").copy()
+
+
+def _looking_at(pkg, orc, pts, W, H, back=3.0):
+    """A pose whose camera looks at the centre of `pts` (finite rows of an (n, 4) array) from `back` x its extent."""
+    q = pts[np.isfinite(pts[:, :3]).all(1), :3].astype(np.float64)
+    c, ext = q.mean(0), float(np.ptp(q, 0).max()) + 1e-3
+    E = np.eye(4)
+    E[:3, 3] = -c + np.array([0.0, 0.0, back * ext])
+    K = np.array([[0.8 * W, 0, W / 2], [0, 0.8 * W, H / 2], [0, 0, 1]])
+    return orc.compose_projection(K, E)
+
+
+@pytest.mark.parametrize("config", sorted(CONFIGS))
+def test_transform_configs_match_one_shot_and_oracle(pkg, orc, config):
+    W, H = 320, 240
+    names = sorted(TRANSFORMS)
+    for scene, n in SCENES:
+        options = _options(config, scene)
+        xyzw, rgba = orc.generate(scene, 73, 0, n, n)
+        a, b = _new(pkg, options, W, H), _new(pkg, options, W, H)
+        try:
+            for j, (shape, sel) in enumerate(_selections(n, 5).items()):
+                M = TRANSFORMS[names[j % len(names)]]
+                a.upload_points(xyzw, rgba)
+                a.transform_points(M, sel)
+                A1 = moved(xyzw, M, sel)
+                b.upload_points(A1, rgba)
+                assert a.num_points == n
+                if scene == "uniform_box":
+                    assert a.get_option("reordered") == 1
+                if config == "pack2" or (config == "default" and scene == "room_shell"):
+                    assert a.get_option("packed") == 1  # (a packed cloud stays packed)
+                for k, filt in enumerate((False, True)):
+                    P = pkg.orbit_projection(37 * j + 11 * k + 5, W, H)
+                    _check(pkg, orc, a, b, A1, rgba, P, filt, (config, scene, shape, names[j % 4], filt))
+                if sel is not None and sel.any():  # (a pose that sees the moved part)
+                    P = _looking_at(pkg, orc, A1[sel], W, H)
+                    _check(pkg, orc, a, b, A1, rgba, P, True, (config, scene, shape, "moved part"))
+        finally:
+            a.close(); b.close()
+
+
+def test_transform_every_kind_on_every_selection(pkg, orc):
+    W, H = 256, 192
+    n = 70_001
+    for scene in ("room_shell", "uniform_box"):
+        xyzw, rgba = orc.generate(scene, 91, 0, n, n)
+        a, b = _new(pkg, {"point_ids": 1}, W, H), _new(pkg, {"point_ids": 1}, W, H)
+        try:
+            for shape, sel in _selections(n, 9).items():
+                for name, M in TRANSFORMS.items():
+                    a.upload_points(xyzw, rgba)
+                    a.transform_points(M, sel)
+                    A1 = moved(xyzw, M, sel)
+                    b.upload_points(A1, rgba)
+                    _check(pkg, orc, a, b, A1, rgba, pkg.orbit_projection(len(shape) + 3 * len(name), W, H), True,
+                           (scene, shape, name))
+        finally:
+            a.close(); b.close()
+
+
+def test_transform_absmax_trap_points_moved_far_outside(pkg, orc):
+    """Points moved far outside the old bounds, lane test on, a camera looking at them: the lane test's margin step is
+    bounded by the cloud's absmax, so it must be recomputed from the new chunk boxes."""
+    W, H = 320, 240
+    n = 150_001
+    xyzw, rgba = orc.generate("room_shell", 17, 0, n, n)
+    idx = np.arange(n)
+    for sel in (idx >= n - 30_000, (idx >= 40_000) & (idx < 41_000), None):
+        M = _m(_rot(0.0, 0.1, 0.0) * 3.0, [2e5, -1e5, 3e5])
+        for options in ({}, {"pack": 0}, {"keep_soa": 1}, {"cull": 1}):
+            a, b = _new(pkg, options, W, H), _new(pkg, options, W, H)
+            try:
+                assert a.get_option("lane_test") == 1
+                a.upload_points(xyzw, rgba)
+                a.project(pkg.orbit_projection(1, W, H))
+                a.transform_points(M, sel)
+                A1 = moved(xyzw, M, sel)
+                b.upload_points(A1, rgba)
+                part = A1 if sel is None else A1[sel]
+                for back in (1.5, 3.0, 8.0):
+                    _check(pkg, orc, a, b, A1, rgba, _looking_at(pkg, orc, part, W, H, back), True, (options, back))
+            finally:
+                a.close(); b.close()
+
+
+def test_transform_downloads_and_special_values(pkg, orc):
+    n = 140_000
+    xyzw, rgba = orc.generate("uniform_box", 41, 0, n, n)
+    sel = np.random.default_rng(41).random(n) < 0.3
+    M = TRANSFORMS["rigid"]
+    for options in ({"auto_reorder": 0}, {"point_ids": 1}, {"auto_reorder": 0, "pack": 0}, {"auto_reorder": 0, "keep_soa": 1}):
+        p = _new(pkg, options, 64, 48)
+        try:
+            p.upload_points(xyzw, rgba)
+            p.transform_points(M, sel)
+            gx, gc = p.download_points()
+            A1 = moved(xyzw, M, sel)
+            want = np.concatenate([A1[:, :3].view(np.uint32), rgba.view(np.uint32)], axis=1)
+            got = np.concatenate([gx[:, :3].view(np.uint32), gc.view(np.uint32)], axis=1)
+            if options.get("auto_reorder") == 0:
+                assert np.array_equal(got, want)  # exactly A' (resident order = upload order)
+            else:
+                key = lambda a: a[np.lexsort(a.T[::-1])]  # noqa: E731
+                assert np.array_equal(key(got), key(want))
+        finally:
+            p.close()
+    # the identity is no no-op: -0 becomes +0, an infinite coordinate turns the point's other coordinates into NaN
+    n = 4099
+    xyzw, rgba = orc.generate("room_shell", 43, 0, n, n)
+    xyzw = xyzw.copy()
+    xyzw[10, 0] = -0.0
+    xyzw[11, 1] = -0.0
+    xyzw[300, 2] = np.inf
+    xyzw[301, 0] = -np.inf
+    xyzw[302, 1] = np.nan
+    for options in ({"auto_reorder": 0}, {"auto_reorder": 0, "pack": 2}, {"auto_reorder": 0, "pack": 0}):
+        p = _new(pkg, options, 64, 48)
+        try:
+            p.upload_points(xyzw, rgba)
+            p.transform_points(TRANSFORMS["identity"])
+            gx, _ = p.download_points()
+            A1 = moved(xyzw, TRANSFORMS["identity"])
+            assert gx[10, 0].view(np.uint32) == 0 and gx[11, 1].view(np.uint32) == 0
+            assert np.isnan(gx[300, 0]) and np.isnan(gx[300, 1]) and gx[300, 2] == np.inf
+            assert gx[301, 0] == -np.inf and np.isnan(gx[301, 1]) and np.isnan(gx[301, 2])
+            g, w = gx[:, :3], A1[:, :3]
+            assert np.array_equal(np.isnan(g), np.isnan(w))  # (NaN payloads are the hardware's)
+            fin = ~np.isnan(w)
+            assert np.array_equal(g[fin].view(np.uint32), w[fin].view(np.uint32))
+        finally:
+            p.close()
+
+
+def test_transform_packed_sizes_match_upload_in_resident_order(pkg, orc):
+    """pack = 2, auto_reorder = 0 on both contexts: the moved cloud and A' uploaded in the same order give equal packed
+    sizes and order measures -- the window's units, the moved tail and the chunk boxes are right."""
+    W, H = 320, 240
+    n = 150_001
+    xyzw, rgba = orc.generate("room_shell", 29, 0, n, n)
+    options = {"pack": 2, "auto_reorder": 0}
+    a, b = _new(pkg, options, W, H), _new(pkg, options, W, H)
+    try:
+        for j, (shape, sel) in enumerate(_selections(n, 29).items()):
+            for name, M in TRANSFORMS.items():
+                a.upload_points(xyzw, rgba)
+                a.transform_points(M, sel)
+                A1 = moved(xyzw, M, sel)
+                b.upload_points(A1, rgba)
+                for key in ("packed", "packed_millibytes_per_point", "order_ratio_ppm"):
+                    assert a.get_option(key) == b.get_option(key), (shape, name, key)
+                _check(pkg, orc, a, b, A1, rgba, pkg.orbit_projection(5 * j + len(name), W, H), False, (shape, name))
+        # moves in a row: the tail moves each time, the sizes follow
+        a.upload_points(xyzw, rgba)
+        A1 = xyzw
+        idx = np.arange(n)
+        for k, (lo, hi) in enumerate(((10_000, 20_000), (100_000, 100_300), (0, 5), (60_000, n))):
+            sel = (idx >= lo) & (idx < hi)
+            M = TRANSFORMS["scale_shear"] if k % 2 else TRANSFORMS["rigid"]
+            a.transform_points(M, sel)
+            A1 = moved(A1, M, sel)
+            b.upload_points(A1, rgba)
+            assert a.get_option("packed_millibytes_per_point") == b.get_option("packed_millibytes_per_point"), k
+            _check(pkg, orc, a, b, A1, rgba, pkg.orbit_projection(17 * k, W, H), True, ("row", k))
+        gx, _ = a.download_points()
+        assert np.array_equal(gx[:, :3].view(np.uint32), A1[:, :3].view(np.uint32))
+    finally:
+        a.close(); b.close()
+
+
+def test_transform_point_pass_keep_mask_and_clip(pkg, orc):
+    L = pkg._lib
+    W, H = 320, 240
+    n = 150_001
+    for scene in ("room_shell", "uniform_box"):
+        xyzw, rgba = orc.generate(scene, 53, 0, n, n)
+        keep = np.random.default_rng(53).random(n) >= 0.2
+        sel = (np.arange(n) // 1000) % 3 == 0
+        M = TRANSFORMS["rigid"]
+        A1 = moved(xyzw, M, sel)
+        a, b = _new(pkg, {"point_ids": 1}, W, H), _new(pkg, {"point_ids": 1}, W, H)
+        try:
+            a.upload_points(xyzw, rgba)
+            a.set_point_keep(keep)
+            w0 = a.download(L.BUF_POINT_KEEP)
+            a.transform_points(M, sel)
+            assert np.array_equal(a.download(L.BUF_POINT_KEEP), w0)  # (the mask in force is untouched)
+            b.upload_points(A1, rgba)
+            b.set_point_keep(keep)
+            P = pkg.orbit_projection(21, W, H)
+            _check(pkg, orc, a, b, A1[keep], rgba[keep], P, True, (scene, "keep"))
+            for p in (a, b):
+                p.project(P)
+                p.point_pass(P)
+            for which in (L.BUF_POINT_ID, L.BUF_VISIBLE):
+                assert np.array_equal(a.download(which), b.download(which)), (scene, which)
+            for p in (a, b):
+                p.set_point_keep(None)
+            # clip planes are world-space: they select the moved coordinates
+            planes = np.array([[1, 0, 0, 2.0], [0, -1, 0, 1.5]], np.float32)
+            for p in (a, b):
+                p.set_clip_planes(planes)
+            inside = np.ones(n, bool)
+            for a_, b_, c_, d_ in planes:
+                inside &= ((a_ * A1[:, 0] + b_ * A1[:, 1]) + c_ * A1[:, 2]) + d_ >= np.float32(0)
+            _check(pkg, orc, a, b, A1[inside], rgba[inside], pkg.orbit_projection(44, W, H), True, (scene, "clip"))
+        finally:
+            a.close(); b.close()
+
+
+def test_transform_sequences_with_appends_and_removals(pkg, orc):
+    W, H = 320, 240
+    n, nA = 150_001, 90_000
+    for scene in ("room_shell", "uniform_box"):
+        xyzw, rgba = orc.generate(scene, 61, 0, n, n)
+        options = {"point_ids": 1}
+        a, b = _new(pkg, options, W, H), _new(pkg, options, W, H)
+        try:
+            a.upload_points(xyzw[:nA], rgba[:nA])
+            a.append_points(xyzw[nA:], rgba[nA:])
+            idx = np.arange(n)
+            s1 = idx >= nA  # (the appended scan re-posed)
+            a.transform_points(TRANSFORMS["rigid"], s1)
+            A1 = moved(xyzw, TRANSFORMS["rigid"], s1)
+            keep = (idx % 7 != 3) & ~((idx >= 20_000) & (idx < 30_000))
+            a.remove_points(keep)
+            A1, C1 = A1[keep], rgba[keep]
+            s2 = (np.arange(A1.shape[0]) >= 50_000) & (np.arange(A1.shape[0]) < 80_000)
+            a.transform_points(TRANSFORMS["scale_shear"], s2)
+            A1 = moved(A1, TRANSFORMS["scale_shear"], s2)
+            a.transform_points(TRANSFORMS["far"])
+            A1 = moved(A1, TRANSFORMS["far"])
+            b.upload_points(A1, C1)
+            for k in range(3):
+                _check(pkg, orc, a, b, A1, C1, pkg.orbit_projection(23 * k + 1, W, H), k == 1, (scene, k))
+            _check(pkg, orc, a, b, A1, C1, _looking_at(pkg, orc, A1, W, H), True, (scene, "look"))
+        finally:
+            a.close(); b.close()
+
+
+def test_transform_views_and_phase_calls(pkg, orc):
+    L = pkg._lib
+    W, H = 320, 240
+    n = 150_001
+    xyzw, rgba = orc.generate("room_shell", 67, 0, n, n)
+    sel = np.arange(n) < 70_000
+    M = TRANSFORMS["rigid"]
+    A1 = moved(xyzw, M, sel)
+    a, b = _new(pkg, {}, W, H), _new(pkg, {}, W, H)
+    try:
+        a.upload_points(xyzw, rgba)
+        Ps = np.stack([pkg.orbit_projection(9 * k, W, H) for k in range(3)])
+        a.render_views(Ps, with_filter=True)
+        a.transform_points(M, sel)
+        b.upload_points(A1, rgba)
+        for p in (a, b):
+            p.render_views(Ps, with_filter=True)
+        for which in (L.BUF_VIEW_DEPTH, L.BUF_VIEW_IMAGE, L.BUF_VIEW_TENSOR, L.BUF_VIEW_MINMAX):
+            assert np.array_equal(a.download(which), b.download(which)), which
+        r = orc.project(A1, rgba, Ps[1], W, H)
+        rf = orc.filter(r["depth_bits"], r["img"])
+        assert np.array_equal(a.download(L.BUF_VIEW_DEPTH)[1], rf["depth"].view(np.uint32))
+        P = pkg.orbit_projection(61, W, H)
+        for p in (a, b):
+            p.clear(); p.min_depth_pass(P); p.accumulate_pass(P); p.resolve()
+        r = orc.project(A1, rgba, P, W, H)
+        for which in (L.BUF_DEPTH, L.BUF_ACCUM, L.BUF_IMAGE):
+            assert np.array_equal(a.download(which), b.download(which)), which
+        assert np.array_equal(a.download(L.BUF_DEPTH), r["depth_bits"])
+        for p in (a, b):
+            p.project(P)
+        sa, sb = a.frame_stats(), b.frame_stats()
+        assert (sa["entries"], sa["heaviest_tile"]) == (sb["entries"], sb["heaviest_tile"])
+    finally:
+        a.close(); b.close()
+
+
+def test_transform_ordering_async_slot_and_stale_bins(pkg, orc):
+    L = pkg._lib
+    W, H = 320, 240
+    n = 150_000
+    xyzw, rgba = orc.generate("room_shell", 31, 0, n, n)
+    sel = np.arange(n) < 60_000
+    M = _m(np.eye(3), [0.4, 0.0, -0.3])
+    A1 = moved(xyzw, M, sel)
+    p = _new(pkg, {}, W, H)
+    try:
+        p.upload_points(xyzw, rgba)
+        P = pkg.orbit_projection(12, W, H)
+        p.project_async(P, 0)
+        p.transform_points(M, sel)
+        p.wait_outputs(0)
+        img, depth = p.host_output_buffers(0)
+        r = orc.project(xyzw, rgba, P, W, H)  # (the slot comes out with the old cloud)
+        assert np.array_equal(depth.view(np.uint32), r["depth_bits"]) and np.array_equal(img, r["img"])
+        _check(pkg, orc, p, None, A1, rgba, P, False, "after")
+        # min depth of the old cloud, a move, then the accumulate pass: the moved cloud against the old depth
+        p.upload_points(xyzw, rgba)
+        p.clear()
+        p.min_depth_pass(P)
+        p.transform_points(M, sel)
+        p.accumulate_pass(P)
+        p.resolve()
+        depth0, acc0 = orc.clear(W, H)
+        depth0 = orc.min_depth_pass(xyzw, P, W, H, depth0)
+        acc0 = orc.accumulate_pass(A1, rgba, P, W, H, depth0, acc0)
+        assert np.array_equal(p.download(L.BUF_DEPTH).reshape(-1), depth0.reshape(-1))
+        assert np.array_equal(p.download(L.BUF_ACCUM).reshape(-1), acc0.reshape(-1))
+        assert np.array_equal(p.download(L.BUF_IMAGE).reshape(-1), orc.resolve(acc0, W, H).reshape(-1))
+        # (the bins of the old cloud were not reused: the old cloud's accumulate pass differs)
+        acc_old = orc.accumulate_pass(xyzw, rgba, P, W, H, depth0, orc.clear(W, H)[1])
+        assert not np.array_equal(acc_old.reshape(-1), acc0.reshape(-1))
+    finally:
+        p.close()
+
+
+def test_transform_throws_cloud_into_view_overflows_pool_and_repairs(pkg, orc):
+    """A move that throws the whole cloud into a view that saw about 1 % of it: the frame overflows the adaptive pool,
+    the next synchronising call renders it again, exact."""
+    xyzw, rgba = sc.cloud(orc)
+    P, K, E = sc.p_one(orc)
+    # a pose that sees a sliver of the cloud first: the cloud is moved so that only ~1 % lies in front of the camera
+    shift = _m(np.eye(3), [0.0, 0.0, -1e3])
+    start = moved(xyzw, shift, np.arange(sc.N) >= sc.N // 100)
+    p = _new(pkg, {"auto_reorder": 0}, sc.W, sc.H)
+    try:
+        p.upload_points(start, rgba)
+        for _ in range(3):
+            p.project(P)  # (the pool is sized by frames that see ~1 % of the cloud)
+        mb0 = p.get_option("resident_millibytes_per_point")
+        p.transform_points(_m(np.eye(3), [0.0, 0.0, 1e3]), np.arange(sc.N) >= sc.N // 100)
+        A1 = moved(start, _m(np.eye(3), [0.0, 0.0, 1e3]), np.arange(sc.N) >= sc.N // 100)
+        p.render(P)  # (~2 n entries into a pool sized for ~1 %: it overflows)
+        p.synchronize()
+        assert p.get_option("resident_millibytes_per_point") - mb0 >= sc.JUMP_MB
+        r = orc.project(A1, rgba, P, sc.W, sc.H)
+        assert np.array_equal(p.download(pkg._lib.BUF_DEPTH), r["depth_bits"])
+        assert np.array_equal(p.download(pkg._lib.BUF_IMAGE), r["img"])
+    finally:
+        p.close()
+
+
+def test_transform_errors_change_nothing(pkg, orc):
+    L = pkg._lib
+    W, H = 160, 128
+    n = 50_000
+    xyzw, rgba = orc.generate("room_shell", 37, 0, n, n)
+    eye = np.eye(4)[:3].astype(np.float32).reshape(12)
+    e = pkg.Projector(0)
+    try:  # no cloud
+        assert e._lib.rtr_transform_points(e._ctx, eye.ctypes.data_as(C.c_void_p), None, 0) == L.RTR_ERR_INVALID
+    finally:
+        e.close()
+    p = _new(pkg, {"point_ids": 1}, W, H)
+    try:
+        p.upload_points(xyzw, rgba)
+        p.set_point_keep(np.arange(n) % 3 != 0)
+        P = pkg.orbit_projection(8, W, H)
+        img0, depth0 = p.project(P)
+        keep0 = p.download(L.BUF_POINT_KEEP)
+        pts0 = p.download_points()[0]
+        words = _words(np.arange(n) % 2 == 0)
+        vp = C.c_void_p(words.ctypes.data)
+        lib, mp = p._lib, C.c_void_p(eye.ctypes.data)
+        bad_m = []
+        for v in (np.nan, np.inf, -np.inf):
+            m = (eye * 2).copy()
+            m[7] = v
+            bad_m.append(m)
+        for args in ((mp, vp, words.size - 1), (mp, vp, words.size + 1), (mp, vp, 0), (mp, None, words.size),
+                     (None, vp, words.size), (None, None, 0)) + tuple((C.c_void_p(m.ctypes.data), None, 0) for m in bad_m):
+            assert lib.rtr_transform_points(p._ctx, *args) == L.RTR_ERR_INVALID, args
+        img1, depth1 = p.project(P)
+        assert np.array_equal(depth0.view(np.uint32), depth1.view(np.uint32)) and np.array_equal(img0, img1)
+        assert np.array_equal(p.download(L.BUF_POINT_KEEP), keep0)
+        assert np.array_equal(p.download_points()[0].view(np.uint32), pts0.view(np.uint32))
+        # an empty selection: RTR_OK, nothing changes
+        p.transform_points(TRANSFORMS["far"], np.zeros(n, bool))
+        img1, depth1 = p.project(P)
+        assert np.array_equal(depth0.view(np.uint32), depth1.view(np.uint32)) and np.array_equal(img0, img1)
+    finally:
+        p.close()
+    # a cloud the library sorted without point_ids: a selection cannot be mapped, every point still moves
+    xu, cu = orc.generate("uniform_box", 37, 0, 70_000, 70_000)
+    p = _new(pkg, {}, W, H)
+    try:
+        p.upload_points(xu, cu)
+        assert p.get_option("reordered") == 1
+        img0, depth0 = p.project(P)
+        with pytest.raises(pkg.RtrError) as err:
+            p.transform_points(TRANSFORMS["rigid"], np.arange(70_000) % 2 == 0)
+        assert err.value.code == L.RTR_ERR_INVALID and "point_ids" in str(err.value)
+        img1, depth1 = p.project(P)
+        assert np.array_equal(depth0.view(np.uint32), depth1.view(np.uint32)) and np.array_equal(img0, img1)
+        p.transform_points(TRANSFORMS["rigid"])
+        _check(pkg, orc, p, None, moved(xu, TRANSFORMS["rigid"]), cu, P, True, "sorted, all")
+    finally:
+        p.close()
+
+
+def test_transform_keeps_p2p_open(pkg, orc):
+    n = 60_000
+    xyzw, rgba = orc.generate("room_shell", 43, 0, n, n)
+    p = _new(pkg, {}, 160, 128)
+    try:
+        p.upload_points(xyzw, rgba)
+        p.p2p_open(0, 1, [p.p2p_export()])
+        assert p.get_option("p2p_open") == 1
+        sel = np.arange(n) < 40_000
+        p.transform_points(TRANSFORMS["rigid"], sel)
+        assert p.get_option("p2p_open") == 1
+        P = pkg.orbit_projection(5, 160, 128)
+        p.p2p_render(P)
+        r = orc.project(moved(xyzw, TRANSFORMS["rigid"], sel), rgba, P, 160, 128)
+        assert np.array_equal(p.download(pkg._lib.BUF_DEPTH), r["depth_bits"])
+        assert np.array_equal(p.download(pkg._lib.BUF_IMAGE), r["img"])
+    finally:
+        p.close()
+
+
+def test_transform_memory_bound(pkg, orc):
+    n, W, H = 10_000_000, 640, 480
+    xyzw, rgba = orc.generate("room_shell", 47, 0, n, n)
+    sel = (np.arange(n) // 100_000) % 2 == 1
+    M = TRANSFORMS["scale_shear"]
+    a, b = _new(pkg, {}, W, H), _new(pkg, {}, W, H)
+    try:
+        a.upload_points(xyzw, rgba)
+        a.transform_points(M, sel)
+        A1 = moved(xyzw, M, sel)
+        b.upload_points(A1, rgba)
+        P = pkg.orbit_projection(3, W, H)
+        a.project(P)
+        b.project(P)
+        ma, mb = a.get_option("resident_millibytes_per_point"), b.get_option("resident_millibytes_per_point")
+        assert ma <= 1.15 * mb, (ma, mb)
+    finally:
+        a.close(); b.close()
+
+
+def test_transform_full_size_appended_block(pkg, orc):
+    """1.1e8 points (1e8 + an appended 1e7) with the appended block moved equals the one-shot context of A'."""
+    N, m, W, H = 100_000_000, 10_000_000, 1920, 1080
+    xyzw, rgba = orc.generate("room_shell", 0xC3, 0, N + m, N + m)
+    M = TRANSFORMS["rigid"]
+    sel = np.arange(N + m) >= N
+    a = _new(pkg, {"auto_reorder": 0}, W, H)
+    try:
+        a.upload_points(xyzw[:N], rgba[:N])
+        a.append_points(xyzw[N:], rgba[N:])
+        a.transform_points(M, sel)
+        A1 = moved(xyzw[N:], M)
+        fa = [_frame(pkg, a, pkg.orbit_projection(k, W, H), k == 1) for k in (0, 1)]
+    finally:
+        a.close()
+    xyzw[N:] = A1
+    del A1
+    b = _new(pkg, {"auto_reorder": 0}, W, H)
+    try:
+        b.upload_points(xyzw, rgba)
+        fb = [_frame(pkg, b, pkg.orbit_projection(k, W, H), k == 1) for k in (0, 1)]
+    finally:
+        b.close()
+    for x, y in zip(fa, fb):
+        for k in x:
+            assert np.array_equal(x[k], y[k]), k
+    r = orc.project(xyzw, rgba, pkg.orbit_projection(0, W, H), W, H)
+    assert np.array_equal(fa[0]["depth_bits"], r["depth_bits"]) and np.array_equal(fa[0]["img"], r["img"])
+
+
+def _free_port():
+    import socket
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+@pytest.mark.parametrize("form", ["p2p", "owned"])
+def test_transform_p2p_render_two_ranks(form):
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "transform_p2p_worker.py"), form]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-3000:]
+    out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("[")][-1])
+    assert len(out) == 2 and all(r["ok"] for r in out), out
