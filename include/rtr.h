@@ -181,7 +181,8 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          timing attribution -- frames are WRONG while it is non-zero; the shipped library rejects it.
  *  "probe_variant": measurement aid of tools/probe_variants.py (selects the rtr_stream_probe kernel).
  *  rtr_get_option("views") reads the view count of the last rtr_render_views batch (section 6c; 0: none current).
- *  rtr_get_option("point_keep") reads 1 while a keep mask is set (section 6e). */
+ *  rtr_get_option("point_keep") reads 1 while a keep mask is set (section 6e).
+ *  rtr_get_option("selection") reads 1 while a selection exists (section 6f). */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
 /* Reads an option back; also "p2p_open" (see "p2p_timeout_ms"), "reordered" (1: the resident cloud was sorted by the library),
  * "order_ratio_ppm" (mean chunk-box diagonal / cloud diagonal as uploaded, in millionths), "packed" and
@@ -459,7 +460,8 @@ typedef enum {
     RTR_BUF_VIEW_IMAGE = 9,   /* u8  [count, H, W, 3]                                                    */
     RTR_BUF_VIEW_TENSOR = 10, /* f16 [count, 5, H, W]  one contiguous batch tensor                       */
     RTR_BUF_VIEW_MINMAX = 11, /* u32 [count, 2]                                                          */
-    RTR_BUF_POINT_KEEP = 12   /* u32 [(n + 31) / 32]  the keep mask in force (section 6e), upload order, bits past n clear */
+    RTR_BUF_POINT_KEEP = 12,  /* u32 [(n + 31) / 32]  the keep mask in force (section 6e), upload order, bits past n clear */
+    RTR_BUF_SELECTION = 13    /* u32 [(n + 31) / 32]  the selection (section 6f), upload order, bits past n clear */
 } rtr_buffer;
 int rtr_device_buffer(rtr_ctx *ctx, int which, void **dev_ptr, size_t *bytes);
 /* Synchronous device->host copy of one buffer (bytes must equal its size). */
@@ -561,6 +563,53 @@ int rtr_get_clip_planes(rtr_ctx *ctx, int *count, float *planes);
  * Errors: no cloud, nwords != (n + 31) / 32, words NULL with nwords > 0, a sorted cloud without point_ids
  * -> RTR_ERR_INVALID, nothing changed. */
 int rtr_set_point_keep(rtr_ctx *ctx, const uint32_t *words, uint64_t nwords);
+
+/* ---- 6f. selection: name the points of a region on the device -----------------------------------------------------
+ * rtr_set_point_keep, rtr_remove_points and rtr_transform_points name their points by (n + 31) / 32 words in upload
+ * order.  rtr_select_points makes such words on the device from a region, without the coordinates leaving it, into
+ * RTR_BUF_SELECTION: bit i % 32 of word i / 32 set = point i is selected, bits past n clear.  rtr_device_buffer gives
+ * its device pointer, which the three editing calls accept as it is (they copy their words before they change anything).
+ * inside(i) holds iff both
+ *   1. every one of the plane_count planes GIVEN TO THIS CALL keeps point i: the contract of section 6d exactly
+ *      (0..RTR_MAX_CLIP_PLANES planes {a, b, c, d}, ((a*x + b*y) + c*z) + d >= 0 with every product and sum rounded on
+ *      its own, NaN is not kept).  plane_count = 0: true;
+ *   2. P is NULL, or the projection of a frame with matrix P at the context's resolution accepts the point at a pixel
+ *      (px, py) with rect[0] <= px < rect[2] and rect[1] <= py < rect[3] (rect = {x0, y0, x1, y1}): the frame's own
+ *      arithmetic, so a point is in the rectangle exactly when that frame would splat it there, before any depth test.
+ * plane_count = 0 with P NULL selects every point.  hit = inside, or, with RTR_SELECT_OUTSIDE OR-ed into op, !inside
+ * for the points below n -- the keep words rtr_remove_points wants in order to delete the inside of a box.  op combines
+ * the hits with the selection so far; one that does not exist yet counts as empty.  RTR_SELECT_TOGGLE with no plane and
+ * no P inverts the selection: no sequence of the other four ops can, and "remove / hide what is selected" needs the
+ * complement as keep words.
+ * The call reads the uploaded coordinates and nothing else: the context's own clip planes and keep mask are ignored, as
+ * in rtr_download_points.  It changes no frame, frame buffer, tile store, pool, statistics or point-pass buffer, and an
+ * open peer-to-peer exchange stays open.  Chunks of 256 resident points whose box lies wholly outside the region, or
+ * (planes only) wholly inside it, are decided without reading their coordinates.
+ * Ordering: queued on the context's stream like rtr_point_pass.  stats NULL: the call does not wait.  With stats it
+ * waits for the stream, like rtr_download_buffer, and writes [0] the points selected after op, [1] chunks decided on
+ * their boxes as wholly outside the region, [2] chunks decided wholly inside, [3] chunks decoded and tested point by
+ * point; [1] + [2] + [3] is the chunk count, (n + 255) / 256.
+ * Life: the buffer is allocated by the first call (8 words per 256-point chunk; counted in option
+ * "resident_millibytes_per_point" while it exists) and survives rtr_transform_points, rtr_reorder_points,
+ * rtr_set_point_keep, rtr_set_clip_planes and rtr_set_resolution.  Whatever renumbers upload indices drops it --
+ * rtr_upload_points, rtr_generate_synthetic, rtr_append_points, rtr_remove_points -- as does rtr_clear_selection:
+ * rtr_device_buffer(RTR_BUF_SELECTION) then fails with RTR_ERR_INVALID and rtr_get_option("selection") reads 0.
+ * Indices are the point pass's; a cloud sorted by the library needs option "point_ids" = 1.
+ * Sharded frames: each rank selects among its own points by its own indices, as with the keep mask.
+ * Errors: no cloud, plane_count outside 0..RTR_MAX_CLIP_PLANES, planes NULL with plane_count > 0, a non-finite
+ * coefficient or a = b = c = 0, P given without a resolution or with rect NULL, a rectangle not within 0 <= x0 < x1 <= W
+ * and 0 <= y0 < y1 <= H, an unknown op, a sorted cloud without point_ids -> RTR_ERR_INVALID, nothing changed;
+ * RTR_ERR_UNSUPPORTED for 2^32 points or more. */
+#define RTR_SELECT_REPLACE   0   /* sel  = hit          */
+#define RTR_SELECT_ADD       1   /* sel |= hit          */
+#define RTR_SELECT_SUBTRACT  2   /* sel &= ~hit         */
+#define RTR_SELECT_INTERSECT 3   /* sel &= hit          */
+#define RTR_SELECT_OUTSIDE   4   /* flag, OR-ed into op: hit = !inside (for the points below n) */
+#define RTR_SELECT_TOGGLE    8   /* sel ^= hit          */
+/* RTR_BUF_SELECTION = 13: u32 [(n + 31) / 32], upload order, bits past n clear */
+int rtr_select_points(rtr_ctx *ctx, int plane_count, const float *planes, const float *P, const int rect[4],
+                      int op, uint64_t stats[4]);
+int rtr_clear_selection(rtr_ctx *ctx);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

@@ -27,6 +27,8 @@
 // removePoints (section 2c) takes vertices out for good and renumbers the rest; commitPointKeep removes what the keep
 // mask in force hides.  transformPoints (section 2d) moves a range of vertices (one re-registered scan) by an affine
 // transform where they lie: indices, order and the keep mask stay.
+// selectBox / selectPlanes / selectRect (section 6f) name the vertices of a region on the device; removeSelected,
+// hideSelected and transformSelected then act on them without a host array of flags.
 //
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
@@ -301,6 +303,76 @@ public:
         check(ctx_, rtr_set_point_keep(ctx_, nullptr, 0));
     }
 
+    // Selection (rtr.h section 6f): the vertices every half-space of `planes` (count x 4 floats, the contract of
+    // setClipPlanes) keeps -- outside: the vertices NOT inside -- combined with the selection so far by op
+    // (RTR_SELECT_REPLACE / ADD / SUBTRACT / INTERSECT / TOGGLE).  Returns the number selected afterwards.  point_ids = true
+    // when the cloud may be sorted; the clip planes and the keep mask in force play no part.
+    uint64_t selectPlanes(const float* planes, int count, int op = RTR_SELECT_REPLACE, bool outside = false) {
+        uint64_t st[4] = {0, 0, 0, 0};
+        check(ctx_, rtr_select_points(ctx_, count, planes, nullptr, nullptr, op | (outside ? RTR_SELECT_OUTSIDE : 0), st));
+        return st[0];
+    }
+    // selectPlanes of the box lo <= q <= hi, q = M p: the six planes of setClipBox.
+    uint64_t selectBox(const float lo[3], const float hi[3], const double* M = nullptr, int op = RTR_SELECT_REPLACE,
+                       bool outside = false) {
+        float pl[6][4] = {};
+        for (int k = 0; k < 3; ++k) {
+            if (!M) {
+                pl[2 * k][k] = 1.f, pl[2 * k][3] = -lo[k];
+                pl[2 * k + 1][k] = -1.f, pl[2 * k + 1][3] = hi[k];
+                continue;
+            }
+            for (int j = 0; j < 3; ++j) {
+                pl[2 * k][j] = (float)M[4 * k + j];
+                pl[2 * k + 1][j] = (float)-M[4 * k + j];
+            }
+            pl[2 * k][3] = (float)(M[4 * k + 3] - (double)lo[k]);
+            pl[2 * k + 1][3] = (float)((double)hi[k] - M[4 * k + 3]);
+        }
+        return selectPlanes(&pl[0][0], 6, op, outside);
+    }
+    // The vertices computeRGBD with this calibration and pose splats onto a pixel x0 <= px < x1, y0 <= py < y1, hidden
+    // behind others or not (a rubber band on the screen).
+    template <class Calibration, class Extrinsics>
+    uint64_t selectRect(const Calibration& calibration, const Extrinsics& extrinsics, int x0, int y0, int x1, int y1,
+                        int op = RTR_SELECT_REPLACE) {
+        float P[16];
+        projection(calibration, extrinsics, P);
+        check(ctx_, rtr_set_resolution(ctx_, calibration.getWidth(), calibration.getHeight()));
+        const int rect[4] = {x0, y0, x1, y1};
+        uint64_t st[4] = {0, 0, 0, 0};
+        check(ctx_, rtr_select_points(ctx_, 0, nullptr, P, rect, op, st));
+        return st[0];
+    }
+    uint64_t selectedCount() {
+        if (!has_selection()) return 0;
+        uint64_t st[4] = {0, 0, 0, 0};  // (adds the complement of every point: nothing)
+        check(ctx_, rtr_select_points(ctx_, 0, nullptr, nullptr, nullptr, RTR_SELECT_ADD | RTR_SELECT_OUTSIDE, st));
+        return st[0];
+    }
+    void clearSelection() { check(ctx_, rtr_clear_selection(ctx_)); }
+    // Takes the selected vertices out of the resident cloud for good (see removePoints); the selection is gone.
+    void removeSelected() {
+        with_complement([&](const uint32_t* words, uint64_t nwords) { check(ctx_, rtr_remove_points(ctx_, words, nwords)); });
+        clearSelection();  // (also when nothing was selected)
+    }
+    // The keep mask becomes everything but the selection (a mask in force is replaced); the selection stays.
+    void hideSelected() {
+        with_complement([&](const uint32_t* words, uint64_t nwords) { check(ctx_, rtr_set_point_keep(ctx_, words, nwords)); });
+    }
+    // Moves the selected vertices by M (see transformPoints); the selection stays, naming the same vertices.
+    void transformSelected(const double M[16]) {
+        if (!(M[12] == 0.0 && M[13] == 0.0 && M[14] == 0.0 && M[15] == 1.0))
+            throw std::invalid_argument("transformSelected: the bottom row of M must be exactly 0 0 0 1");
+        if (!has_selection()) return;
+        float m[12];
+        for (int i = 0; i < 12; ++i) m[i] = (float)M[i];
+        void* p = nullptr;
+        size_t bytes = 0;
+        check(ctx_, rtr_device_buffer(ctx_, RTR_BUF_SELECTION, &p, &bytes));
+        check(ctx_, rtr_transform_points(ctx_, m, static_cast<const uint32_t*>(p), bytes / 4));
+    }
+
     // Renders the frame (computeRGBD / computeFilteredRGBD without host copies) and returns, per pixel (row-major
     // H x W), the vertex index of the point it shows, -1 for none (empty or prefiltered-away pixels).
     template <class Calibration, class Extrinsics>
@@ -326,6 +398,29 @@ public:
     }
 
 private:
+    bool has_selection() const {
+        int set = 0;
+        check(ctx_, rtr_get_option(ctx_, "selection", &set));
+        return set != 0;
+    }
+    // fn(device words of everything but the selection): inverted on the device (RTR_SELECT_TOGGLE) and back
+    template <class Fn>
+    void with_complement(Fn fn) {
+        if (!has_selection())  // (none yet: an empty one)
+            check(ctx_, rtr_select_points(ctx_, 0, nullptr, nullptr, nullptr, RTR_SELECT_SUBTRACT, nullptr));
+        check(ctx_, rtr_select_points(ctx_, 0, nullptr, nullptr, nullptr, RTR_SELECT_TOGGLE, nullptr));
+        void* p = nullptr;
+        size_t bytes = 0;
+        check(ctx_, rtr_device_buffer(ctx_, RTR_BUF_SELECTION, &p, &bytes));
+        try {
+            fn(static_cast<const uint32_t*>(p), (uint64_t)(bytes / 4));
+        } catch (...) {
+            if (has_selection()) rtr_select_points(ctx_, 0, nullptr, nullptr, nullptr, RTR_SELECT_TOGGLE, nullptr);
+            throw;
+        }
+        if (has_selection())  // (a removal drops it)
+            check(ctx_, rtr_select_points(ctx_, 0, nullptr, nullptr, nullptr, RTR_SELECT_TOGGLE, nullptr));
+    }
     template <class Calibration, class Extrinsics>
     static void projection(const Calibration& calibration, const Extrinsics& extrinsics, float P[16]) {
         double K[9], E[16];

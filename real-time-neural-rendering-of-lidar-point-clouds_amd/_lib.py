@@ -24,13 +24,18 @@ SYMBOLS = [
     "rtr_device_count", "rtr_p2p_export", "rtr_p2p_open", "rtr_p2p_close", "rtr_p2p_min_depth", "rtr_p2p_sum_resolve", "rtr_p2p_status",
     "rtr_p2p_render", "rtr_frame_stats", "rtr_get_option", "rtr_host_output_buffers", "rtr_project_async", "rtr_wait",
     "rtr_p2p_render_owned", "rtr_point_pass", "rtr_render_views", "rtr_set_clip_planes", "rtr_get_clip_planes",
-    "rtr_set_point_keep", "rtr_append_points", "rtr_remove_points", "rtr_transform_points",
+    "rtr_set_point_keep", "rtr_append_points", "rtr_remove_points", "rtr_transform_points", "rtr_select_points",
+    "rtr_clear_selection",
 ]
 
 RTR_OK, RTR_ERR_INVALID, RTR_ERR_HIP, RTR_ERR_NO_OUTPUT, RTR_ERR_UNSUPPORTED, RTR_ERR_INTERNAL = 0, -1, -2, -3, -4, -5
 BUF_DEPTH, BUF_ACCUM, BUF_IMAGE, BUF_TENSOR, BUF_MASK, BUF_MINMAX, BUF_POINT_ID, BUF_VISIBLE = range(8)
 BUF_VIEW_DEPTH, BUF_VIEW_IMAGE, BUF_VIEW_TENSOR, BUF_VIEW_MINMAX = range(8, 12)  # the last rtr_render_views batch
 BUF_POINT_KEEP = 12  # the keep mask in force (rtr_set_point_keep), upload order
+BUF_SELECTION = 13  # the selection (rtr_select_points), upload order
+SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_INTERSECT = range(4)  # rtr_select_points `op` ...
+SELECT_OUTSIDE = 4  # ... the flag OR-ed into it: hit = not inside ...
+SELECT_TOGGLE = 8  # ... and sel ^= hit (with no region: inverts the selection)
 MAX_VIEWS = 8  # RTR_MAX_VIEWS
 MAX_CLIP_PLANES = 8  # RTR_MAX_CLIP_PLANES
 POINTS_IDS, POINTS_VISIBLE = 1, 2  # rtr_point_pass `what` bits
@@ -133,6 +138,8 @@ def lib():
     L.rtr_set_clip_planes.argtypes = [vp, i32, vp]
     L.rtr_get_clip_planes.argtypes = [vp, C.POINTER(i32), vp]
     L.rtr_set_point_keep.argtypes = [vp, vp, C.c_uint64]
+    L.rtr_select_points.argtypes = [vp, i32, vp, vp, vp, i32, vp]
+    L.rtr_clear_selection.argtypes = [vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rtr_last_error", "rtr_default_params"):

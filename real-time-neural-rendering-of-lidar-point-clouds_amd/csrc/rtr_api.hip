@@ -132,6 +132,11 @@ struct rtr_ctx {
     uint64_t pp_vis_words = 0;
     bool pp_vis_current = false;  // the mask was computed for the resident cloud
     hipEvent_t pp_done = nullptr;  // recorded behind the last point pass
+    // the selection (rtr_select_points; sel null: none): upload-order words, 8 per 256-point chunk of the cloud it was made
+    // for ((n + 31) / 32 of them are the buffer), and the four device words a call with `stats` counts into.  Dropped by
+    // everything that renumbers upload indices
+    uint32_t *sel = nullptr;
+    uint64_t *sel_stats = nullptr;
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
     int opt_grid = rtr::kDefaultPointGrid;  // workgroups of the point kernels
 
@@ -402,8 +407,15 @@ void free_keep(rtr_ctx *c) {
     dfree(c->keep_up); dfree(c->keep_res); dfree(c->keep_sum);
 }
 
+void free_select(rtr_ctx *c) {
+    if (!c->sel) return;
+    (void)sync_streams(c);  // (a selection in flight may still write it)
+    dfree(c->sel); dfree(c->sel_stats);
+}
+
 void free_cloud(rtr_ctx *c) {
     free_keep(c);
+    free_select(c);
     dfree(c->x); dfree(c->y); dfree(c->z); dfree(c->rgba); dfree(c->bounds); dfree(c->spread); dfree(c->perm);
     dfree(c->pp_vis);
     c->pp_vis_words = 0;
@@ -564,6 +576,7 @@ int alloc_cloud(rtr_ctx *c, uint64_t n) {
         reset_pool_sizing(c->frame);
     }
     free_keep(c);  // (a new cloud: no mask)
+    free_select(c);  // (... and no selection)
     c->n = n;
     ++c->cloud_seq;
     c->list_valid = false;
@@ -1011,6 +1024,7 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     if (!strcmp(key, "mode")) *value = c->opt_mode;
     else if (!strcmp(key, "auto_reorder")) *value = c->opt_auto_reorder;
     else if (!strcmp(key, "reordered")) *value = c->reordered ? 1 : 0;
+    else if (!strcmp(key, "selection")) *value = c->sel ? 1 : 0;  // a selection exists (rtr_select_points)
     else if (!strcmp(key, "point_keep")) *value = c->keep_up ? 1 : 0;  // a keep mask is set (rtr_set_point_keep)  // the resident cloud was sorted by the library
     else if (!strcmp(key, "order_ratio_ppm")) *value = (int)(c->order_ratio * 1e6f);  // chunk / cloud diagonal as uploaded
     else if (!strcmp(key, "cull")) *value = c->opt_cull;
@@ -1031,7 +1045,8 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
         const uint64_t nchunks = ((c->cap / 4) + 63) / 64;
         uint64_t b = (c->x ? 12 * c->cap : 0) + (c->rgba ? 4 * c->cap : 0) + nchunks * 28 +
                      (c->pk_hdr ? c->pk_bytes + (c->pk_units_cap - c->pk_units) * 32 + 64 : 0) +
-                     (c->perm ? 4 * c->cap : 0) + (c->keep_up ? (c->n + 31) / 32 * 4 + nchunks * 33 + 4 : 0);
+                     (c->perm ? 4 * c->cap : 0) + (c->keep_up ? (c->n + 31) / 32 * 4 + nchunks * 33 + 4 : 0) +
+                     (c->sel ? std::max<uint64_t>((c->n + 255) / 256, 1) * 32 + 32 : 0);
         const uint64_t npix = (uint64_t)c->W * c->H;
         for (const auto *t : {&c->frame, &c->views}) {
             for (const auto &f : t->fs) {
@@ -1685,6 +1700,7 @@ int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
     }
     if (c->keep_up) { buf.swap_in(c->keep_up, up1); buf.swap_in(c->keep_res, res1); buf.swap_in(c->keep_sum, sum1); }
     c->n = n1;
+    free_select(c);  // (made for the old count)
     c->reordered = reordered1;
     ++c->cloud_seq;
     c->list_valid = false;
@@ -1759,7 +1775,8 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = launch_check(c, "remove count")) return rc;
     const uint64_t n1 = head[1], c0 = head[0] < nch0 ? head[0] : nch0;
-    if (n1 == n0) return RTR_OK;  // (every point stays: nothing changes)
+    free_select(c);  // (the caller's words are in kw: the selection's own buffer may have been passed)
+    if (n1 == n0) return RTR_OK;  // (every point stays: nothing else changes)
     if (n1 == 0) {  // (no point stays: the context of an upload of 0 points)
         // (its 4-point arrays are allocated before the cloud is freed: a failed allocation leaves the cloud as it was;
         // the upload then finds them and allocates nothing)
@@ -1917,6 +1934,7 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
         c->pp_vis_words = 0;
     }
     c->n = n1;
+    free_select(c);  // (the upload indices were renumbered)
     ++c->cloud_seq;
     c->list_valid = false;
     c->jr.frame.count = 0;
@@ -2856,6 +2874,74 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
     return RTR_OK;
 }
 
+// ---- selection (rtr.h, section 6f) ----------------------------------------------------
+// One sweep over the resident coordinates on the context's stream (rtr::launch_select), nothing else read or written:
+// the cloud's own planes and mask, the frames, their journal and the point pass's buffers stay as they are.
+int rtr_select_points(rtr_ctx *c, int plane_count, const float *planes, const float *P, const int rect[4], int op,
+                      uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, c->cap > 0, "rtr_select_points: no cloud");
+    NEED(c, plane_count >= 0 && plane_count <= RTR_MAX_CLIP_PLANES, "rtr_select_points: plane_count outside 0..RTR_MAX_CLIP_PLANES");
+    NEED(c, plane_count == 0 || planes != nullptr, "rtr_select_points: planes is NULL");
+    rtr::Clip clip{};
+    for (int j = 0; j < plane_count; ++j) {
+        for (int k = 0; k < 4; ++k) {
+            NEED(c, std::isfinite(planes[4 * j + k]), "rtr_select_points: a coefficient is not finite");
+            clip.p[j][k] = planes[4 * j + k];
+        }
+        NEED(c, clip.p[j][0] != 0.f || clip.p[j][1] != 0.f || clip.p[j][2] != 0.f, "rtr_select_points: a = b = c = 0");
+    }
+    clip.count = plane_count;
+    if (P) {
+        NEED(c, c->W > 0 && c->H > 0, "rtr_select_points: a rectangle needs a resolution (rtr_set_resolution)");
+        NEED(c, rect != nullptr, "rtr_select_points: rect is NULL");
+        NEED(c, 0 <= rect[0] && rect[0] < rect[2] && rect[2] <= c->W && 0 <= rect[1] && rect[1] < rect[3] && rect[3] <= c->H,
+             "rtr_select_points: the rectangle must satisfy 0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H");
+    }
+    const int base = op & ~RTR_SELECT_OUTSIDE;
+    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_points: unknown op");
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    NEED(c, !c->reordered || c->perm,
+         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be formed: set "
+         "point_ids = 1 before the upload (or upload with auto_reorder = 0)");
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t words = std::max<uint64_t>((c->n + 255) / 256, 1) * 8;  // (8 per 256-point chunk: whole-chunk stores)
+    if (!c->sel) {  // (a selection that does not exist yet is empty)
+        struct Buf {  // freed on every exit path unless taken
+            void *p = nullptr;
+            ~Buf() { if (p) (void)hipFree(p); }
+        } w, st;
+        HIP_TRY(c, hipMalloc(&w.p, words * 4));
+        HIP_TRY(c, hipMalloc(&st.p, 4 * sizeof(uint64_t)));
+        HIP_TRY(c, hipMemsetAsync(w.p, 0, words * 4, s));
+        c->sel = (uint32_t *)w.p, c->sel_stats = (uint64_t *)st.p, w.p = st.p = nullptr;
+    }
+    const uint32_t *perm = c->reordered ? c->perm : nullptr;
+    if (perm && base == RTR_SELECT_REPLACE) HIP_TRY(c, hipMemsetAsync(c->sel, 0, words * 4, s));
+    if (stats) HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
+    rtr::Proj proj{};
+    if (P) proj = make_proj(P);
+    rtr::launch_select(s, cloud_of(c), c->bounds, clip, P ? &proj : nullptr, c->W, c->H, rect, base, (op & RTR_SELECT_OUTSIDE) != 0,
+                       c->sel, perm, stats ? c->sel_stats : nullptr);
+    if (int rc = launch_check(c, "select")) return rc;
+    if (!stats) return RTR_OK;
+    rtr::launch_select_count(s, c->sel, c->n, c->sel_stats);
+    if (int rc = launch_check(c, "select count")) return rc;
+    uint64_t out[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, sizeof out, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+int rtr_clear_selection(rtr_ctx *c) {
+    if (!c) return RTR_ERR_INVALID;
+    DevGuard g(c->device);
+    free_select(c);
+    return RTR_OK;
+}
+
 // ---- several views -----------------------------------------------------------------
 // rtr_render_views (rtr.h, section 6c).  Binned batches: ONE point-kernel launch appends every view's points to that
 // view's tile store (rtr::launch_project_bin_views), then per view a lean tile launch (and the prefilter) writes the
@@ -2980,7 +3066,7 @@ int rtr_render_views(rtr_ctx *c, int count, const float *P, int with_filter) {
 int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
     if (!c) return RTR_ERR_INVALID;
     NEED(c, ptr != nullptr, "dev_ptr is NULL");
-    if (which != RTR_BUF_MINMAX && which != RTR_BUF_VIEW_MINMAX && which != RTR_BUF_POINT_KEEP)
+    if (which != RTR_BUF_MINMAX && which != RTR_BUF_VIEW_MINMAX && which != RTR_BUF_POINT_KEEP && which != RTR_BUF_SELECTION)
         if (int rc = check_frame(c)) return rc;
     size_t npix = (size_t)c->W * c->H, b = 0;
     void *p = nullptr;
@@ -3009,6 +3095,9 @@ int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
         case RTR_BUF_POINT_KEEP:
             NEED(c, c->keep_up != nullptr, "RTR_BUF_POINT_KEEP: no keep mask is set (rtr_set_point_keep)");
             p = c->keep_up; b = (size_t)((c->n + 31) / 32) * 4; break;
+        case RTR_BUF_SELECTION:
+            NEED(c, c->sel != nullptr, "RTR_BUF_SELECTION: no selection (rtr_select_points)");
+            p = c->sel; b = (size_t)((c->n + 31) / 32) * 4; break;
         default: return fail(c, RTR_ERR_INVALID, "unknown buffer id %d", which);
     }
     *ptr = p;

@@ -28,6 +28,20 @@ RTR_HD FrustumPlanes frustum_planes(const float m[12], float fW, float fH) {
     }
     return f;
 }
+// The same five half-spaces for the pixels of a screen rectangle x0 <= px < x1, y0 <= py < y1 (rtr_select_points): r.z >= 0,
+// r.x - (x0 - 1) r.z >= 0, x1 r.z - r.x >= 0 and the same in y -- one pixel of slack on each side, as above (a point
+// that lands in column px >= x0 has a quotient >= x0 - 1/2 before rintf).  frustum_planes(m, W, H) is rect_planes(m, 0,
+// 0, W, H) bit for bit: 1 - 0 is the 1 of its table.
+RTR_HD FrustumPlanes rect_planes(const float m[12], float x0, float y0, float x1, float y1) {
+    FrustumPlanes f;
+    const float comb[5][3] = {{0.f, 0.f, 1.f}, {1.f, 0.f, 1.f - x0}, {-1.f, 0.f, x1}, {0.f, 1.f, 1.f - y0}, {0.f, -1.f, y1}};
+    for (int q = 0; q < 5; ++q) {
+        for (int k = 0; k < 4; ++k) f.pl[q][k] = comb[q][0] * m[k] + comb[q][1] * m[4 + k] + comb[q][2] * m[8 + k];
+        for (int k = 0; k < 3; ++k) f.plm[q][k] = __builtin_fabsf(comb[q][0] * m[k]) + __builtin_fabsf(comb[q][1] * m[4 + k]) + __builtin_fabsf(comb[q][2] * m[8 + k]);
+        f.pld[q] = __builtin_fabsf(comb[q][0] * m[3]) + __builtin_fabsf(comb[q][1] * m[7]) + __builtin_fabsf(comb[q][2] * m[11]);
+    }
+    return f;
+}
 // The box [lo, hi] lies entirely on the wrong side of one half-space by more than 1e-4 x the magnitude of the terms
 // involved: no point in it can pass the exact test (see "CULL" in rtr_kernels.hip).  NaN / inf boxes never do.
 RTR_HD bool box_outside(const FrustumPlanes &f, const float lo[3], const float hi[3]) {
@@ -110,6 +124,34 @@ RTR_HD bool clip_box_outside(const Clip &c, const float lo[3], const float hi[3]
         culled = culled || (v < -1e-4f * m - 0x1p-126f);
     }
     return culled;
+}
+// The box [lo, hi] lies entirely on the kept side of EVERY clip plane: clip_keep keeps each point in it (rtr_select_points
+// sets a chunk's 256 bits without reading its coordinates; a frame could skip the per-point test the same way).  The
+// mirror image of clip_box_outside -- the SMALLEST value of a.p + d over the box, v = d + sum of min(a_k lo_k, a_k hi_k),
+// must exceed the same slack, 1e-4 m + 2^-126.  The error argument above carries over with the signs turned (u = 2^-24,
+// M the real value of m, p any point of the box):
+//   - the box arithmetic: its products round the real ones monotonically, so min(fl(a lo), fl(a hi)) <= fl(a p_k) <=
+//     a p_k + u |a p_k| + 2^-150; the three sums of those minima err by <= 3.01 u M, hence the real a.p + d >=
+//     v - 4.02 u M - 2^-148;
+//   - the point test: its computed value is >= (a.p + d) - 3.01 u T - 3 x 2^-150 with T <= M, so it is at least
+//     v - 7.1 u M - 2^-147, and the computed m is >= M (1 - 7.1 u);
+//   - acceptance needs v > 1e-4 m + 2^-126, more than 200 times that distance: the point test's value is > 0, the
+//     point is kept.
+// Only for boxes whose every point is a number: a packed chunk that has a box (chunk_box) holds no NaN.  NaN (a NaN
+// box end) compares false and an infinite end makes m infinite: neither is ever inside.  No plane: every box is inside.
+RTR_HD bool clip_box_inside(const Clip &c, const float lo[3], const float hi[3]) {
+    bool inside = true;
+    for (int j = 0; j < c.count; ++j) {
+        float v = c.p[j][3], m = __builtin_fabsf(c.p[j][3]);
+        for (int k = 0; k < 3; ++k) {
+            const float t0 = c.p[j][k] * lo[k], t1 = c.p[j][k] * hi[k];
+            v += t0 < t1 ? t0 : t1;
+            const float e0 = __builtin_fabsf(lo[k]), e1 = __builtin_fabsf(hi[k]);
+            m += __builtin_fabsf(c.p[j][k]) * (e0 > e1 ? e0 : e1);
+        }
+        inside = inside && (v > 1e-4f * m + 0x1p-126f);
+    }
+    return inside;
 }
 
 // ---- moving resident points (rtr_transform_points) ---------------------------------------------------------------

@@ -381,5 +381,16 @@ void launch_transform_window(hipStream_t s, const Cloud &c, const uint32_t *perm
                              const Affine &M, float *wx, float *wy, float *wz, bool in_place);
 // the block offsets hdr[2 c + 1].xy of chunks [c_from, c_to) move by delta units (the blocks behind a rebuilt window moved)
 void launch_shift_units(hipStream_t s, uint4 *hdr, uint64_t c_from, uint64_t c_to, int64_t delta);
+// rtr_select_points: sel (8 u32 per 256-point chunk, upload order, no bit set at or past n) := op(sel, hit) with
+// hit = inside or, invert, !inside for the points below n; inside = clip_keep over `clip` (the CALL's planes, not the
+// cloud's) and, P given, project_point landing on a pixel of rect {x0, y0, x1, y1}.  c: the resident cloud -- its packed
+// form when it has one, else its fp32 SoA with the chunk boxes `bounds`; the cloud's own clip planes and keep mask are
+// not read.  perm as for the point pass (with it and op REPLACE the caller clears sel first).  stats (device, may be
+// null): [1] / [2] / [3] += chunks decided outside / inside on their boxes / decoded.  op: 0 replace, 1 add, 2 subtract,
+// 3 intersect, 8 toggle.
+void launch_select(hipStream_t s, const Cloud &c, const float *bounds, const Clip &clip, const Proj *P, int W, int H,
+                   const int rect[4], int op, bool invert, uint32_t *sel, const uint32_t *perm, uint64_t *stats);
+// *out (device) += the set bits of sel, all 8 words of every chunk of n points
+void launch_select_count(hipStream_t s, const uint32_t *sel, uint64_t n, uint64_t *out);
 
 }  // namespace rtr

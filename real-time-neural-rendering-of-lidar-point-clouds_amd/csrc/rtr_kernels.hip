@@ -4897,4 +4897,267 @@ void launch_shift_units(hipStream_t s, uint4 *hdr, uint64_t c_from, uint64_t c_t
                        (long long)delta);
 }
 
+// ---------------------------------------------------------------------------------
+// Selection (rtr_select_points, rtr.h section 6f): which points lie inside a region -- clip_keep over the call's planes
+// and, RECT, the frame's own project_point landing on a pixel of the rectangle -- as upload-order bit words combined
+// with the selection so far by `op`.  The point pass's skeleton: one wave per 256-point chunk (lane l: points 4 l ..
+// 4 l + 3), chunks dealt round robin, PACKED 64 headers tested per wave step and only the survivors decoded.  The
+// chunk decision has three outcomes:
+//   outside: the box lies beyond one plane (clip_box_outside) or beyond one half-space of the rectangle (rect_planes +
+//            box_outside): no point of it is inside;
+//   inside:  planes only -- the box lies within every plane (clip_box_inside): every point of it is inside (a packed
+//            chunk that has a box holds no NaN).  No plane and no rectangle: every chunk, boxed or not;
+//   mixed:   decoded and tested point by point.
+// Not PACKED the boxes are k_chunk_bounds', whose fminf / fmaxf skip NaN coordinates: a NaN may hide behind a finite
+// box, so such a chunk is classed outside (a NaN point is not inside either) but never inside on its box.
+// hit = inside, or, `invert`, !inside for the points below n; the points at or past n are never hit.
+// Writing, PERM = false: a decoded chunk's 256 hits are four ballots interleaved into eight words (lanes 0..7, as the
+// point pass) and combined with the old words by plain loads and stores -- each chunk's words belong to one wave.  An
+// undecoded chunk's hits are all alike: the header lane itself stores its eight words, and only where `op` changes
+// them (ADD / SUBTRACT / TOGGLE of nothing and INTERSECT with everything leave the old words; TOGGLE of everything
+// flips them; the rest are constants: the old words hold no bit past n, so nothing is loaded).
+// PERM: bits go through perm[resident index] with atomicOr (REPLACE -- the caller cleared the words -- and ADD),
+// atomicAnd (SUBTRACT: the hits; INTERSECT: the misses) or atomicXor (TOGGLE); an undecoded chunk reads its 256 perm entries when `op` has
+// something to change, never its coordinates.
+// stats (null: not requested): [1] / [2] / [3] += chunks outside / inside / decoded, folded per workgroup in LDS: three
+// atomics per workgroup ([0] is k_select_count's).
+constexpr int kSelReplace = 0, kSelAdd = 1, kSelSubtract = 2, kSelIntersect = 3, kSelToggle = 8;  // (RTR_SELECT_*)
+struct SelectArgs {
+    const float4 *x4, *y4, *z4;  // fp32 SoA (not PACKED) ...
+    const float *bounds;         // ... and its chunk boxes (k_chunk_bounds)
+    PackedXyz pk;                // packed form (PACKED)
+    uint64_t n;
+    uint32_t *sel;               // 8 words per chunk
+    const uint32_t *perm;        // resident index -> upload index (PERM)
+    unsigned long long *stats;
+    int op, invert;
+    int x0, y0, x1, y1;          // RECT
+};
+__device__ __forceinline__ uint32_t select_word_mask(uint64_t n, uint64_t c, uint32_t j) {  // the bits of word j of chunk c below n
+    const uint64_t first = c * 256u + 32u * j;
+    if (first >= n) return 0u;
+    const uint64_t left = n - first;
+    return left >= 32u ? 0xFFFFFFFFu : (1u << (uint32_t)left) - 1u;
+}
+// the eight words of a chunk whose points below n are all hit / all missed (one lane; PERM = false)
+__device__ __forceinline__ void select_store_uniform(const SelectArgs &a, uint64_t c, bool hit) {
+    if (hit ? a.op == kSelIntersect : (a.op == kSelAdd || a.op == kSelSubtract || a.op == kSelToggle)) return;  // (the old words stay)
+    uint4 *w = reinterpret_cast<uint4 *>(a.sel + 8 * c);
+    if (a.op == kSelToggle) {  // (of everything below n: the only case that reads the old words)
+        const uint4 o0 = w[0], o1 = w[1];
+        w[0] = make_uint4(o0.x ^ select_word_mask(a.n, c, 0), o0.y ^ select_word_mask(a.n, c, 1), o0.z ^ select_word_mask(a.n, c, 2), o0.w ^ select_word_mask(a.n, c, 3));
+        w[1] = make_uint4(o1.x ^ select_word_mask(a.n, c, 4), o1.y ^ select_word_mask(a.n, c, 5), o1.z ^ select_word_mask(a.n, c, 6), o1.w ^ select_word_mask(a.n, c, 7));
+    } else if (!hit || a.op == kSelSubtract) {  // (REPLACE / INTERSECT with nothing, SUBTRACT of everything)
+        w[0] = make_uint4(0u, 0u, 0u, 0u);
+        w[1] = make_uint4(0u, 0u, 0u, 0u);
+    } else {  // (REPLACE by / ADD of everything below n)
+        w[0] = make_uint4(select_word_mask(a.n, c, 0), select_word_mask(a.n, c, 1), select_word_mask(a.n, c, 2), select_word_mask(a.n, c, 3));
+        w[1] = make_uint4(select_word_mask(a.n, c, 4), select_word_mask(a.n, c, 5), select_word_mask(a.n, c, 6), select_word_mask(a.n, c, 7));
+    }
+}
+// the wave writes the hits of chunk c (hit[k]: point 4 lane + k, already false at or past n)
+template <bool PERM>
+__device__ __forceinline__ void select_write(const SelectArgs &a, uint64_t c, int lane, const bool hit[4]) {
+    if (PERM) {
+        const uint64_t i0 = c * 256u + 4u * (uint64_t)lane;
+        if (i0 < a.n) {  // (perm holds whole quads: its arrays are padded to a multiple of 4 points)
+            const uint4 q = *reinterpret_cast<const uint4 *>(a.perm + i0);
+            const uint32_t u[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (i0 + k >= a.n) continue;
+                const uint32_t bit = 1u << (u[k] & 31u);
+                if (a.op == kSelIntersect) {
+                    if (!hit[k]) atomicAnd(a.sel + (u[k] >> 5), ~bit);
+                } else if (hit[k]) {
+                    if (a.op == kSelSubtract) atomicAnd(a.sel + (u[k] >> 5), ~bit);
+                    else if (a.op == kSelToggle) atomicXor(a.sel + (u[k] >> 5), bit);
+                    else atomicOr(a.sel + (u[k] >> 5), bit);
+                }
+            }
+        }
+    } else {
+        // word j of the chunk = points 32 j .. 32 j + 31 = lanes 8 j .. 8 j + 7; point 4 l + k is bit l of ballot k
+        const unsigned long long b0 = __ballot(hit[0]), b1 = __ballot(hit[1]), b2 = __ballot(hit[2]), b3 = __ballot(hit[3]);
+        if (lane < 8) {
+            const int sh = 8 * lane;
+            const uint32_t h = spread_nibbles((uint32_t)(b0 >> sh)) | (spread_nibbles((uint32_t)(b1 >> sh)) << 1) |
+                               (spread_nibbles((uint32_t)(b2 >> sh)) << 2) | (spread_nibbles((uint32_t)(b3 >> sh)) << 3);
+            uint32_t *w = a.sel + 8 * c + lane;
+            if (a.op == kSelReplace) *w = h;
+            else {
+                const uint32_t old = *w;
+                *w = a.op == kSelAdd ? (old | h) : (a.op == kSelSubtract ? (old & ~h) : (a.op == kSelToggle ? (old ^ h) : (old & h)));
+            }
+        }
+    }
+}
+// a decoded chunk: the predicate per point
+template <bool PERM, bool RECT>
+__device__ __forceinline__ void select_chunk(const SelectArgs &a, const Clip &clip, const Proj &P, int W, int H, float fW, float fH,
+                                             uint64_t c, const float4 &X, const float4 &Y, const float4 &Z, int lane) {
+    const uint64_t i0 = c * 256u + 4u * (uint64_t)lane;
+    const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
+    bool hit[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        bool in = clip_keep(clip, xs[k], ys[k], zs[k]);
+        if (RECT) {
+            float d;
+            const int pix = project_point(P, xs[k], ys[k], zs[k], W, H, fW, fH, d);
+            const int py = pix >= 0 ? (int)((uint32_t)pix / (uint32_t)W) : -1, px = pix - py * W;
+            in = in && pix >= 0 && px >= a.x0 && px < a.x1 && py >= a.y0 && py < a.y1;
+        }
+        hit[k] = i0 + k < a.n && in != (a.invert != 0);
+    }
+    select_write<PERM>(a, c, lane, hit);
+}
+constexpr int kSelOutside = 0, kSelInside = 1, kSelMixed = 2;
+template <bool PACKED, bool PERM, bool RECT>
+__global__ __launch_bounds__(kBlock) void k_select(SelectArgs a, Clip clip, Proj P, int W, int H) {
+    __shared__ uint32_t s_cnt[3];
+    const float fW = (float)W, fH = (float)H;
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * kBlock) >> 6;
+    const uint64_t n4 = (a.n + 3) / 4, nchunks = (n4 + 63) / 64;
+    const bool every = !RECT && clip.count == 0;  // (no condition at all: every point, NaN included, is inside)
+    const bool invert = a.invert != 0;
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    FrustumPlanes rpl{};
+    if (RECT) rpl = rect_planes(P.m, (float)a.x0, (float)a.y0, (float)a.x1, (float)a.y1);
+    uint32_t cnt[3] = {0u, 0u, 0u};  // (wave-uniform)
+    if (!PACKED) {
+        for (uint64_t c = wave; c < nchunks; c += nwaves) {  // (wave-uniform)
+            int state = every ? kSelInside : kSelMixed;
+            if (!every) {
+                const float *b = a.bounds + 6 * c;
+                const float lo[3] = {b[0], b[1], b[2]}, hi[3] = {b[3], b[4], b[5]};
+                if (clip_box_outside(clip, lo, hi) || (RECT && box_outside(rpl, lo, hi))) state = kSelOutside;
+            }
+            cnt[kSelOutside] += state == kSelOutside, cnt[kSelInside] += state == kSelInside, cnt[kSelMixed] += state == kSelMixed;
+            const bool hit_u = (state == kSelInside) != invert;
+            if (state != kSelMixed && !PERM) {
+                if (lane == 0) select_store_uniform(a, c, hit_u);
+                continue;
+            }
+            if (state != kSelMixed) {
+                if (a.op == kSelIntersect ? !hit_u : hit_u) {
+                    const uint64_t i0 = c * 256u + 4u * (uint64_t)lane;
+                    const bool hit[4] = {hit_u && i0 < a.n, hit_u && i0 + 1 < a.n, hit_u && i0 + 2 < a.n, hit_u && i0 + 3 < a.n};
+                    select_write<PERM>(a, c, lane, hit);
+                }
+                continue;
+            }
+            const uint64_t i = c * 64u + (uint64_t)lane, ic = i < n4 ? i : n4 - 1u;
+            const float4 X = ld_stream(a.x4 + ic), Y = ld_stream(a.y4 + ic), Z = ld_stream(a.z4 + ic);
+            select_chunk<PERM, RECT>(a, clip, P, W, H, fW, fH, c, X, Y, Z, lane);
+        }
+    } else {
+        for (uint64_t j0 = 0; wave + nwaves * j0 < nchunks; j0 += 64u) {  // (wave-uniform)
+            const uint64_t chunk = wave + nwaves * (j0 + (uint64_t)lane);
+            const bool valid = chunk < nchunks;
+            int state = kSelMixed;
+            if (valid) {
+                if (every) state = kSelInside;
+                else {
+                    const uint4 h0 = a.pk.hdr[2 * chunk];
+                    float lo[3], hi[3];
+                    if (chunk_box(h0.x, h0.y, h0.z, h0.w, lo, hi)) {
+                        if (clip_box_outside(clip, lo, hi) || (RECT && box_outside(rpl, lo, hi))) state = kSelOutside;
+                        else if (!RECT && clip_box_inside(clip, lo, hi)) state = kSelInside;
+                    }
+                }
+            }
+            const bool hit_u = (state == kSelInside) != invert;
+            bool work = valid && state == kSelMixed;  // (the chunks that need the whole wave)
+            if (valid && state != kSelMixed) {
+                if (!PERM) select_store_uniform(a, chunk, hit_u);
+                else work = a.op == kSelIntersect ? !hit_u : hit_u;
+            }
+            cnt[kSelOutside] += (uint32_t)__popcll(__ballot(valid && state == kSelOutside));
+            cnt[kSelInside] += (uint32_t)__popcll(__ballot(valid && state == kSelInside));
+            cnt[kSelMixed] += (uint32_t)__popcll(__ballot(valid && state == kSelMixed));
+            const unsigned long long mixed = __ballot(valid && state == kSelMixed);
+            unsigned long long mask = __ballot(work);
+            while (mask) {
+                const int l = __ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const uint64_t cc = wave + nwaves * (j0 + (uint64_t)l);
+                if (PERM && !((mixed >> l) & 1ull)) {  // (an undecoded chunk through the permutation: `work` says all hit / all missed)
+                    const bool hu = a.op != kSelIntersect;
+                    const uint64_t i0 = cc * 256u + 4u * (uint64_t)lane;
+                    const bool hit[4] = {hu && i0 < a.n, hu && i0 + 1 < a.n, hu && i0 + 2 < a.n, hu && i0 + 3 < a.n};
+                    select_write<PERM>(a, cc, lane, hit);
+                    continue;
+                }
+                const uint4 h0 = a.pk.hdr[2 * cc], h1 = a.pk.hdr[2 * cc + 1];
+                const ChunkRawA raw_a = load_chunk_a(a.pk.planes, h0, h1, lane);
+                const ChunkRaw raw = load_chunk_b(a.pk.planes_b, h0, h1, lane);
+                float4 X, Y, Z;
+                unpack_chunk(raw_a, raw, h0.w, h0.x, h0.y, h0.z, X, Y, Z, lane);
+                select_chunk<PERM, RECT>(a, clip, P, W, H, fW, fH, cc, X, Y, Z, lane);
+            }
+        }
+    }
+    if (a.stats) {  // (wave-uniform)
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (cnt[k]) atomicAdd(&s_cnt[k], cnt[k]);
+        }
+        __syncthreads();
+        if (threadIdx.x < 3 && s_cnt[threadIdx.x]) atomicAdd(a.stats + 1 + threadIdx.x, (unsigned long long)s_cnt[threadIdx.x]);
+    }
+}
+// *out += the set bits of `words` (16-byte units; the bits past n are clear): one atomic per workgroup
+__global__ __launch_bounds__(kBlock) void k_select_count(const uint4 *__restrict__ words, uint64_t n16, unsigned long long *__restrict__ out) {
+    __shared__ uint32_t s_sum;
+    if (threadIdx.x == 0) s_sum = 0u;
+    __syncthreads();
+    uint32_t mine = 0u;  // (a thread sees at most 2^32 / 128 units' bits)
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n16; i += (uint64_t)gridDim.x * kBlock) {
+        const uint4 q = words[i];
+        mine += (uint32_t)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_sum, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_sum) atomicAdd(out, (unsigned long long)s_sum);
+}
+void launch_select(hipStream_t s, const Cloud &c, const float *bounds, const Clip &clip, const Proj *P, int W, int H,
+                   const int rect[4], int op, bool invert, uint32_t *sel, const uint32_t *perm, uint64_t *stats) {
+    const uint64_t n4 = (c.n + 3) / 4, nchunks = (n4 + 63) / 64;
+    if (nchunks == 0) return;
+    const bool packed = c.pk.hdr != nullptr;
+    SelectArgs a{(const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, bounds, c.pk, c.n, sel, perm,
+                 (unsigned long long *)stats, op, invert ? 1 : 0, 0, 0, 0, 0};
+    Proj proj{};
+    if (P) proj = *P, a.x0 = rect[0], a.y0 = rect[1], a.x1 = rect[2], a.y1 = rect[3];
+    const uint64_t blocks = (nchunks + 3) / 4;  // (up to 8 waves per CU, every chunk dealt round robin: the point pass's grid)
+    const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048)), block(kBlock);
+    auto go = [&](auto pk, auto pm, auto rc) {  // (PACKED, PERM, RECT)
+        hipLaunchKernelGGL((k_select<decltype(pk)::value, decltype(pm)::value, decltype(rc)::value>), grid, block, 0, s, a, clip,
+                           proj, W, H);
+    };
+    auto with_rect = [&](auto pk, auto pm) {
+        if (P) go(pk, pm, std::true_type{}); else go(pk, pm, std::false_type{});
+    };
+    const std::true_type on;
+    const std::false_type off;
+    if (packed && perm) with_rect(on, on);
+    else if (packed) with_rect(on, off);
+    else if (perm) with_rect(off, on);
+    else with_rect(off, off);
+}
+void launch_select_count(hipStream_t s, const uint32_t *sel, uint64_t n, uint64_t *out) {
+    const uint64_t n16 = ((n + 255) / 256) * 2;
+    if (n16 == 0) return;
+    const uint64_t blocks = (n16 + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_select_count, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(kBlock), 0, s, (const uint4 *)sel, n16,
+                       (unsigned long long *)out);
+}
+
 }  // namespace rtr

@@ -309,6 +309,46 @@ class Projector:
         words = self.download(L.BUF_POINT_KEEP)
         return np.unpackbits(words.astype("<u4").view(np.uint8), bitorder="little")[:self.num_points].astype(bool)
 
+    # -- selection (rtr.h section 6f)
+    _SELECT_OPS = {"replace": L.SELECT_REPLACE, "add": L.SELECT_ADD, "subtract": L.SELECT_SUBTRACT,
+                   "intersect": L.SELECT_INTERSECT, "toggle": L.SELECT_TOGGLE}
+
+    def select_points(self, planes=None, P=None, rect=None, op="replace", outside=False, stats=True):
+        """Selects on the device the points inside a region and combines them with the selection so far (BUF_SELECTION,
+        upload-order words as set_point_keep / remove_points / transform_points take them).  planes: (k, 4) half-spaces
+        {a, b, c, d} with the contract of set_clip_planes (None: no plane); P with rect = (x0, y0, x1, y1): also the
+        points a frame with P splats onto a pixel x0 <= px < x1, y0 <= py < y1 at the context's resolution.  Neither:
+        every point.  op: "replace", "add", "subtract", "intersect" or "toggle" (or the SELECT_* value); outside: the
+        points NOT inside are the hits.  The context's own clip planes and keep mask are not looked at.
+        stats: waits and returns (selected points after op, chunks decided outside on their boxes, chunks decided inside,
+        chunks decoded); False: queued like point_pass, returns None."""
+        k, pl = 0, None
+        if planes is not None:
+            pl = np.ascontiguousarray(planes, dtype=np.float32)
+            if pl.size and (pl.ndim != 2 or pl.shape[1] != 4):
+                raise ValueError("planes must have shape (k, 4)")
+            k = pl.shape[0] if pl.size else 0
+        if (P is None) != (rect is None):
+            raise ValueError("P and rect come together")
+        Pm = None if P is None else self._P(P)
+        rc4 = None if rect is None else np.ascontiguousarray(rect, dtype=np.int32).reshape(4)
+        code = self._SELECT_OPS[op] if isinstance(op, str) else int(op)
+        if outside:
+            code |= L.SELECT_OUTSIDE
+        out = np.zeros(4, np.uint64) if stats else None
+        self._chk(self._lib.rtr_select_points(self._ctx, k, _vp(pl) if k else None, _vp(Pm), _vp(rc4), code, _vp(out)))
+        return tuple(int(v) for v in out) if stats else None
+
+    def selection(self):
+        """The selection as a DeviceBuffer of upload-order words (pass it to remove_points, transform_points,
+        set_point_keep or torch.as_tensor), or None when there is none."""
+        if not self.get_option("selection"):
+            return None
+        return self.device_buffer(L.BUF_SELECTION)
+
+    def clear_selection(self):
+        self._chk(self._lib.rtr_clear_selection(self._ctx))
+
     # -- point pass (rtr.h section 6b)
     def point_pass(self, P, ids=True, visible=True):
         """Per-pixel point IDs (BUF_POINT_ID: upload index, NO_POINT for none) and / or the per-point visibility
@@ -353,11 +393,12 @@ class Projector:
             L.BUF_VIEW_IMAGE: (np.uint8, "|u1", lambda w, h, k: (k, h, w, 3)),
             L.BUF_VIEW_TENSOR: (np.uint16, "<f2", lambda w, h, k: (k, 5, h, w)),
             L.BUF_VIEW_MINMAX: (np.uint32, "<u4", lambda w, h, k: (k, 2)),
-            L.BUF_POINT_KEEP: (np.uint32, "<u4", lambda w, h, n: ((n + 31) // 32,))}
+            L.BUF_POINT_KEEP: (np.uint32, "<u4", lambda w, h, n: ((n + 31) // 32,)),
+            L.BUF_SELECTION: (np.uint32, "<u4", lambda w, h, n: ((n + 31) // 32,))}
 
     def _shape(self, which):
         shp = self._BUF[which][2]
-        if which in (L.BUF_VISIBLE, L.BUF_POINT_KEEP):
+        if which in (L.BUF_VISIBLE, L.BUF_POINT_KEEP, L.BUF_SELECTION):
             return shp(self.W, self.H, self.num_points)
         if L.BUF_VIEW_DEPTH <= which <= L.BUF_VIEW_MINMAX:
             return shp(self.W, self.H, self.get_option("views"))
@@ -571,6 +612,63 @@ class ProjectCloud:
         sel = np.zeros(n, bool)
         sel[first:first + count] = True
         self._p.transform_points(m.reshape(3, 4), sel)
+
+    # -- selection (rtr.h section 6f): regions named on the device, then removed, hidden or moved without a host array
+    def selectPlanes(self, planes, op="replace", outside=False):
+        """Selects the uploaded vertices every half-space of `planes` ((k, 4), see Projector.select_points) keeps and
+        combines them with the selection so far by op ("replace", "add", "subtract", "intersect", "toggle"); outside:
+        the vertices NOT inside.  Returns the number selected afterwards.  Needs point_ids=True when the cloud may be
+        sorted; the clip planes and the keep mask in force play no part."""
+        return self._p.select_points(planes=planes, op=op, outside=outside)[0]
+
+    def selectBox(self, lo, hi, M=None, op="replace", outside=False):
+        """selectPlanes of the box lo <= q <= hi, q = M p (M: 4x4 world -> box; None: the world axes, exactly
+        lo <= p <= hi per axis, faces included).  See camera.clip_box_planes."""
+        return self.selectPlanes(clip_box_planes(lo, hi, M), op, outside)
+
+    def selectRect(self, calibration, extrinsics, x0, y0, x1, y1, op="replace"):
+        """Selects the vertices that computeRGBD with this calibration and pose splats onto a pixel x0 <= px < x1,
+        y0 <= py < y1, hidden behind others or not (a rubber band on the screen).  Returns the number selected."""
+        self._p.set_resolution(calibration.getWidth(), calibration.getHeight())
+        P = compose_projection(calibration.getIntrinsicsMatrix(), extrinsics)
+        return self._p.select_points(P=P, rect=(x0, y0, x1, y1), op=op)[0]
+
+    def selectedCount(self):
+        """The number of selected vertices (0 without a selection)."""
+        if not self._p.get_option("selection"):
+            return 0
+        return self._p.select_points(op="add", outside=True)[0]  # (adds the complement of every point: nothing)
+
+    def clearSelection(self):
+        self._p.clear_selection()
+
+    def _with_complement(self, fn):
+        """fn(the words of everything but the selection), the inversion done on the device (SELECT_TOGGLE)."""
+        if not self._p.get_option("selection"):
+            self._p.select_points(op="subtract", stats=False)  # (none yet: an empty one)
+        self._p.select_points(op="toggle", stats=False)
+        try:
+            fn(self._p.selection())
+        finally:
+            if self._p.get_option("selection"):  # (a removal drops it)
+                self._p.select_points(op="toggle", stats=False)
+
+    def removeSelected(self):
+        """Takes the selected vertices out of the resident cloud for good (see removePoints); the others are renumbered
+        and the selection is gone."""
+        self._with_complement(self._p.remove_points)
+        self._p.clear_selection()  # (also when nothing was selected)
+
+    def hideSelected(self):
+        """The keep mask becomes everything but the selection (a mask in force is replaced: add to the selection and
+        hide again to hide more); the selection stays."""
+        self._with_complement(self._p.set_point_keep)
+
+    def transformSelected(self, M):
+        """Moves the selected vertices by the affine transform M (see transformPoints); the selection stays, naming
+        the same vertices where they now lie."""
+        if self._p.get_option("selection"):
+            self._p.transform_points(_affine_rows(M).reshape(3, 4), self._p.selection())
 
     def commitPointKeep(self):
         """Removes the vertices the keep mask in force hides (see removePoints), then clears the mask: the frames stay
