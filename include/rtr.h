@@ -126,7 +126,11 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          option "cull") and streams only the chunks that may reach the frustum; the lane test and the exact
  *          arithmetic then run on those as before.  0 = every chunk through the stream (the loop structure
  *          of round 4, in a kernel instance of its own).  Same
- *          frame either way; no effect on unpacked clouds or with "cull" = 1.
+ *          frame either way; no effect on unpacked clouds or with "cull" = 1.  A chunk with an axis the packed
+ *          form cannot bound by a common prefix (mixed signs: every chunk on a coordinate plane) is tested on
+ *          a box word its header carries for that axis, written when the cloud is packed.  rtr_get_option:
+ *          "wide_chunks" (such chunks in the resident packed form) and "wide_chunks_boxed" (those of them that
+ *          carry the word: all but chunks holding a NaN or an infinity); both read-only, 0 for an unpacked cloud.
  *  "pack": the tile-binned point kernel reads the coordinates from a LOSSLESS packed form, built once after
  *          every upload / generation / sort (and at once for the resident cloud when the option is set): per
  *          256-point chunk and axis the fp32 bit patterns are a common prefix + the 0..25 (or 32) bits below it

@@ -1061,6 +1061,25 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "packed")) *value = c->pk_hdr ? 1 : 0;  // the point kernel reads the packed coordinates
     else if (!strcmp(key, "packed_millibytes_per_point"))         // its coordinate stream, headers included (12000 = raw)
         *value = c->pk_hdr && c->n ? (int)(c->pk_bytes * 1000 / c->n) : 12000;
+    else if (!strcmp(key, "wide_chunks") || !strcmp(key, "wide_chunks_boxed")) {
+        // chunks of the packed form with an axis of 32 bits / those of them whose header carries a box word (round 6).
+        // Counted over the resident headers when asked, so every edit path is covered by construction.
+        *value = 0;
+        if (c->pk_hdr && c->n) {
+            uint64_t *dev = nullptr, host[2] = {0, 0};
+            hipError_t e = hipMalloc((void **)&dev, sizeof host);
+            if (e == hipSuccess) e = hipMemsetAsync(dev, 0, sizeof host, c->stream);
+            if (e == hipSuccess) {
+                rtr::launch_wide_counts(c->stream, c->pk_hdr, (((uint64_t)c->n + 3) / 4 + 63) / 64, dev);
+                e = hipMemcpyAsync(host, dev, sizeof host, hipMemcpyDeviceToHost, c->stream);
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (dev) (void)hipFree(dev);
+            if (e != hipSuccess) return fail(c, RTR_ERR_HIP, "wide_chunks: %s", hipGetErrorString(e));
+            const uint64_t v = host[key[11] ? 1 : 0];
+            *value = v > 0x7FFFFFFFull ? 0x7FFFFFFF : (int)v;
+        }
+    }
     else if (!strcmp(key, "keep_accum")) *value = c->opt_keep_accum;
     else if (!strcmp(key, "split_threshold")) *value = c->opt_heavy;
     else if (!strcmp(key, "split_slice")) *value = c->opt_slice;

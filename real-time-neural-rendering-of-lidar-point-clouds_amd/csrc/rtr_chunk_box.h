@@ -78,6 +78,54 @@ RTR_HD bool chunk_box(uint32_t bx, uint32_t by, uint32_t bz, uint32_t widths, fl
     }
     return ok;
 }
+// The box word of a wide chunk, hdr[2 c + 1].w (round 6).  A chunk that straddles a coordinate plane has an axis without
+// a usable prefix -- no box above, so the chunk test kept it and the long path decoded it for nothing.  k_pack_measure
+// therefore stores, for the chunk's FIRST wide axis, the smallest and the largest of its values below n as two 16-bit
+// truncated floats (the top half of the fp32 pattern): lo in the low half, rounded toward -inf, hi in the high half,
+// rounded toward +inf.  0 = no box: the chunk holds a NaN or an infinity below n (on any axis), or a rounded end reaches
+// exponent 0xFF.  0 is no real box: lo = hi = +0 means every value is +0 (a -0 among them would make lo -0, see
+// float_order_key), and such an axis is not wide.
+//   Error argument.  Truncating a pattern to its top 16 bits moves the value toward zero and adding one unit to the
+// truncated pattern moves it away from zero past the original (patterns of one sign are ordered like their magnitudes,
+// denormals included), so lo16 <= min and hi16 >= max EXACTLY: the interval holds every value, and at most 2^-7 of an
+// end's magnitude is given away.  box_outside / clip_box_outside ask no more of a box than that it contains the points
+// (see there: the 1e-4 slack covers the arithmetic of the test, and is unchanged).
+// (total order of the finite patterns as unsigned keys: -max < ... < -0 < +0 < ... < +max)
+RTR_HD uint32_t float_order_key(uint32_t bits) { return bits ^ ((bits >> 31) != 0u ? 0xFFFFFFFFu : 0x80000000u); }
+RTR_HD uint32_t float_order_bits(uint32_t key) { return key ^ ((key >> 31) != 0u ? 0x80000000u : 0xFFFFFFFFu); }
+// min_bits / max_bits: the patterns of the smallest / largest value (by float_order_key), both finite
+RTR_HD uint32_t wide_box_word(uint32_t min_bits, uint32_t max_bits) {
+    const uint32_t lo_low = min_bits & 0xFFFFu, hi_low = max_bits & 0xFFFFu;
+    // away from zero exactly when that is the direction asked for: lo of a negative, hi of a positive value
+    const uint32_t lo16 = (min_bits >> 16) + (((min_bits >> 31) != 0u && lo_low != 0u) ? 1u : 0u);
+    const uint32_t hi16 = (max_bits >> 16) + (((max_bits >> 31) == 0u && hi_low != 0u) ? 1u : 0u);
+    const bool finite = (lo16 & 0x7F80u) != 0x7F80u && (hi16 & 0x7F80u) != 0x7F80u;
+    return finite ? (lo16 | (hi16 << 16)) : 0u;
+}
+// chunk_box with the box word: the same box for a chunk that is not wide (wbox is not looked at), and for a wide chunk
+// with a box word: its first wide axis from the word, every other wide axis (two or three planes straddled: one chunk in
+// two thousand) unbounded, the other axes from their prefix as above.  Unbounded = [-FLT_MAX, FLT_MAX]: it holds every
+// finite value (the word vouches that the chunk holds no other), 0 x FLT_MAX is 0, not NaN, and a term that overflows
+// makes v = +inf or NaN and m = inf, which never reject.  Returns false -- keep the chunk -- for wbox = 0 on a wide chunk.
+RTR_HD bool chunk_box(uint32_t bx, uint32_t by, uint32_t bz, uint32_t widths, uint32_t wbox, float lo[3], float hi[3]) {
+    const uint32_t base[3] = {bx, by, bz};
+    bool ok = (widths & kPackWideFlag) == 0u || wbox != 0u;
+    bool first = true;
+    for (int a = 0; a < 3; ++a) {
+        const uint32_t b = (widths >> (6 * a)) & 63u;  // (<= 25, or 32)
+        const bool wide = b == 32u;
+        const uint32_t top = base[a] | ((1u << (b & 31u)) - 1u);
+        const uint32_t p0 = wide ? (first ? wbox << 16 : 0xFF7FFFFFu) : base[a];
+        const uint32_t p1 = wide ? (first ? wbox & 0xFFFF0000u : 0x7F7FFFFFu) : top;
+        ok = ok && (p0 & 0x7F800000u) != 0x7F800000u && (p1 & 0x7F800000u) != 0x7F800000u;
+        const float f0 = __builtin_bit_cast(float, p0), f1 = __builtin_bit_cast(float, p1);
+        const bool neg = !wide && (base[a] >> 31) != 0u;
+        lo[a] = neg ? f1 : f0;
+        hi[a] = neg ? f0 : f1;
+        first = first && !wide;
+    }
+    return ok;
+}
 
 // ---- user clip planes (rtr_set_clip_planes) ----------------------------------------------------------------------
 // A point (x, y, z) of the uploaded cloud is kept iff ((a x + b y) + c z) + d >= 0 for every plane {a, b, c, d}, each

@@ -28,7 +28,8 @@ struct Proj {
 // starts into that dword.  All A streams lie in one array, chunk after chunk (x, y, z), all B streams in another.
 // hdr[2 c] = {base x, base y, base z, bx | by << 6 | bz << 12 | kPackWideFlag if some b is 32},
 // hdr[2 c + 1] = {first 32-byte unit (lo, hi) -- the chunk's A streams start 8 bytes x that into the A array, its B
-// streams 24 bytes x that into the B array --, lane spread of the chunk (fp32 bits, see Cloud::spread), 0}.
+// streams 24 bytes x that into the B array --, lane spread of the chunk (fp32 bits, see Cloud::spread), the box word of
+// a wide chunk (rtr_chunk_box.h, wide_box_word; 0: none)}.
 // Both arrays end with spare bytes (the last lanes' loads run past their values).
 // Spatially ordered clouds need 16-21 bits per coordinate (neighbours share sign, exponent and leading
 // mantissa bits): 5-8 B/pt instead of 12 (round 2 stored whole bytes: 6.5-9.2 B/pt).
@@ -381,6 +382,8 @@ void launch_transform_window(hipStream_t s, const Cloud &c, const uint32_t *perm
                              const Affine &M, float *wx, float *wy, float *wz, bool in_place);
 // the block offsets hdr[2 c + 1].xy of chunks [c_from, c_to) move by delta units (the blocks behind a rebuilt window moved)
 void launch_shift_units(hipStream_t s, uint4 *hdr, uint64_t c_from, uint64_t c_to, int64_t delta);
+// out[0] / out[1] (device, zeroed by the caller) += the wide chunks of the packed form / those that carry a box word
+void launch_wide_counts(hipStream_t s, const uint4 *hdr, uint64_t nchunks, uint64_t *out);
 // rtr_select_points: sel (8 u32 per 256-point chunk, upload order, no bit set at or past n) := op(sel, hit) with
 // hit = inside or, invert, !inside for the points below n; inside = clip_keep over `clip` (the CALL's planes, not the
 // cloud's) and, P given, project_point landing on a pixel of rect {x0, y0, x1, y1}.  c: the resident cloud -- its packed

@@ -1708,7 +1708,8 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL && !MV) ? RTR_T1_WAVES : 4
                 bool keep = c < nchunks;
                 float lo[3], hi[3];
                 uint32_t vm = MV ? (1u << vt->count) - 1u : 0u;  // (MV: the views that keep the chunk; no box: all of them)
-                if (MV && keep && chunk_box(cur0.x, cur0.y, cur0.z, cur0.w, lo, hi)) {
+                const uint32_t wbox = cur1.w;  // (a wide chunk's box word, read before the chunk number takes its place)
+                if (MV && keep && chunk_box(cur0.x, cur0.y, cur0.z, cur0.w, wbox, lo, hi)) {
                     vm = 0u;
                     for (int v = 0; v < vt->count; ++v) {
                         float m[12];
@@ -1721,7 +1722,7 @@ __global__ __launch_bounds__(kBlock, (PACKED && !CULL && !MV) ? RTR_T1_WAVES : 4
                     }
                     if (CLIP && clip_box_outside(clip, lo, hi)) vm = 0u;  // (the planes are shared by every view)
                     keep = vm != 0u;
-                } else if (!MV && keep && chunk_box(cur0.x, cur0.y, cur0.z, cur0.w, lo, hi)) {
+                } else if (!MV && keep && chunk_box(cur0.x, cur0.y, cur0.z, cur0.w, wbox, lo, hi)) {
                     // (the planes from the matrix in vector registers, once per batch: the barrier keeps the compiler
                     // from holding forty of them through the loop)
                     float m[12];
@@ -3082,8 +3083,8 @@ __device__ __forceinline__ void chunk_bits(const uint4 *__restrict__ x4, const u
     }
 }
 __global__ __launch_bounds__(kBlock) void k_pack_measure(const uint4 *__restrict__ x4, const uint4 *__restrict__ y4,
-                                                         const uint4 *__restrict__ z4, uint64_t n4, uint4 *__restrict__ hdr,
-                                                         uint32_t *__restrict__ chunk_planes) {
+                                                         const uint4 *__restrict__ z4, uint64_t n4, uint64_t n,
+                                                         uint4 *__restrict__ hdr, uint32_t *__restrict__ chunk_planes) {
     const uint64_t nchunks = (n4 + 63) / 64;
     const int lane = threadIdx.x & 63;
     for (uint64_t c = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
@@ -3096,6 +3097,31 @@ __global__ __launch_bounds__(kBlock) void k_pack_measure(const uint4 *__restrict
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) diff[a] |= (uint32_t)__shfl_xor((int)diff[a], off, 64);
         }
+        // (diff is wave-uniform now.)  A wide chunk's box word (rtr_chunk_box.h, wide_box_word): min / max of its first
+        // wide axis over the values below n -- the NaN padding of the cloud's last quad is no point -- as order keys
+        const int wa = diff[0] >> kPackMaxBits ? 0 : (diff[1] >> kPackMaxBits ? 1 : (diff[2] >> kPackMaxBits ? 2 : -1));
+        uint32_t wbox = 0u;
+        if (wa >= 0) {  // (wave-uniform)
+            const uint64_t iq = c * 64 + lane < n4 ? c * 64 + lane : n4 - 1;
+            uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
+            bool finite = true;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (4 * iq + k >= n) continue;
+                finite = finite && (v[0][k] & 0x7F800000u) != 0x7F800000u && (v[1][k] & 0x7F800000u) != 0x7F800000u &&
+                         (v[2][k] & 0x7F800000u) != 0x7F800000u;
+                const uint32_t key = float_order_key(wa == 0 ? v[0][k] : (wa == 1 ? v[1][k] : v[2][k]));
+                kmin = key < kmin ? key : kmin;
+                kmax = key > kmax ? key : kmax;
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t omin = (uint32_t)__shfl_xor((int)kmin, off, 64), omax = (uint32_t)__shfl_xor((int)kmax, off, 64);
+                kmin = omin < kmin ? omin : kmin;
+                kmax = omax > kmax ? omax : kmax;
+            }
+            if (__ballot(!finite) == 0ull) wbox = wide_box_word(float_order_bits(kmin), float_order_bits(kmax));
+        }
         if (lane == 0) {
             uint32_t w[3], base[3];
 #pragma unroll
@@ -3106,6 +3132,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_measure(const uint4 *__restrict
             }
             const uint32_t wide = (w[0] == 32u || w[1] == 32u || w[2] == 32u) ? kPackWideFlag : 0u;
             hdr[2 * c] = make_uint4(base[0], base[1], base[2], w[0] | (w[1] << 6) | (w[2] << 12) | wide);
+            hdr[2 * c + 1] = make_uint4(0u, 0u, 0u, wbox);  // (k_pack_scan fills in the rest and keeps .w)
             chunk_planes[c] = w[0] + w[1] + w[2];  // in units of 32 bytes
         }
     }
@@ -3124,7 +3151,9 @@ __global__ __launch_bounds__(512) void k_pack_scan(const uint32_t *__restrict__ 
         if (c < nchunks) {
             const uint64_t off = carry + (incl - v);
             // (.z: the chunk's lane spread, +inf -- no lane test -- when it was not measured)
-            hdr[2 * c + 1] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), spread ? __float_as_uint(spread[c]) : 0x7F800000u, 0u);
+            // (.w: the box word of a wide chunk, left there by k_pack_measure)
+            hdr[2 * c + 1] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), spread ? __float_as_uint(spread[c]) : 0x7F800000u,
+                                        hdr[2 * c + 1].w);
         }
         carry += tot;
     }
@@ -3238,7 +3267,7 @@ void pack_measure(hipStream_t s, const Cloud &c, uint4 *hdr, uint32_t *chunk_pla
     const uint64_t n4 = (c.n + 3) / 4;
     if (n4 == 0) return;
     hipLaunchKernelGGL(k_pack_measure, dim3(pack_grid(n4)), dim3(kBlock), 0, s, (const uint4 *)c.x, (const uint4 *)c.y,
-                       (const uint4 *)c.z, n4, hdr, chunk_planes);
+                       (const uint4 *)c.z, n4, (uint64_t)c.n, hdr, chunk_planes);
     hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(512), 0, s, chunk_planes, (n4 + 63) / 64, hdr, total_planes, c.spread,
                        first_unit);
 }
@@ -4464,7 +4493,8 @@ __device__ __forceinline__ void point_pass_body(const PointPassArgs &a, const Pr
         if (valid) {
             const uint4 h0 = a.pk.hdr[2 * chunk];
             float lo[3], hi[3];
-            keep = !(chunk_box(h0.x, h0.y, h0.z, h0.w, lo, hi) && (box_outside(fpl, lo, hi) || (CLIP && clip_box_outside(clip, lo, hi))));
+            const uint32_t wbox = reinterpret_cast<const uint32_t *>(a.pk.hdr + 2 * chunk + 1)[3];  // (the header's own 32 bytes)
+            keep = !(chunk_box(h0.x, h0.y, h0.z, h0.w, wbox, lo, hi) && (box_outside(fpl, lo, hi) || (CLIP && clip_box_outside(clip, lo, hi))));
             if constexpr (KEEP) keep = keep && kp.sum[chunk] != kKeepNone;
         }
         if (!PERM && a.vis && valid && !keep) {  // (no point of a rejected chunk is visible)
@@ -4890,6 +4920,29 @@ __global__ __launch_bounds__(kBlock) void k_shift_units(uint4 *__restrict__ hdr,
         hdr[2 * c + 1] = h;
     }
 }
+// out[0] += the wide chunks among hdr's first nchunks headers, out[1] += those of them that carry a box word
+__global__ __launch_bounds__(kBlock) void k_wide_counts(const uint4 *__restrict__ hdr, uint64_t nchunks, unsigned long long *out) {
+    uint32_t wide = 0, boxed = 0;
+    for (uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < nchunks; c += (uint64_t)gridDim.x * kBlock) {
+        const bool w = (hdr[2 * c].w & kPackWideFlag) != 0u;
+        wide += w ? 1u : 0u;
+        boxed += w && hdr[2 * c + 1].w != 0u ? 1u : 0u;
+    }
+    const uint32_t nw = (uint32_t)__popcll(__ballot(wide != 0u));  // (most waves hold none)
+    if (nw == 0u) return;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) wide += (uint32_t)__shfl_xor((int)wide, off, 64), boxed += (uint32_t)__shfl_xor((int)boxed, off, 64);
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&out[0], (unsigned long long)wide);
+        atomicAdd(&out[1], (unsigned long long)boxed);
+    }
+}
+void launch_wide_counts(hipStream_t s, const uint4 *hdr, uint64_t nchunks, uint64_t *out) {
+    if (nchunks == 0) return;
+    const uint64_t blocks = (nchunks + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_wide_counts, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(kBlock), 0, s, hdr, nchunks,
+                       (unsigned long long *)out);
+}
 void launch_shift_units(hipStream_t s, uint4 *hdr, uint64_t c_from, uint64_t c_to, int64_t delta) {
     if (c_from >= c_to || delta == 0) return;
     const uint64_t blocks = (c_to - c_from + kBlock - 1) / kBlock;
@@ -5064,7 +5117,8 @@ __global__ __launch_bounds__(kBlock) void k_select(SelectArgs a, Clip clip, Proj
                 else {
                     const uint4 h0 = a.pk.hdr[2 * chunk];
                     float lo[3], hi[3];
-                    if (chunk_box(h0.x, h0.y, h0.z, h0.w, lo, hi)) {
+                    const uint32_t wbox = reinterpret_cast<const uint32_t *>(a.pk.hdr + 2 * chunk + 1)[3];  // (the header's own 32 bytes)
+                    if (chunk_box(h0.x, h0.y, h0.z, h0.w, wbox, lo, hi)) {
                         if (clip_box_outside(clip, lo, hi) || (RECT && box_outside(rpl, lo, hi))) state = kSelOutside;
                         else if (!RECT && clip_box_inside(clip, lo, hi)) state = kSelInside;
                     }
