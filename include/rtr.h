@@ -181,6 +181,7 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          open again, together.  The exchange and option "overlap" exclude each other.
  *  "debug_dyn_cap": test aid -- caps the pool of dynamic stream extents at this many entries (-1 = off), so that a
  *          heavy tile overflows it and the error path (RTR_ERR_INTERNAL) can be exercised.
+ *  "debug_extract_window": test aid -- caps the points per internal window of rtr_extract_points (section 2e; -1 = off).
  *  "xp": only in RTR_EXPERIMENT builds (make experiment): switches parts of the point kernel off for
  *          timing attribution -- frames are WRONG while it is non-zero; the shipped library rejects it.
  *  "probe_variant": measurement aid of tools/probe_variants.py (selects the rtr_stream_probe kernel).
@@ -344,6 +345,64 @@ int rtr_remove_points(rtr_ctx *ctx, const uint32_t *keep_words, uint64_t nwords)
  * points of the chunks rebuilt; a device-to-device move of the packed blocks behind them when their size changes; and
  * O(n / 256) passes over per-chunk arrays. */
 int rtr_transform_points(rtr_ctx *ctx, const float M[12], const uint32_t *select_words, uint64_t nwords);
+
+/* ---- 2e. reading points back out of the resident cloud ------------------------------------------------------------
+ * Gives resident points back in UPLOAD order, all of them or a selection, without decoding the rest of the cloud (save
+ * an edited session, hand a selected region to another tool, context or rank).  The read side of sections 2b-2d and 6f.
+ *
+ * Selection: select_words is (n + 31) / 32 words in UPLOAD order, bit i % 32 of word i / 32 set = point i is extracted
+ * -- the layout of rtr_remove_points, rtr_set_point_keep, RTR_BUF_VISIBLE and RTR_BUF_SELECTION.  Host memory or device
+ * memory of the context's device (the pointer of rtr_device_buffer(RTR_BUF_SELECTION) or RTR_BUF_POINT_KEEP can be passed
+ * as it is); the words are copied.  Bits past n are ignored.  select_words = NULL with nwords = 0 means every point, on
+ * any cloud; a selection on a cloud the library sorted needs option "point_ids" = 1, as everywhere else.
+ *
+ * Order: let the selected upload indices in ascending order be s_0 < s_1 < ... < s_{k-1}.  *total (when non-NULL)
+ * receives k.  The call writes the points of ranks r in [first, min(first + count, k)) to output slot r - first.  With
+ * first >= k or count = 0 it writes nothing and returns RTR_OK: a caller sizes its buffers with one call with count = 0
+ * and may then extract in pieces.
+ *
+ * Sorted clouds without a selection: every point of a cloud the library sorted with "point_ids" = 0 cannot be put into
+ * upload order.  In that one case the order is the RESIDENT one (rtr_download_points') and indices must be NULL
+ * (RTR_ERR_INVALID otherwise; the message names point_ids).  With "point_ids" = 1 the order is the upload order.
+ *
+ * Outputs: each of xyz, rgb and indices may be NULL (that stream is skipped), and each may be host memory or device
+ * memory of the context's device, independently of the others.  Slot j of xyz is the three floats at byte offset
+ * j * xyz_stride_bytes (the rules of rtr_upload_points: at least 12, a multiple of 4), slot j of rgb three bytes at
+ * j * rgb_stride_bytes (at least 3), in the channel order as uploaded.  At strides of exactly 16 and 4 the fourth float
+ * is written as 1.0f and the fourth byte as 255 -- the reference's float4 / uchar4 layouts, what rtr_download_points
+ * gives; at any other stride the bytes beyond the first 12 or 3 of a record are left untouched.  indices[j] is
+ * s_{first + j}.  Coordinates are bit for bit the resident ones: any bit pattern round-trips (NaN payloads, -0,
+ * denormals); after rtr_transform_points they are the moved coordinates.  The output can be fed unchanged to
+ * rtr_upload_points or rtr_append_points, of this context or another.
+ *
+ * What it ignores and leaves alone: like rtr_download_points and rtr_select_points the call reads the cloud only.  The
+ * context's clip planes and keep mask are ignored (hidden points are extracted too); no frame, frame buffer, tile store,
+ * pool, statistic, point-pass buffer, selection or keep mask changes, and an open peer-to-peer exchange stays open.  A
+ * cloud resident in packed form only is NOT decoded into fp32 arrays: the chunks holding a requested point are decoded
+ * on the fly.  Scratch: one internal window of outputs (at most 2^24 points, for host destinations) plus O(n / 32)
+ * words.  Option "debug_extract_window" (test aid, -1 = off) caps the points per internal window so that small clouds
+ * reach the multi-window path.
+ *
+ * Ordering: the work is queued on the context's stream behind everything issued before it, and the call waits for it
+ * before it returns, as rtr_download_points does.  It does not repeat overflowed frames; a pending frame error stays
+ * pending for the next synchronising call.
+ *
+ * Cost: one pass over the selection words (none without a selection); then kernel work proportional to the 256-point
+ * chunks that hold a selected point of the requested window -- a chunk with none is skipped before its header or
+ * streams are read.  On a sorted cloud the selection bits are gathered through the permutation, for every chunk and
+ * internal window.
+ *
+ * Sharded use: each rank extracts its own points by its own indices.
+ *
+ * Errors (RTR_ERR_INVALID, nothing is written): no cloud; nwords != (n + 31) / 32 with a selection; select_words NULL
+ * with nwords > 0; a bad stride for a non-NULL stream; a selection on a sorted cloud without "point_ids" = 1; indices on
+ * a sorted cloud without "point_ids" = 1; xyz, rgb, indices and total all NULL.  2^32 points or more:
+ * RTR_ERR_UNSUPPORTED. */
+int rtr_extract_points(rtr_ctx *ctx, const uint32_t *select_words, uint64_t nwords,
+                       uint64_t first, uint64_t count,
+                       float *xyz, size_t xyz_stride_bytes,
+                       uint8_t *rgb, size_t rgb_stride_bytes,
+                       uint32_t *indices, uint64_t *total);
 
 /* ---- 3. camera (project_cloud.cu:318, project_cloud.h:50-59) -------------------- */
 /* P = K4 * E in fp32, row-major, exactly as the reference composes it with glm:

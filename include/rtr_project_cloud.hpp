@@ -29,6 +29,7 @@
 // transform where they lie: indices, order and the keep mask stay.
 // selectBox / selectPlanes / selectRect (section 6f) name the vertices of a region on the device; removeSelected,
 // hideSelected and transformSelected then act on them without a host array of flags.
+// extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
 //
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
@@ -373,6 +374,30 @@ public:
         check(ctx_, rtr_transform_points(ctx_, m, static_cast<const uint32_t*>(p), bytes / 4));
     }
 
+    // Reads the selected vertices back out in upload order (section 2e): tight xyz (3 floats per vertex) and tight colour
+    // triples -- the layouts appendPoints(xyz, 12, rgb, 3, m) takes, so the result can be handed to another ProjectCloud
+    // -- and, when asked for, their vertex indices.  Returns their number (0 and empty vectors without a selection).
+    // Only the chunks holding a selected vertex are decoded; the clip planes and the keep mask play no part.
+    uint64_t extractSelected(std::vector<float>& vertices, std::vector<uint8_t>& colors,
+                             std::vector<uint32_t>* indices = nullptr) {
+        vertices.clear(); colors.clear();
+        if (indices) indices->clear();
+        if (!has_selection()) return 0;
+        void* p = nullptr;
+        size_t bytes = 0;
+        check(ctx_, rtr_device_buffer(ctx_, RTR_BUF_SELECTION, &p, &bytes));
+        return extract(static_cast<const uint32_t*>(p), (uint64_t)(bytes / 4), vertices, colors, indices);
+    }
+    // Every vertex as it is resident now (after appends, removals and moves), in upload order; a cloud sorted without
+    // point_ids comes in the sorted order.  Returns the vertex count.
+    uint64_t extractAll(std::vector<float>& vertices, std::vector<uint8_t>& colors) {
+        vertices.clear(); colors.clear();
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        if (n == 0) return 0;
+        return extract(nullptr, 0, vertices, colors, nullptr);
+    }
+
     // Renders the frame (computeRGBD / computeFilteredRGBD without host copies) and returns, per pixel (row-major
     // H x W), the vertex index of the point it shows, -1 for none (empty or prefiltered-away pixels).
     template <class Calibration, class Extrinsics>
@@ -420,6 +445,18 @@ private:
         }
         if (has_selection())  // (a removal drops it)
             check(ctx_, rtr_select_points(ctx_, 0, nullptr, nullptr, nullptr, RTR_SELECT_TOGGLE, nullptr));
+    }
+    uint64_t extract(const uint32_t* words, uint64_t nwords, std::vector<float>& vertices, std::vector<uint8_t>& colors,
+                     std::vector<uint32_t>* indices) {
+        uint64_t k = 0;
+        check(ctx_, rtr_extract_points(ctx_, words, nwords, 0, 0, nullptr, 0, nullptr, 0, nullptr, &k));
+        vertices.resize((size_t)k * 3);
+        colors.resize((size_t)k * 3);
+        if (indices) indices->resize((size_t)k);
+        if (k)
+            check(ctx_, rtr_extract_points(ctx_, words, nwords, 0, k, vertices.data(), 12, colors.data(), 3,
+                                           indices ? indices->data() : nullptr, nullptr));
+        return k;
     }
     template <class Calibration, class Extrinsics>
     static void projection(const Calibration& calibration, const Extrinsics& extrinsics, float P[16]) {

@@ -18,6 +18,7 @@
 
 #include "../../include/rtr.h"
 #include "rtr_kernels.h"
+#include "rtr_extract_index.h"
 
 constexpr int kSplitCooldown = 8;  // whole frames keep launching k_tile_split this long after the last report of a tile above the threshold
 
@@ -105,6 +106,7 @@ struct rtr_ctx {
     int opt_p2p_timeout_ms = 2000;   // peer-to-peer flag barriers give up after this long (option "p2p_timeout_ms")
     int opt_fill_shift = -1;         // spacing of the stream counters, 4 << value bytes; -1: by the frames seen (see "fill_shift")
     int opt_debug_dyn_cap = -1;      // test aid: cap the dynamic extent pool at this many entries (-1: off)
+    int opt_debug_extract_window = -1;  // test aid: cap rtr_extract_points' internal window at this many points (-1: off)
     // whole frames launch k_tile_split (an empty launch costs ~5 us) only while tiles above the split threshold have
     // been seen: T1's epilogue stores their number here (mapped host word, read without a sync -- it describes the
     // last frame whose T1 has COMPLETED, the host may be frames ahead), and the launch stays on for kSplitCooldown
@@ -923,6 +925,11 @@ int rtr_set_option(rtr_ctx *c, const char *key, int value) {
         c->list_valid = false;
         return RTR_OK;
     }
+    if (!strcmp(key, "debug_extract_window")) {  // test aid: small clouds reach rtr_extract_points' multi-window path
+        NEED(c, value == -1 || value >= 1, "debug_extract_window must be >= 1 (-1: off)");
+        c->opt_debug_extract_window = value;
+        return RTR_OK;
+    }
     if (!strcmp(key, "p2p_timeout_ms")) {
         NEED(c, value >= 1 && value <= 60000, "p2p_timeout_ms must be in 1..60000");
         c->opt_p2p_timeout_ms = value;
@@ -1084,6 +1091,7 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "split_threshold")) *value = c->opt_heavy;
     else if (!strcmp(key, "split_slice")) *value = c->opt_slice;
     else if (!strcmp(key, "point_grid")) *value = c->opt_grid;
+    else if (!strcmp(key, "debug_extract_window")) *value = c->opt_debug_extract_window;
     else return fail(c, RTR_ERR_INVALID, "unknown option '%s'", key);
     return RTR_OK;
 }
@@ -2204,6 +2212,123 @@ int rtr_download_points(rtr_ctx *c, float *xyzw, uint8_t *rgba, uint64_t first, 
     }
     drop_soa(c);
     return launch_check(c, "soa_to_aos");
+}
+
+// ---- reading points back out (rtr.h, section 2e) ------------------------------------------------------------------
+// Reads the cloud only, on the context's stream: one popcount scan of the selection words, then per internal window one
+// launch of rtr::launch_extract, which decodes the chunks holding a point of the window and no others.  Device
+// destinations are written by the kernel; host destinations go through a device staging window (at the caller's stride
+// when every byte of a record is written -- 12 / 16 and 3 / 4 -- else tight, and the records are laid into the caller's
+// memory by the host, so that the bytes between them stay).  No fp32 SoA is built for a packed-only cloud.
+namespace {
+bool on_device(const void *p) {  // device (or managed) memory, as opposed to anything the host owns
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // (plain host memory is unknown to the runtime)
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+}  // namespace
+
+int rtr_extract_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords, uint64_t first, uint64_t count, float *xyz,
+                       size_t xs, uint8_t *rgb, size_t rs, uint32_t *indices, uint64_t *total) {
+    if (!c) return RTR_ERR_INVALID;
+    NEED(c, c->n > 0, "rtr_extract_points: no cloud");
+    NEED(c, xyz || rgb || indices || total, "rtr_extract_points: nothing to produce (xyz, rgb, indices and total are all NULL)");
+    const bool every = select_words == nullptr && nwords == 0;
+    NEED(c, select_words != nullptr || nwords == 0, "rtr_extract_points: select_words is NULL");
+    if (!every && nwords != (c->n + 31) / 32)
+        return fail(c, RTR_ERR_INVALID, "rtr_extract_points: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
+    NEED(c, !xyz || (xs >= 12 && xs % 4 == 0), "rtr_extract_points: xyz_stride_bytes must be >= 12 and a multiple of 4");
+    NEED(c, !rgb || rs >= 3, "rtr_extract_points: rgb_stride_bytes must be >= 3");
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    const bool lost_order = c->reordered && !c->perm;
+    NEED(c, every || !lost_order,
+         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be mapped: set "
+         "point_ids = 1 before the upload (or upload with auto_reorder = 0), or extract every point (select_words NULL)");
+    NEED(c, !(every && lost_order && indices),
+         "the resident cloud was reordered without option point_ids = 1: every point comes out in the RESIDENT order and "
+         "has no upload index, so indices must be NULL (set point_ids = 1 before the upload to get them)");
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nch = (n + 255) / 256;
+    const uint32_t *perm = c->reordered ? c->perm : nullptr;
+    AppendBufs buf;
+
+    // the selection's popcount scan and k, the number of selected points
+    uint32_t *sel = nullptr, *wscan = nullptr;
+    uint64_t k = n;
+    if (!every) {
+        uint32_t *scratch;
+        uint64_t *tot;
+        HIP_TRY(c, buf.get(&sel, nwords * 4));
+        HIP_TRY(c, buf.get(&wscan, nwords * 4));
+        HIP_TRY(c, buf.get(&scratch, rtr::scan_scratch_words(nwords) * 4));
+        HIP_TRY(c, buf.get(&tot, sizeof(uint64_t)));
+        HIP_TRY(c, hipMemcpyAsync(sel, select_words, nwords * 4, hipMemcpyDefault, s));
+        rtr::launch_scan_u32(s, sel, nwords, n, wscan, scratch, tot);
+        HIP_TRY(c, hipMemcpyAsync(&k, tot, sizeof k, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (int rc = launch_check(c, "extract scan")) return rc;
+    }
+    if (total) *total = k;
+    const uint64_t produce = first < k ? std::min(count, k - first) : 0;
+    if (produce == 0 || !(xyz || rgb || indices)) return RTR_OK;
+
+    // the window: everything at once into device buffers, at most 2^24 points at a time through staging otherwise
+    const bool xyz_dev = xyz && on_device(xyz), rgb_dev = rgb && on_device(rgb), idx_dev = indices && on_device(indices);
+    const bool staged = (xyz && !xyz_dev) || (rgb && !rgb_dev) || (indices && !idx_dev);
+    uint64_t win = produce;
+    if (staged) win = std::min<uint64_t>(win, 1ull << 24);
+    if (c->opt_debug_extract_window > 0) win = std::min<uint64_t>(win, (uint64_t)c->opt_debug_extract_window);
+    // host streams whose records have gaps the call must not touch are staged tight and laid out by the host
+    const bool xyz_gaps = xyz && !xyz_dev && xs != 12 && xs != 16, rgb_gaps = rgb && !rgb_dev && rs != 3 && rs != 4;
+    const uint64_t sxs = xyz_gaps ? 12 : xs, srs = rgb_gaps ? 3 : rs;
+    uint8_t *stx = nullptr, *stc = nullptr;
+    uint32_t *sti = nullptr;
+    if (xyz && !xyz_dev) HIP_TRY(c, buf.get(&stx, win * sxs + 16));
+    if (rgb && !rgb_dev) HIP_TRY(c, buf.get(&stc, win * srs + 16));
+    if (indices && !idx_dev) HIP_TRY(c, buf.get(&sti, win * 4));
+    std::vector<uint8_t> bounce;
+    if (xyz_gaps || rgb_gaps) bounce.resize(win * (xyz_gaps ? 12 : 3));
+
+    const rtr::Cloud cl = cloud_of(c);
+    rtr::ExtractArgs a{};
+    a.pk = cl.pk;
+    a.x4 = (const float4 *)cl.x, a.y4 = (const float4 *)cl.y, a.z4 = (const float4 *)cl.z;
+    a.rgba4 = (const uint4 *)cl.rgba;
+    a.perm = perm, a.sel = sel, a.wscan = wscan;
+    a.n = n, a.total = k;
+    for (uint64_t off = 0; off < produce; off += win) {
+        const uint64_t w = std::min(win, produce - off);
+        a.first = first + off, a.count = w;
+        a.c0 = 0, a.c1 = nch;
+        if (every && !perm) rtr::extract_all_chunks(a.first, w, &a.c0, &a.c1);
+        a.xyz = !xyz ? nullptr : xyz_dev ? (uint8_t *)xyz + off * xs : stx;
+        a.rgb = !rgb ? nullptr : rgb_dev ? rgb + off * rs : stc;
+        a.idx = !indices ? nullptr : idx_dev ? indices + off : sti;
+        a.xyz_stride = xyz_dev ? xs : sxs, a.rgb_stride = rgb_dev ? rs : srs;
+        a.xyz_form = a.xyz_stride != 16 ? 0 : ((uintptr_t)a.xyz % 16 == 0 ? 2 : 1);
+        a.rgb_form = a.rgb_stride != 4 ? 0 : ((uintptr_t)a.rgb % 4 == 0 ? 2 : 1);
+        rtr::launch_extract(s, a);
+        if (int rc = launch_check(c, "extract")) return rc;
+        if (stx && !xyz_gaps) HIP_TRY(c, hipMemcpyAsync((uint8_t *)xyz + off * xs, stx, w * xs, hipMemcpyDeviceToHost, s));
+        if (stc && !rgb_gaps) HIP_TRY(c, hipMemcpyAsync(rgb + off * rs, stc, w * rs, hipMemcpyDeviceToHost, s));
+        if (sti) HIP_TRY(c, hipMemcpyAsync(indices + off, sti, w * 4, hipMemcpyDeviceToHost, s));
+        if (xyz_gaps) {
+            HIP_TRY(c, hipMemcpyAsync(bounce.data(), stx, w * 12, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            for (uint64_t j = 0; j < w; ++j) memcpy((uint8_t *)xyz + (off + j) * xs, bounce.data() + j * 12, 12);
+        }
+        if (rgb_gaps) {
+            HIP_TRY(c, hipMemcpyAsync(bounce.data(), stc, w * 3, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            for (uint64_t j = 0; j < w; ++j) memcpy(rgb + (off + j) * rs, bounce.data() + j * 3, 3);
+        }
+        HIP_TRY(c, hipStreamSynchronize(s));  // (the staging window is reused; the call returns with the data in place)
+    }
+    return launch_check(c, "extract");
 }
 
 // ---- camera ------------------------------------------------------------------------

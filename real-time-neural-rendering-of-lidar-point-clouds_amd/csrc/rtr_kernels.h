@@ -368,6 +368,26 @@ void launch_scan_u32(hipStream_t s, const uint32_t *in, uint64_t count, uint64_t
 // popcount scan of keep) from dst[c] - 256 c0 on, dst = the exclusive scan of cnt
 void launch_remove_compact(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *keep, const uint32_t *wscan,
                            const uint32_t *dst, uint64_t c0, float *wx, float *wy, float *wz, uint32_t *wrgba, uint32_t *wperm);
+// rtr_extract_points (section 2e): one window of the extraction.  The selected points (sel: upload-order words, bits at
+// or past n ignored, null = every point; perm as for remove; wscan = the exclusive popcount scan of sel, total = its
+// sum) of ranks [first, first + count) go to slot rank - first of the device buffers xyz / rgb / idx (each may be null):
+// xyz_form 0 = three floats per record, 1 = x, y, z, 1.0f as four floats, 2 = the same as one 16-byte store (base and
+// stride multiples of 16); rgb_form 0 = three bytes, 1 = c0, c1, c2, 255 as four bytes, 2 = the same as one dword (base
+// and stride multiples of 4).  Only chunks [c0, c1) are visited; without sel and perm the rank is the resident index
+// and the caller passes the window's chunks (extract_all_chunks).  Coordinates from the fp32 SoA (x4, y4, z4) when x4
+// is set, else from the packed form pk; rgba4: the resident colours.
+struct ExtractArgs {
+    PackedXyz pk;
+    const float4 *x4, *y4, *z4;
+    const uint4 *rgba4;
+    const uint32_t *perm, *sel, *wscan;
+    uint64_t n, total, c0, c1, first, count;
+    uint8_t *xyz, *rgb;
+    uint32_t *idx;
+    uint64_t xyz_stride, rgb_stride;
+    int xyz_form, rgb_form;
+};
+void launch_extract(hipStream_t s, const ExtractArgs &a);
 // the upload-order mask `up` of n points compacted onto the survivors: up1 (zeroed by the caller) gets old[keep]
 void launch_remove_mask(hipStream_t s, const uint32_t *keep, const uint32_t *wscan, const uint32_t *up, uint64_t n, uint32_t *up1);
 

@@ -349,6 +349,99 @@ class Projector:
     def clear_selection(self):
         self._chk(self._lib.rtr_clear_selection(self._ctx))
 
+    # -- reading points back out (rtr.h section 2e)
+    @staticmethod
+    def _extract_dest(arr, dtype, min_cols, name):
+        """(pointer, row stride in bytes, rows, owner) of an output of extract_points: a numpy array, a torch tensor or an
+        object with __cuda_array_interface__; 2-D with at least min_cols contiguous columns of dtype (1-D for indices)."""
+        dt = np.dtype(dtype)
+        if hasattr(arr, "data_ptr"):  # a torch tensor (host or device)
+            if arr.element_size() != dt.itemsize or arr.dtype.is_floating_point != (dt.kind == "f"):
+                raise ValueError("out[%r] must hold %s elements" % (name, dt))
+            shape, strides, ptr = tuple(arr.shape), tuple(st * dt.itemsize for st in arr.stride()), arr.data_ptr()
+        elif hasattr(arr, "__cuda_array_interface__"):
+            cai = arr.__cuda_array_interface__
+            if np.dtype(cai["typestr"]).itemsize != dt.itemsize:
+                raise ValueError("out[%r] must hold %s elements" % (name, dt))
+            shape, ptr = tuple(cai["shape"]), cai["data"][0]
+            strides = cai.get("strides") or tuple(int(np.prod(shape[i + 1:])) * dt.itemsize for i in range(len(shape)))
+        else:
+            if not isinstance(arr, np.ndarray) or arr.dtype != dt or not arr.flags.writeable:
+                raise ValueError("out[%r] must be a writeable %s array" % (name, dt))
+            shape, strides, ptr = arr.shape, arr.strides, arr.ctypes.data
+        if len(shape) in (1, 2) and shape[0] == 0:  # (no rows: nothing is written, whatever strides the array reports)
+            return C.c_void_p(ptr), max(min_cols, shape[-1] if len(shape) == 2 else 1) * dt.itemsize, 0, arr
+        if min_cols == 1:
+            if len(shape) != 1 or (shape[0] > 1 and strides[0] != dt.itemsize):
+                raise ValueError("out[%r] must be a contiguous 1-D array" % name)
+            return C.c_void_p(ptr), dt.itemsize, shape[0], arr
+        if len(shape) != 2 or shape[1] < min_cols or strides[1] != dt.itemsize or strides[0] < min_cols * dt.itemsize:
+            raise ValueError("out[%r] must be 2-D with at least %d contiguous columns" % (name, min_cols))
+        return C.c_void_p(ptr), strides[0], shape[0], arr
+
+    def count_selected(self, select):
+        """The number of points `select` names (the forms of set_point_keep; None: every point): extract_points'
+        count = 0 form, one pass over the words."""
+        ptr, nwords, _hold = (None, 0, None) if select is None else self._keep_words(select)
+        k = C.c_uint64()
+        self._chk(self._lib.rtr_extract_points(self._ctx, ptr, nwords, 0, 0, None, 0, None, 0, None, C.byref(k)))
+        return k.value
+
+    def extract_points(self, select=None, first=0, count=None, xyz=True, rgb=True, indices=False, out=None):
+        """Reads resident points back in UPLOAD order (include/rtr.h section 2e).  select: None = every point, else the
+        forms of set_point_keep (a bool array of length n, uint32 words, device memory such as selection()); of the k
+        selected points, in ascending upload index, those of ranks [first, first + count) come out (count None: to the
+        last).  Returns the list of the streams asked for, in this order: xyz -> (k', 4) float32 (x, y, z, 1), rgb ->
+        (k', 4) uint8 (c0, c1, c2, 255), indices -> (k',) uint32 upload indices.  Coordinates are the resident bits; the
+        clip planes and the keep mask play no part; only the chunks holding a requested point are decoded.
+        out: a dict with any of the keys "xyz", "rgb", "indices" naming caller arrays to fill instead -- numpy arrays,
+        torch tensors (host or device) or objects with __cuda_array_interface__, 2-D with a row per point (at least 3
+        columns; rows of exactly 4 columns get 1.0 / 255 in the fourth, wider rows keep what lies behind the first three)
+        and 1-D uint32 for the indices; the xyz / rgb / indices flags are then ignored and the number of points written
+        is returned.  A cloud the library sorted without point_ids = 1 gives every point in the resident order, and
+        neither a selection nor indices."""
+        ptr, nwords, _hold = (None, 0, None) if select is None else self._keep_words(select)
+        k = C.c_uint64()
+        self._chk(self._lib.rtr_extract_points(self._ctx, ptr, nwords, 0, 0, None, 0, None, 0, None, C.byref(k)))
+        first = int(first)
+        m = max(0, k.value - first)
+        if count is not None:
+            m = min(m, int(count))
+        if out is None:
+            dst = {}
+            if xyz:
+                dst["xyz"] = np.empty((m, 4), np.float32)
+            if rgb:
+                dst["rgb"] = np.empty((m, 4), np.uint8)
+            if indices:
+                dst["indices"] = np.empty(m, np.uint32)
+        else:
+            dst = dict(out)
+            if set(dst) - {"xyz", "rgb", "indices"}:
+                raise ValueError("out may hold the keys 'xyz', 'rgb' and 'indices'")
+        if not dst:
+            raise ValueError("extract_points: no stream asked for")
+        px, sx, pc, sc, pi = None, 0, None, 0, None
+        hold = []
+        for name, dt, cols in (("xyz", np.float32, 3), ("rgb", np.uint8, 3), ("indices", np.uint32, 1)):
+            if name not in dst:
+                continue
+            p, stride, rows, owner = self._extract_dest(dst[name], dt, cols, name)
+            if rows < m:
+                raise ValueError("out[%r] has %d rows, %d points are extracted" % (name, rows, m))
+            hold.append(owner)
+            if name == "xyz":
+                px, sx = p, stride
+            elif name == "rgb":
+                pc, sc = p, stride
+            else:
+                pi = p
+        if m:
+            self._chk(self._lib.rtr_extract_points(self._ctx, ptr, nwords, first, m, px, sx, pc, sc, pi, None))
+        if out is not None:
+            return m
+        return [dst[name] for name in ("xyz", "rgb", "indices") if name in dst]
+
     # -- point pass (rtr.h section 6b)
     def point_pass(self, P, ids=True, visible=True):
         """Per-pixel point IDs (BUF_POINT_ID: upload index, NO_POINT for none) and / or the per-point visibility
@@ -669,6 +762,44 @@ class ProjectCloud:
         the same vertices where they now lie."""
         if self._p.get_option("selection"):
             self._p.transform_points(_affine_rows(M).reshape(3, 4), self._p.selection())
+
+    # -- reading points back out (rtr.h section 2e)
+    def extractSelected(self, indices=False):
+        """The selected vertices in upload order: (vertices (k, 4) float32, colors (k, 4) uint8), with indices=True
+        also their (k,) uint32 vertex indices -- the arrays the constructor and appendPoints take.  Nothing selected:
+        empty arrays.  Vertices the clip planes or the keep mask hide are extracted like the others."""
+        if not self._p.get_option("selection"):
+            empty = [np.empty((0, 4), np.float32), np.empty((0, 4), np.uint8)] + ([np.empty(0, np.uint32)] if indices else [])
+            return tuple(empty)
+        return tuple(self._p.extract_points(self._p.selection(), indices=indices))
+
+    def extractPoints(self, indices_or_mask):
+        """The uploaded vertices a bool mask over them or an array of vertex indices names, in ASCENDING vertex index
+        (an index given twice comes out once): (vertices (k, 4) float32, colors (k, 4) uint8)."""
+        n = self._p.num_points
+        sel = np.asarray(indices_or_mask)
+        if sel.dtype != bool:
+            idx = sel.astype(np.int64)
+            if idx.size and (idx.min() < 0 or idx.max() >= n):  # (as removePoints: no index counted from the end)
+                raise IndexError("extractPoints: indices must lie in [0, %d)" % n)
+            sel = np.zeros(n, bool)
+            sel[idx] = True
+        return tuple(self._p.extract_points(sel))
+
+    def extractAll(self):
+        """Every vertex as it is resident now -- after appends, removals and moves -- in upload order:
+        (vertices (n, 4) float32, colors (n, 4) uint8).  (A cloud sorted without point_ids=True comes in the sorted
+        order.)"""
+        return tuple(self._p.extract_points())
+
+    def savePly(self, path, selected=False, bgr=True):
+        """Writes every vertex (selected: the selected ones) to a binary PLY through formats.write_ply.  bgr: the
+        colours were given in B, G, R order, as the reference's loader and formats.read_ply deliver them, and are
+        written as red, green, blue; False writes the channels as they are.  Returns the number of vertices written."""
+        from .formats import write_ply
+        xyz, rgb = (self.extractSelected() if selected else self.extractAll())[:2]
+        write_ply(path, xyz[:, :3], rgb[:, 2::-1] if bgr else rgb[:, :3])
+        return xyz.shape[0]
 
     def commitPointKeep(self):
         """Removes the vertices the keep mask in force hides (see removePoints), then clears the mask: the frames stay
