@@ -104,7 +104,7 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          (exact: same frame; an algorithmic byte reduction, off by default and reported
  *          separately from the roofline figure; needs a spatially coherent point order).
  *  "lean": 1 (default) = a whole single-GPU frame (rtr_render and the calls built on it) whose point kernel needs no
- *          epilogue -- no tile above "split_threshold" seen lately, option "overlap" off, no peer-to-peer exchange open
+ *          epilogue -- no tile above "split_threshold" seen lately, no peer-to-peer exchange open; overlapped or not
  *          -- ends that kernel without last-workgroup detection and bookkeeping pass: the tile kernel's workgroups read
  *          and reset their stream counters themselves, one extra workgroup does the frame's bookkeeping off the
  *          critical path (5-6 us per frame).  0 = always the epilogue.  After a lean frame rtr_accumulate_pass
@@ -157,12 +157,26 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          rtr_get_option("resident_millibytes_per_point"): device memory held for the cloud and its frames, per point.
  *  "keep_accum": 1 = the whole-frame calls also write RTR_BUF_ACCUM (default 0; the phase
  *          calls always do).
- *  "overlap": 1 = rtr_render queues the point stream (T1) of a frame on a second, internal
- *          stream and alternates between two list / bin sets, so it may run beside the tail of
- *          the previous frame; results are still ordered on the context's stream.  Default 0:
- *          on MI355X the gain is 0-3 % ("Overlap").  "tail_cus" = t (0..31, set
- *          before "overlap") additionally gives the two streams disjoint CU masks, t CUs of every
- *          XCD for the tail.
+ *  "overlap": rtr_render queues the point kernel (T1) of a frame on a second, internal stream and into a second tile
+ *          store and extent pool, so it runs beside the tile kernel and prefilter of the previous frame; results are
+ *          still ordered on the context's stream, and every frame is bit-identical to the serial one.  1 = every
+ *          whole frame; 0 = never; -1 (default) = automatic: from the third consecutive rtr_render of the context on
+ *          -- with the prefilter, same resolution and cloud, tile-binned form, one GPU, no peer-to-peer exchange
+ *          exported or open -- and until any other entry point is called (all but rtr_get_option and the other read-only queries end the
+ *          streak; the next one counts from one again).  Footprint while in use: the second tile store, 134 MB at
+ *          1920x1080, and the second extent pool, 4 B per point with the adaptive pool (0.4 GB for 1e8 points).  Both
+ *          are first allocated by the frame that engages; if that fails in the automatic mode the context stays
+ *          serial, without an error.  They are kept until the resolution changes (the store), the cloud is replaced
+ *          (the pool), the context closes -- or the option is set to 0, which gives both back.
+ *          Frames without the prefilter stay serial in the automatic mode: their tail is the tile kernel alone, and
+ *          overlapped they are 1-9 % slower ("Overlap"); 1 overlaps them all the same.
+ *          rtr_get_option("overlap_active") reads 1 when the last whole frame ran overlapped.
+ *          "front_priority": the stream priority the internal stream is created with -- 0 (default) the default
+ *          priority, 1 the lowest the device offers (the context's stream, i.e. the tail and what the caller queues
+ *          behind a frame, then wins dispatch), 2 the highest.  Read when the stream is created: set it before
+ *          "overlap".  Measured on MI355X ("Overlap"): 0 is fastest.
+ *          "tail_cus" = t (0..31, set before "overlap" = 1, which alone uses it) gives the two streams disjoint CU
+ *          masks instead, t CUs of every XCD for the tail.
  *  "point_grid": workgroups of the grid-stride point kernels (default 1024 = 4 per CU; at the default the
  *          tile-binned point kernel takes what is resident at once: 5 per CU when it reads packed coordinates
  *          and its registers admit it, else 4).
@@ -178,7 +192,7 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          that does not arrive before it flags the frame in rtr_p2p_status (default 2000).  rtr_get_option("p2p_open")
  *          reads 1 while the peers' buffers are mapped: a new cloud (rtr_upload_points, rtr_generate_synthetic with
  *          another point count) or resolution closes the exchange on this rank -- every rank must then export /
- *          open again, together.  The exchange and option "overlap" exclude each other.
+ *          open again, together.  The exchange and option "overlap" = 1 exclude each other (-1 is inactive meanwhile).
  *  "debug_dyn_cap": test aid -- caps the pool of dynamic stream extents at this many entries (-1 = off), so that a
  *          heavy tile overflows it and the error path (RTR_ERR_INTERNAL) can be exercised.
  *  "debug_extract_window": test aid -- caps the points per internal window of rtr_extract_points (section 2e; -1 = off).

@@ -19,6 +19,7 @@
 #include "../../include/rtr.h"
 #include "rtr_kernels.h"
 #include "rtr_extract_index.h"
+#include "rtr_overlap_policy.h"
 
 constexpr int kSplitCooldown = 8;  // whole frames keep launching k_tile_split this long after the last report of a tile above the threshold
 
@@ -43,8 +44,7 @@ struct rtr_ctx {
     int opt_lean_identity = 1;  // lean frames: tile workgroup b takes tile b when the whole launch is resident (option "lean_identity")
     int opt_lean_early = -1;    // lean frames: first batch of entries requested before the stream counters are known: 0 never,
                                 // 1 always, -1 when the previous frame's tiles were full (option "lean_early")
-    bool last_lean = false;     // the last binned frame was a lean one (its statistics are folded on demand) ...
-    int lean_parity = 0;        // ... and this was its parity
+    bool last_lean = false;     // the last binned frame was a lean one (its statistics are folded on demand; FrontSet::parity)
     uint64_t n = 0, cap = 0;
     uint4 *pk_hdr = nullptr;        // rtr::PackedXyz of the resident cloud (option "pack"); null: not in use
     uint32_t *pk_planes = nullptr, *pk_planes_b = nullptr;  // (one allocation: A streams, then B streams)
@@ -66,7 +66,8 @@ struct rtr_ctx {
         uint64_t dyn_cap = 0;
         hipEvent_t binned = nullptr, consumed = nullptr;  // T1 done (front stream) / T4 done (tail stream)
         bool consumed_valid = false;
-        int parity = 0;             // lean-frame parity of a view's store (the single frame keeps lean_parity)
+        int parity = 0;             // lean-frame parity of this store: order[], lcnt[] and the lflag words live in it
+        bool lean_pending = false;  // its last frame was a lean one whose statistics no later frame has folded yet
     };
 
     // What a set of frames renders into: the single frame (rtr_render, the phase calls; with option "overlap" T1 of
@@ -91,10 +92,13 @@ struct rtr_ctx {
         bool pool_worst = false;     // the pools are worst-case sized for this cloud: a frame overflowed them, or the peers map them
     } frame, views;
     FrontSet &F() { return frame.fs[frame.cur]; }
-    int opt_overlap = 0;        // whole-frame renders run T1 on `front`, everything else on `stream`
+    rtr::OverlapPolicy ov;      // option "overlap" and the streak of whole frames: which of them run T1 on `front`
+    bool frame_overlapped = false;  // the whole frame being queued runs overlapped (mark_consumed)
+    int opt_front_priority = 0; // stream priority `front` is created with: 0 default, 1 lowest, 2 highest (option "front_priority")
     int opt_tail_cus = 0;       // CUs per XCD reserved for the tail stream when overlapping (0 = no CU masks)
     hipStream_t front = nullptr;
     hipStream_t masked_tail = nullptr;
+    hipEvent_t joined = nullptr;  // recorded on `stream` when a streak of overlapped frames begins: `front` waits for it
     bool list_valid = false;    // bins match list_P / current cloud / resolution / window
     float list_P[12] = {0};
     int opt_mode = 1;           // 0 = two-pass global atomics (the reference's structure),
@@ -439,6 +443,7 @@ int ensure_store(rtr_ctx *c, rtr_ctx::Target &t, rtr_ctx::FrontSet &f, int k, hi
         dfree(st.ext0); dfree(st.meta);
         f.nst = f.ntiles = 0;
         f.consts = rtr::StoreConsts{};
+        f.lean_pending = false;
         const size_t meta_bytes = rtr::ts_meta_words(nst, nt) * sizeof(uint32_t);
         // (+ 16 entries of slack: the tile kernel's sweeps read a few entries past the piece they are masking)
         HIP_TRY(c, hipMalloc((void **)&st.ext0, ((size_t)nst * rtr::kS0 + 16) * sizeof(uint64_t)));
@@ -637,8 +642,10 @@ hipError_t sync_streams(rtr_ctx *c) {
 }
 
 // after the last reader of the active list / bin set has been queued on the tail stream
+// (with option "overlap" = 1 behind every reader, as ever; otherwise only behind overlapped frames -- a streak starts
+// by joining the two streams, bin_points)
 void mark_consumed(rtr_ctx *c) {
-    if (!c->front) return;
+    if (!c->front || !(c->ov.mode == 1 || c->frame_overlapped)) return;
     auto &f = c->F();
     if (hipEventRecord(f.consumed, c->stream) == hipSuccess) f.consumed_valid = true;
 }
@@ -720,7 +727,8 @@ rtr::TilePyr tile_pyr(const rtr_ctx *c, const rtr_ctx::Target &t, int k, bool en
 
 }  // namespace
 
-static int set_overlap(rtr_ctx *c, bool on);
+static int set_overlap(rtr_ctx *c, int value);
+static void overlap_teardown(rtr_ctx *c);
 
 extern "C" {
 
@@ -764,6 +772,7 @@ int rtr_create(rtr_ctx **out, int device) {
     }
     c->stream = c->own_stream;
     c->split_cooldown = kSplitCooldown;
+    c->ov.set_mode(-1);
     // (the minmax words serve RTR_BUF_MINMAX before any resolution is set)
     e = mapped_word(&c->split_host, &c->split_dev);
     for (auto *t : {&c->frame, &c->views}) {
@@ -785,7 +794,7 @@ int rtr_destroy(rtr_ctx *c) {
     DevGuard g(c->device);
     (void)sync_streams(c);
     (void)collect_timing(c);
-    (void)set_overlap(c, false);
+    overlap_teardown(c);
     for (auto &p : c->pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     free_frame(c);
     free_cloud(c);
@@ -810,6 +819,7 @@ const char *rtr_last_error(const rtr_ctx *c) { return c ? c->err.c_str() : g_cre
 
 int rtr_set_params(rtr_ctx *c, const rtr_params *p) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, p != nullptr, "params is NULL");
     NEED(c, p->levels >= 1 && p->levels <= 8, "levels must be in 1..8");
     c->prm = *p;
@@ -817,74 +827,127 @@ int rtr_set_params(rtr_ctx *c, const rtr_params *p) {
     return RTR_OK;
 }
 
-// Option "overlap": whole-frame renders put T1 on a second stream and alternate between two
-// list / bin sets, so the HBM-bound stream of frame k+1 runs beside the latency-bound tail of
-// frame k.  With "tail_cus" = t > 0 the two streams get disjoint CU masks (t CUs of every XCD for
+// Option "overlap": whole-frame renders put T1 on a second stream and alternate between two tile stores and extent
+// pools, so the point kernel of frame k+1 -- a latency chain whose wave slots drain from a quarter of its run on --
+// runs beside the tile kernel and prefilter of frame k.  1: every whole frame that can; -1: by the streak of whole
+// frames (rtr_overlap_policy.h); 0: never, and the second store and pool are given back.
+// The front stream has the default priority: created with the lowest one, so that the context's or caller's stream wins
+// dispatch, T1 ends later and the tile kernel gains nothing ("Overlap"; option "front_priority").
+// With "tail_cus" = t > 0 (and "overlap" = 1) the two streams get disjoint CU masks instead (t CUs of every XCD for
 // the tail, the rest for T1) so neither takes the other's wave slots.  The bit -> CU mapping of a
 // mask is not documented for 8-XCD parts (XCD-interleaved or XCD-blocked); the pattern below
 // gives every XCD exactly t tail CUs under both numberings.
-static int set_overlap(rtr_ctx *c, bool on) {
-    DevGuard g(c->device);
-    HIP_TRY(c, sync_streams(c));
-    (void)collect_timing(c);
-    if (!on) {
-        if (c->masked_tail && c->stream == c->masked_tail) c->stream = c->own_stream;
-        if (c->front) (void)hipStreamDestroy(c->front);
-        if (c->masked_tail) (void)hipStreamDestroy(c->masked_tail);
-        c->front = c->masked_tail = nullptr;
-        for (auto &f : c->frame.fs) {
-            if (f.binned) (void)hipEventDestroy(f.binned);
-            if (f.consumed) (void)hipEventDestroy(f.consumed);
-            f.binned = f.consumed = nullptr;
-            f.consumed_valid = false;
-        }
-        c->opt_overlap = 0;
-        return RTR_OK;
+static void overlap_teardown(rtr_ctx *c) {  // (both streams idle)
+    if (c->masked_tail && c->stream == c->masked_tail) c->stream = c->own_stream;
+    if (c->front) (void)hipStreamDestroy(c->front);
+    if (c->masked_tail) (void)hipStreamDestroy(c->masked_tail);
+    c->front = c->masked_tail = nullptr;
+    for (auto &f : c->frame.fs) {
+        if (f.binned) (void)hipEventDestroy(f.binned);
+        if (f.consumed) (void)hipEventDestroy(f.consumed);
+        f.binned = f.consumed = nullptr;
+        f.consumed_valid = false;
     }
-    if (c->opt_overlap) return RTR_OK;
-    // (the peers of a sharded frame read THE exported tile store; alternating between two of them is for single-GPU frames)
-    if (c->p2p.open) return fail(c, RTR_ERR_INVALID, "option overlap cannot be switched on while the peer-to-peer exchange is open (rtr_p2p_close first)");
-    int ncu = 0;
-    HIP_TRY(c, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-    if (c->opt_tail_cus > 0) {
-        if (ncu != 256) return fail(c, RTR_ERR_UNSUPPORTED, "tail_cus needs the 256-CU / 8-XCD part (device has %d CUs)", ncu);
+    if (c->joined) (void)hipEventDestroy(c->joined);
+    c->joined = nullptr;
+}
+
+// the front stream and the events of the single frame's two sets, created once and kept (all or nothing)
+static hipError_t overlap_streams(rtr_ctx *c) {
+    if (c->front) return hipSuccess;
+    hipError_t e = hipSuccess;
+    if (c->ov.mode == 1 && c->opt_tail_cus > 0) {
         uint32_t tail[8] = {0}, head[8] = {0};
         for (int i = 0; i < 256; ++i) {
             int a = i % 8, b = (i / 8) % 4, x = i / 32;
             bool is_tail = b * 8 + (a + x) % 8 < c->opt_tail_cus;
             (is_tail ? tail : head)[i / 32] |= 1u << (i % 32);
         }
-        HIP_TRY(c, hipExtStreamCreateWithCUMask(&c->front, 8, head));
-        hipError_t e = hipExtStreamCreateWithCUMask(&c->masked_tail, 8, tail);
-        if (e != hipSuccess) {
-            (void)hipStreamDestroy(c->front);
-            c->front = nullptr;
-            return fail(c, RTR_ERR_HIP, "hipExtStreamCreateWithCUMask failed: %s", hipGetErrorString(e));
-        }
-        if (c->stream == c->own_stream) c->stream = c->masked_tail;
+        e = hipExtStreamCreateWithCUMask(&c->front, 8, head);
+        if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&c->masked_tail, 8, tail);
+        if (e == hipSuccess && c->stream == c->own_stream) c->stream = c->masked_tail;
+    } else if (c->opt_front_priority) {
+        int least = 0, greatest = 0;  // (numerically, the least priority is the larger value)
+        e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->front, hipStreamNonBlocking, c->opt_front_priority == 1 ? least : greatest);
     } else {
-        HIP_TRY(c, hipStreamCreateWithFlags(&c->front, hipStreamNonBlocking));
+        e = hipStreamCreateWithFlags(&c->front, hipStreamNonBlocking);
     }
-    for (int k = 0; k < 2; ++k) {  // (the single frame's two sets)
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {  // (the single frame's two sets)
         auto &f = c->frame.fs[k];
-        hipError_t e = hipEventCreateWithFlags(&f.binned, hipEventDisableTiming);
+        e = hipEventCreateWithFlags(&f.binned, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&f.consumed, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            int rc = fail(c, RTR_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(e));
-            c->opt_overlap = 1;  // so that the teardown below runs
-            (void)set_overlap(c, false);
-            return rc;
-        }
         f.consumed_valid = false;
     }
-    c->opt_overlap = 1;
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->joined, hipEventDisableTiming);
+    if (e != hipSuccess) overlap_teardown(c);
+    return e;
+}
+
+static int set_overlap(rtr_ctx *c, int value) {
+    NEED(c, value >= -1 && value <= 1, "overlap: -1 (automatic), 0 or 1");
+    if (value == c->ov.mode && value != 0) return RTR_OK;
+    // (the peers of a sharded frame read THE exported tile store; alternating between two of them is for single-GPU frames)
+    if (value == 1 && c->p2p.open) return fail(c, RTR_ERR_INVALID, "option overlap cannot be switched on while the peer-to-peer exchange is open (rtr_p2p_close first)");
+    DevGuard g(c->device);
+    HIP_TRY(c, sync_streams(c));
+    (void)collect_timing(c);
+    if (value == 1 && c->opt_tail_cus > 0) {
+        int ncu = 0;
+        HIP_TRY(c, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+        if (ncu != 256) return fail(c, RTR_ERR_UNSUPPORTED, "tail_cus needs the 256-CU / 8-XCD part (device has %d CUs)", ncu);
+    }
+    overlap_teardown(c);  // (the streams of 1 and -1 differ with "tail_cus")
+    c->ov.set_mode(value);
+    if (value == 0) {  // the set the last frame did not use goes back -- unless the peers were given its handles
+        auto &o = c->frame.fs[c->frame.cur ^ 1];
+        if (!(c->frame.cur == 1 && (c->p2p.open || c->p2p.red))) {
+            dfree(o.dyn); dfree(o.store.ext0); dfree(o.store.meta);
+            o.dyn_cap = o.pool_n = 0;
+            o.nst = o.ntiles = 0;
+            o.consts = rtr::StoreConsts{};
+            o.parity = 0;
+            o.lean_pending = false;
+        }
+        return RTR_OK;
+    }
+    if (value == 1) {
+        const hipError_t e = overlap_streams(c);
+        if (e != hipSuccess) {
+            c->ov.set_mode(0);
+            return fail(c, RTR_ERR_HIP, "option overlap: creating the front stream failed: %s", hipGetErrorString(e));
+        }
+    }
     return RTR_OK;
+}
+
+// A whole frame that the policy wants overlapped and that does not follow an overlapped one: the streams, and in the
+// automatic mode the second store and pool -- there a failure is no error, the context stays serial
+static bool overlap_ready(rtr_ctx *c) {
+    if (overlap_streams(c) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (c->ov.mode == 1) return true;  // (the sets are allocated by the frames that use them, failures are errors)
+    auto &o = c->frame.fs[c->frame.cur ^ 1];
+    const std::string err = c->err;
+    if (ensure_pool(c, c->frame, o, 0) != RTR_OK || ensure_store(c, c->frame, o, 0, c->front) != RTR_OK) {
+        (void)hipGetLastError();
+        c->err = err;
+        dfree(o.dyn); dfree(o.store.ext0); dfree(o.store.meta);
+        o.dyn_cap = o.pool_n = 0;
+        o.nst = o.ntiles = 0;
+        o.consts = rtr::StoreConsts{};
+        return false;
+    }
+    return true;
 }
 
 static int pack_cloud(rtr_ctx *c);
 
 int rtr_set_option(rtr_ctx *c, const char *key, int value) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, key != nullptr, "key is NULL");
     if (!strcmp(key, "mode")) {
         NEED(c, value == 0 || value == 1, "mode must be 0 or 1");
@@ -1013,11 +1076,16 @@ int rtr_set_option(rtr_ctx *c, const char *key, int value) {
     }
     if (!strcmp(key, "tail_cus")) {  // takes effect when "overlap" is switched on
         NEED(c, value >= 0 && value < 32, "tail_cus must be in 0..31 (CUs per XCD)");
-        NEED(c, !c->opt_overlap, "set tail_cus before overlap");
+        NEED(c, c->ov.mode != 1, "set tail_cus before overlap");
         c->opt_tail_cus = value;
         return RTR_OK;
     }
-    if (!strcmp(key, "overlap")) return set_overlap(c, value != 0);
+    if (!strcmp(key, "overlap")) return set_overlap(c, value);
+    if (!strcmp(key, "front_priority")) {  // takes effect when the front stream is next created ("overlap")
+        NEED(c, value >= 0 && value <= 2, "front_priority: 0 (default priority), 1 (lowest) or 2 (highest)");
+        c->opt_front_priority = value;
+        return RTR_OK;
+    }
     if (!strcmp(key, "keep_accum")) {
         c->opt_keep_accum = value != 0;
         return RTR_OK;
@@ -1039,6 +1107,9 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "lane_test")) *value = c->opt_lane_test;
     else if (!strcmp(key, "chunk_test")) *value = c->opt_chunk_test;
     else if (!strcmp(key, "phases")) *value = c->opt_phases;
+    else if (!strcmp(key, "overlap")) *value = c->ov.mode;
+    else if (!strcmp(key, "overlap_active")) *value = c->ov.active ? 1 : 0;  // the last whole frame ran overlapped
+    else if (!strcmp(key, "front_priority")) *value = c->opt_front_priority;
     else if (!strcmp(key, "lean")) *value = c->opt_lean;
     else if (!strcmp(key, "lean_identity")) *value = c->opt_lean_identity;
     else if (!strcmp(key, "lean_early")) *value = c->opt_lean_early;
@@ -1099,6 +1170,7 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
 // ---- clip planes (rtr.h, section 6d) ------------------------------------------------
 int rtr_set_clip_planes(rtr_ctx *c, int count, const float *planes) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, count >= 0 && count <= RTR_MAX_CLIP_PLANES, "clip planes: count outside 0..RTR_MAX_CLIP_PLANES");
     NEED(c, count == 0 || planes != nullptr, "clip planes: planes is NULL");
     rtr::Clip next{};
@@ -1127,6 +1199,7 @@ int rtr_get_clip_planes(rtr_ctx *c, int *count, float *planes) {
 
 int rtr_stream_probe(rtr_ctx *c, const float P[16]) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, P != nullptr, "P is NULL");
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
@@ -1151,11 +1224,13 @@ static int switch_stream(rtr_ctx *c, hipStream_t s) {
 
 int rtr_set_stream(rtr_ctx *c, void *s) {  // NULL is HIP's default stream, a valid choice
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     return switch_stream(c, reinterpret_cast<hipStream_t>(s));
 }
 
 int rtr_reset_stream(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     return switch_stream(c, c->masked_tail ? c->masked_tail : c->own_stream);
 }
 
@@ -1265,6 +1340,7 @@ static int repair(rtr_ctx *c, rtr_ctx::Target &t, bool slots = false, const Copy
 
 int rtr_synchronize(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
     if (int rc = repair(c, c->frame)) return rc;
@@ -1312,6 +1388,7 @@ static int complete_all(rtr_ctx *c) {
 
 int rtr_set_point_keep(rtr_ctx *c, const uint32_t *words, uint64_t nwords) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     const bool clear = words == nullptr && nwords == 0;
     NEED(c, clear || c->n > 0, "rtr_set_point_keep: no cloud");
     NEED(c, words != nullptr || nwords == 0, "rtr_set_point_keep: words is NULL");
@@ -1445,6 +1522,7 @@ static int auto_reorder(rtr_ctx *c) {
 
 int rtr_upload_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rgb, size_t rs, size_t n) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, n == 0 || (xyz && rgb), "xyz / rgb is NULL");
     NEED(c, xs >= 12 && xs % 4 == 0, "xyz_stride_bytes must be >= 12 and a multiple of 4");
     NEED(c, rs >= 3, "rgb_stride_bytes must be >= 3");
@@ -1486,6 +1564,7 @@ int rtr_upload_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
 
 int rtr_generate_synthetic(rtr_ctx *c, int scene, uint64_t seed, uint64_t first, uint64_t count, uint64_t total) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, scene == RTR_SCENE_UNIFORM_BOX || scene == RTR_SCENE_ROOM_SHELL, "unknown scene");
     NEED(c, first + count <= total, "first + count exceeds total");
     NEED(c, total < (1ull << 33), "total too large");
@@ -1522,6 +1601,7 @@ static uint64_t grown(uint64_t have, uint64_t need) {
 
 int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rgb, size_t rs, size_t m) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, m == 0 || (xyz && rgb), "xyz / rgb is NULL");
     NEED(c, xs >= 12 && xs % 4 == 0, "xyz_stride_bytes must be >= 12 and a multiple of 4");
     NEED(c, rs >= 3, "rgb_stride_bytes must be >= 3");
@@ -1768,6 +1848,7 @@ static uint64_t fitted(uint64_t have, uint64_t need) {  // capacity after a remo
 
 int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, c->n > 0, "rtr_remove_points: no cloud");
     NEED(c, keep_words != nullptr, "rtr_remove_points: keep_words is NULL");
     if (nwords != (c->n + 31) / 32)
@@ -1998,6 +2079,7 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
 // and its headers' offsets with them.  Every buffer is allocated before the first resident byte changes.
 int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_words, uint64_t nwords) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, c->n > 0, "rtr_transform_points: no cloud");
     NEED(c, M != nullptr, "rtr_transform_points: M is NULL");
     for (int i = 0; i < 12; ++i) NEED(c, std::isfinite(M[i]), "rtr_transform_points: M has a non-finite coefficient");
@@ -2150,6 +2232,7 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
 
 int rtr_reorder_points(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     DevGuard g(c->device);
     NEED(c, !c->keep_up || (c->opt_point_ids && (!c->reordered || c->perm)),
          "the cloud has a keep mask (rtr_set_point_keep), which a sort without option point_ids = 1 would lose: set "
@@ -2187,6 +2270,7 @@ int rtr_num_points(const rtr_ctx *c, uint64_t *n) {
 
 int rtr_download_points(rtr_ctx *c, float *xyzw, uint8_t *rgba, uint64_t first, uint64_t count) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, xyzw && rgba, "output is NULL");
     NEED(c, first + count <= c->n, "range exceeds the resident cloud");
     if (count == 0) return RTR_OK;
@@ -2234,6 +2318,7 @@ bool on_device(const void *p) {  // device (or managed) memory, as opposed to an
 int rtr_extract_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords, uint64_t first, uint64_t count, float *xyz,
                        size_t xs, uint8_t *rgb, size_t rs, uint32_t *indices, uint64_t *total) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, c->n > 0, "rtr_extract_points: no cloud");
     NEED(c, xyz || rgb || indices || total, "rtr_extract_points: nothing to produce (xyz, rgb, indices and total are all NULL)");
     const bool every = select_words == nullptr && nwords == 0;
@@ -2359,6 +2444,7 @@ int rtr_compose_projection(const double K[9], const double E[16], float P[16]) {
 
 int rtr_set_resolution(rtr_ctx *c, int W, int H) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, W > 0 && H > 0 && (int64_t)W * H < (1ll << 31), "bad resolution");
     if (W == c->W && H == c->H) return RTR_OK;
     DevGuard g(c->device);
@@ -2376,6 +2462,7 @@ int rtr_set_resolution(rtr_ctx *c, int W, int H) {
 
 int rtr_clear(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
     { Timed t(c, RTR_K_CLEAR); rtr::launch_clear(c->stream, c->frame.depth, c->frame.acc, (size_t)c->W * c->H); }
@@ -2401,6 +2488,10 @@ static int bin_points(rtr_ctx *c, const float P[16], bool overlapped, bool clear
     c->p2p.occ_from_scan = false;
     hipStream_t s1 = c->stream;
     if (overlapped) {
+        if (!c->ov.active) {  // (a streak begins: whatever the stream holds may still read either set)
+            HIP_TRY(c, hipEventRecord(c->joined, c->stream));
+            HIP_TRY(c, hipStreamWaitEvent(c->front, c->joined, 0));
+        }
         c->frame.cur ^= 1;
         s1 = c->front;
         if (c->F().consumed_valid) HIP_TRY(c, hipStreamWaitEvent(c->front, c->F().consumed, 0));
@@ -2408,6 +2499,10 @@ static int bin_points(rtr_ctx *c, const float P[16], bool overlapped, bool clear
     if (int rc = ensure_pool(c, c->frame, c->F(), 0)) return rc;
     if (int rc = ensure_store(c, c->frame, c->F(), 0, s1)) return rc;
     auto &t = c->F().store;
+    // (a lean frame's statistics are folded by the NEXT lean frame of its store: behind a bin with an epilogue that fold
+    // would put the older frame's counts over the newer ones, so they are folded now)
+    if (c->F().lean_pending && !lean) rtr::launch_lean_fold(s1, c->W, c->H, t, c->F().parity);
+    c->F().lean_pending = lean;
     // (automatic: 8 bytes apart -- fewer cache lines for T1's epilogue to read and reset: -2 us on C3, -2.5 us on C2 --
     // unless tiles above the split threshold have been seen lately, where the claims of all waves queue on a dozen
     // counters and those want lines of their own; any spacing can follow any other, the counters are zero between frames)
@@ -2431,6 +2526,7 @@ static int bin_points(rtr_ctx *c, const float P[16], bool overlapped, bool clear
 
 int rtr_min_depth_pass(rtr_ctx *c, const float P[16]) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, P != nullptr, "P is NULL");
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
@@ -2443,7 +2539,7 @@ int rtr_min_depth_pass(rtr_ctx *c, const float P[16]) {
         if (int rc = bin_points(c, P, false, c->p2p.whole_frame)) return rc;
         Timed t(c, RTR_K_TILE);
         rtr::launch_tile(c->stream, 1, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, c->frame.img,
-                         (c->p2p.whole_frame ? 6 : 0) | (c->lean_parity << 4), nullptr);  // 2: only writer, 4: tiles without entries are not written
+                         (c->p2p.whole_frame ? 6 : 0) | (c->F().parity << 4), nullptr);  // 2: only writer, 4: tiles without entries are not written
         mark_consumed(c);
     } else {
         if (int rc = ensure_soa(c)) return rc;
@@ -2455,6 +2551,7 @@ int rtr_min_depth_pass(rtr_ctx *c, const float P[16]) {
 
 int rtr_accumulate_pass(rtr_ctx *c, const float P[16]) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, P != nullptr, "P is NULL");
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
@@ -2493,6 +2590,7 @@ int rtr_accumulate_pass(rtr_ctx *c, const float P[16]) {
 
 int rtr_resolve(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
     { Timed t(c, RTR_K_RESOLVE); rtr::launch_resolve(c->stream, c->frame.acc, c->frame.img, (size_t)c->W * c->H); }
@@ -2501,6 +2599,7 @@ int rtr_resolve(rtr_ctx *c) {
 
 int rtr_resolve_range(rtr_ctx *c, const void *acc_dev, uint64_t first_pixel, uint64_t count) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     if (int rc = check_frame(c)) return rc;
     const uint64_t npix = (uint64_t)c->W * c->H;
     NEED(c, first_pixel % 4 == 0 && first_pixel + count <= npix, "bad pixel range (first must be a multiple of 4)");
@@ -2527,6 +2626,7 @@ static int filter_impl(rtr_ctx *c, int pyramid_parts, const rtr::Sliced *img_sli
 
 int rtr_filter(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     return filter_impl(c, 0);
 }
 
@@ -2547,19 +2647,29 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
         DevGuard g(c->device);
         // (T1 beside the previous frame's tail must not touch the frame buffers: the split tiles' pixels are then
         // reset by a launch of their own on the tail's stream)
-        const bool overlapped = c->opt_overlap && c->front;
+        bool overlapped = c->ov.frame(!c->p2p.open && (c->ov.mode == 1 || !c->p2p.red), with_filter != 0, c->W, c->H, c->cloud_seq);
+        if (overlapped && !c->ov.active && !overlap_ready(c)) {
+            c->ov.resources_failed();
+            overlapped = false;
+        }
+        c->frame_overlapped = overlapped;
         bool split_launch = c->opt_heavy > 0;  // (split_threshold 0: nothing is ever split)
         if (split_launch) {
             if (__atomic_load_n(c->split_host, __ATOMIC_RELAXED) != 0u) c->split_cooldown = kSplitCooldown;
             split_launch = c->split_cooldown > 0;
             if (c->split_cooldown > 0) --c->split_cooldown;
         }
-        // LEAN frames (rtr_kernels.h, ts_off_order): no split launch pending, one stream, no peers -- T1 ends without
-        // ticket and epilogue, the tile workgroups read and reset their stream counters themselves
-        const bool lean = c->opt_lean && !overlapped && !split_launch && !c->p2p.open;
-        if ((rc = bin_points(c, P, overlapped, !overlapped, !split_launch, lean))) return rc;
+        // LEAN frames (rtr_kernels.h, ts_off_order): no split launch pending, no peers -- T1 ends without ticket and
+        // epilogue, the tile workgroups read and reset the stream counters of the store they consume themselves.  The
+        // parity is the store's: each of an overlapped streak's two stores sees every second frame
+        const bool lean = c->opt_lean && !split_launch && !c->p2p.open;
+        if ((rc = bin_points(c, P, overlapped, !overlapped, !split_launch, lean))) {
+            c->frame_overlapped = false;
+            c->ov.other_call();
+            return rc;
+        }
         if (lean) {
-            c->lean_parity ^= 1;
+            c->F().parity ^= 1;
             c->last_lean = true;
         }
         if (overlapped && split_launch) rtr::launch_reset_split(c->stream, c->W, c->H, c->F().store, c->frame.depth, c->frame.acc);
@@ -2570,7 +2680,7 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
         {
             Timed t(c, RTR_K_TILE);
             rtr::launch_tile(c->stream, 0, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, c->frame.img,
-                             c->opt_keep_accum | (lean ? lean_bits(c, c->frame) : 0) | (c->lean_parity << 4), fused ? &pyr : nullptr);
+                             c->opt_keep_accum | (lean ? lean_bits(c, c->frame) : 0) | (c->F().parity << 4), fused ? &pyr : nullptr);
             if (lean) c->list_valid = false;  // (the tile launch has consumed and reset the stream counters)
             // tiles heavier than option "split_threshold" are split over several workgroups: a second launch takes
             // the minimum over each slice (they meet in the depth buffer), then -- behind a barrier over its 256
@@ -2581,6 +2691,8 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
                                  c->opt_keep_accum, fused ? &pyr : nullptr);
         }
         mark_consumed(c);
+        c->frame_overlapped = false;
+        c->ov.frame_done(overlapped);
         if ((rc = launch_check(c, "tile frame"))) return rc;
         auto &rec = c->jr.frame;  // (what a synchronising call repeats if the adaptive pool overflowed)
         memcpy(rec.P, P, sizeof(float) * 16);
@@ -2588,6 +2700,8 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
         rec.count = 1;
         rec.clip = c->clip;
     } else {
+        (void)c->ov.frame(false, false, c->W, c->H, c->cloud_seq);
+        c->ov.frame_done(false);
         c->force_atomic = true;  // the phase calls below must not take the binned form either
         rc = rtr_clear(c);
         if (!rc) rc = rtr_min_depth_pass(c, P);
@@ -2603,6 +2717,7 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
 static int frame_to_host(rtr_ctx *c, const float P[16], uint8_t *host_img, float *host_depth, int with_filter) {
     if (!c) return RTR_ERR_INVALID;
     if (!host_img && !host_depth) return fail(c, RTR_ERR_NO_OUTPUT, "both outputs are NULL (project_cloud.cu:270-273)");
+    c->ov.other_call();
     if (int rc = rtr_render(c, P, with_filter)) return rc;
     DevGuard g(c->device);
     const size_t npix = (size_t)c->W * c->H;
@@ -2646,6 +2761,7 @@ static int ensure_host_out(rtr_ctx *c) {
 
 int rtr_host_output_buffers(rtr_ctx *c, int slot, uint8_t **img, float **depth) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, slot >= 0 && slot < RTR_ASYNC_SLOTS, "slot out of range");
     if (int rc = check_frame(c)) return rc;
     DevGuard g(c->device);
@@ -2681,6 +2797,7 @@ static int queue_slot(rtr_ctx *c, const float P[16], int slot, int with_filter) 
 
 int rtr_project_async(rtr_ctx *c, const float P[16], int slot, int with_filter) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, P != nullptr, "P is NULL");
     NEED(c, slot >= 0 && slot < RTR_ASYNC_SLOTS, "slot out of range");
     if (int rc = check_frame(c)) return rc;
@@ -2691,6 +2808,7 @@ int rtr_project_async(rtr_ctx *c, const float P[16], int slot, int with_filter) 
 
 int rtr_wait(rtr_ctx *c, int slot) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, slot >= -1 && slot < RTR_ASYNC_SLOTS, "slot out of range (-1: every slot)");
     DevGuard g(c->device);
     for (int k = 0; k < RTR_ASYNC_SLOTS; ++k)
@@ -2728,10 +2846,11 @@ static int p2p_alloc(rtr_ctx *c) {  // this rank's exchange buffers (per resolut
 
 int rtr_p2p_export(rtr_ctx *c, rtr_p2p_handles *mine) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, mine != nullptr, "handles is NULL");
     if (int rc = check_frame(c)) return rc;
     static_assert(sizeof(hipIpcMemHandle_t) <= 64, "handle block too small");
-    NEED(c, !c->opt_overlap, "the peer-to-peer exchange needs option overlap off (the peers map ONE tile store)");
+    NEED(c, c->ov.mode != 1, "the peer-to-peer exchange needs option overlap off (the peers map ONE tile store)");
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
     // (the owner-computes form reads the peers' tile stores: allocate this rank's now -- it is sized by the cloud, for
@@ -2757,6 +2876,7 @@ int rtr_p2p_export(rtr_ctx *c, rtr_p2p_handles *mine) {
 
 int rtr_p2p_open(rtr_ctx *c, int rank, int world, const rtr_p2p_handles *all) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, all != nullptr, "handles is NULL");
     NEED(c, world >= 1 && world <= RTR_P2P_MAX_RANKS && rank >= 0 && rank < world, "bad rank / world");
     if (int rc = check_frame(c)) return rc;
@@ -2811,6 +2931,7 @@ int rtr_p2p_open(rtr_ctx *c, int rank, int world, const rtr_p2p_handles *all) {
 
 int rtr_p2p_close(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
     p2p_release(c);
@@ -2833,6 +2954,7 @@ void p2p_barrier(rtr_ctx *c) {
 
 int rtr_p2p_min_depth(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     if (int rc = check_frame(c)) return rc;
     NEED(c, c->p2p.open, "rtr_p2p_open has not been called");
     DevGuard g(c->device);
@@ -2857,6 +2979,7 @@ int rtr_p2p_min_depth(rtr_ctx *c) {
 
 int rtr_p2p_sum_resolve(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     if (int rc = check_frame(c)) return rc;
     NEED(c, c->p2p.open, "rtr_p2p_open has not been called");
     DevGuard g(c->device);
@@ -2877,6 +3000,7 @@ int rtr_p2p_sum_resolve(rtr_ctx *c) {
 
 int rtr_p2p_render(rtr_ctx *c, const float P[16], int with_filter) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, P != nullptr, "P is NULL");
     NEED(c, c->p2p.open, "rtr_p2p_open has not been called");
     if (with_filter) {  // fail before any rank enters a barrier the others would wait in
@@ -2936,12 +3060,13 @@ int rtr_p2p_render(rtr_ctx *c, const float P[16], int with_filter) {
 // previous frame's owner is still collecting (that owner arrives at it only behind its collect and prefilter).
 int rtr_p2p_render_owned(rtr_ctx *c, const float P[16], int with_filter, int frame_owner) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, P != nullptr, "P is NULL");
     NEED(c, c->p2p.open, "rtr_p2p_open has not been called");
     auto &q = c->p2p;
     NEED(c, frame_owner >= 0 && frame_owner < q.world, "frame_owner out of range");
     NEED(c, use_tiles(c), "the owner-computes form needs the tile-binned mode (option mode = 1, <= 4096 tiles)");
-    NEED(c, !c->opt_overlap, "the owner-computes form does not combine with option overlap");
+    NEED(c, c->ov.mode != 1, "the owner-computes form does not combine with option overlap");
     const bool mine = frame_owner == q.rank;
     DevGuard g(c->device);
     if (with_filter && mine)  // (fail before any rank enters a barrier the others would wait in)
@@ -2981,6 +3106,7 @@ int rtr_p2p_render_owned(rtr_ctx *c, const float P[16], int with_filter, int fra
 
 int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, P != nullptr, "P is NULL");
     NEED(c, what >= 1 && what <= 3, "what must be a non-empty mask of RTR_POINTS_IDS (1) and RTR_POINTS_VISIBLE (2)");
     NEED(c, c->cap > 0, "no cloud: rtr_upload_points / rtr_generate_synthetic first");
@@ -3024,6 +3150,7 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
 int rtr_select_points(rtr_ctx *c, int plane_count, const float *planes, const float *P, const int rect[4], int op,
                       uint64_t stats[4]) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, c->cap > 0, "rtr_select_points: no cloud");
     NEED(c, plane_count >= 0 && plane_count <= RTR_MAX_CLIP_PLANES, "rtr_select_points: plane_count outside 0..RTR_MAX_CLIP_PLANES");
     NEED(c, plane_count == 0 || planes != nullptr, "rtr_select_points: planes is NULL");
@@ -3081,6 +3208,7 @@ int rtr_select_points(rtr_ctx *c, int plane_count, const float *planes, const fl
 
 int rtr_clear_selection(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     DevGuard g(c->device);
     free_select(c);
     return RTR_OK;
@@ -3097,7 +3225,7 @@ int rtr_clear_selection(rtr_ctx *c) {
 // batch (repair).
 
 static bool views_binned(const rtr_ctx *c) {  // the binned form serves batches; the rest loop over the atomic form
-    return c->opt_mode == 1 && rtr::tile_count(c->W, c->H) <= 4096 && !c->p2p.open && !c->opt_overlap;
+    return c->opt_mode == 1 && rtr::tile_count(c->W, c->H) <= 4096 && !c->p2p.open && c->ov.mode != 1;
 }
 
 // buffers, scratch and (binned) tile stores / pools for `count` views at this resolution and cloud
@@ -3187,6 +3315,7 @@ static int views_enqueue(rtr_ctx *c, int count, const float *P, int with_filter)
 
 int rtr_render_views(rtr_ctx *c, int count, const float *P, int with_filter) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, count >= 1 && count <= RTR_MAX_VIEWS, "count must be in 1..RTR_MAX_VIEWS");
     NEED(c, P != nullptr, "P is NULL");
     NEED(c, c->cap > 0, "no cloud has been uploaded");
@@ -3209,6 +3338,7 @@ int rtr_render_views(rtr_ctx *c, int count, const float *P, int with_filter) {
 
 int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, ptr != nullptr, "dev_ptr is NULL");
     if (which != RTR_BUF_MINMAX && which != RTR_BUF_VIEW_MINMAX && which != RTR_BUF_POINT_KEEP && which != RTR_BUF_SELECTION)
         if (int rc = check_frame(c)) return rc;
@@ -3251,6 +3381,7 @@ int rtr_device_buffer(rtr_ctx *c, int which, void **ptr, size_t *bytes) {
 
 int rtr_download_buffer(rtr_ctx *c, int which, void *host, size_t bytes) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, host != nullptr, "host is NULL");
     void *p = nullptr; size_t b = 0;
     int rc = rtr_device_buffer(c, which, &p, &b);
@@ -3293,10 +3424,11 @@ extern "C" int rtr_debug_stamps(rtr_ctx *c, unsigned long long out[64]) {  // ti
 
 int rtr_frame_stats(rtr_ctx *c, uint32_t out[8]) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, out != nullptr, "out is NULL");
     NEED(c, c->F().store.meta != nullptr, "no binned frame yet");
     DevGuard g(c->device);
-    if (c->last_lean) rtr::launch_lean_fold(c->stream, c->W, c->H, c->F().store, c->lean_parity);  // (lean frames fold lazily)
+    if (c->last_lean) rtr::launch_lean_fold(c->stream, c->W, c->H, c->F().store, c->F().parity);  // (lean frames fold lazily)
     HIP_TRY(c, hipMemcpyAsync(out, rtr::ts_hdr(c->F().store), 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, sync_streams(c));
     return RTR_OK;
@@ -3304,6 +3436,7 @@ int rtr_frame_stats(rtr_ctx *c, uint32_t out[8]) {
 
 int rtr_timing_enable(rtr_ctx *c, int on) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     DevGuard g(c->device);
     (void)collect_timing(c);
     c->timing = on < 0 ? 0 : (on > 4 ? 1 : on);
@@ -3313,6 +3446,7 @@ int rtr_timing_enable(rtr_ctx *c, int on) {
 
 int rtr_timing_reset(rtr_ctx *c) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     DevGuard g(c->device);
     (void)collect_timing(c);
     for (int k = 0; k < RTR_K_COUNT; ++k) { c->total_ms[k] = 0; c->launches[k] = 0; }
@@ -3321,6 +3455,7 @@ int rtr_timing_reset(rtr_ctx *c) {
 
 int rtr_timing_get(rtr_ctx *c, int k, double *total_ms, uint64_t *launches) {
     if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
     NEED(c, k >= 0 && k < RTR_K_COUNT, "bad kernel id");
     DevGuard g(c->device);
     if (int rc = collect_timing(c)) return rc;

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Frame throughput with option "overlap" (GPU box only): wall time of a run of whole-frame
-renders for each (overlap, tail_cus) setting, plus a tensor checksum per setting so that any
-difference between the settings shows.  Not part of the product; used to fill DESIGN.md."""
+renders for each (overlap, tail_cus) setting -- overlap -1 is the automatic mode, e.g. --settings 0:0,1:0,-1:0 --
+plus a tensor checksum per setting so that any difference between the settings shows.  --front-priority 0 / 1 / 2 sets
+option "front_priority" first (the front stream is created anew for every setting), --point-grid the point kernel's
+grid.  Not part of the product; used to fill DESIGN.md."""
 import argparse
 import json
 import os
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--filter", type=int, default=1)
     ap.add_argument("--cull", type=int, default=0)
     ap.add_argument("--point-grid", type=int, default=0)
+    ap.add_argument("--front-priority", type=int, default=-1, choices=[-1, 0, 1, 2])
     args = ap.parse_args()
     pkg = entry.load_package()
     W, H, n = args.width, args.height, args.points
@@ -37,6 +40,8 @@ def main():
         p.set_option("cull", 1)
     if args.point_grid:
         p.set_option("point_grid", args.point_grid)
+    if args.front_priority >= 0:
+        p.set_option("front_priority", args.front_priority)
     poses = [pkg.orbit_projection(k, W, H) for k in range(args.frames + 10)]
     for setting in args.settings.split(","):
         ov, cus = (int(v) for v in setting.split(":"))
@@ -53,6 +58,11 @@ def main():
         t0 = time.perf_counter()
         for k in range(args.frames):
             p.render(poses[10 + k], bool(args.filter))
+        host = time.perf_counter() - t0  # (the calls alone: near ms_per_frame when the host is the limit)
+        try:
+            active = p.get_option("overlap_active")
+        except Exception:  # (a library older than the option)
+            active = None
         p.synchronize()
         dt = time.perf_counter() - t0
         # checksum of the last frame and of one rendered right after a pose change
@@ -67,7 +77,8 @@ def main():
         t = p.timing()
         p.timing_enable(False)
         t1 = {name: round(ms / max(cnt, 1) * 1e3, 1) for name, (ms, cnt) in t.items() if cnt}
-        print(json.dumps({"overlap": ov, "tail_cus": cus, "ms_per_frame": round(dt / args.frames * 1e3, 4),
+        print(json.dumps({"overlap": ov, "tail_cus": cus, "overlap_active": active, "ms_per_frame": round(dt / args.frames * 1e3, 4),
+                          "host_ms_per_frame": round(host / args.frames * 1e3, 4),
                           "gpts_per_s": round(n * args.frames / dt / 1e9, 1), "crc_last": crc, "crc_pose7": crc2,
                           "timed": t1}), flush=True)
     p.close()
