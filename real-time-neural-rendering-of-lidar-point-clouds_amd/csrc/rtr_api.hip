@@ -1350,9 +1350,9 @@ int rtr_synchronize(rtr_ctx *c) {
 }  // extern "C"
 
 namespace {
-struct AppendBufs {  // rtr_append_points' / rtr_remove_points' buffers: freed on every exit path unless taken
+struct DevBufs {  // a call's device buffers: freed on every exit path unless a resident array has taken them (swap_in)
     std::vector<void *> p;
-    ~AppendBufs() { for (void *q : p) if (q) (void)hipFree(q); }
+    ~DevBufs() { for (void *q : p) if (q) (void)hipFree(q); }
     template <class T> hipError_t get(T **out, size_t bytes) {
         void *q = nullptr;
         const hipError_t e = hipMalloc(&q, bytes ? bytes : 4);
@@ -1367,6 +1367,33 @@ struct AppendBufs {  // rtr_append_points' / rtr_remove_points' buffers: freed o
         field = next;
     }
 };
+
+hipError_t d2d(hipStream_t s, void *dst, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+}
+
+// The packed form's invariants, each in one place (rtr::PackedXyz; `units`: 32-byte units of both plane streams).
+// Resident bytes: blocks + headers
+uint64_t pack_bytes(uint64_t units, uint64_t chunks) { return units * 32 + chunks * 32; }
+// The spare bytes behind both plane streams read as zero: the last lanes' loads run into them
+hipError_t zero_spare(hipStream_t s, uint32_t *planes, uint32_t *planes_b, uint64_t units) {
+    const hipError_t e = hipMemsetAsync(planes + units * 2, 0, (rtr::pack_b_dwords(units) - units * 2) * 4, s);
+    return e != hipSuccess ? e : hipMemsetAsync(planes_b + units * 6, 0, 64, s);
+}
+// The blocks of the chunks in front of a rebuilt window, `units` of them, into fresh planes (the A region's size
+// changes, so the B region moves)
+hipError_t copy_blocks(hipStream_t s, uint32_t *planes, uint32_t *planes_b, const rtr_ctx *c, uint64_t units) {
+    const hipError_t e = d2d(s, planes, c->pk_planes, units * 2 * 4);
+    return e != hipSuccess ? e : d2d(s, planes_b, c->pk_planes_b, units * 6 * 4);
+}
+
+// Calls that take or return upload-order indices: a cloud sorted by the library must have kept its permutation.
+// `verb`: what the call would do with the indices; `or_else`: the call's own way round it, if it has one
+int need_upload_order(rtr_ctx *c, const char *verb = "mapped", const char *or_else = "") {
+    if (!c->reordered || c->perm) return RTR_OK;
+    return fail(c, RTR_ERR_INVALID, "the resident cloud was reordered without option point_ids = 1, so upload-order indices "
+                "cannot be %s: set point_ids = 1 before the upload (or upload with auto_reorder = 0)%s", verb, or_else);
+}
 }  // namespace
 
 extern "C" {
@@ -1394,9 +1421,8 @@ int rtr_set_point_keep(rtr_ctx *c, const uint32_t *words, uint64_t nwords) {
     NEED(c, words != nullptr || nwords == 0, "rtr_set_point_keep: words is NULL");
     if (!clear && nwords != (c->n + 31) / 32)
         return fail(c, RTR_ERR_INVALID, "rtr_set_point_keep: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
-    NEED(c, clear || !c->reordered || c->perm,
-         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be mapped: set "
-         "point_ids = 1 before the upload (or upload with auto_reorder = 0)");
+    if (!clear)
+        if (int rc = need_upload_order(c)) return rc;
     DevGuard g(c->device);
     if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the mask they were issued with)
     if (clear) {
@@ -1405,26 +1431,21 @@ int rtr_set_point_keep(rtr_ctx *c, const uint32_t *words, uint64_t nwords) {
         return RTR_OK;
     }
     const uint64_t nchunks = (c->n + 255) / 256;
-    struct Buf {  // freed on every exit path unless taken
-        void *p = nullptr;
-        ~Buf() { if (p) (void)hipFree(p); }
-    } up, res, sum;
-    HIP_TRY(c, hipMalloc(&up.p, nwords * 4));
+    DevBufs buf;
+    uint32_t *up, *res = c->keep_res;
+    uint8_t *sum = c->keep_sum;
+    HIP_TRY(c, buf.get(&up, nwords * 4));
     // (the caller's words, host or device memory, into a new buffer: a failed copy leaves the old mask in force)
-    HIP_TRY(c, hipMemcpyAsync(up.p, words, nwords * 4, hipMemcpyDefault, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(up, words, nwords * 4, hipMemcpyDefault, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!c->keep_res) {
-        HIP_TRY(c, hipMalloc(&res.p, nchunks * 32));
-        HIP_TRY(c, hipMalloc(&sum.p, (nchunks + 3) & ~3ull));  // (read as whole dwords)
+    if (!res) {
+        HIP_TRY(c, buf.get(&res, nchunks * 32));
+        HIP_TRY(c, buf.get(&sum, (nchunks + 3) & ~3ull));  // (read as whole dwords)
     }
-    uint32_t *const kres = c->keep_res ? c->keep_res : (uint32_t *)res.p;
-    uint8_t *const ksum = c->keep_sum ? c->keep_sum : (uint8_t *)sum.p;
-    rtr::launch_keep_build(c->stream, (uint32_t *)up.p, c->reordered ? c->perm : nullptr, c->n, kres, ksum);
+    rtr::launch_keep_build(c->stream, up, c->reordered ? c->perm : nullptr, c->n, res, sum);
     HIP_TRY(c, sync_streams(c));
     if (int rc = launch_check(c, "keep mask")) return rc;
-    dfree(c->keep_up);
-    c->keep_up = (uint32_t *)up.p, up.p = nullptr;
-    if (res.p) c->keep_res = (uint32_t *)res.p, c->keep_sum = (uint8_t *)sum.p, res.p = sum.p = nullptr;
+    buf.swap_in(c->keep_up, up); buf.swap_in(c->keep_res, res); buf.swap_in(c->keep_sum, sum);
     c->list_valid = false;  // (bins of another mask serve no later pass)
     return RTR_OK;
 }
@@ -1448,49 +1469,43 @@ static int pack_cloud(rtr_ctx *c) {
     free_pack(c);
     if (c->opt_pack == 0 || c->n == 0) return RTR_OK;
     const uint64_t n4 = (c->n + 3) / 4, nchunks = (n4 + 63) / 64;
-    struct Scratch {  // freed on every exit path
-        void *p = nullptr;
-        ~Scratch() { if (p) (void)hipFree(p); }
-    } cnt, tot;
-    uint4 *hdr = nullptr;
-    uint32_t *planes = nullptr;
-    auto give_up = [&]() {
+    DevBufs buf;
+    uint4 *hdr;
+    uint32_t *planes, *cnt;
+    uint64_t *tot;
+    auto give_up = [&]() {  // (buf frees what was allocated)
         (void)hipGetLastError();
-        if (hdr) (void)hipFree(hdr);
-        if (planes) (void)hipFree(planes);
         return RTR_OK;
     };
     // (+ one zero header: the point kernel reads headers in pairs)
-    if (hipMalloc((void **)&hdr, (nchunks + 1) * 2 * sizeof(uint4)) != hipSuccess) return give_up();
+    if (buf.get(&hdr, (nchunks + 1) * 2 * sizeof(uint4)) != hipSuccess) return give_up();
     if (hipMemsetAsync(hdr + nchunks * 2, 0, 2 * sizeof(uint4), c->stream) != hipSuccess) return give_up();
-    if (hipMalloc(&cnt.p, nchunks * sizeof(uint32_t)) != hipSuccess) return give_up();
-    if (hipMalloc(&tot.p, 2 * sizeof(uint64_t)) != hipSuccess) return give_up();
-    if (hipMemsetAsync(tot.p, 0, 2 * sizeof(uint64_t), c->stream) != hipSuccess) return give_up();
+    if (buf.get(&cnt, nchunks * sizeof(uint32_t)) != hipSuccess) return give_up();
+    if (buf.get(&tot, 2 * sizeof(uint64_t)) != hipSuccess) return give_up();
+    if (hipMemsetAsync(tot, 0, 2 * sizeof(uint64_t), c->stream) != hipSuccess) return give_up();
     const rtr::Cloud cl = cloud_of(c);
-    rtr::pack_measure(c->stream, cl, hdr, (uint32_t *)cnt.p, (uint64_t *)tot.p);
+    rtr::pack_measure(c->stream, cl, hdr, cnt, tot);
     uint64_t host[2] = {0, 0};
-    if (hipMemcpyAsync(host, tot.p, sizeof host, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return give_up();
+    if (hipMemcpyAsync(host, tot, sizeof host, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return give_up();
     if (hipStreamSynchronize(c->stream) != hipSuccess) return give_up();
-    const uint64_t bytes = host[0] * 32 + nchunks * 32;  // blocks (32-byte units) + headers
+    const uint64_t bytes = pack_bytes(host[0], nchunks);
     if (c->opt_pack == 1 && bytes * 8 > n4 * 48 * 7) return give_up();  // saves less than 1/8 of the 12 B/pt stream
     // (one allocation: the A streams, 64 spare bytes, the B streams, 64 spare bytes -- the last lanes' loads run up to
     // 12 bytes past the last value of their stream)
     const uint64_t b_dw = rtr::pack_b_dwords(host[0]);
-    if (hipMalloc((void **)&planes, rtr::pack_total_dwords(host[0]) * 4) != hipSuccess) return give_up();
-    if (hipMemsetAsync(planes + host[0] * 2, 0, (b_dw - host[0] * 2) * 4, c->stream) != hipSuccess) return give_up();
-    if (hipMemsetAsync(planes + b_dw + host[0] * 6, 0, 64, c->stream) != hipSuccess) return give_up();
+    if (buf.get(&planes, rtr::pack_total_dwords(host[0]) * 4) != hipSuccess) return give_up();
+    if (zero_spare(c->stream, planes, planes + b_dw, host[0]) != hipSuccess) return give_up();
     rtr::pack_write(c->stream, cl, hdr, planes, planes + b_dw);
     if (c->opt_pack == 2) {
-        rtr::pack_verify(c->stream, cl, hdr, planes, planes + b_dw, (uint64_t *)tot.p + 1);
-        if (hipMemcpyAsync(host, tot.p, sizeof host, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return give_up();
+        rtr::pack_verify(c->stream, cl, hdr, planes, planes + b_dw, tot + 1);
+        if (hipMemcpyAsync(host, tot, sizeof host, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return give_up();
     }
     if (hipStreamSynchronize(c->stream) != hipSuccess) return give_up();
     if (c->opt_pack == 2 && host[1] != 0) {
         (void)give_up();
         return fail(c, RTR_ERR_HIP, "pack: %llu points decode to other coordinates", (unsigned long long)host[1]);
     }
-    c->pk_hdr = hdr;
-    c->pk_planes = planes;
+    buf.swap_in(c->pk_hdr, hdr); buf.swap_in(c->pk_planes, planes);
     c->pk_planes_b = planes + b_dw;
     c->pk_bytes = bytes;
     c->pk_units = c->pk_units_cap = host[0];
@@ -1520,6 +1535,40 @@ static int auto_reorder(rtr_ctx *c) {
     return RTR_OK;
 }
 
+// Host AoS points into device SoA arrays through device staging pieces of 16 Mi points (AoS -> SoA on the GPU).  Between
+// pieces only the context's stream is synchronised: both callers have drained every stream before (sync_streams /
+// complete_all) and nothing here queues on another one, so waiting for the others too would wait for nothing.
+static int stage_points(rtr_ctx *c, DevBufs &buf, const float *xyz, size_t xs, const uint8_t *rgb, size_t rs, uint64_t n,
+                        float *x, float *y, float *z, uint32_t *rgba) {
+    if (n == 0) return RTR_OK;
+    const uint64_t piece = 1ull << 24;
+    uint8_t *sx, *sc;
+    HIP_TRY(c, buf.get(&sx, std::min(n, piece) * xs));
+    HIP_TRY(c, buf.get(&sc, std::min(n, piece) * rs));
+    for (uint64_t off = 0; off < n; off += piece) {
+        const uint64_t cnt = std::min(n - off, piece);
+        HIP_TRY(c, hipMemcpyAsync(sx, (const uint8_t *)xyz + off * xs, cnt * xs, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(sc, rgb + off * rs, cnt * rs, hipMemcpyHostToDevice, c->stream));
+        rtr::launch_aos_to_soa(c->stream, sx, xs, sc, rs, cnt, x + off, y + off, z + off, rgba + off);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return RTR_OK;
+}
+
+// What every new cloud ends with (`what` filled its arrays): NaN padding, chunk boxes, options "auto_reorder" and "pack"
+static int finish_new_cloud(rtr_ctx *c, const char *what) {
+    rtr::launch_pad_nan(c->stream, c->x, c->y, c->z, c->rgba, c->n, (c->n + 3) & ~3ull);
+    rtr::launch_chunk_bounds(c->stream, cloud_of(c), c->bounds, c->spread);
+    HIP_TRY(c, sync_streams(c));
+    if (int rc = launch_check(c, what)) return rc;
+    free_pack(c);
+    if (int rc = auto_reorder(c)) return rc;
+    if (!c->pk_hdr)  // (a sort has packed already)
+        if (int rc = pack_cloud(c)) return rc;
+    drop_soa(c);
+    return RTR_OK;
+}
+
 int rtr_upload_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rgb, size_t rs, size_t n) {
     if (!c) return RTR_ERR_INVALID;
     c->ov.other_call();
@@ -1529,37 +1578,10 @@ int rtr_upload_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
     NEED(c, n < (1ull << 32), "too many points for one context (point indices are 32-bit): shard the cloud");
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
-    int rc = alloc_cloud(c, n);
-    if (rc) return rc;
-    // stage through device chunks; AoS -> SoA on the GPU
-    const uint64_t chunk = 1ull << 24;
-    struct Staging {  // freed on every exit path
-        uint8_t *p = nullptr;
-        ~Staging() { if (p) (void)hipFree(p); }
-    } stx, stc;
-    uint64_t m = n < chunk ? n : chunk;
-    if (m) {
-        HIP_TRY(c, hipMalloc((void **)&stx.p, m * xs));
-        HIP_TRY(c, hipMalloc((void **)&stc.p, m * rs));
-    }
-    uint8_t *sx = stx.p, *sc = stc.p;
-    for (uint64_t off = 0; off < n; off += chunk) {
-        uint64_t cnt = (n - off) < chunk ? (n - off) : chunk;
-        HIP_TRY(c, hipMemcpyAsync(sx, (const uint8_t *)xyz + off * xs, cnt * xs, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(sc, rgb + off * rs, cnt * rs, hipMemcpyHostToDevice, c->stream));
-        rtr::launch_aos_to_soa(c->stream, sx, xs, sc, rs, cnt, c->x + off, c->y + off, c->z + off, c->rgba + off);
-        HIP_TRY(c, sync_streams(c));
-    }
-    rtr::launch_pad_nan(c->stream, c->x, c->y, c->z, c->rgba, n, (n + 3) & ~3ull);
-    rtr::launch_chunk_bounds(c->stream, cloud_of(c), c->bounds, c->spread);
-    HIP_TRY(c, sync_streams(c));
-    if (int rc2 = launch_check(c, "aos_to_soa")) return rc2;
-    free_pack(c);
-    if (int rc2 = auto_reorder(c)) return rc2;
-    if (!c->pk_hdr)  // (a sort has packed already)
-        if (int rc2 = pack_cloud(c)) return rc2;
-    drop_soa(c);
-    return RTR_OK;
+    if (int rc = alloc_cloud(c, n)) return rc;
+    DevBufs buf;
+    if (int rc = stage_points(c, buf, xyz, xs, rgb, rs, n, c->x, c->y, c->z, c->rgba)) return rc;
+    return finish_new_cloud(c, "aos_to_soa");
 }
 
 int rtr_generate_synthetic(rtr_ctx *c, int scene, uint64_t seed, uint64_t first, uint64_t count, uint64_t total) {
@@ -1571,34 +1593,244 @@ int rtr_generate_synthetic(rtr_ctx *c, int scene, uint64_t seed, uint64_t first,
     NEED(c, count < (1ull << 32), "too many points for one context (point indices are 32-bit): shard the cloud");
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
-    int rc = alloc_cloud(c, count);
-    if (rc) return rc;
+    if (int rc = alloc_cloud(c, count)) return rc;
     rtr::launch_generate(c->stream, scene, seed, first, count, total, c->x, c->y, c->z, c->rgba);
-    rtr::launch_pad_nan(c->stream, c->x, c->y, c->z, c->rgba, count, (count + 3) & ~3ull);
-    rtr::launch_chunk_bounds(c->stream, cloud_of(c), c->bounds, c->spread);
-    HIP_TRY(c, sync_streams(c));
-    if (int rc2 = launch_check(c, "generate")) return rc2;
-    free_pack(c);
-    if (int rc2 = auto_reorder(c)) return rc2;
-    if (!c->pk_hdr)
-        if (int rc2 = pack_cloud(c)) return rc2;
-    drop_soa(c);
+    return finish_new_cloud(c, "generate");
+}
+
+// ---- editing the resident cloud (rtr.h, sections 2b - 2d) ---------------------------------------------------------
+// rtr_append_points, rtr_remove_points and rtr_transform_points change the points of some 256-point chunks, so the
+// per-chunk state of those chunks is rebuilt over a WINDOW: fp32 SoA scratch holding the chunks' new points, on which the
+// upload's kernels run in their range forms (rtr_kernels.h) -- chunk boxes and lane spreads, packed headers (the scan
+// continues from the first chunk's block offset) and blocks.  Each call builds its window in its own way (window_alloc,
+// then its own kernels fill wx / wy / wz), measures it (window_measure), commits it and ends in cloud_edited.  Append
+// and remove rebuild every chunk from c0 on and share commit_window; transform rebuilds chunks c0 .. c1, keeps the blocks
+// behind them and has a commit of its own, from the same helpers (d2d, copy_blocks, zero_spare, pack_bytes).
+struct Window {
+    uint64_t c0 = 0, wn = 0, wpad = 0, wch = 0;  // first chunk; points, padded to a multiple of 4; chunks
+    float *wx = nullptr, *wy = nullptr, *wz = nullptr;  // the points (NaN-padded by the caller)
+    float *wb = nullptr, *wsp = nullptr;         // chunk boxes, lane spreads (window_measure)
+    uint4 *whdr = nullptr;                       // packed: headers ...
+    uint32_t *cnt = nullptr;                     // ... scratch of the measure, wch words (allocated unless the caller lends some) ...
+    uint64_t first_unit = 0, units = 0;          // ... chunk c0's block offset, and the offset behind the window's last block
+    rtr::Cloud cl{};                             // the view the range forms take: the cloud from chunk c0 on
+};
+
+// The resident cloud's settings over other coordinates: no colours, packed form or keep mask
+static rtr::Cloud window_view(const rtr_ctx *c, const float *x, const float *y, const float *z, uint64_t n, const float *spread) {
+    rtr::Cloud v = cloud_of(c);
+    v.x = x, v.y = y, v.z = z, v.n = n, v.spread = spread;
+    v.rgba = nullptr;
+    v.pk = rtr::PackedXyz{nullptr, nullptr, nullptr};
+    v.keep = rtr::Keep{nullptr, nullptr};
+    return v;
+}
+
+// The counts of a window of wn points from chunk c0 on, and its point arrays for the caller to fill
+static int window_alloc(rtr_ctx *c, DevBufs &buf, Window &w, uint64_t c0, uint64_t wn) {
+    w.c0 = c0, w.wn = wn, w.wpad = (wn + 3) & ~3ull, w.wch = (wn + 255) / 256;
+    HIP_TRY(c, buf.get(&w.wx, w.wpad * 4)); HIP_TRY(c, buf.get(&w.wy, w.wpad * 4)); HIP_TRY(c, buf.get(&w.wz, w.wpad * 4));
     return RTR_OK;
 }
 
-// ---- appending (rtr.h, section 2b) ----------------------------------------------------
-// The block goes behind the resident points.  Its first points may complete the last partial 256-point chunk c0, so the
-// per-chunk state from c0 on is rebuilt over a WINDOW: fp32 SoA arrays holding chunk c0's resident points (copied, or
-// decoded from the packed form when the SoA arrays are not resident) followed by the block.  The upload's kernels run
-// on the window in their range forms (rtr_kernels.h): chunk boxes and lane spreads, packed headers (the scan continues
-// from chunk c0's block offset) and blocks, the keep mask's resident words and summaries.  Every buffer that may fail
-// to allocate is allocated before the first resident byte changes; the arrays grow with 1/8 head-room.
+// The derived half of a window whose points are queued: boxes and spreads, and for a packed cloud the headers.  Chunk
+// c0's block offset is read from its resident header -- except where the window begins a fresh chunk behind the cloud
+// (an append to whole chunks: the zero pair there holds no offset), which starts at pk_units.  An empty window (a
+// removal of whole trailing chunks) adds no unit.  units_dev: device word of the scan's total; old_end (transform): the
+// block offset of the first resident chunk behind the window.  Synchronises; `what` names the launches in an error.
+static int window_measure(rtr_ctx *c, DevBufs &buf, Window &w, uint64_t *units_dev, const char *what, uint64_t *old_end = nullptr) {
+    hipStream_t s = c->stream;
+    HIP_TRY(c, buf.get(&w.wb, w.wch * 6 * sizeof(float)));
+    HIP_TRY(c, buf.get(&w.wsp, w.wch * sizeof(float)));
+    w.cl = window_view(c, w.wx, w.wy, w.wz, w.wn, w.wsp);
+    rtr::launch_chunk_bounds(s, w.cl, w.wb, w.wsp);
+    if (c->pk_hdr) {
+        const uint64_t nch = (c->n + 255) / 256, end = w.c0 + w.wch;
+        uint4 h0 = make_uint4(0, 0, 0, 0), h1 = h0;
+        const bool resident = w.c0 < nch, tail = old_end && end < nch;
+        if (resident) HIP_TRY(c, hipMemcpyAsync(&h0, c->pk_hdr + 2 * w.c0 + 1, sizeof h0, hipMemcpyDeviceToHost, s));
+        if (tail) HIP_TRY(c, hipMemcpyAsync(&h1, c->pk_hdr + 2 * end + 1, sizeof h1, hipMemcpyDeviceToHost, s));
+        if (resident || tail) HIP_TRY(c, hipStreamSynchronize(s));
+        w.first_unit = resident ? (((uint64_t)h0.y << 32) | h0.x) : c->pk_units;
+        if (old_end) *old_end = tail ? (((uint64_t)h1.y << 32) | h1.x) : c->pk_units;
+        w.units = w.first_unit;
+        if (w.wn) {
+            HIP_TRY(c, buf.get(&w.whdr, w.wch * 2 * sizeof(uint4)));
+            if (!w.cnt) HIP_TRY(c, buf.get(&w.cnt, w.wch * sizeof(uint32_t)));
+            rtr::pack_measure(s, w.cl, w.whdr, w.cnt, units_dev, w.first_unit);
+            HIP_TRY(c, hipMemcpyAsync(&w.units, units_dev, sizeof w.units, hipMemcpyDeviceToHost, s));
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return launch_check(c, what);
+}
+
+// Capacity rules of the resident arrays.  After an append: `have`, grown with 1/8 head-room when it is too small
 static uint64_t grown(uint64_t have, uint64_t need) {
     if (need <= have) return have;
     const uint64_t g = have + have / 8;
     return g > need ? g : need;
 }
+// After a removal or a move: `have` unless it is too small or wastes more than 1/8
+static uint64_t fitted(uint64_t have, uint64_t need) {
+    const uint64_t fit = need + need / 8;
+    return need > have ? fit : (have > fit ? fit : have);
+}
 
+// What rtr_append_points and rtr_remove_points hand to commit_window beside the window.  Their per-point arrays stand for
+// the points from `at` on: the block behind the n0 resident points, or every survivor from chunk c0 on
+struct Splice {
+    uint64_t n1;                                // points afterwards
+    uint64_t (*capacity)(uint64_t, uint64_t);   // grown / fitted
+    uint64_t at;
+    const uint32_t *rgba;                       // colours of points at .. at + rgba_n - 1 (zero up to the padded count behind them)
+    uint64_t rgba_n;
+    const uint32_t *perm;                       // upload indices of points at .. n1 - 1; null: the cloud keeps no permutation
+    uint32_t *keep_up;                          // with a keep mask: its new upload-order words, a fresh buffer the caller filled
+    uint64_t *bad;                              // option "pack" = 2: device counter of pack_verify (read by cloud_edited)
+    const char *what;                           // names the launches in an error
+};
+
+// Splices a rebuilt window into the resident arrays: chunks [0, c0) stay, the window's chunks follow, n becomes n1.
+// Three phases, and the boundary between the first two is the invariant: EVERY buffer that may fail to allocate is
+// allocated before the first resident byte changes, so a failed call leaves the cloud as it was.  (1) The replacement
+// of every array whose capacity rule asks for another size.  (2) Copies and kernels, queued in one order for both
+// calls, writing into the replacements or -- from chunk c0 on only -- into the arrays that stay; then one
+// synchronisation.  (3) The new arrays swapped in, the packed form's bookkeeping, the point count.
+static int commit_window(rtr_ctx *c, DevBufs &buf, const Window &w, const Splice &e) {
+    hipStream_t s = c->stream;
+    const uint64_t c0 = w.c0, p0 = 256 * c0, nch1 = c0 + w.wch, n1 = e.n1, n1pad = (n1 + 3) & ~3ull;
+    const bool packed = c->pk_hdr != nullptr;
+
+    // (1) allocate
+    const uint64_t cap1 = (e.capacity(c->cap, n1pad) + 3) & ~3ull, cch1 = (cap1 / 4 + 63) / 64;
+    const bool realloc = cap1 != c->cap;
+    float *x1 = c->x, *y1 = c->y, *z1 = c->z, *bounds1 = c->bounds, *spread1 = c->spread;
+    uint32_t *rgba1 = c->rgba, *perm1 = e.perm ? c->perm : nullptr;
+    if (realloc) {
+        HIP_TRY(c, buf.get(&rgba1, cap1 * 4));
+        HIP_TRY(c, buf.get(&bounds1, cch1 * 6 * sizeof(float)));
+        HIP_TRY(c, buf.get(&spread1, cch1 * sizeof(float)));
+        if (c->x) {
+            HIP_TRY(c, buf.get(&x1, cap1 * 4)); HIP_TRY(c, buf.get(&y1, cap1 * 4)); HIP_TRY(c, buf.get(&z1, cap1 * 4));
+        }
+    }
+    if (e.perm && (realloc || !c->perm)) HIP_TRY(c, buf.get(&perm1, cap1 * 4));  // (no perm yet: this block is the first one sorted)
+    uint4 *hdr1 = c->pk_hdr;
+    uint32_t *planes1 = c->pk_planes, *planes1_b = c->pk_planes_b;
+    uint64_t hch1 = c->pk_hdr_chunks, ucap1 = c->pk_units_cap;
+    if (packed) {  // (a removal's merged chunks may span wider boxes: its planes can grow as well as shrink)
+        hch1 = e.capacity(c->pk_hdr_chunks, nch1);
+        if (hch1 != c->pk_hdr_chunks) HIP_TRY(c, buf.get(&hdr1, (hch1 + 1) * 2 * sizeof(uint4)));  // (+ the zero pair: read in pairs)
+        ucap1 = e.capacity(c->pk_units_cap, w.units);
+        if (ucap1 != c->pk_units_cap) {
+            HIP_TRY(c, buf.get(&planes1, rtr::pack_total_dwords(ucap1) * 4));
+            planes1_b = planes1 + rtr::pack_b_dwords(ucap1);
+        }
+    }
+    uint32_t *res1 = nullptr;
+    uint8_t *sum1 = nullptr;
+    if (e.keep_up) {
+        HIP_TRY(c, buf.get(&res1, nch1 * 32));
+        HIP_TRY(c, buf.get(&sum1, (nch1 + 3) & ~3ull));  // (read as whole dwords)
+    }
+
+    // (2) write: the resident prefix into replaced arrays, then the window's chunks from c0 on
+    if (realloc) {
+        HIP_TRY(c, d2d(s, rgba1, c->rgba, e.at * 4));
+        HIP_TRY(c, d2d(s, bounds1, c->bounds, c0 * 6 * sizeof(float)));
+        HIP_TRY(c, d2d(s, spread1, c->spread, c0 * sizeof(float)));
+        if (c->x) {
+            HIP_TRY(c, d2d(s, x1, c->x, p0 * 4)); HIP_TRY(c, d2d(s, y1, c->y, p0 * 4)); HIP_TRY(c, d2d(s, z1, c->z, p0 * 4));
+        }
+    }
+    HIP_TRY(c, d2d(s, rgba1 + e.at, e.rgba, e.rgba_n * 4));
+    if (n1pad > e.at + e.rgba_n) HIP_TRY(c, hipMemsetAsync(rgba1 + e.at + e.rgba_n, 0, (n1pad - e.at - e.rgba_n) * 4, s));
+    if (x1) {
+        HIP_TRY(c, d2d(s, x1 + p0, w.wx, w.wpad * 4)); HIP_TRY(c, d2d(s, y1 + p0, w.wy, w.wpad * 4));
+        HIP_TRY(c, d2d(s, z1 + p0, w.wz, w.wpad * 4));
+    }
+    HIP_TRY(c, d2d(s, bounds1 + 6 * c0, w.wb, w.wch * 6 * sizeof(float)));
+    HIP_TRY(c, d2d(s, spread1 + c0, w.wsp, w.wch * sizeof(float)));
+    if (e.perm) {
+        if (perm1 != c->perm) {
+            if (c->perm) HIP_TRY(c, d2d(s, perm1, c->perm, e.at * 4));
+            else rtr::launch_iota(s, perm1, e.at);  // (the cloud was in upload order until this block's sort)
+        }
+        HIP_TRY(c, d2d(s, perm1 + e.at, e.perm, (n1 - e.at) * 4));
+    }
+    if (packed) {
+        if (hdr1 != c->pk_hdr) HIP_TRY(c, d2d(s, hdr1, c->pk_hdr, c0 * 2 * sizeof(uint4)));
+        HIP_TRY(c, d2d(s, hdr1 + 2 * c0, w.whdr, w.wch * 2 * sizeof(uint4)));
+        HIP_TRY(c, hipMemsetAsync(hdr1 + 2 * nch1, 0, 2 * sizeof(uint4), s));  // (the zero pair sits behind the last chunk)
+        if (planes1 != c->pk_planes) HIP_TRY(c, copy_blocks(s, planes1, planes1_b, c, w.first_unit));
+        rtr::pack_write(s, w.cl, hdr1 + 2 * c0, planes1, planes1_b);
+        HIP_TRY(c, zero_spare(s, planes1, planes1_b, w.units));
+        if (c->opt_pack == 2) rtr::pack_verify(s, w.cl, hdr1 + 2 * c0, planes1, planes1_b, e.bad);
+    }
+    if (e.keep_up) {  // (resident words and summaries from chunk c0 on)
+        HIP_TRY(c, d2d(s, res1, c->keep_res, c0 * 32));
+        HIP_TRY(c, d2d(s, sum1, c->keep_sum, c0));
+        rtr::launch_keep_build(s, e.keep_up, perm1, n1, res1, sum1, c0);
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = launch_check(c, e.what)) return rc;
+
+    // (3) the new state
+    buf.swap_in(c->rgba, rgba1); buf.swap_in(c->bounds, bounds1); buf.swap_in(c->spread, spread1);
+    buf.swap_in(c->x, x1); buf.swap_in(c->y, y1); buf.swap_in(c->z, z1);
+    if (e.perm) buf.swap_in(c->perm, perm1);
+    c->cap = cap1;
+    if (packed) {
+        buf.swap_in(c->pk_hdr, hdr1); buf.swap_in(c->pk_planes, planes1);
+        c->pk_planes_b = planes1_b;
+        c->pk_units = w.units, c->pk_units_cap = ucap1, c->pk_hdr_chunks = hch1;
+        c->pk_bytes = pack_bytes(w.units, nch1);
+    }
+    if (e.keep_up) { buf.swap_in(c->keep_up, e.keep_up); buf.swap_in(c->keep_res, res1); buf.swap_in(c->keep_sum, sum1); }
+    c->n = n1;
+    return RTR_OK;
+}
+
+// The cloud has changed: what was computed from the old one is dropped, what is measured over every chunk box is
+// measured again.  resized (append, remove): upload indices or the point count changed too -- the selection goes, and
+// the n-sized state (the peers' mappings of this rank's pools, the adaptive pool sizing) starts over; a move keeps all
+// of that.  bad / which: option "pack" = 2, the commit's pack_verify counter and what it counted
+static int cloud_edited(rtr_ctx *c, bool resized, const uint64_t *bad, const char *which) {
+    if (resized) free_select(c);
+    ++c->cloud_seq;
+    c->list_valid = false;
+    c->jr.frame.count = 0;
+    c->jr.views.count = 0;
+    c->pp_vis_current = false;
+    c->split_cooldown = kSplitCooldown;
+    if (resized) {
+        if (c->p2p.open || c->p2p.red) p2p_release(c);  // (the peers map pools sized for the old cloud)
+        reset_pool_sizing(c->frame);
+        reset_pool_sizing(c->views);
+    }
+    {   // order measure and absmax over every chunk box: the lane test's margin steps and the incoherent form read them
+        float ratio = 0.f;
+        if (rtr::order_quality(c->stream, c->bounds, c->n, &ratio, c->absmax) != 0) {
+            (void)hipGetLastError();
+            c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();
+        }
+        c->order_ratio = c->n >= (1u << 16) ? ratio : 0.f;
+    }
+    if (c->pk_hdr && c->opt_pack == 2) {
+        uint64_t n_bad = 0;
+        HIP_TRY(c, hipMemcpy(&n_bad, bad, sizeof n_bad, hipMemcpyDeviceToHost));
+        if (n_bad) return fail(c, RTR_ERR_HIP, "pack: %llu %s decode to other coordinates", (unsigned long long)n_bad, which);
+    }
+    return RTR_OK;
+}
+
+// ---- appending (rtr.h, section 2b) ----------------------------------------------------
+// The block goes behind the resident points.  Its first points may complete the last partial 256-point chunk c0, so the
+// window holds chunk c0's resident points (copied, or decoded from the packed form when the SoA arrays are not
+// resident) followed by the block.  commit_window with `grown`: the arrays grow with 1/8 head-room and never shrink.
+// The block's colours and upload indices go behind the n0 resident ones; a block sorted on its own may give the cloud
+// its first permutation; the new points are kept by a keep mask.
 int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rgb, size_t rs, size_t m) {
     if (!c) return RTR_ERR_INVALID;
     c->ov.other_call();
@@ -1613,49 +1845,29 @@ int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
     if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
     drop_soa(c);  // (SoA arrays decoded for a call in between are not kept: the window decodes what it needs)
     hipStream_t s = c->stream;
-    const uint64_t n0 = c->n, n1 = n0 + m, c0 = n0 / 256, r = n0 - c0 * 256;
-    const uint64_t nch0 = (n0 + 255) / 256, nch1 = (n1 + 255) / 256, wch = nch1 - c0;
-    const uint64_t wn = r + m, wpad = (wn + 3) & ~3ull, m4 = (m + 3) & ~3ull, n1pad = (n1 + 3) & ~3ull;
-    AppendBufs buf;
+    const uint64_t n0 = c->n, n1 = n0 + m, c0 = n0 / 256, r = n0 - c0 * 256, m4 = (m + 3) & ~3ull;
+    DevBufs buf;
 
     // the block: host -> device in pieces, AoS -> SoA (b*), NaN-padded to a multiple of 4
-    float *bx, *by, *bz, *wx, *wy, *wz;
+    float *bx, *by, *bz;
     uint32_t *bc, *bperm = nullptr;
     HIP_TRY(c, buf.get(&bx, m4 * 4)); HIP_TRY(c, buf.get(&by, m4 * 4)); HIP_TRY(c, buf.get(&bz, m4 * 4));
     HIP_TRY(c, buf.get(&bc, m4 * 4));
-    {
-        const uint64_t chunk = 1ull << 24, sm = m < chunk ? m : chunk;
-        uint8_t *sx, *sc;
-        HIP_TRY(c, buf.get(&sx, sm * xs));
-        HIP_TRY(c, buf.get(&sc, sm * rs));
-        for (uint64_t off = 0; off < m; off += chunk) {
-            const uint64_t cnt = (m - off) < chunk ? (m - off) : chunk;
-            HIP_TRY(c, hipMemcpyAsync(sx, (const uint8_t *)xyz + off * xs, cnt * xs, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(sc, rgb + off * rs, cnt * rs, hipMemcpyHostToDevice, s));
-            rtr::launch_aos_to_soa(s, sx, xs, sc, rs, cnt, bx + off, by + off, bz + off, bc + off);
-            HIP_TRY(c, hipStreamSynchronize(s));
-        }
-        rtr::launch_pad_nan(s, bx, by, bz, bc, m, m4);
-        if (int rc = launch_check(c, "aos_to_soa")) return rc;
-    }
+    if (int rc = stage_points(c, buf, xyz, xs, rgb, rs, m, bx, by, bz, bc)) return rc;
+    rtr::launch_pad_nan(s, bx, by, bz, bc, m, m4);
+    if (int rc = launch_check(c, "aos_to_soa")) return rc;
 
     // option "auto_reorder" on the block alone (auto_reorder's rule), never losing the order a keep mask needs
-    rtr::Cloud wcl = cloud_of(c);
-    wcl.rgba = nullptr;
-    wcl.pk = rtr::PackedXyz{nullptr, nullptr, nullptr};
-    wcl.keep = rtr::Keep{nullptr, nullptr};
     bool sort = c->opt_auto_reorder == 1;
     if (c->opt_auto_reorder == 2 && m >= (1u << 16)) {
         float *bb, ratio = 0.f, am[3];
         HIP_TRY(c, buf.get(&bb, ((m + 255) / 256) * 6 * sizeof(float)));
-        wcl.x = bx, wcl.y = by, wcl.z = bz, wcl.n = m, wcl.spread = nullptr;
-        rtr::launch_chunk_bounds(s, wcl, bb, nullptr);
+        rtr::launch_chunk_bounds(s, window_view(c, bx, by, bz, m, nullptr), bb, nullptr);
         const int e = rtr::order_quality(s, bb, m, &ratio, am);
         if (e != 0) return fail(c, RTR_ERR_HIP, "block order measure failed: %s", hipGetErrorString((hipError_t)e));
         sort = ratio > 2.0f * cbrtf(256.0f / (float)m);
     }
     sort = sort && m >= 2 && !(c->keep_up && !c->reordered && !c->opt_point_ids);
-    const bool reordered1 = c->reordered || sort;
     const bool with_perm = c->reordered ? c->perm != nullptr : (sort && c->opt_point_ids);
     if (with_perm) {  // upload indices of the block: n0 .. n1 - 1, sorted with it
         HIP_TRY(c, buf.get(&bperm, m * 4));
@@ -1666,186 +1878,44 @@ int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
         if (e != 0) return fail(c, RTR_ERR_HIP, "block sort failed: %s", hipGetErrorString((hipError_t)e));
     }
 
-    // the window: chunk c0's resident points, then the block; its chunk boxes and lane spreads
-    HIP_TRY(c, buf.get(&wx, wpad * 4)); HIP_TRY(c, buf.get(&wy, wpad * 4)); HIP_TRY(c, buf.get(&wz, wpad * 4));
+    // the window: chunk c0's resident points, then the block
+    Window w;
+    if (int rc = window_alloc(c, buf, w, c0, r + m)) return rc;
     if (r) {
         if (c->x) {
-            HIP_TRY(c, hipMemcpyAsync(wx, c->x + c0 * 256, r * 4, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(wy, c->y + c0 * 256, r * 4, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(wz, c->z + c0 * 256, r * 4, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(c, d2d(s, w.wx, c->x + c0 * 256, r * 4)); HIP_TRY(c, d2d(s, w.wy, c->y + c0 * 256, r * 4));
+            HIP_TRY(c, d2d(s, w.wz, c->z + c0 * 256, r * 4));
         } else {  // (packed form only: chunk c0 alone is decoded, bit for bit; it writes whole quads, the block follows)
-            rtr::unpack_to_soa(s, rtr::PackedXyz{c->pk_hdr + 2 * c0, c->pk_planes, c->pk_planes_b}, r, wx, wy, wz);
+            rtr::unpack_to_soa(s, rtr::PackedXyz{c->pk_hdr + 2 * c0, c->pk_planes, c->pk_planes_b}, r, w.wx, w.wy, w.wz);
         }
     }
-    HIP_TRY(c, hipMemcpyAsync(wx + r, bx, m * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(wy + r, by, m * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(wz + r, bz, m * 4, hipMemcpyDeviceToDevice, s));
-    rtr::launch_pad_nan(s, wx, wy, wz, nullptr, wn, wpad);
-    float *wb, *wsp;
-    HIP_TRY(c, buf.get(&wb, wch * 6 * sizeof(float)));
-    HIP_TRY(c, buf.get(&wsp, wch * sizeof(float)));
-    wcl.x = wx, wcl.y = wy, wcl.z = wz, wcl.n = wn, wcl.spread = wsp;
-    rtr::launch_chunk_bounds(s, wcl, wb, wsp);
-
-    // packed: the window's headers, the scan continued from chunk c0's block offset
-    const bool packed = c->pk_hdr != nullptr;
-    uint4 *whdr = nullptr;
-    uint64_t *tot = nullptr, first_unit = c->pk_units, units1 = 0;
-    if (packed) {
-        if (c0 < nch0) {
-            uint4 h1;
-            HIP_TRY(c, hipMemcpyAsync(&h1, c->pk_hdr + 2 * c0 + 1, sizeof h1, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            first_unit = ((uint64_t)h1.y << 32) | h1.x;
-        }
-        uint32_t *cnt;
-        HIP_TRY(c, buf.get(&whdr, wch * 2 * sizeof(uint4)));
-        HIP_TRY(c, buf.get(&cnt, wch * sizeof(uint32_t)));
+    HIP_TRY(c, d2d(s, w.wx + r, bx, m * 4)); HIP_TRY(c, d2d(s, w.wy + r, by, m * 4)); HIP_TRY(c, d2d(s, w.wz + r, bz, m * 4));
+    rtr::launch_pad_nan(s, w.wx, w.wy, w.wz, nullptr, w.wn, w.wpad);
+    uint64_t *tot = nullptr, *bad = nullptr;  // packed: the window's units, pack mismatches
+    if (c->pk_hdr) {
         HIP_TRY(c, buf.get(&tot, 2 * sizeof(uint64_t)));
         HIP_TRY(c, hipMemsetAsync(tot, 0, 2 * sizeof(uint64_t), s));
-        rtr::pack_measure(s, wcl, whdr, cnt, tot, first_unit);
-        HIP_TRY(c, hipMemcpyAsync(&units1, tot, sizeof units1, hipMemcpyDeviceToHost, s));
+        bad = tot + 1;
     }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (int rc = launch_check(c, "append window")) return rc;
+    if (int rc = window_measure(c, buf, w, tot, "append window")) return rc;
 
-    // every buffer the commit needs, before anything resident changes
-    const uint64_t cap1 = (grown(c->cap, n1pad) + 3) & ~3ull, cch1 = (cap1 / 4 + 63) / 64;
-    const bool regrow = cap1 > c->cap;
-    float *x1 = c->x, *y1 = c->y, *z1 = c->z, *bounds1 = c->bounds, *spread1 = c->spread;
-    uint32_t *rgba1 = c->rgba, *perm1 = with_perm ? c->perm : nullptr;
-    if (regrow) {
-        HIP_TRY(c, buf.get(&rgba1, cap1 * 4));
-        HIP_TRY(c, buf.get(&bounds1, cch1 * 6 * sizeof(float)));
-        HIP_TRY(c, buf.get(&spread1, cch1 * sizeof(float)));
-        if (c->x) {
-            HIP_TRY(c, buf.get(&x1, cap1 * 4)); HIP_TRY(c, buf.get(&y1, cap1 * 4)); HIP_TRY(c, buf.get(&z1, cap1 * 4));
-        }
-    }
-    if (with_perm && (regrow || !c->perm)) HIP_TRY(c, buf.get(&perm1, cap1 * 4));
-    uint4 *hdr1 = c->pk_hdr;
-    uint32_t *planes1 = c->pk_planes, *planes1_b = c->pk_planes_b;
-    uint64_t hch1 = c->pk_hdr_chunks, ucap1 = c->pk_units_cap;
-    if (packed && nch1 > c->pk_hdr_chunks) {
-        hch1 = grown(c->pk_hdr_chunks, nch1);
-        HIP_TRY(c, buf.get(&hdr1, (hch1 + 1) * 2 * sizeof(uint4)));  // (+ one zero header: read in pairs)
-    }
-    if (packed && units1 > c->pk_units_cap) {
-        ucap1 = grown(c->pk_units_cap, units1);
-        HIP_TRY(c, buf.get(&planes1, rtr::pack_total_dwords(ucap1) * 4));
-        planes1_b = planes1 + rtr::pack_b_dwords(ucap1);
-    }
-    uint32_t *up1 = nullptr, *res1 = nullptr;
-    uint8_t *sum1 = nullptr;
-    if (c->keep_up) {
+    uint32_t *up1 = nullptr;
+    if (c->keep_up) {  // (the new points kept)
         HIP_TRY(c, buf.get(&up1, (n1 + 31) / 32 * 4));
-        HIP_TRY(c, buf.get(&res1, nch1 * 32));
-        HIP_TRY(c, buf.get(&sum1, (nch1 + 3) & ~3ull));  // (read as whole dwords)
-    }
-
-    // commit: the resident prefix into grown arrays, then the window's chunks from c0 on
-    auto d2d = [&](void *dst, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
-    };
-    if (regrow) {
-        HIP_TRY(c, d2d(rgba1, c->rgba, n0 * 4));
-        HIP_TRY(c, d2d(bounds1, c->bounds, c0 * 6 * sizeof(float)));
-        HIP_TRY(c, d2d(spread1, c->spread, c0 * sizeof(float)));
-        if (c->x) {
-            HIP_TRY(c, d2d(x1, c->x, c0 * 256 * 4)); HIP_TRY(c, d2d(y1, c->y, c0 * 256 * 4)); HIP_TRY(c, d2d(z1, c->z, c0 * 256 * 4));
-        }
-    }
-    HIP_TRY(c, d2d(rgba1 + n0, bc, m * 4));
-    if (n1pad > n1) HIP_TRY(c, hipMemsetAsync(rgba1 + n1, 0, (n1pad - n1) * 4, s));
-    if (x1) {
-        HIP_TRY(c, d2d(x1 + c0 * 256, wx, wpad * 4)); HIP_TRY(c, d2d(y1 + c0 * 256, wy, wpad * 4));
-        HIP_TRY(c, d2d(z1 + c0 * 256, wz, wpad * 4));
-    }
-    HIP_TRY(c, d2d(bounds1 + 6 * c0, wb, wch * 6 * sizeof(float)));
-    HIP_TRY(c, d2d(spread1 + c0, wsp, wch * sizeof(float)));
-    if (with_perm) {
-        if (perm1 != c->perm) {
-            if (c->perm) HIP_TRY(c, d2d(perm1, c->perm, n0 * 4));
-            else rtr::launch_iota(s, perm1, n0);  // (the cloud was in upload order until this block's sort)
-        }
-        HIP_TRY(c, d2d(perm1 + n0, bperm, m * 4));
-    }
-    if (packed) {
-        if (hdr1 != c->pk_hdr) HIP_TRY(c, d2d(hdr1, c->pk_hdr, c0 * 2 * sizeof(uint4)));
-        HIP_TRY(c, d2d(hdr1 + 2 * c0, whdr, wch * 2 * sizeof(uint4)));
-        HIP_TRY(c, hipMemsetAsync(hdr1 + 2 * nch1, 0, 2 * sizeof(uint4), s));
-        if (planes1 != c->pk_planes) {  // (the A region grows, so the B region moves)
-            HIP_TRY(c, d2d(planes1, c->pk_planes, first_unit * 2 * 4));
-            HIP_TRY(c, d2d(planes1_b, c->pk_planes_b, first_unit * 6 * 4));
-        }
-        rtr::pack_write(s, wcl, hdr1 + 2 * c0, planes1, planes1_b);
-        // (the spare bytes behind both streams read as zero, as after an upload: the last lanes' loads run into them)
-        HIP_TRY(c, hipMemsetAsync(planes1 + units1 * 2, 0, (rtr::pack_b_dwords(units1) - units1 * 2) * 4, s));
-        HIP_TRY(c, hipMemsetAsync(planes1_b + units1 * 6, 0, 64, s));
-        if (c->opt_pack == 2) rtr::pack_verify(s, wcl, hdr1 + 2 * c0, planes1, planes1_b, tot + 1);
-    }
-    if (c->keep_up) {  // (the new points kept; resident words and summaries from chunk c0 on)
-        HIP_TRY(c, d2d(up1, c->keep_up, (n0 + 31) / 32 * 4));
+        HIP_TRY(c, d2d(s, up1, c->keep_up, (n0 + 31) / 32 * 4));
         rtr::launch_keep_append(s, up1, n0, n1);
-        HIP_TRY(c, d2d(res1, c->keep_res, c0 * 32));
-        HIP_TRY(c, d2d(sum1, c->keep_sum, c0));
-        rtr::launch_keep_build(s, up1, reordered1 ? perm1 : nullptr, n1, res1, sum1, c0);
     }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (int rc = launch_check(c, "append")) return rc;
-
-    // the new state
-    buf.swap_in(c->rgba, rgba1); buf.swap_in(c->bounds, bounds1); buf.swap_in(c->spread, spread1);
-    buf.swap_in(c->x, x1); buf.swap_in(c->y, y1); buf.swap_in(c->z, z1);
-    if (with_perm) buf.swap_in(c->perm, perm1);
-    c->cap = cap1;
-    if (packed) {
-        buf.swap_in(c->pk_hdr, hdr1); buf.swap_in(c->pk_planes, planes1);
-        c->pk_planes_b = planes1_b;
-        c->pk_units = units1, c->pk_units_cap = ucap1, c->pk_hdr_chunks = hch1;
-        c->pk_bytes = units1 * 32 + nch1 * 32;
-    }
-    if (c->keep_up) { buf.swap_in(c->keep_up, up1); buf.swap_in(c->keep_res, res1); buf.swap_in(c->keep_sum, sum1); }
-    c->n = n1;
-    free_select(c);  // (made for the old count)
-    c->reordered = reordered1;
-    ++c->cloud_seq;
-    c->list_valid = false;
-    c->jr.frame.count = 0;
-    c->jr.views.count = 0;
-    c->pp_vis_current = false;
-    c->split_cooldown = kSplitCooldown;
-    if (c->p2p.open || c->p2p.red) p2p_release(c);  // (the peers map pools sized for the old cloud)
-    reset_pool_sizing(c->frame);
-    reset_pool_sizing(c->views);
-    {   // order measure and absmax over every chunk box: the lane test's margin steps and the incoherent form read them
-        float ratio = 0.f;
-        if (rtr::order_quality(s, c->bounds, n1, &ratio, c->absmax) != 0) {
-            (void)hipGetLastError();
-            c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();
-        }
-        c->order_ratio = n1 >= (1u << 16) ? ratio : 0.f;
-    }
-    if (packed && c->opt_pack == 2) {
-        uint64_t bad = 0;
-        HIP_TRY(c, hipMemcpy(&bad, tot + 1, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad) return fail(c, RTR_ERR_HIP, "pack: %llu appended points decode to other coordinates", (unsigned long long)bad);
-    }
-    return RTR_OK;
+    if (int rc = commit_window(c, buf, w, Splice{n1, grown, n0, bc, m, bperm, up1, bad, "append"})) return rc;
+    c->reordered = c->reordered || sort;
+    return cloud_edited(c, true, bad, "appended points");
 }
 
 // ---- removing (rtr.h, section 2c) -------------------------------------------------------------------------------
 // A stable compaction of the resident order.  One wave per chunk counts its survivors (through perm when the cloud is
-// sorted) and names the first chunk c0 that loses a point; chunks before it stay where they are.  The survivors of the
-// chunks from c0 on are compacted into a WINDOW (fp32 SoA, colours, renumbered upload indices) that then takes
-// rtr_append_points' commit path: chunk boxes and lane spreads, packed headers (the scan continues from chunk c0's block
-// offset) and blocks, the keep mask's resident words and summaries.  Every buffer is allocated before the first resident
-// byte changes; arrays that would hold more than 1/8 head-room over the survivors are reallocated to that size.
-static uint64_t fitted(uint64_t have, uint64_t need) {  // capacity after a removal: `have` unless it wastes > 1/8
-    const uint64_t fit = need + need / 8;
-    return need > have ? fit : (have > fit ? fit : have);
-}
-
+// sorted) and names the first chunk c0 that loses a point; chunks before it stay where they are.  The window holds the
+// survivors of the chunks from c0 on, compacted, with their colours and renumbered upload indices.  commit_window with
+// `fitted`: arrays that would hold more than 1/8 head-room over the survivors are reallocated to that size.  A keep
+// mask is compacted onto the survivors; a visibility mask much larger than they need is dropped.
 int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     if (!c) return RTR_ERR_INVALID;
     c->ov.other_call();
@@ -1853,16 +1923,14 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     NEED(c, keep_words != nullptr, "rtr_remove_points: keep_words is NULL");
     if (nwords != (c->n + 31) / 32)
         return fail(c, RTR_ERR_INVALID, "rtr_remove_points: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
-    NEED(c, !c->reordered || c->perm,
-         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be mapped: set "
-         "point_ids = 1 before the upload (or upload with auto_reorder = 0)");
+    if (int rc = need_upload_order(c)) return rc;
     DevGuard g(c->device);
     if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
     drop_soa(c);
     hipStream_t s = c->stream;
     const uint64_t n0 = c->n, nch0 = (n0 + 255) / 256;
     const uint32_t *perm0 = c->reordered ? c->perm : nullptr;
-    AppendBufs buf;
+    DevBufs buf;
 
     // the caller's words (host or device memory), survivors per chunk, their exclusive scan, the first chunk losing one
     uint32_t *kw, *cnt, *dst, *scr;
@@ -1872,7 +1940,7 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     HIP_TRY(c, buf.get(&dst, nch0 * 4));
     const uint64_t scr_words = std::max(rtr::scan_scratch_words(nch0), rtr::scan_scratch_words(nwords));
     HIP_TRY(c, buf.get(&scr, scr_words * 4));
-    HIP_TRY(c, buf.get(&tot, 4 * sizeof(uint64_t)));  // first loss, survivors, kept words' total, pack mismatches
+    HIP_TRY(c, buf.get(&tot, 4 * sizeof(uint64_t)));  // first loss, survivors (then the window's units), kept words' total, pack mismatches
     HIP_TRY(c, hipMemcpyAsync(kw, keep_words, nwords * 4, hipMemcpyDefault, s));
     HIP_TRY(c, hipMemsetAsync(tot, 0xFF, sizeof(uint64_t), s));
     HIP_TRY(c, hipMemsetAsync(tot + 1, 0, 3 * sizeof(uint64_t), s));
@@ -1902,181 +1970,43 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     }
 
     // the window: the survivors of chunks c0.., compacted (renumbered upload indices when the permutation is kept)
-    const uint64_t wn = n1 - 256 * c0, wpad = (wn + 3) & ~3ull, wch = (wn + 255) / 256, nch1 = c0 + wch;
-    const uint64_t n1pad = (n1 + 3) & ~3ull;
-    const bool with_perm = perm0 != nullptr;
+    Window w;
     uint32_t *wscan = nullptr, *wrgba, *wperm = nullptr;
-    float *wx, *wy, *wz;
-    if (with_perm || c->keep_up) {
+    if (perm0 || c->keep_up) {
         HIP_TRY(c, buf.get(&wscan, nwords * 4));
         rtr::launch_scan_u32(s, kw, nwords, n0, wscan, scr, tot + 2);
     }
-    HIP_TRY(c, buf.get(&wx, wpad * 4)); HIP_TRY(c, buf.get(&wy, wpad * 4)); HIP_TRY(c, buf.get(&wz, wpad * 4));
-    HIP_TRY(c, buf.get(&wrgba, wpad * 4));
-    if (with_perm) HIP_TRY(c, buf.get(&wperm, wpad * 4));
-    rtr::Cloud cl = cloud_of(c);
-    rtr::launch_remove_compact(s, cl, perm0, kw, wscan, dst, c0, wx, wy, wz, wrgba, wperm);
-    rtr::launch_pad_nan(s, wx, wy, wz, wrgba, wn, wpad);
-    float *wb, *wsp;
-    HIP_TRY(c, buf.get(&wb, wch * 6 * sizeof(float)));
-    HIP_TRY(c, buf.get(&wsp, wch * sizeof(float)));
-    rtr::Cloud wcl = cl;
-    wcl.rgba = nullptr;
-    wcl.pk = rtr::PackedXyz{nullptr, nullptr, nullptr};
-    wcl.keep = rtr::Keep{nullptr, nullptr};
-    wcl.x = wx, wcl.y = wy, wcl.z = wz, wcl.n = wn, wcl.spread = wsp;
-    rtr::launch_chunk_bounds(s, wcl, wb, wsp);
+    if (int rc = window_alloc(c, buf, w, c0, n1 - 256 * c0)) return rc;
+    w.cnt = cnt;  // (free again: the survivors' scan has read it)
+    HIP_TRY(c, buf.get(&wrgba, w.wpad * 4));
+    if (perm0) HIP_TRY(c, buf.get(&wperm, w.wpad * 4));
+    rtr::launch_remove_compact(s, cloud_of(c), perm0, kw, wscan, dst, c0, w.wx, w.wy, w.wz, wrgba, wperm);
+    rtr::launch_pad_nan(s, w.wx, w.wy, w.wz, wrgba, w.wn, w.wpad);
+    if (int rc = window_measure(c, buf, w, tot + 1, "remove window")) return rc;
 
-    // packed: the window's headers, the scan continued from chunk c0's block offset
-    const bool packed = c->pk_hdr != nullptr;
-    uint4 *whdr = nullptr;
-    uint64_t first_unit = 0, units1 = 0;
-    if (packed) {
-        uint4 h1;
-        HIP_TRY(c, hipMemcpyAsync(&h1, c->pk_hdr + 2 * c0 + 1, sizeof h1, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        first_unit = ((uint64_t)h1.y << 32) | h1.x;
-        units1 = first_unit;  // (an empty window -- only whole trailing chunks removed -- adds no unit)
-        if (wn) {
-            HIP_TRY(c, buf.get(&whdr, wch * 2 * sizeof(uint4)));
-            rtr::pack_measure(s, wcl, whdr, cnt, tot + 1, first_unit);  // (cnt is free again; tot[1] ends as the units)
-            HIP_TRY(c, hipMemcpyAsync(&units1, tot + 1, sizeof units1, hipMemcpyDeviceToHost, s));
-        }
-    }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (int rc = launch_check(c, "remove window")) return rc;
-
-    // every buffer the commit needs, before anything resident changes
-    const uint64_t cap1 = (fitted(c->cap, n1pad) + 3) & ~3ull, cch1 = (cap1 / 4 + 63) / 64;
-    const bool realloc = cap1 != c->cap;
-    float *x1 = c->x, *y1 = c->y, *z1 = c->z, *bounds1 = c->bounds, *spread1 = c->spread;
-    uint32_t *rgba1 = c->rgba, *perm1 = with_perm ? c->perm : nullptr;
-    if (realloc) {
-        HIP_TRY(c, buf.get(&rgba1, cap1 * 4));
-        HIP_TRY(c, buf.get(&bounds1, cch1 * 6 * sizeof(float)));
-        HIP_TRY(c, buf.get(&spread1, cch1 * sizeof(float)));
-        if (c->x) {
-            HIP_TRY(c, buf.get(&x1, cap1 * 4)); HIP_TRY(c, buf.get(&y1, cap1 * 4)); HIP_TRY(c, buf.get(&z1, cap1 * 4));
-        }
-        if (with_perm) HIP_TRY(c, buf.get(&perm1, cap1 * 4));
-    }
-    uint4 *hdr1 = c->pk_hdr;
-    uint32_t *planes1 = c->pk_planes, *planes1_b = c->pk_planes_b;
-    uint64_t hch1 = c->pk_hdr_chunks, ucap1 = c->pk_units_cap;
-    if (packed) {  // (merged chunks may span wider boxes: the planes can grow)
-        hch1 = fitted(c->pk_hdr_chunks, nch1);
-        if (hch1 != c->pk_hdr_chunks) HIP_TRY(c, buf.get(&hdr1, (hch1 + 1) * 2 * sizeof(uint4)));  // (+ one zero pair)
-        ucap1 = fitted(c->pk_units_cap, units1);
-        if (ucap1 != c->pk_units_cap) {
-            HIP_TRY(c, buf.get(&planes1, rtr::pack_total_dwords(ucap1) * 4));
-            planes1_b = planes1 + rtr::pack_b_dwords(ucap1);
-        }
-    }
-    uint32_t *up1 = nullptr, *res1 = nullptr;
-    uint8_t *sum1 = nullptr;
-    if (c->keep_up) {
+    uint32_t *up1 = nullptr;
+    if (c->keep_up) {  // (old[keep] in upload order)
         HIP_TRY(c, buf.get(&up1, (n1 + 31) / 32 * 4));
-        HIP_TRY(c, buf.get(&res1, nch1 * 32));
-        HIP_TRY(c, buf.get(&sum1, (nch1 + 3) & ~3ull));  // (read as whole dwords)
-    }
-
-    // commit: the kept prefix into reallocated arrays, then the window's chunks from c0 on
-    auto d2d = [&](void *dst_, const void *src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(dst_, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
-    };
-    const uint64_t p0 = 256 * c0;  // (the untouched prefix: whole chunks)
-    if (realloc) {
-        HIP_TRY(c, d2d(rgba1, c->rgba, p0 * 4));
-        HIP_TRY(c, d2d(bounds1, c->bounds, c0 * 6 * sizeof(float)));
-        HIP_TRY(c, d2d(spread1, c->spread, c0 * sizeof(float)));
-        if (c->x) {
-            HIP_TRY(c, d2d(x1, c->x, p0 * 4)); HIP_TRY(c, d2d(y1, c->y, p0 * 4)); HIP_TRY(c, d2d(z1, c->z, p0 * 4));
-        }
-        if (with_perm) HIP_TRY(c, d2d(perm1, c->perm, p0 * 4));
-    }
-    HIP_TRY(c, d2d(rgba1 + p0, wrgba, wpad * 4));
-    if (x1) {
-        HIP_TRY(c, d2d(x1 + p0, wx, wpad * 4)); HIP_TRY(c, d2d(y1 + p0, wy, wpad * 4)); HIP_TRY(c, d2d(z1 + p0, wz, wpad * 4));
-    }
-    HIP_TRY(c, d2d(bounds1 + 6 * c0, wb, wch * 6 * sizeof(float)));
-    HIP_TRY(c, d2d(spread1 + c0, wsp, wch * sizeof(float)));
-    if (with_perm) HIP_TRY(c, d2d(perm1 + p0, wperm, wn * 4));
-    if (packed) {
-        if (hdr1 != c->pk_hdr) HIP_TRY(c, d2d(hdr1, c->pk_hdr, c0 * 2 * sizeof(uint4)));
-        HIP_TRY(c, d2d(hdr1 + 2 * c0, whdr, wch * 2 * sizeof(uint4)));
-        HIP_TRY(c, hipMemsetAsync(hdr1 + 2 * nch1, 0, 2 * sizeof(uint4), s));
-        if (planes1 != c->pk_planes) {  // (the A region's size changes, so the B region moves)
-            HIP_TRY(c, d2d(planes1, c->pk_planes, first_unit * 2 * 4));
-            HIP_TRY(c, d2d(planes1_b, c->pk_planes_b, first_unit * 6 * 4));
-        }
-        rtr::pack_write(s, wcl, hdr1 + 2 * c0, planes1, planes1_b);
-        // (the spare bytes behind both streams read as zero, as after an upload: the last lanes' loads run into them)
-        HIP_TRY(c, hipMemsetAsync(planes1 + units1 * 2, 0, (rtr::pack_b_dwords(units1) - units1 * 2) * 4, s));
-        HIP_TRY(c, hipMemsetAsync(planes1_b + units1 * 6, 0, 64, s));
-        if (c->opt_pack == 2) rtr::pack_verify(s, wcl, hdr1 + 2 * c0, planes1, planes1_b, tot + 3);
-    }
-    if (c->keep_up) {  // (old[keep] in upload order; resident words and summaries from chunk c0 on)
         HIP_TRY(c, hipMemsetAsync(up1, 0, (n1 + 31) / 32 * 4, s));
         rtr::launch_remove_mask(s, kw, wscan, c->keep_up, n0, up1);
-        HIP_TRY(c, d2d(res1, c->keep_res, c0 * 32));
-        HIP_TRY(c, d2d(sum1, c->keep_sum, c0));
-        rtr::launch_keep_build(s, up1, with_perm ? perm1 : nullptr, n1, res1, sum1, c0);
     }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (int rc = launch_check(c, "remove")) return rc;
-
-    // the new state
-    buf.swap_in(c->rgba, rgba1); buf.swap_in(c->bounds, bounds1); buf.swap_in(c->spread, spread1);
-    buf.swap_in(c->x, x1); buf.swap_in(c->y, y1); buf.swap_in(c->z, z1);
-    if (with_perm) buf.swap_in(c->perm, perm1);
-    c->cap = cap1;
-    if (packed) {
-        buf.swap_in(c->pk_hdr, hdr1); buf.swap_in(c->pk_planes, planes1);
-        c->pk_planes_b = planes1_b;
-        c->pk_units = units1, c->pk_units_cap = ucap1, c->pk_hdr_chunks = hch1;
-        c->pk_bytes = units1 * 32 + nch1 * 32;
-    }
-    if (c->keep_up) { buf.swap_in(c->keep_up, up1); buf.swap_in(c->keep_res, res1); buf.swap_in(c->keep_sum, sum1); }
+    if (int rc = commit_window(c, buf, w, Splice{n1, fitted, 256 * c0, wrgba, w.wpad, wperm, up1, tot + 3, "remove"})) return rc;
     if (c->pp_vis && c->pp_vis_words > ((n1 + 31) / 32 > 8 ? (n1 + 31) / 32 : 8)) {  // (sized again by the next point pass)
         dfree(c->pp_vis);
         c->pp_vis_words = 0;
     }
-    c->n = n1;
-    free_select(c);  // (the upload indices were renumbered)
-    ++c->cloud_seq;
-    c->list_valid = false;
-    c->jr.frame.count = 0;
-    c->jr.views.count = 0;
-    c->pp_vis_current = false;
-    c->split_cooldown = kSplitCooldown;
-    if (c->p2p.open || c->p2p.red) p2p_release(c);  // (the peers map pools sized for the old cloud)
-    reset_pool_sizing(c->frame);
-    reset_pool_sizing(c->views);
-    {   // order measure and absmax over every chunk box: the lane test's margin steps and the incoherent form read them
-        float ratio = 0.f;
-        if (rtr::order_quality(s, c->bounds, n1, &ratio, c->absmax) != 0) {
-            (void)hipGetLastError();
-            c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();
-        }
-        c->order_ratio = n1 >= (1u << 16) ? ratio : 0.f;
-    }
-    if (packed && c->opt_pack == 2) {
-        uint64_t bad = 0;
-        HIP_TRY(c, hipMemcpy(&bad, tot + 3, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad) return fail(c, RTR_ERR_HIP, "pack: %llu points of the rebuilt chunks decode to other coordinates", (unsigned long long)bad);
-    }
-    return RTR_OK;
+    return cloud_edited(c, true, tot + 3, "points of the rebuilt chunks");
 }
 
 // ---- moving points (rtr.h, section 2d) --------------------------------------------------------------------------
 // Points move where they lie: upload indices, the resident order, colours, the permutation and the keep mask stay.  A
 // selection pass names the first and last chunk holding a selected point, c0 and c1 (no pass for "every point"); only
 // chunks c0 .. c1 are rebuilt.  An unpacked cloud is moved in place (its SoA arrays, then the boxes of c0 .. c1).  A packed
-// one gets a WINDOW: chunks c0 .. c1 decoded (read from the SoA arrays with "keep_soa" = 1), the selected points moved,
-// then rtr_append_points' range forms -- chunk boxes and lane spreads, headers (the scan continues from chunk c0's block
-// offset), blocks.  The blocks behind c1 are not decoded: when the window's units differ from the old ones by delta, the
-// tail's A and B blocks move by delta (through a scratch copy, or into fresh planes when the capacity changes; `fitted`)
-// and its headers' offsets with them.  Every buffer is allocated before the first resident byte changes.
+// one gets a window: chunks c0 .. c1 decoded (read from the SoA arrays with "keep_soa" = 1), the selected points moved.
+// Its commit is its own, because the blocks behind c1 are not decoded: when the window's units differ from the old ones by
+// delta, the tail's A and B blocks move by delta (through a scratch copy, or into fresh planes when the capacity changes;
+// `fitted`) and its headers' offsets with them.  Every buffer is allocated before the first resident byte changes, as in
+// commit_window.  The n-sized state stays: cloud_edited without `resized`.
 int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_words, uint64_t nwords) {
     if (!c) return RTR_ERR_INVALID;
     c->ov.other_call();
@@ -2087,9 +2017,8 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
     NEED(c, select_words != nullptr || nwords == 0, "rtr_transform_points: select_words is NULL");
     if (!every && nwords != (c->n + 31) / 32)
         return fail(c, RTR_ERR_INVALID, "rtr_transform_points: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
-    NEED(c, every || !c->reordered || c->perm,
-         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be mapped: set "
-         "point_ids = 1 before the upload (or upload with auto_reorder = 0), or move every point (select_words NULL)");
+    if (!every)
+        if (int rc = need_upload_order(c, "mapped", ", or move every point (select_words NULL)")) return rc;
     DevGuard g(c->device);
     if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
     drop_soa(c);  // (SoA arrays decoded for a call in between are not kept: they would hold the old coordinates)
@@ -2098,7 +2027,7 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
     const uint32_t *perm0 = c->reordered ? c->perm : nullptr;
     rtr::Affine A;
     memcpy(A.m, M, sizeof A.m);
-    AppendBufs buf;
+    DevBufs buf;
 
     // the caller's words (host or device memory) and the span of the chunks holding a selected point
     uint32_t *sel = nullptr;
@@ -2118,46 +2047,23 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
         if (span[0] >= nch) return RTR_OK;  // (no point selected: nothing changes)
         c0 = span[0], c1 = span[1];
     }
-    const uint64_t p0 = 256 * c0, wn = std::min(n, 256 * (c1 + 1)) - p0, wpad = (wn + 3) & ~3ull, wch = c1 + 1 - c0;
+    const uint64_t p0 = 256 * c0, wn = std::min(n, 256 * (c1 + 1)) - p0;
     const rtr::Cloud cl = cloud_of(c);
-    rtr::Cloud wcl = cl;
-    wcl.rgba = nullptr;
-    wcl.pk = rtr::PackedXyz{nullptr, nullptr, nullptr};
-    wcl.keep = rtr::Keep{nullptr, nullptr};
-    wcl.n = wn;
-    const bool packed = c->pk_hdr != nullptr;
-    if (!packed) {  // (in place: nothing left to allocate)
+    if (!c->pk_hdr) {  // (in place: nothing left to allocate)
         rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, c->x + p0, c->y + p0, c->z + p0, true);
-        wcl.x = c->x + p0, wcl.y = c->y + p0, wcl.z = c->z + p0, wcl.spread = c->spread + c0;
-        rtr::launch_chunk_bounds(s, wcl, c->bounds + 6 * c0, c->spread + c0);
+        rtr::launch_chunk_bounds(s, window_view(c, c->x + p0, c->y + p0, c->z + p0, wn, c->spread + c0), c->bounds + 6 * c0,
+                                 c->spread + c0);
         HIP_TRY(c, hipStreamSynchronize(s));
         if (int rc = launch_check(c, "transform")) return rc;
     } else {
-        // the window: chunks c0 .. c1 with the selected points moved, their boxes, lane spreads and headers
-        float *wx, *wy, *wz, *wb, *wsp;
-        HIP_TRY(c, buf.get(&wx, wpad * 4)); HIP_TRY(c, buf.get(&wy, wpad * 4)); HIP_TRY(c, buf.get(&wz, wpad * 4));
-        HIP_TRY(c, buf.get(&wb, wch * 6 * sizeof(float)));
-        HIP_TRY(c, buf.get(&wsp, wch * sizeof(float)));
-        rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, wx, wy, wz, false);
-        wcl.x = wx, wcl.y = wy, wcl.z = wz, wcl.spread = wsp;
-        rtr::launch_chunk_bounds(s, wcl, wb, wsp);
-        uint4 h0, h1 = make_uint4(0, 0, 0, 0);
-        HIP_TRY(c, hipMemcpyAsync(&h0, c->pk_hdr + 2 * c0 + 1, sizeof h0, hipMemcpyDeviceToHost, s));
-        if (c1 + 1 < nch) HIP_TRY(c, hipMemcpyAsync(&h1, c->pk_hdr + 2 * (c1 + 1) + 1, sizeof h1, hipMemcpyDeviceToHost, s));
-        uint4 *whdr;
-        uint32_t *cnt;
-        HIP_TRY(c, buf.get(&whdr, wch * 2 * sizeof(uint4)));
-        HIP_TRY(c, buf.get(&cnt, wch * sizeof(uint32_t)));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const uint64_t first_unit = ((uint64_t)h0.y << 32) | h0.x;
-        const uint64_t old_end = c1 + 1 < nch ? (((uint64_t)h1.y << 32) | h1.x) : c->pk_units;  // (the tail's first unit)
-        rtr::pack_measure(s, wcl, whdr, cnt, tot + 2, first_unit);
-        uint64_t new_end = 0;
-        HIP_TRY(c, hipMemcpyAsync(&new_end, tot + 2, sizeof new_end, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (int rc = launch_check(c, "transform window")) return rc;
+        // the window: chunks c0 .. c1 with the selected points moved; old_end: the tail's first unit
+        Window w;
+        uint64_t old_end = 0;
+        if (int rc = window_alloc(c, buf, w, c0, wn)) return rc;
+        rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, w.wx, w.wy, w.wz, false);
+        if (int rc = window_measure(c, buf, w, tot + 2, "transform window", &old_end)) return rc;
+        const uint64_t new_end = w.units, tail = c->pk_units - old_end, units1 = new_end + tail;
         const int64_t delta = (int64_t)(new_end - old_end);
-        const uint64_t tail = c->pk_units - old_end, units1 = new_end + tail;
 
         // every buffer the commit needs, before anything resident changes
         const uint64_t ucap1 = fitted(c->pk_units_cap, units1);
@@ -2170,31 +2076,26 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
         }
 
         // commit: the tail's blocks to their new place, the window's headers and blocks, the tail's block offsets
-        auto d2d = [&](void *dst_, const void *src, size_t bytes) {
-            return bytes ? hipMemcpyAsync(dst_, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
-        };
         if (planes1 != c->pk_planes) {  // (fresh planes: the prefix and the tail are copied, nothing overlaps)
-            HIP_TRY(c, d2d(planes1, c->pk_planes, first_unit * 2 * 4));
-            HIP_TRY(c, d2d(planes1_b, c->pk_planes_b, first_unit * 6 * 4));
-            HIP_TRY(c, d2d(planes1 + new_end * 2, c->pk_planes + old_end * 2, tail * 2 * 4));
-            HIP_TRY(c, d2d(planes1_b + new_end * 6, c->pk_planes_b + old_end * 6, tail * 6 * 4));
+            HIP_TRY(c, copy_blocks(s, planes1, planes1_b, c, w.first_unit));
+            HIP_TRY(c, d2d(s, planes1 + new_end * 2, c->pk_planes + old_end * 2, tail * 2 * 4));
+            HIP_TRY(c, d2d(s, planes1_b + new_end * 6, c->pk_planes_b + old_end * 6, tail * 6 * 4));
         } else if (tmp) {  // (source and destination overlap: through the scratch copy)
-            HIP_TRY(c, d2d(tmp, c->pk_planes + old_end * 2, tail * 2 * 4));
-            HIP_TRY(c, d2d(tmp + tail * 2, c->pk_planes_b + old_end * 6, tail * 6 * 4));
-            HIP_TRY(c, d2d(planes1 + new_end * 2, tmp, tail * 2 * 4));
-            HIP_TRY(c, d2d(planes1_b + new_end * 6, tmp + tail * 2, tail * 6 * 4));
+            HIP_TRY(c, d2d(s, tmp, c->pk_planes + old_end * 2, tail * 2 * 4));
+            HIP_TRY(c, d2d(s, tmp + tail * 2, c->pk_planes_b + old_end * 6, tail * 6 * 4));
+            HIP_TRY(c, d2d(s, planes1 + new_end * 2, tmp, tail * 2 * 4));
+            HIP_TRY(c, d2d(s, planes1_b + new_end * 6, tmp + tail * 2, tail * 6 * 4));
         }
-        HIP_TRY(c, d2d(c->pk_hdr + 2 * c0, whdr, wch * 2 * sizeof(uint4)));
+        HIP_TRY(c, d2d(s, c->pk_hdr + 2 * c0, w.whdr, w.wch * 2 * sizeof(uint4)));
         rtr::launch_shift_units(s, c->pk_hdr, c1 + 1, nch, delta);
-        rtr::pack_write(s, wcl, c->pk_hdr + 2 * c0, planes1, planes1_b);
-        // (the spare bytes behind both streams read as zero, as after an upload: the last lanes' loads run into them)
-        HIP_TRY(c, hipMemsetAsync(planes1 + units1 * 2, 0, (rtr::pack_b_dwords(units1) - units1 * 2) * 4, s));
-        HIP_TRY(c, hipMemsetAsync(planes1_b + units1 * 6, 0, 64, s));
-        if (c->opt_pack == 2) rtr::pack_verify(s, wcl, c->pk_hdr + 2 * c0, planes1, planes1_b, tot + 3);
-        HIP_TRY(c, d2d(c->bounds + 6 * c0, wb, wch * 6 * sizeof(float)));
-        HIP_TRY(c, d2d(c->spread + c0, wsp, wch * sizeof(float)));
+        rtr::pack_write(s, w.cl, c->pk_hdr + 2 * c0, planes1, planes1_b);
+        HIP_TRY(c, zero_spare(s, planes1, planes1_b, units1));
+        if (c->opt_pack == 2) rtr::pack_verify(s, w.cl, c->pk_hdr + 2 * c0, planes1, planes1_b, tot + 3);
+        HIP_TRY(c, d2d(s, c->bounds + 6 * c0, w.wb, w.wch * 6 * sizeof(float)));
+        HIP_TRY(c, d2d(s, c->spread + c0, w.wsp, w.wch * sizeof(float)));
         if (c->x) {  // ("keep_soa" = 1: the SoA arrays take the window as well)
-            HIP_TRY(c, d2d(c->x + p0, wx, wpad * 4)); HIP_TRY(c, d2d(c->y + p0, wy, wpad * 4)); HIP_TRY(c, d2d(c->z + p0, wz, wpad * 4));
+            HIP_TRY(c, d2d(s, c->x + p0, w.wx, w.wpad * 4)); HIP_TRY(c, d2d(s, c->y + p0, w.wy, w.wpad * 4));
+            HIP_TRY(c, d2d(s, c->z + p0, w.wz, w.wpad * 4));
         }
         HIP_TRY(c, hipStreamSynchronize(s));
         if (int rc = launch_check(c, "transform")) return rc;
@@ -2204,30 +2105,9 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
             c->pk_units_cap = ucap1;
         }
         c->pk_units = units1;
-        c->pk_bytes = units1 * 32 + nch * 32;
+        c->pk_bytes = pack_bytes(units1, nch);
     }
-
-    // what depends on the coordinates (n-sized state -- stores, pools, the peers' mappings -- stays)
-    ++c->cloud_seq;
-    c->list_valid = false;
-    c->jr.frame.count = 0;
-    c->jr.views.count = 0;
-    c->pp_vis_current = false;
-    c->split_cooldown = kSplitCooldown;
-    {   // order measure and absmax over every chunk box: the lane test's margin steps and the incoherent form read them
-        float ratio = 0.f;
-        if (rtr::order_quality(s, c->bounds, n, &ratio, c->absmax) != 0) {
-            (void)hipGetLastError();
-            c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();
-        }
-        c->order_ratio = n >= (1u << 16) ? ratio : 0.f;
-    }
-    if (packed && c->opt_pack == 2) {
-        uint64_t bad = 0;
-        HIP_TRY(c, hipMemcpy(&bad, tot + 3, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad) return fail(c, RTR_ERR_HIP, "pack: %llu moved points decode to other coordinates", (unsigned long long)bad);
-    }
-    return RTR_OK;
+    return cloud_edited(c, false, tot + 3, "moved points");
 }
 
 int rtr_reorder_points(rtr_ctx *c) {
@@ -2278,14 +2158,11 @@ int rtr_download_points(rtr_ctx *c, float *xyzw, uint8_t *rgba, uint64_t first, 
     if (int rc = ensure_soa(c)) return rc;  // (a cloud resident in packed form only is decoded for the copy, bit for bit)
     const uint64_t chunk = 1ull << 24;
     uint64_t m = count < chunk ? count : chunk;
-    struct Staging {  // freed on every exit path
-        void *p = nullptr;
-        ~Staging() { if (p) (void)hipFree(p); }
-    } stx, stc;
-    HIP_TRY(c, hipMalloc(&stx.p, m * 16));
-    HIP_TRY(c, hipMalloc(&stc.p, m * 4));
-    float *dx = static_cast<float *>(stx.p);
-    uint8_t *dc = static_cast<uint8_t *>(stc.p);
+    DevBufs buf;
+    float *dx;
+    uint8_t *dc;
+    HIP_TRY(c, buf.get(&dx, m * 16));
+    HIP_TRY(c, buf.get(&dc, m * 4));
     for (uint64_t off = 0; off < count; off += chunk) {
         uint64_t cnt = (count - off) < chunk ? (count - off) : chunk;
         uint64_t s0 = first + off;
@@ -2329,9 +2206,8 @@ int rtr_extract_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords
     NEED(c, !rgb || rs >= 3, "rtr_extract_points: rgb_stride_bytes must be >= 3");
     if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
     const bool lost_order = c->reordered && !c->perm;
-    NEED(c, every || !lost_order,
-         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be mapped: set "
-         "point_ids = 1 before the upload (or upload with auto_reorder = 0), or extract every point (select_words NULL)");
+    if (!every)
+        if (int rc = need_upload_order(c, "mapped", ", or extract every point (select_words NULL)")) return rc;
     NEED(c, !(every && lost_order && indices),
          "the resident cloud was reordered without option point_ids = 1: every point comes out in the RESIDENT order and "
          "has no upload index, so indices must be NULL (set point_ids = 1 before the upload to get them)");
@@ -2339,7 +2215,7 @@ int rtr_extract_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords
     hipStream_t s = c->stream;
     const uint64_t n = c->n, nch = (n + 255) / 256;
     const uint32_t *perm = c->reordered ? c->perm : nullptr;
-    AppendBufs buf;
+    DevBufs buf;
 
     // the selection's popcount scan and k, the number of selected points
     uint32_t *sel = nullptr, *wscan = nullptr;
@@ -3112,9 +2988,7 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
     NEED(c, c->cap > 0, "no cloud: rtr_upload_points / rtr_generate_synthetic first");
     if (int rc = check_frame(c)) return rc;
     if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point IDs are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    NEED(c, !c->reordered || c->perm,
-         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be formed: set "
-         "point_ids = 1 before the upload (or upload with auto_reorder = 0)");
+    if (int rc = need_upload_order(c, "formed")) return rc;
     DevGuard g(c->device);
     const size_t npix = (size_t)c->W * c->H;
     const uint64_t words = (((c->n + 3) / 4 + 63) / 64) * 8;  // (8 per 256-point chunk: whole-chunk stores)
@@ -3172,21 +3046,18 @@ int rtr_select_points(rtr_ctx *c, int plane_count, const float *planes, const fl
     const int base = op & ~RTR_SELECT_OUTSIDE;
     NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_points: unknown op");
     if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    NEED(c, !c->reordered || c->perm,
-         "the resident cloud was reordered without option point_ids = 1, so upload-order indices cannot be formed: set "
-         "point_ids = 1 before the upload (or upload with auto_reorder = 0)");
+    if (int rc = need_upload_order(c, "formed")) return rc;
     DevGuard g(c->device);
     hipStream_t s = c->stream;
     const uint64_t words = std::max<uint64_t>((c->n + 255) / 256, 1) * 8;  // (8 per 256-point chunk: whole-chunk stores)
     if (!c->sel) {  // (a selection that does not exist yet is empty)
-        struct Buf {  // freed on every exit path unless taken
-            void *p = nullptr;
-            ~Buf() { if (p) (void)hipFree(p); }
-        } w, st;
-        HIP_TRY(c, hipMalloc(&w.p, words * 4));
-        HIP_TRY(c, hipMalloc(&st.p, 4 * sizeof(uint64_t)));
-        HIP_TRY(c, hipMemsetAsync(w.p, 0, words * 4, s));
-        c->sel = (uint32_t *)w.p, c->sel_stats = (uint64_t *)st.p, w.p = st.p = nullptr;
+        DevBufs buf;
+        uint32_t *w;
+        uint64_t *st;
+        HIP_TRY(c, buf.get(&w, words * 4));
+        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
+        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
+        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
     }
     const uint32_t *perm = c->reordered ? c->perm : nullptr;
     if (perm && base == RTR_SELECT_REPLACE) HIP_TRY(c, hipMemsetAsync(c->sel, 0, words * 4, s));
