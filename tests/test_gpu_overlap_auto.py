@@ -17,37 +17,9 @@ import numpy as np
 import pytest
 
 import pool_overflow_scenes as sc
+from streak_ctx import AUTO, SHAPES, Ctx, Scene, _exact
 
 pytestmark = pytest.mark.gpu
-
-# name -> W, H, points, prefilter possible (W % 16 == 0)
-SHAPES = {"96x64": (96, 64, 50_000, True), "200x120": (200, 120, 120_000, False), "208x112": (208, 112, 120_000, True),
-          "640x480": (640, 480, 300_000, True)}
-POSE_IDS = (3, 58, 121, 190, 247, 316, 402, 467, 533)
-AUTO = [0, 0, 1, 1, 1, 1, 1, 1, 1]
-
-
-class Scene:
-    """A cloud, its poses and the oracle's frames, computed once per module and never changed."""
-
-    def __init__(self, pkg, orc, name, seed=0xC0FFEE10):
-        self.pkg, self.orc = pkg, orc
-        self.W, self.H, self.n, self.can_filter = SHAPES[name]
-        self.xyzw, self.rgba = orc.generate("room_shell", seed, 0, self.n, self.n)
-        self.poses = [pkg.orbit_projection(k, self.W, self.H) for k in POSE_IDS]
-        self._refs = {}
-
-    def ref(self, P, filtered, cloud=None, tag="base"):
-        key = (np.asarray(P, np.float32).tobytes(), bool(filtered), tag)
-        if key not in self._refs:
-            xyzw, rgba = cloud if cloud is not None else (self.xyzw, self.rgba)
-            r = self.orc.project(xyzw, rgba, P, self.W, self.H)
-            out = {"depth": r["depth_bits"], "img": r["img"]}
-            if filtered:
-                f = self.orc.filter(r["depth_bits"], r["img"])
-                out = {"depth": f["depth"].view(np.uint32), "img": f["img"], "tensor": f["tensor"], "minmax": f["minmax"]}
-            self._refs[key] = out
-        return self._refs[key]
 
 
 @pytest.fixture(scope="module")
@@ -59,68 +31,6 @@ def scenes(pkg, orc):
             cache[name] = Scene(pkg, orc, name)
         return cache[name]
     return get
-
-
-class Ctx:
-    """A context of its own on a torch stream, with the frame buffers aliased as tensors."""
-
-    def __init__(self, pkg, scene, options=(), upload=True):
-        import torch
-        self.torch, self.pkg, self.scene = torch, pkg, scene
-        self.p = pkg.Projector(0)
-        try:
-            for k, v in dict(options).items():
-                self.p.set_option(k, v)
-            if upload:
-                self.p.upload_points(scene.xyzw, scene.rgba)
-            self.st = torch.cuda.Stream(device=0)
-            self.p.set_stream(self.st.cuda_stream)
-            self.resolution(scene.W, scene.H)
-        except BaseException:
-            self.p.close()
-            raise
-
-    def resolution(self, W, H):
-        L, dev = self.pkg._lib, self.torch.device("cuda", 0)
-        self.p.set_resolution(W, H)
-        self.bufs = {"depth": self.torch.as_tensor(self.p.device_buffer(L.BUF_DEPTH, "<i4"), device=dev),
-                     "img": self.torch.as_tensor(self.p.device_buffer(L.BUF_IMAGE), device=dev),
-                     "tensor": self.torch.as_tensor(self.p.device_buffer(L.BUF_TENSOR), device=dev),
-                     "minmax": self.torch.as_tensor(self.p.device_buffer(L.BUF_MINMAX, "<i4"), device=dev)}
-
-    def run(self, poses, filtered):
-        """Renders the poses back to back; -> overlap_active per frame, the frames (numpy, after one synchronisation)."""
-        active, snaps = [], []
-        names = ("depth", "img", "tensor", "minmax") if filtered else ("depth", "img")
-        for P in poses:
-            self.p.render(P, filtered)
-            active.append(self.p.get_option("overlap_active"))
-            with self.torch.cuda.stream(self.st):
-                snaps.append({k: self.bufs[k].clone() for k in names})
-        self.st.synchronize()
-        frames = []
-        for s in snaps:
-            f = {k: v.cpu().numpy() for k, v in s.items()}
-            f["depth"] = f["depth"].view(np.uint32)
-            if filtered:
-                f["tensor"] = f["tensor"].view(np.uint16).reshape(5, self.p.H, self.p.W)
-                f["minmax"] = f["minmax"].view(np.uint32)
-            frames.append(f)
-        return active, frames
-
-    def close(self):
-        self.p.close()
-
-
-def _exact(frames, scene, poses, filtered, what, cloud=None, tag="base"):
-    for k, (f, P) in enumerate(zip(frames, poses)):
-        want = scene.ref(P, filtered, cloud, tag)
-        for name, got in f.items():
-            w = np.asarray(want[name])
-            if name == "tensor":
-                w = w.view(np.uint16).reshape(got.shape)
-            assert np.array_equal(got.reshape(-1), w.reshape(-1).view(got.dtype)), (what, "frame", k, name,
-                                                                                  int((got.reshape(-1) != w.reshape(-1).view(got.dtype)).sum()))
 
 
 def _cases():
