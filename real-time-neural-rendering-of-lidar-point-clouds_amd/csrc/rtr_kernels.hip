@@ -3386,6 +3386,7 @@ void launch_resolve(hipStream_t s, const uint32_t *acc, uint8_t *img, size_t npi
 //   F2..F4 k_up  : per level: Laplacian of the parent (A9, recomputed per child), compare
 //                  (A10) and in-place bilinear fill of rejected pixels (A11)
 //   F5 k_final   : level-0 compare + removeMask + fp16 tensor (A13), four pixels a thread
+//                  (k_final_px, one pixel a thread, where W % 4 != 0: levels == 1 at W = 6, 10, ...)
 // Arithmetic is op-for-op that of oracle/rtr_oracle.c.
 
 // F1.  A8 reduce (project_cloud.cu:28-53) for every level at once.  Level i pixel (x, y)
@@ -3670,8 +3671,10 @@ __device__ __forceinline__ float half_round(float f) { return __half2float(__flo
 __device__ __forceinline__ uint32_t colour_half(uint32_t b) { return to_half_bits(half_round((float)b) / 255.0f); }
 
 // Level-0 compare (A10) + removeMask (A13, project_cloud.cu:163-187) for four horizontally
-// adjacent pixels (W % 16 == 0), tensor plane stride W*H (the reference strides by W*H_eff:
-// quirk Q3).  Rows >= H_eff never saw the pyramid test: their mask is "non-empty".
+// adjacent pixels x..x+3 of ONE row: x % 4 == 0 and W % 4 == 0, so that the quad neither straddles
+// two rows nor the end of a plane and its vector accesses are aligned (k_filter4 has W % 16 == 0,
+// k_final any W % 4 == 0; other widths take k_final_px).  Tensor plane stride W*H (the reference
+// strides by W*H_eff: quirk Q3).  Rows >= H_eff never saw the pyramid test: their mask is "non-empty".
 template <class Lv>
 __device__ __forceinline__ void final_quad(const Lv &l1, float4 d4, uint32_t iw0, uint32_t iw1, uint32_t iw2,
                                            float *__restrict__ depth, uint8_t *__restrict__ img,
@@ -3730,7 +3733,38 @@ __device__ __forceinline__ void final_quad(const Lv &l1, float4 d4, uint32_t iw0
             make_uint2(th[c][0] | (th[c][1] << 16), th[c][2] | (th[c][3] << 16));
 }
 
-// F5 of the generic sequence: final_quad over ALL W*H pixels, level 1 read from memory
+// F5 of the generic sequence for widths that are no multiple of 4 (levels == 1 only asks for an even W: 6, 10, 14, ...):
+// a quad would straddle two rows there, and the last one the end of the frame and of every tensor plane when
+// W*H % 4 == 2.  One pixel a thread, scalar accesses only; same arithmetic as final_quad.
+__global__ __launch_bounds__(kBlock) void k_final_px(const float *__restrict__ l1, float *__restrict__ depth,
+                                                     uint8_t *__restrict__ img, uint8_t *__restrict__ mask,
+                                                     uint16_t *__restrict__ tensor, const uint32_t *__restrict__ minmax,
+                                                     int W, int H, int lw, int lh, float strength, float thr) {
+    const size_t npix = (size_t)W * H, idx = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx >= npix) return;
+    const int x = (int)(idx % W), y = (int)(idx / W);
+    const float mn = __uint_as_float(minmax[0]), range = f_sub(__uint_as_float(minmax[1]), mn);
+    const float d = depth[idx];
+    // rows >= H_eff never saw the pyramid test: their mask is "non-empty"
+    const bool keep = y < 2 * lh ? keep_px(MemLevel{l1, lw, lh}, d, x, y, strength, thr) : !at_max_float(d);
+    if (!keep) {
+        depth[idx] = -1.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) img[idx * 3 + c] = 0;
+        mask[idx] = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) tensor[(size_t)c * npix + idx] = 0;
+        tensor[(size_t)4 * npix + idx] = 0xBC00u;
+        return;
+    }
+    mask[idx] = 0xFFu;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tensor[(size_t)c * npix + idx] = (uint16_t)colour_half(img[idx * 3 + c]);
+    tensor[(size_t)3 * npix + idx] = 0x3C00u;  // half(float(half(255)) / 255.0f)
+    tensor[(size_t)4 * npix + idx] = (uint16_t)to_half_bits(half_round(f_sub(d, mn)) / range);
+}
+
+// F5 of the generic sequence: final_quad over ALL W*H pixels (W % 4 == 0), level 1 read from memory
 __global__ __launch_bounds__(kBlock) void k_final(const float *__restrict__ l1, float *__restrict__ depth,
                                                   uint8_t *__restrict__ img, uint8_t *__restrict__ mask,
                                                   uint16_t *__restrict__ tensor, const uint32_t *__restrict__ minmax,
@@ -3916,6 +3950,11 @@ void launch_filter(hipStream_t s, const FilterLevels &L, uint32_t *depth_bits, u
     if (first) {  // levels == 1: nothing folded the partials yet
         hipLaunchKernelGGL(k_up, dim3(1), dim3(kBlock), 0, s, L.lv[1], L.lv[0], 0, 0, strength, thr, part_min, part_max,
                            nparts, minmax);
+    }
+    if ((W & 3) != 0) {  // levels == 1 with W % 4 == 2: a quad is not four pixels of one row
+        hipLaunchKernelGGL(k_final_px, blocks((size_t)W * H), dim3(kBlock), 0, s, L.lv[1], (float *)depth_bits, img, mask,
+                           tensor, minmax, W, H, cw, ch, strength, thr);
+        return;
     }
     size_t quads = ((size_t)W * H + 3) / 4;
     hipLaunchKernelGGL(k_final, blocks(quads), dim3(kBlock), 0, s, L.lv[1], (float *)depth_bits, img, mask, tensor,
