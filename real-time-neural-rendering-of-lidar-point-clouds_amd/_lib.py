@@ -60,7 +60,7 @@ class RtrError(RuntimeError):
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 build of the in-tree extension (cross-compiles without a GPU)."""
-    args = ["make", "-C", CSRC, "-s"] + (["-B"] if force else [])
+    args = ["make", "-C", CSRC, "-s", "-j4"] + (["-B"] if force else [])  # (the two kernel files compile side by side)
     subprocess.check_call(args)
     return LIB_PATH
 

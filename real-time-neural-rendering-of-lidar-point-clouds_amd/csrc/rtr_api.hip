@@ -1394,6 +1394,18 @@ int need_upload_order(rtr_ctx *c, const char *verb = "mapped", const char *or_el
     return fail(c, RTR_ERR_INVALID, "the resident cloud was reordered without option point_ids = 1, so upload-order indices "
                 "cannot be %s: set point_ids = 1 before the upload (or upload with auto_reorder = 0)%s", verb, or_else);
 }
+// An upload-order bit-word argument (`words`, `nwords`; `fn` and `what` name the call and the argument in the messages):
+// one bit per resident point, so nwords must be (n + 31) / 32, and a cloud the library sorted must have kept its
+// permutation (need_upload_order with `or_else`) -- unless `order_checked_later`: the call asks that itself, behind its
+// other arguments.  null_means_every: NULL with nwords 0 stands for every point and passes as it is.
+int check_point_words(rtr_ctx *c, const char *fn, const char *what, const uint32_t *words, uint64_t nwords, bool null_means_every,
+                      const char *or_else = "", bool order_checked_later = false) {
+    if (!words && !(null_means_every && nwords == 0)) return fail(c, RTR_ERR_INVALID, "%s: %s is NULL", fn, what);
+    if (!words) return RTR_OK;
+    if (nwords != (c->n + 31) / 32)
+        return fail(c, RTR_ERR_INVALID, "%s: nwords must be (n + 31) / 32 = %llu", fn, (unsigned long long)((c->n + 31) / 32));
+    return order_checked_later ? RTR_OK : need_upload_order(c, "mapped", or_else);
+}
 }  // namespace
 
 extern "C" {
@@ -1418,11 +1430,7 @@ int rtr_set_point_keep(rtr_ctx *c, const uint32_t *words, uint64_t nwords) {
     c->ov.other_call();
     const bool clear = words == nullptr && nwords == 0;
     NEED(c, clear || c->n > 0, "rtr_set_point_keep: no cloud");
-    NEED(c, words != nullptr || nwords == 0, "rtr_set_point_keep: words is NULL");
-    if (!clear && nwords != (c->n + 31) / 32)
-        return fail(c, RTR_ERR_INVALID, "rtr_set_point_keep: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
-    if (!clear)
-        if (int rc = need_upload_order(c)) return rc;
+    if (int rc = check_point_words(c, "rtr_set_point_keep", "words", words, nwords, true)) return rc;
     DevGuard g(c->device);
     if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the mask they were issued with)
     if (clear) {
@@ -1926,10 +1934,7 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     if (!c) return RTR_ERR_INVALID;
     c->ov.other_call();
     NEED(c, c->n > 0, "rtr_remove_points: no cloud");
-    NEED(c, keep_words != nullptr, "rtr_remove_points: keep_words is NULL");
-    if (nwords != (c->n + 31) / 32)
-        return fail(c, RTR_ERR_INVALID, "rtr_remove_points: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
-    if (int rc = need_upload_order(c)) return rc;
+    if (int rc = check_point_words(c, "rtr_remove_points", "keep_words", keep_words, nwords, false)) return rc;
     DevGuard g(c->device);
     if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
     drop_soa(c);
@@ -2020,11 +2025,8 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
     NEED(c, M != nullptr, "rtr_transform_points: M is NULL");
     for (int i = 0; i < 12; ++i) NEED(c, std::isfinite(M[i]), "rtr_transform_points: M has a non-finite coefficient");
     const bool every = select_words == nullptr && nwords == 0;
-    NEED(c, select_words != nullptr || nwords == 0, "rtr_transform_points: select_words is NULL");
-    if (!every && nwords != (c->n + 31) / 32)
-        return fail(c, RTR_ERR_INVALID, "rtr_transform_points: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
-    if (!every)
-        if (int rc = need_upload_order(c, "mapped", ", or move every point (select_words NULL)")) return rc;
+    if (int rc = check_point_words(c, "rtr_transform_points", "select_words", select_words, nwords, true,
+                                   ", or move every point (select_words NULL)")) return rc;
     DevGuard g(c->device);
     if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
     drop_soa(c);  // (SoA arrays decoded for a call in between are not kept: they would hold the old coordinates)
@@ -2205,9 +2207,8 @@ int rtr_extract_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords
     NEED(c, c->n > 0, "rtr_extract_points: no cloud");
     NEED(c, xyz || rgb || indices || total, "rtr_extract_points: nothing to produce (xyz, rgb, indices and total are all NULL)");
     const bool every = select_words == nullptr && nwords == 0;
-    NEED(c, select_words != nullptr || nwords == 0, "rtr_extract_points: select_words is NULL");
-    if (!every && nwords != (c->n + 31) / 32)
-        return fail(c, RTR_ERR_INVALID, "rtr_extract_points: nwords must be (n + 31) / 32 = %llu", (unsigned long long)((c->n + 31) / 32));
+    if (int rc = check_point_words(c, "rtr_extract_points", "select_words", select_words, nwords, true, "", /*order_checked_later=*/true))
+        return rc;
     NEED(c, !xyz || (xs >= 12 && xs % 4 == 0), "rtr_extract_points: xyz_stride_bytes must be >= 12 and a multiple of 4");
     NEED(c, !rgb || rs >= 3, "rtr_extract_points: rgb_stride_bytes must be >= 3");
     if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);

@@ -5,7 +5,7 @@
 // compiled with -ffp-contract=off and hipcc's default correctly rounded fp32
 // divide / sqrt.  Nothing here is GEMM-shaped: the path is an HBM-bound stream plus
 // a scatter, so the work goes into coalescing, atomic traffic and launch count.
-#include "rtr_kernels.h"
+#include "rtr_device.h"
 #include "rtr_remove_index.h"
 #include "rtr_extract_index.h"
 
@@ -15,35 +15,6 @@
 #include <type_traits>
 
 namespace rtr {
-
-#define RTR_EMPTY 0x7F7FFFFFu
-constexpr int kBlock = 256;   // 4 waves
-// The grid-stride point kernels run Cloud::grid workgroups (kDefaultPointGrid = 1024, i.e. 4
-// per CU, measured best: 1024 -> 205 us, 1536 -> 218, 2048 -> 239 for k_project_bin; 2048 would
-// not even be co-resident: its 84 SGPRs admit 7 x 256 threads per CU, not 8).
-
-// one rounding per operation: plain operators under -ffp-contract=off (hipcc's __fmul_rn &
-// co. are the same plain operators; __fsqrt_rn is NOT correctly rounded, sqrtf is)
-__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
-__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float f_sub(float a, float b) { return a - b; }
-
-// ---------------------------------------------------------------------------------
-// projection of one point: render.cu:33-40 (matmul rows 0..2), :63 (z cull),
-// :65-66 (rintf of the quotient), :68 (frustum cull), :70 (pixel id).
-// Returns pixel id or -1.
-__device__ __forceinline__ int project_point(const Proj &P, float x, float y, float z, int W, int H, float fW,
-                                             float fH, float &depth) {
-    float rx = f_add(fmaf(P.m[2], z, fmaf(P.m[1], y, f_mul(P.m[0], x))), P.m[3]);
-    float ry = f_add(fmaf(P.m[6], z, fmaf(P.m[5], y, f_mul(P.m[4], x))), P.m[7]);
-    float rz = f_add(fmaf(P.m[10], z, fmaf(P.m[9], y, f_mul(P.m[8], x))), P.m[11]);
-    float inv = 1.0f / rz;  // correctly rounded (v_div_scale / v_div_fmas / v_div_fixup)
-    float fu = rintf(f_mul(rx, inv));
-    float fv = rintf(f_mul(ry, inv));
-    bool ok = (rz > 0.0f) && (fu >= 0.0f) && (fu < fW) && (fv >= 0.0f) && (fv < fH);
-    depth = rz;
-    return ok ? ((int)fv * W + (int)fu) : -1;
-}
 
 // ---------------------------------------------------------------------------------
 // A1 + A2 fused: depth <- sentinel, accumulators <- 0, FULL coverage (the reference's
@@ -75,12 +46,6 @@ struct Quad {
     int pix[4];
     float d[4];
 };
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld_stream(const float4 *p) {
-    v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
 
 template <bool CLIP = false>
 __device__ __forceinline__ Quad project_quad(const float4 *__restrict__ x4, const float4 *__restrict__ y4,
@@ -589,26 +554,6 @@ __device__ __forceinline__ uint64_t *extent_slot(const TileStore &S, uint32_t st
     return sc->dyn + base + (v - start);
 }
 
-// inclusive scan over the workgroup (<= 8 waves); returns the inclusive prefix, `total` = sum of all
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *s_w /*[8]*/, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(v, off, 64);
-        if (lane >= off) v += o;
-    }
-    __syncthreads();  // s_w may still be read from the previous scan
-    if (lane == 63) s_w[wv] = v;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-    for (int k = 0; k < nw; ++k) {
-        const uint32_t w = s_w[k];
-        base += k < wv ? w : 0u;
-        total += w;
-    }
-    return v + base;
-}
 __device__ __forceinline__ uint32_t block_max(uint32_t v, uint32_t *s_w) {
     const int nw = blockDim.x >> 6;
 #pragma unroll
@@ -967,96 +912,6 @@ __global__ __launch_bounds__(kBlock) void k_lean_fold(TileStore S, int parity) {
 void launch_lean_fold(hipStream_t s, int W, int H, const TileStore &S, int parity) {
     (void)W, (void)H;
     hipLaunchKernelGGL(k_lean_fold, dim3(1), dim3(kBlock), 0, s, S, parity);
-}
-
-// PackedXyz helpers ---------------------------------------------------------------
-// An axis block is TWO little-endian bit streams (rtr_kernels.h): the FIRST value of every lane -- lane l's b bits at bit
-// b l of the A stream, 8 b bytes -- and its other three -- 3 b bits at bit 3 b l of the B stream, 24 b bytes.  A lane
-// reads the 8 (16) bytes that start at the DWORD holding its first bit (loads whose lane stride is not a multiple of
-// four bytes run at a third of the rate: 2.2-3.8 TB/s against 7.0, tools/align_probe.hip) and shifts its data down by
-// the remaining 0..31 bits; b <= 25 keeps shift + b <= 64 and shift + 3 b <= 128.  A fixed number of loads per chunk,
-// no branch around any of them; both streams end with spare bytes for the last lane's over-read.
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-struct AxisRawA { uint32_t d[2]; };
-struct AxisRaw { uint32_t d[4]; };
-__device__ __forceinline__ AxisRawA ld_axis_a(const uint8_t *block, uint32_t b, int lane) {
-    const uint32_t dw = (b * (uint32_t)lane) >> 5;
-    const u32x2_a4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_a4 *>(block + 4u * dw));
-    return AxisRawA{{v.x, v.y}};
-}
-__device__ __forceinline__ AxisRaw ld_axis_b(const uint8_t *block, uint32_t b, int lane) {
-    const uint32_t dw = (3u * b * (uint32_t)lane) >> 5;
-    const u32x4_a4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_a4 *>(block + 4u * dw));
-    return AxisRaw{{v.x, v.y, v.z, v.w}};
-}
-// value 0 = base | the lane's b bits of the A stream, value k = base | bits [b (k - 1), b k) of its realigned B data.
-// Branch-free for every b <= 25 (b = 0: the mask is empty and the value is the base).  A first version picked the dwords
-// a value straddles by width class behind wave-uniform branches: ~10 branches per axis made the point kernel 14 us
-// slower than the byte-granular form it was meant to beat.  b is wave-uniform.
-__device__ __forceinline__ float4 unpack_axis_narrow(const AxisRawA &ra, const AxisRaw &r, uint32_t b, uint32_t base, int lane) {
-    // (a VOP3 instruction reads at most one scalar register on gfx950: with mask AND base scalar the compiler splits every
-    // v_and_or into two instructions; the base in a vector register keeps it one)
-    uint32_t vbase = base;
-    asm("" : "+v"(vbase));
-    uint32_t sha, shb;  // (b l) & 31, (3 b l) & 31: alignbit takes the low five bits of its shift
-    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(sha) : "s"(b), "v"(lane));
-    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(shb) : "s"(3u * b), "v"(lane));
-    const uint32_t mask = (1u << b) - 1u;  // (b <= 25)
-    const uint32_t a0 = __builtin_amdgcn_alignbit(ra.d[1], ra.d[0], sha);
-    const uint32_t e0 = __builtin_amdgcn_alignbit(r.d[1], r.d[0], shb), e1 = __builtin_amdgcn_alignbit(r.d[2], r.d[1], shb);
-    const uint32_t e2 = __builtin_amdgcn_alignbit(r.d[3], r.d[2], shb);
-    const uint32_t f0 = __builtin_amdgcn_alignbit(e1, e0, b), f1 = __builtin_amdgcn_alignbit(e2, e1, b);
-    const uint32_t g0 = __builtin_amdgcn_alignbit(f1, f0, b);
-    auto and_or = [&](uint32_t e) -> float {  // (the compiler leaves v_and + v_or here)
-        uint32_t x;
-        asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(x) : "v"(e), "s"(mask), "v"(vbase));
-        return __uint_as_float(x);
-    };
-    return make_float4(and_or(a0), and_or(e0), and_or(f0), and_or(g0));
-}
-__device__ __forceinline__ float4 unpack_axis(const AxisRawA &ra, const AxisRaw &r, uint32_t b, uint32_t base, int lane) {
-    if (b == 32u)  // (lane l's first value is dword l of the A stream, its other three dwords 3 l .. 3 l + 2 of the B stream)
-        return make_float4(__uint_as_float(ra.d[0]), __uint_as_float(r.d[0]), __uint_as_float(r.d[1]), __uint_as_float(r.d[2]));
-    return unpack_axis_narrow(ra, r, b, base, lane);
-}
-struct ChunkRawA { AxisRawA a[3]; };
-struct ChunkRaw { AxisRaw a[3]; };
-__device__ __forceinline__ ChunkRawA load_chunk_a(const uint32_t *__restrict__ planes_a, const uint4 &h0, const uint4 &h1, int lane) {
-    const uint8_t *p = reinterpret_cast<const uint8_t *>(planes_a) + (((((uint64_t)h1.y) << 32) | (uint64_t)h1.x) << 3);
-    ChunkRawA c;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const uint32_t b = (h0.w >> (6 * a)) & 63u;
-        c.a[a] = ld_axis_a(p, b, lane);
-        p += 8u * b;
-    }
-    return c;
-}
-__device__ __forceinline__ ChunkRaw load_chunk_b(const uint32_t *__restrict__ planes_b, const uint4 &h0, const uint4 &h1, int lane) {
-    const uint8_t *p = reinterpret_cast<const uint8_t *>(planes_b) + (((((uint64_t)h1.y) << 32) | (uint64_t)h1.x) * 24u);
-    ChunkRaw c;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const uint32_t b = (h0.w >> (6 * a)) & 63u;
-        c.a[a] = ld_axis_b(p, b, lane);
-        p += 24u * b;
-    }
-    return c;
-}
-__device__ __forceinline__ void unpack_chunk(const ChunkRawA &ca, const ChunkRaw &c, uint32_t widths, uint32_t bx, uint32_t by, uint32_t bz,
-                                             float4 &X, float4 &Y, float4 &Z, int lane) {
-    if (!(widths & kPackWideFlag)) {  // no axis of the chunk needs all 32 bits (the usual case)
-        // (a constant axis -- a wall of the synthetic room, 30 % of its axis blocks -- skips the fifteen instructions)
-        const uint32_t wx = widths & 63u, wy = (widths >> 6) & 63u, wz = (widths >> 12) & 63u;
-        X = wx ? unpack_axis_narrow(ca.a[0], c.a[0], wx, bx, lane) : make_float4(__uint_as_float(bx), __uint_as_float(bx), __uint_as_float(bx), __uint_as_float(bx));
-        Y = wy ? unpack_axis_narrow(ca.a[1], c.a[1], wy, by, lane) : make_float4(__uint_as_float(by), __uint_as_float(by), __uint_as_float(by), __uint_as_float(by));
-        Z = wz ? unpack_axis_narrow(ca.a[2], c.a[2], wz, bz, lane) : make_float4(__uint_as_float(bz), __uint_as_float(bz), __uint_as_float(bz), __uint_as_float(bz));
-    } else {
-        X = unpack_axis(ca.a[0], c.a[0], widths & 63u, bx, lane);
-        Y = unpack_axis(ca.a[1], c.a[1], (widths >> 6) & 63u, by, lane);
-        Z = unpack_axis(ca.a[2], c.a[2], (widths >> 12) & 63u, bz, lane);
-    }
 }
 
 // T1 ------------------------------------------------------------------------------
@@ -2095,7 +1950,6 @@ __device__ __forceinline__ void tile_pyramid(const uint32_t *s_depth, uint32_t *
     }
 }
 
-
 // The three truncating divisions of the resolve (render.cu:147-162) with ONE reciprocal: for count < 2^16 the
 // sums are < 2^24, exact as floats; sum * rcp(count) is within 1e-4 of the quotient (v_rcp_f32: 1 ulp), so its
 // floor is the exact quotient or one off, which the remainder settles.  The u32 division the compiler
@@ -3070,7 +2924,6 @@ void launch_chunk_bounds(hipStream_t s, const Cloud &c, float *bounds, float *sp
     hipLaunchKernelGGL(k_chunk_bounds, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s,
                        (const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, n4, bounds, spread);
 }
-
 
 // PackedXyz: measure (one wave per chunk: unsigned min / max of the bit patterns -> base and width per axis)
 __device__ __forceinline__ void chunk_bits(const uint4 *__restrict__ x4, const uint4 *__restrict__ y4,
@@ -4441,13 +4294,6 @@ struct PointPassArgs {
     const uint32_t *perm;        // resident index -> upload index (PERM)
     float window;
 };
-__device__ __forceinline__ uint32_t spread_nibbles(uint32_t b) {  // bit m of the low byte -> bit 4 m
-    uint32_t x = b & 0xFFu;
-    x = (x | (x << 12)) & 0x000F000Fu;
-    x = (x | (x << 6)) & 0x03030303u;
-    x = (x | (x << 3)) & 0x11111111u;
-    return x;
-}
 template <bool PERM, bool CLIP, bool KEEP = false>
 __device__ __forceinline__ void point_pass_chunk(const PointPassArgs &a, const Proj &P, int W, int H, float fW, float fH,
                                                  uint64_t c, const float4 &X, const float4 &Y, const float4 &Z, int lane,
@@ -4588,302 +4434,6 @@ void launch_point_pass(hipStream_t s, const Cloud &c, const Proj &P, int W, int 
     else if (packed) pass(on, off);
     else if (perm) pass(off, on);
     else pass(off, off);
-}
-
-__global__ __launch_bounds__(kBlock) void k_iota(uint32_t *__restrict__ out, uint64_t n, uint64_t first) {
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) out[i] = (uint32_t)(first + i);
-}
-void launch_iota(hipStream_t s, uint32_t *out, uint64_t n, uint64_t first) {
-    if (n == 0) return;
-    const uint64_t blocks = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_iota, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, out, n, first);
-}
-
-// The keep mask in resident order (rtr_set_point_keep, after a sort): one wave per 256-point chunk, lane l gathers the
-// bits of its points 4 l .. 4 l + 3 from the upload-order mask (through perm when the cloud is sorted), the four ballots
-// are interleaved into the chunk's eight words as in the point pass, and lane 0 writes the chunk's summary
-// (keep_chunk_state: the same rule on the ballots).  Points at or past n are hidden and do not count.
-__global__ __launch_bounds__(kBlock) void k_keep_build(const uint32_t *__restrict__ up, const uint32_t *__restrict__ perm,
-                                                       uint64_t n, uint32_t *__restrict__ res, uint8_t *__restrict__ sum,
-                                                       uint64_t c0) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t nchunks = (n + 255) / 256;
-    for (uint64_t c = c0 + (((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6); c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
-        bool kept[4], valid[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint64_t r = c * 256u + 4u * (uint64_t)lane + (uint64_t)k;
-            valid[k] = r < n;
-            const uint64_t u = valid[k] ? (perm ? (uint64_t)perm[r] : r) : 0u;
-            kept[k] = valid[k] && ((up[u >> 5] >> (u & 31u)) & 1u);
-        }
-        unsigned long long b[4], v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) b[k] = __ballot(kept[k]), v[k] = __ballot(valid[k]);
-        if (lane < 8) {
-            const int sh = 8 * lane;
-            res[8 * c + lane] = spread_nibbles((uint32_t)(b[0] >> sh)) | (spread_nibbles((uint32_t)(b[1] >> sh)) << 1) |
-                                (spread_nibbles((uint32_t)(b[2] >> sh)) << 2) | (spread_nibbles((uint32_t)(b[3] >> sh)) << 3);
-        }
-        if (lane == 0) {
-            const bool none = (b[0] | b[1] | b[2] | b[3]) == 0ull;
-            const bool all = b[0] == v[0] && b[1] == v[1] && b[2] == v[2] && b[3] == v[3];
-            sum[c] = none ? kKeepNone : (all ? kKeepAll : kKeepSome);
-        }
-    }
-}
-// the bits of the upload-order mask at or past n read back as 0 (after every wave of k_keep_build has read it)
-__global__ void k_keep_tail(uint32_t *up, uint64_t n) {
-    if (n % 32u) up[n / 32u] &= (1u << (n % 32u)) - 1u;
-}
-void launch_keep_build(hipStream_t s, uint32_t *up, const uint32_t *perm, uint64_t n, uint32_t *res, uint8_t *sum,
-                       uint64_t c0) {
-    const uint64_t nchunks = (n + 255) / 256;
-    if (c0 >= nchunks) return;
-    const uint64_t blocks = (nchunks - c0 + 3) / 4;  // (a wave per chunk)
-    hipLaunchKernelGGL(k_keep_build, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, up, perm, n, res, sum, c0);
-    hipLaunchKernelGGL(k_keep_tail, dim3(1), dim3(1), 0, s, up, n);
-}
-
-// rtr_append_points: the upload-order mask of a cloud of n0 points, grown to n1, keeps the new points -- the bits
-// [n0, n1) are set.  Word n0 / 32 keeps its bits below n0 (the ones at or past n0 are clear, k_keep_tail); the words
-// behind it are written whole.
-__global__ __launch_bounds__(kBlock) void k_keep_append(uint32_t *__restrict__ up, uint64_t n0, uint64_t n1) {
-    const uint64_t w0 = n0 / 32u, w1 = (n1 + 31u) / 32u;
-    for (uint64_t w = w0 + (uint64_t)blockIdx.x * kBlock + threadIdx.x; w < w1; w += (uint64_t)gridDim.x * kBlock) {
-        const uint64_t lo = w * 32u > n0 ? w * 32u : n0, hi = w * 32u + 32u < n1 ? w * 32u + 32u : n1;  // bits [lo, hi)
-        const uint32_t bits = (uint32_t)((((1ull << (hi - lo)) - 1ull) << (lo - w * 32u)));
-        up[w] = (w == w0 && (n0 % 32u) ? up[w] : 0u) | bits;
-    }
-}
-void launch_keep_append(hipStream_t s, uint32_t *up, uint64_t n0, uint64_t n1) {
-    if (n1 <= n0) return;
-    const uint64_t words = (n1 + 31) / 32 - n0 / 32, blocks = (words + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_keep_append, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, up, n0, n1);
-}
-
-
-// ---- rtr_remove_points (rtr.h section 2c) ------------------------------------------------------------------------
-// A stable compaction of the resident order.  keep: the caller's upload-order words (bits at or past n ignored), perm:
-// resident index -> upload index (null while the cloud is in upload order).  Lane l of the wave that holds chunk c
-// gathers the keep bits of its points 4 l .. 4 l + 3, as k_keep_build does; the four ballots give the chunk's survivor
-// count and every survivor's slot in it (rtr_remove_index.h).
-__device__ __forceinline__ void remove_gather(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ perm, uint64_t n,
-                                              uint64_t c, int lane, uint32_t u[4], bool kept[4], bool valid[4]) {
-    const uint64_t r0 = c * 256u + 4u * (uint64_t)lane;
-    if (perm && r0 < n) {  // (perm holds whole quads: its arrays are padded to a multiple of 4 points)
-        const uint4 q = *reinterpret_cast<const uint4 *>(perm + r0);
-        u[0] = q.x, u[1] = q.y, u[2] = q.z, u[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) u[k] = (uint32_t)(r0 + k);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        valid[k] = r0 + k < n;
-        kept[k] = valid[k] && ((keep[u[k] >> 5] >> (u[k] & 31u)) & 1u);
-    }
-}
-// cnt[c] = the survivors of chunk c; *first_loss = the first chunk that loses a point (the caller sets ~0).  A wave's
-// chunks ascend, so its first loss is its least; the workgroup folds its waves' in LDS and issues one atomic (one per
-// chunk, all on one address, cost 4.4 ms at 1e8 points)
-__global__ __launch_bounds__(kBlock) void k_remove_count(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ perm,
-                                                         uint64_t n, uint32_t *__restrict__ cnt,
-                                                         unsigned long long *__restrict__ first_loss) {
-    __shared__ unsigned long long s_first;
-    const int lane = threadIdx.x & 63;
-    const uint64_t nchunks = (n + 255) / 256;
-    if (threadIdx.x == 0) s_first = ~0ull;
-    __syncthreads();
-    unsigned long long mine = ~0ull;
-    for (uint64_t c = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
-        uint32_t u[4];
-        bool kept[4], valid[4];
-        remove_gather(keep, perm, n, c, lane, u, kept, valid);
-        uint32_t s = 0, v = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s += __popcll(__ballot(kept[k])), v += __popcll(__ballot(valid[k]));
-        if (lane == 0) cnt[c] = s;
-        if (s != v && mine == ~0ull) mine = c;
-    }
-    if (lane == 0 && mine != ~0ull) atomicMin(&s_first, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_first != ~0ull) atomicMin(first_loss, s_first);
-}
-void launch_remove_count(hipStream_t s, const uint32_t *keep, const uint32_t *perm, uint64_t n, uint32_t *cnt, uint64_t *first_loss) {
-    const uint64_t nchunks = (n + 255) / 256;
-    if (nchunks == 0) return;
-    const uint64_t blocks = (nchunks + 3) / 4;  // (a wave per chunk)
-    hipLaunchKernelGGL(k_remove_count, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, keep, perm, n, cnt,
-                       (unsigned long long *)first_loss);
-}
-
-// Exclusive scan of `count` u32 values (popc_bits > 0: of the popcounts of words holding popc_bits bits, the bits past
-// them ignored) in three launches: tile sums (kScanTile values per workgroup), one workgroup scans the sums, every
-// tile scans itself from its sum's prefix.
-constexpr uint64_t kScanPer = 8, kScanTile = kBlock * kScanPer;
-__device__ __forceinline__ uint32_t scan_value(const uint32_t *__restrict__ in, uint64_t i, uint64_t count, uint64_t popc_bits) {
-    if (i >= count) return 0u;
-    const uint32_t v = in[i];
-    if (!popc_bits) return v;
-    const uint32_t m = (i == popc_bits / 32u && (popc_bits % 32u)) ? (1u << (popc_bits % 32u)) - 1u : 0xFFFFFFFFu;
-    return (uint32_t)__popc(v & m);
-}
-__global__ __launch_bounds__(kBlock) void k_scan_tiles(const uint32_t *__restrict__ in, uint64_t count, uint64_t popc_bits,
-                                                       uint32_t *__restrict__ tile_sum) {
-    __shared__ uint32_t s_w[8];
-    const uint64_t ntiles = (count + kScanTile - 1) / kScanTile;
-    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint64_t i0 = t * kScanTile + threadIdx.x * kScanPer;
-        uint32_t v = 0, tot = 0;
-#pragma unroll
-        for (uint64_t k = 0; k < kScanPer; ++k) v += scan_value(in, i0 + k, count, popc_bits);
-        (void)block_scan(v, s_w, tot);
-        if (threadIdx.x == 0) tile_sum[t] = tot;
-    }
-}
-__global__ __launch_bounds__(512) void k_scan_top(uint32_t *__restrict__ tile_sum, uint64_t ntiles, uint64_t *__restrict__ total) {
-    __shared__ uint32_t s_w[8];
-    uint64_t carry = 0;
-    for (uint64_t t0 = 0; t0 < ntiles; t0 += 512) {
-        const uint64_t t = t0 + threadIdx.x;
-        const uint32_t v = t < ntiles ? tile_sum[t] : 0u;
-        uint32_t tot = 0;
-        const uint32_t incl = block_scan(v, s_w, tot);
-        if (t < ntiles) tile_sum[t] = (uint32_t)(carry + (incl - v));  // (sums of fewer than 2^32 points)
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-__global__ __launch_bounds__(kBlock) void k_scan_apply(const uint32_t *__restrict__ in, uint64_t count, uint64_t popc_bits,
-                                                       const uint32_t *__restrict__ tile_sum, uint32_t *__restrict__ out) {
-    __shared__ uint32_t s_w[8];
-    const uint64_t ntiles = (count + kScanTile - 1) / kScanTile;
-    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const uint64_t i0 = t * kScanTile + threadIdx.x * kScanPer;
-        uint32_t v[kScanPer], sum = 0, tot = 0;
-#pragma unroll
-        for (uint64_t k = 0; k < kScanPer; ++k) v[k] = scan_value(in, i0 + k, count, popc_bits), sum += v[k];
-        uint32_t run = tile_sum[t] + block_scan(sum, s_w, tot) - sum;
-#pragma unroll
-        for (uint64_t k = 0; k < kScanPer; ++k) {
-            if (i0 + k < count) out[i0 + k] = run;
-            run += v[k];
-        }
-    }
-}
-uint64_t scan_scratch_words(uint64_t count) { return (count + kScanTile - 1) / kScanTile + 1; }
-void launch_scan_u32(hipStream_t s, const uint32_t *in, uint64_t count, uint64_t popc_bits, uint32_t *out, uint32_t *scratch,
-                     uint64_t *total) {
-    const uint64_t ntiles = (count + kScanTile - 1) / kScanTile;
-    const unsigned grid = (unsigned)(ntiles < 8192 ? (ntiles ? ntiles : 1) : 8192);
-    if (ntiles) hipLaunchKernelGGL(k_scan_tiles, dim3(grid), dim3(kBlock), 0, s, in, count, popc_bits, scratch);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(512), 0, s, scratch, ntiles, total);
-    if (ntiles) hipLaunchKernelGGL(k_scan_apply, dim3(grid), dim3(kBlock), 0, s, in, count, popc_bits, scratch, out);
-}
-
-// The survivors of chunks c0.. into the window (fp32 SoA, colours, renumbered upload indices when perm is kept): chunk
-// c's go to dst[c] - 256 c0 on, in their order.  Coordinates from the fp32 SoA when resident, else decoded from the
-// packed form (bit for bit); wscan: the exclusive popcount scan of `keep` (renumbering; read only with perm).
-__global__ __launch_bounds__(kBlock) void k_remove_compact(const uint4 *__restrict__ hdr, const uint32_t *__restrict__ planes,
-                                                           const uint32_t *__restrict__ planes_b, const float4 *__restrict__ x4,
-                                                           const float4 *__restrict__ y4, const float4 *__restrict__ z4,
-                                                           const uint4 *__restrict__ rgba4, const uint32_t *__restrict__ perm,
-                                                           const uint32_t *__restrict__ keep, const uint32_t *__restrict__ wscan,
-                                                           const uint32_t *__restrict__ dst, uint64_t n, uint64_t c0,
-                                                           float *__restrict__ wx, float *__restrict__ wy, float *__restrict__ wz,
-                                                           uint32_t *__restrict__ wrgba, uint32_t *__restrict__ wperm) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t nchunks = (n + 255) / 256, n4 = (n + 3) / 4;
-    for (uint64_t c = c0 + (((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6); c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
-        uint32_t u[4];
-        bool kept[4], valid[4];
-        remove_gather(keep, perm, n, c, lane, u, kept, valid);
-        unsigned long long b[4];
-        uint32_t below = 0, own = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            b[k] = __ballot(kept[k]);
-            below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b[k], below));
-            own |= kept[k] ? 1u << k : 0u;
-        }
-        if ((b[0] | b[1] | b[2] | b[3]) == 0ull) continue;  // (wave-uniform)
-        const uint64_t i = c * 64 + lane;
-        float4 X, Y, Z;
-        if (x4) {
-            if (i < n4) X = x4[i], Y = y4[i], Z = z4[i];
-        } else {  // (every lane decodes, as k_unpack_soa does: lanes past the end read the spare bytes)
-            const uint4 h0 = hdr[2 * c], h1 = hdr[2 * c + 1];
-            const ChunkRawA raw_a = load_chunk_a(planes, h0, h1, lane);
-            const ChunkRaw raw = load_chunk_b(planes_b, h0, h1, lane);
-            unpack_chunk(raw_a, raw, h0.w, h0.x, h0.y, h0.z, X, Y, Z, lane);
-        }
-        if (!own) continue;  // (i < n4 from here on)
-        const uint4 col = rgba4[i];
-        const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
-        const uint32_t cs[4] = {col.x, col.y, col.z, col.w};
-        const uint64_t base = (uint64_t)dst[c] - 256u * c0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (!kept[k]) continue;
-            const uint64_t o = base + remove_slot(below, own, (uint32_t)k);
-            wx[o] = xs[k], wy[o] = ys[k], wz[o] = zs[k], wrgba[o] = cs[k];
-            if (wperm) wperm[o] = remove_rank(wscan[u[k] >> 5], keep[u[k] >> 5], u[k]);
-        }
-    }
-}
-void launch_remove_compact(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *keep, const uint32_t *wscan,
-                           const uint32_t *dst, uint64_t c0, float *wx, float *wy, float *wz, uint32_t *wrgba, uint32_t *wperm) {
-    const uint64_t nchunks = (c.n + 255) / 256;
-    if (c0 >= nchunks) return;
-    const uint64_t blocks = (nchunks - c0 + 3) / 4;
-    hipLaunchKernelGGL(k_remove_compact, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, c.pk.hdr, c.pk.planes,
-                       c.pk.planes_b, (const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, (const uint4 *)c.rgba, perm,
-                       keep, wscan, dst, c.n, c0, wx, wy, wz, wrgba, wperm);
-}
-
-// The upload-order keep mask in force compacted onto the survivors: the mask bits of word w's kept points go to bits
-// wscan[w] .. of up1 (cleared by the caller), in order.
-__global__ __launch_bounds__(kBlock) void k_remove_mask(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ wscan,
-                                                        const uint32_t *__restrict__ up, uint64_t n, uint32_t *__restrict__ up1) {
-    const uint64_t nwords = (n + 31) / 32;
-    for (uint64_t w = (uint64_t)blockIdx.x * kBlock + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t kw = keep[w] & ((w == n / 32u && (n % 32u)) ? (1u << (n % 32u)) - 1u : 0xFFFFFFFFu);
-        const uint32_t bits = remove_extract(up[w], kw);
-        if (!bits) continue;
-        const uint32_t base = wscan[w], sh = base & 31u;
-        atomicOr(&up1[base >> 5], bits << sh);
-        if (sh && (bits >> (32u - sh))) atomicOr(&up1[(base >> 5) + 1], bits >> (32u - sh));
-    }
-}
-void launch_remove_mask(hipStream_t s, const uint32_t *keep, const uint32_t *wscan, const uint32_t *up, uint64_t n, uint32_t *up1) {
-    const uint64_t nwords = (n + 31) / 32, blocks = (nwords + kBlock - 1) / kBlock;
-    if (nwords == 0) return;
-    hipLaunchKernelGGL(k_remove_mask, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, keep, wscan, up, n, up1);
-}
-
-// The chunks in front of the first one that loses a point keep their points, but on a sorted cloud not their upload
-// indices: a removed point with a smaller index lies in a LATER chunk, and every index above it drops by one.  A quad of
-// perm per lane, each index replaced by its rank among the kept points, into the permutation's replacement.
-__global__ __launch_bounds__(kBlock) void k_remove_renumber(const uint4 *__restrict__ perm4, uint64_t quads,
-                                                            const uint32_t *__restrict__ keep, const uint32_t *__restrict__ wscan,
-                                                            uint4 *__restrict__ out4) {
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < quads; i += (uint64_t)gridDim.x * kBlock) {
-        const uint4 u = perm4[i];
-        uint4 r;
-        r.x = remove_rank(wscan[u.x >> 5], keep[u.x >> 5], u.x);
-        r.y = remove_rank(wscan[u.y >> 5], keep[u.y >> 5], u.y);
-        r.z = remove_rank(wscan[u.z >> 5], keep[u.z >> 5], u.z);
-        r.w = remove_rank(wscan[u.w >> 5], keep[u.w >> 5], u.w);
-        out4[i] = r;
-    }
-}
-void launch_remove_renumber(hipStream_t s, const uint32_t *perm, uint64_t count, const uint32_t *keep, const uint32_t *wscan,
-                            uint32_t *out) {
-    const uint64_t quads = count / 4, blocks = (quads + kBlock - 1) / kBlock;
-    if (quads == 0) return;
-    hipLaunchKernelGGL(k_remove_renumber, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kBlock), 0, s, (const uint4 *)perm,
-                       quads, keep, wscan, (uint4 *)out);
 }
 
 // ---- rtr_extract_points (rtr.h section 2e) -----------------------------------------------------------------------
@@ -5104,308 +4654,6 @@ void launch_transform_window(hipStream_t s, const Cloud &c, const uint32_t *perm
     hipLaunchKernelGGL(k_transform_window, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, c.pk.hdr,
                        c.pk.planes, c.pk.planes_b, (const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, perm, sel,
                        c.n, c0, c1, M, in_place ? 1 : 0, (float4 *)wx, (float4 *)wy, (float4 *)wz);
-}
-
-__global__ __launch_bounds__(kBlock) void k_shift_units(uint4 *__restrict__ hdr, uint64_t c_from, uint64_t c_to, long long delta) {
-    for (uint64_t c = c_from + (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < c_to; c += (uint64_t)gridDim.x * kBlock) {
-        uint4 h = hdr[2 * c + 1];
-        const uint64_t off = ((((uint64_t)h.y) << 32) | (uint64_t)h.x) + (uint64_t)delta;
-        h.x = (uint32_t)off, h.y = (uint32_t)(off >> 32);
-        hdr[2 * c + 1] = h;
-    }
-}
-// out[0] += the wide chunks among hdr's first nchunks headers, out[1] += those of them that carry a box word
-__global__ __launch_bounds__(kBlock) void k_wide_counts(const uint4 *__restrict__ hdr, uint64_t nchunks, unsigned long long *out) {
-    uint32_t wide = 0, boxed = 0;
-    for (uint64_t c = (uint64_t)blockIdx.x * kBlock + threadIdx.x; c < nchunks; c += (uint64_t)gridDim.x * kBlock) {
-        const bool w = (hdr[2 * c].w & kPackWideFlag) != 0u;
-        wide += w ? 1u : 0u;
-        boxed += w && hdr[2 * c + 1].w != 0u ? 1u : 0u;
-    }
-    const uint32_t nw = (uint32_t)__popcll(__ballot(wide != 0u));  // (most waves hold none)
-    if (nw == 0u) return;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) wide += (uint32_t)__shfl_xor((int)wide, off, 64), boxed += (uint32_t)__shfl_xor((int)boxed, off, 64);
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&out[0], (unsigned long long)wide);
-        atomicAdd(&out[1], (unsigned long long)boxed);
-    }
-}
-void launch_wide_counts(hipStream_t s, const uint4 *hdr, uint64_t nchunks, uint64_t *out) {
-    if (nchunks == 0) return;
-    const uint64_t blocks = (nchunks + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_wide_counts, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(kBlock), 0, s, hdr, nchunks,
-                       (unsigned long long *)out);
-}
-void launch_shift_units(hipStream_t s, uint4 *hdr, uint64_t c_from, uint64_t c_to, int64_t delta) {
-    if (c_from >= c_to || delta == 0) return;
-    const uint64_t blocks = (c_to - c_from + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_shift_units, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kBlock), 0, s, hdr, c_from, c_to,
-                       (long long)delta);
-}
-
-// ---------------------------------------------------------------------------------
-// Selection (rtr_select_points, rtr.h section 6f): which points lie inside a region -- clip_keep over the call's planes
-// and, RECT, the frame's own project_point landing on a pixel of the rectangle -- as upload-order bit words combined
-// with the selection so far by `op`.  The point pass's skeleton: one wave per 256-point chunk (lane l: points 4 l ..
-// 4 l + 3), chunks dealt round robin, PACKED 64 headers tested per wave step and only the survivors decoded.  The
-// chunk decision has three outcomes:
-//   outside: the box lies beyond one plane (clip_box_outside) or beyond one half-space of the rectangle (rect_planes +
-//            box_outside): no point of it is inside;
-//   inside:  planes only -- the box lies within every plane (clip_box_inside): every point of it is inside (a packed
-//            chunk that has a box holds no NaN).  No plane and no rectangle: every chunk, boxed or not;
-//   mixed:   decoded and tested point by point.
-// Not PACKED the boxes are k_chunk_bounds', whose fminf / fmaxf skip NaN coordinates: a NaN may hide behind a finite
-// box, so such a chunk is classed outside (a NaN point is not inside either) but never inside on its box.
-// hit = inside, or, `invert`, !inside for the points below n; the points at or past n are never hit.
-// Writing, PERM = false: a decoded chunk's 256 hits are four ballots interleaved into eight words (lanes 0..7, as the
-// point pass) and combined with the old words by plain loads and stores -- each chunk's words belong to one wave.  An
-// undecoded chunk's hits are all alike: the header lane itself stores its eight words, and only where `op` changes
-// them (ADD / SUBTRACT / TOGGLE of nothing and INTERSECT with everything leave the old words; TOGGLE of everything
-// flips them; the rest are constants: the old words hold no bit past n, so nothing is loaded).
-// PERM: bits go through perm[resident index] with atomicOr (REPLACE -- the caller cleared the words -- and ADD),
-// atomicAnd (SUBTRACT: the hits; INTERSECT: the misses) or atomicXor (TOGGLE); an undecoded chunk reads its 256 perm entries when `op` has
-// something to change, never its coordinates.
-// stats (null: not requested): [1] / [2] / [3] += chunks outside / inside / decoded, folded per workgroup in LDS: three
-// atomics per workgroup ([0] is k_select_count's).
-constexpr int kSelReplace = 0, kSelAdd = 1, kSelSubtract = 2, kSelIntersect = 3, kSelToggle = 8;  // (RTR_SELECT_*)
-struct SelectArgs {
-    const float4 *x4, *y4, *z4;  // fp32 SoA (not PACKED) ...
-    const float *bounds;         // ... and its chunk boxes (k_chunk_bounds)
-    PackedXyz pk;                // packed form (PACKED)
-    uint64_t n;
-    uint32_t *sel;               // 8 words per chunk
-    const uint32_t *perm;        // resident index -> upload index (PERM)
-    unsigned long long *stats;
-    int op, invert;
-    int x0, y0, x1, y1;          // RECT
-};
-__device__ __forceinline__ uint32_t select_word_mask(uint64_t n, uint64_t c, uint32_t j) {  // the bits of word j of chunk c below n
-    const uint64_t first = c * 256u + 32u * j;
-    if (first >= n) return 0u;
-    const uint64_t left = n - first;
-    return left >= 32u ? 0xFFFFFFFFu : (1u << (uint32_t)left) - 1u;
-}
-// the eight words of a chunk whose points below n are all hit / all missed (one lane; PERM = false)
-__device__ __forceinline__ void select_store_uniform(const SelectArgs &a, uint64_t c, bool hit) {
-    if (hit ? a.op == kSelIntersect : (a.op == kSelAdd || a.op == kSelSubtract || a.op == kSelToggle)) return;  // (the old words stay)
-    uint4 *w = reinterpret_cast<uint4 *>(a.sel + 8 * c);
-    if (a.op == kSelToggle) {  // (of everything below n: the only case that reads the old words)
-        const uint4 o0 = w[0], o1 = w[1];
-        w[0] = make_uint4(o0.x ^ select_word_mask(a.n, c, 0), o0.y ^ select_word_mask(a.n, c, 1), o0.z ^ select_word_mask(a.n, c, 2), o0.w ^ select_word_mask(a.n, c, 3));
-        w[1] = make_uint4(o1.x ^ select_word_mask(a.n, c, 4), o1.y ^ select_word_mask(a.n, c, 5), o1.z ^ select_word_mask(a.n, c, 6), o1.w ^ select_word_mask(a.n, c, 7));
-    } else if (!hit || a.op == kSelSubtract) {  // (REPLACE / INTERSECT with nothing, SUBTRACT of everything)
-        w[0] = make_uint4(0u, 0u, 0u, 0u);
-        w[1] = make_uint4(0u, 0u, 0u, 0u);
-    } else {  // (REPLACE by / ADD of everything below n)
-        w[0] = make_uint4(select_word_mask(a.n, c, 0), select_word_mask(a.n, c, 1), select_word_mask(a.n, c, 2), select_word_mask(a.n, c, 3));
-        w[1] = make_uint4(select_word_mask(a.n, c, 4), select_word_mask(a.n, c, 5), select_word_mask(a.n, c, 6), select_word_mask(a.n, c, 7));
-    }
-}
-// the wave writes the hits of chunk c (hit[k]: point 4 lane + k, already false at or past n)
-template <bool PERM>
-__device__ __forceinline__ void select_write(const SelectArgs &a, uint64_t c, int lane, const bool hit[4]) {
-    if (PERM) {
-        const uint64_t i0 = c * 256u + 4u * (uint64_t)lane;
-        if (i0 < a.n) {  // (perm holds whole quads: its arrays are padded to a multiple of 4 points)
-            const uint4 q = *reinterpret_cast<const uint4 *>(a.perm + i0);
-            const uint32_t u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (i0 + k >= a.n) continue;
-                const uint32_t bit = 1u << (u[k] & 31u);
-                if (a.op == kSelIntersect) {
-                    if (!hit[k]) atomicAnd(a.sel + (u[k] >> 5), ~bit);
-                } else if (hit[k]) {
-                    if (a.op == kSelSubtract) atomicAnd(a.sel + (u[k] >> 5), ~bit);
-                    else if (a.op == kSelToggle) atomicXor(a.sel + (u[k] >> 5), bit);
-                    else atomicOr(a.sel + (u[k] >> 5), bit);
-                }
-            }
-        }
-    } else {
-        // word j of the chunk = points 32 j .. 32 j + 31 = lanes 8 j .. 8 j + 7; point 4 l + k is bit l of ballot k
-        const unsigned long long b0 = __ballot(hit[0]), b1 = __ballot(hit[1]), b2 = __ballot(hit[2]), b3 = __ballot(hit[3]);
-        if (lane < 8) {
-            const int sh = 8 * lane;
-            const uint32_t h = spread_nibbles((uint32_t)(b0 >> sh)) | (spread_nibbles((uint32_t)(b1 >> sh)) << 1) |
-                               (spread_nibbles((uint32_t)(b2 >> sh)) << 2) | (spread_nibbles((uint32_t)(b3 >> sh)) << 3);
-            uint32_t *w = a.sel + 8 * c + lane;
-            if (a.op == kSelReplace) *w = h;
-            else {
-                const uint32_t old = *w;
-                *w = a.op == kSelAdd ? (old | h) : (a.op == kSelSubtract ? (old & ~h) : (a.op == kSelToggle ? (old ^ h) : (old & h)));
-            }
-        }
-    }
-}
-// a decoded chunk: the predicate per point
-template <bool PERM, bool RECT>
-__device__ __forceinline__ void select_chunk(const SelectArgs &a, const Clip &clip, const Proj &P, int W, int H, float fW, float fH,
-                                             uint64_t c, const float4 &X, const float4 &Y, const float4 &Z, int lane) {
-    const uint64_t i0 = c * 256u + 4u * (uint64_t)lane;
-    const float xs[4] = {X.x, X.y, X.z, X.w}, ys[4] = {Y.x, Y.y, Y.z, Y.w}, zs[4] = {Z.x, Z.y, Z.z, Z.w};
-    bool hit[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        bool in = clip_keep(clip, xs[k], ys[k], zs[k]);
-        if (RECT) {
-            float d;
-            const int pix = project_point(P, xs[k], ys[k], zs[k], W, H, fW, fH, d);
-            const int py = pix >= 0 ? (int)((uint32_t)pix / (uint32_t)W) : -1, px = pix - py * W;
-            in = in && pix >= 0 && px >= a.x0 && px < a.x1 && py >= a.y0 && py < a.y1;
-        }
-        hit[k] = i0 + k < a.n && in != (a.invert != 0);
-    }
-    select_write<PERM>(a, c, lane, hit);
-}
-constexpr int kSelOutside = 0, kSelInside = 1, kSelMixed = 2;
-template <bool PACKED, bool PERM, bool RECT>
-__global__ __launch_bounds__(kBlock) void k_select(SelectArgs a, Clip clip, Proj P, int W, int H) {
-    __shared__ uint32_t s_cnt[3];
-    const float fW = (float)W, fH = (float)H;
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
-    const uint64_t nwaves = ((uint64_t)gridDim.x * kBlock) >> 6;
-    const uint64_t n4 = (a.n + 3) / 4, nchunks = (n4 + 63) / 64;
-    const bool every = !RECT && clip.count == 0;  // (no condition at all: every point, NaN included, is inside)
-    const bool invert = a.invert != 0;
-    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    FrustumPlanes rpl{};
-    if (RECT) rpl = rect_planes(P.m, (float)a.x0, (float)a.y0, (float)a.x1, (float)a.y1);
-    uint32_t cnt[3] = {0u, 0u, 0u};  // (wave-uniform)
-    if (!PACKED) {
-        for (uint64_t c = wave; c < nchunks; c += nwaves) {  // (wave-uniform)
-            int state = every ? kSelInside : kSelMixed;
-            if (!every) {
-                const float *b = a.bounds + 6 * c;
-                const float lo[3] = {b[0], b[1], b[2]}, hi[3] = {b[3], b[4], b[5]};
-                if (clip_box_outside(clip, lo, hi) || (RECT && box_outside(rpl, lo, hi))) state = kSelOutside;
-            }
-            cnt[kSelOutside] += state == kSelOutside, cnt[kSelInside] += state == kSelInside, cnt[kSelMixed] += state == kSelMixed;
-            const bool hit_u = (state == kSelInside) != invert;
-            if (state != kSelMixed && !PERM) {
-                if (lane == 0) select_store_uniform(a, c, hit_u);
-                continue;
-            }
-            if (state != kSelMixed) {
-                if (a.op == kSelIntersect ? !hit_u : hit_u) {
-                    const uint64_t i0 = c * 256u + 4u * (uint64_t)lane;
-                    const bool hit[4] = {hit_u && i0 < a.n, hit_u && i0 + 1 < a.n, hit_u && i0 + 2 < a.n, hit_u && i0 + 3 < a.n};
-                    select_write<PERM>(a, c, lane, hit);
-                }
-                continue;
-            }
-            const uint64_t i = c * 64u + (uint64_t)lane, ic = i < n4 ? i : n4 - 1u;
-            const float4 X = ld_stream(a.x4 + ic), Y = ld_stream(a.y4 + ic), Z = ld_stream(a.z4 + ic);
-            select_chunk<PERM, RECT>(a, clip, P, W, H, fW, fH, c, X, Y, Z, lane);
-        }
-    } else {
-        for (uint64_t j0 = 0; wave + nwaves * j0 < nchunks; j0 += 64u) {  // (wave-uniform)
-            const uint64_t chunk = wave + nwaves * (j0 + (uint64_t)lane);
-            const bool valid = chunk < nchunks;
-            int state = kSelMixed;
-            if (valid) {
-                if (every) state = kSelInside;
-                else {
-                    const uint4 h0 = a.pk.hdr[2 * chunk];
-                    float lo[3], hi[3];
-                    const uint32_t wbox = reinterpret_cast<const uint32_t *>(a.pk.hdr + 2 * chunk + 1)[3];  // (the header's own 32 bytes)
-                    if (chunk_box(h0.x, h0.y, h0.z, h0.w, wbox, lo, hi)) {
-                        if (clip_box_outside(clip, lo, hi) || (RECT && box_outside(rpl, lo, hi))) state = kSelOutside;
-                        else if (!RECT && clip_box_inside(clip, lo, hi)) state = kSelInside;
-                    }
-                }
-            }
-            const bool hit_u = (state == kSelInside) != invert;
-            bool work = valid && state == kSelMixed;  // (the chunks that need the whole wave)
-            if (valid && state != kSelMixed) {
-                if (!PERM) select_store_uniform(a, chunk, hit_u);
-                else work = a.op == kSelIntersect ? !hit_u : hit_u;
-            }
-            cnt[kSelOutside] += (uint32_t)__popcll(__ballot(valid && state == kSelOutside));
-            cnt[kSelInside] += (uint32_t)__popcll(__ballot(valid && state == kSelInside));
-            cnt[kSelMixed] += (uint32_t)__popcll(__ballot(valid && state == kSelMixed));
-            const unsigned long long mixed = __ballot(valid && state == kSelMixed);
-            unsigned long long mask = __ballot(work);
-            while (mask) {
-                const int l = __ffsll((long long)mask) - 1;
-                mask &= mask - 1;
-                const uint64_t cc = wave + nwaves * (j0 + (uint64_t)l);
-                if (PERM && !((mixed >> l) & 1ull)) {  // (an undecoded chunk through the permutation: `work` says all hit / all missed)
-                    const bool hu = a.op != kSelIntersect;
-                    const uint64_t i0 = cc * 256u + 4u * (uint64_t)lane;
-                    const bool hit[4] = {hu && i0 < a.n, hu && i0 + 1 < a.n, hu && i0 + 2 < a.n, hu && i0 + 3 < a.n};
-                    select_write<PERM>(a, cc, lane, hit);
-                    continue;
-                }
-                const uint4 h0 = a.pk.hdr[2 * cc], h1 = a.pk.hdr[2 * cc + 1];
-                const ChunkRawA raw_a = load_chunk_a(a.pk.planes, h0, h1, lane);
-                const ChunkRaw raw = load_chunk_b(a.pk.planes_b, h0, h1, lane);
-                float4 X, Y, Z;
-                unpack_chunk(raw_a, raw, h0.w, h0.x, h0.y, h0.z, X, Y, Z, lane);
-                select_chunk<PERM, RECT>(a, clip, P, W, H, fW, fH, cc, X, Y, Z, lane);
-            }
-        }
-    }
-    if (a.stats) {  // (wave-uniform)
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                if (cnt[k]) atomicAdd(&s_cnt[k], cnt[k]);
-        }
-        __syncthreads();
-        if (threadIdx.x < 3 && s_cnt[threadIdx.x]) atomicAdd(a.stats + 1 + threadIdx.x, (unsigned long long)s_cnt[threadIdx.x]);
-    }
-}
-// *out += the set bits of `words` (16-byte units; the bits past n are clear): one atomic per workgroup
-__global__ __launch_bounds__(kBlock) void k_select_count(const uint4 *__restrict__ words, uint64_t n16, unsigned long long *__restrict__ out) {
-    __shared__ uint32_t s_sum;
-    if (threadIdx.x == 0) s_sum = 0u;
-    __syncthreads();
-    uint32_t mine = 0u;  // (a thread sees at most 2^32 / 128 units' bits)
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n16; i += (uint64_t)gridDim.x * kBlock) {
-        const uint4 q = words[i];
-        mine += (uint32_t)(__popc(q.x) + __popc(q.y) + __popc(q.z) + __popc(q.w));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_sum, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_sum) atomicAdd(out, (unsigned long long)s_sum);
-}
-void launch_select(hipStream_t s, const Cloud &c, const float *bounds, const Clip &clip, const Proj *P, int W, int H,
-                   const int rect[4], int op, bool invert, uint32_t *sel, const uint32_t *perm, uint64_t *stats) {
-    const uint64_t n4 = (c.n + 3) / 4, nchunks = (n4 + 63) / 64;
-    if (nchunks == 0) return;
-    const bool packed = c.pk.hdr != nullptr;
-    SelectArgs a{(const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, bounds, c.pk, c.n, sel, perm,
-                 (unsigned long long *)stats, op, invert ? 1 : 0, 0, 0, 0, 0};
-    Proj proj{};
-    if (P) proj = *P, a.x0 = rect[0], a.y0 = rect[1], a.x1 = rect[2], a.y1 = rect[3];
-    const uint64_t blocks = (nchunks + 3) / 4;  // (up to 8 waves per CU, every chunk dealt round robin: the point pass's grid)
-    const dim3 grid((unsigned)(blocks < 2048 ? blocks : 2048)), block(kBlock);
-    auto go = [&](auto pk, auto pm, auto rc) {  // (PACKED, PERM, RECT)
-        hipLaunchKernelGGL((k_select<decltype(pk)::value, decltype(pm)::value, decltype(rc)::value>), grid, block, 0, s, a, clip,
-                           proj, W, H);
-    };
-    auto with_rect = [&](auto pk, auto pm) {
-        if (P) go(pk, pm, std::true_type{}); else go(pk, pm, std::false_type{});
-    };
-    const std::true_type on;
-    const std::false_type off;
-    if (packed && perm) with_rect(on, on);
-    else if (packed) with_rect(on, off);
-    else if (perm) with_rect(off, on);
-    else with_rect(off, off);
-}
-void launch_select_count(hipStream_t s, const uint32_t *sel, uint64_t n, uint64_t *out) {
-    const uint64_t n16 = ((n + 255) / 256) * 2;
-    if (n16 == 0) return;
-    const uint64_t blocks = (n16 + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_select_count, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(kBlock), 0, s, (const uint4 *)sel, n16,
-                       (unsigned long long *)out);
 }
 
 }  // namespace rtr
