@@ -420,6 +420,64 @@ int rtr_extract_points(rtr_ctx *ctx, const uint32_t *select_words, uint64_t nwor
                        uint8_t *rgb, size_t rgb_stride_bytes,
                        uint32_t *indices, uint64_t *total);
 
+/* ---- 2f. writing points back into the resident cloud ---------------------------------------------------------------
+ * Gives resident points new coordinates and / or colours, point by point, where they lie: the mirror image of section
+ * 2e (a selection extracted, recoloured by class or intensity and put back; a highlight; a non-rigid loop-closure or
+ * bundle-adjustment correction; de-noised ranges).  Upload indices do not change, so the selection, the keep mask and
+ * a block sort survive, which uploading the cloud again or removing and appending the points would lose.
+ *
+ * Selection and ranks: exactly section 2e's.  select_words is (n + 31) / 32 words in UPLOAD order, host memory or
+ * device memory of the context's device (the pointer of rtr_device_buffer(RTR_BUF_SELECTION) can be passed as it is);
+ * the words are copied, bits past n are ignored, NULL with nwords = 0 means every point.  Let the selected upload
+ * indices be s_0 < s_1 < ... < s_{k-1}; *total (when non-NULL) receives k.  Record j of the caller's arrays is written
+ * into point s_{first + j}, for j in [0, min(count, k - first)); no record beyond that is read.  first >= k or count = 0
+ * changes nothing and returns RTR_OK, so a sizing call is possible, and a caller may write in pieces.  A selection on a
+ * cloud the library sorted needs option "point_ids" = 1, as everywhere else; on a cloud sorted without it "every point"
+ * addresses the RESIDENT order, as section 2e reads it, so extract-all, edit, write-all round-trips on any cloud.
+ *
+ * Streams: each of xyz and rgb may be NULL -- that stream stays as it is resident; both NULL is an error -- and each may
+ * be host memory or device memory of the context's device, independently of the other.  Strides follow
+ * rtr_upload_points (xyz at least 12 and a multiple of 4, rgb at least 3); only the first 12 bytes of an xyz record and
+ * the first 3 bytes of an rgb record are read.  The resident colour becomes c0 | c1 << 8 | c2 << 16 | 0xFF000000, as an
+ * upload builds it.  rgb_stride_bytes = 0 is the one extension: every written point takes record 0 (one colour for the
+ * whole selection).  xyz_stride_bytes = 0 is an error.
+ *
+ * Values: coordinates are stored bit for bit -- NaN payloads, -0, infinities and denormals round-trip through
+ * rtr_extract_points.  Unlike section 2d there is no device arithmetic, hence no "which NaN" caveat.
+ *
+ * Equivalence: rtr_upload_points(A), then rtr_write_points(sel, first, count, X, C), renders bit for bit what one
+ * rtr_upload_points(A') renders with the same options, params, clip planes and resolution, A' = A except that the points
+ * s_{first + j} take X[j] and / or C[j] -- the outputs section 2b lists, with what depends on the resident order excepted
+ * as there; and so across any sequence of uploads, appends, removals, moves and writes.
+ *
+ * What stays: section 2d's list -- the point count, upload indices and the resident order (no sort), the permutation,
+ * the keep mask in force, the SELECTION (indices do not change), an open peer-to-peer exchange (nothing the peers map is
+ * reallocated).  A packed cloud stays packed ("pack" = 2 verifies the rebuilt chunks), an unpacked one unpacked;
+ * "keep_soa" is honoured.  A colour-only write touches no chunk box, header or packed block.
+ *
+ * Ordering: section 2d's.  The call first completes everything issued before it: frames, passes, view batches and
+ * async slots come out with the old cloud; a frame that overflowed the adaptive extent pool is rendered again with the
+ * old cloud -- if that fails, the call returns the error and changes nothing.  It ends an overlap streak.
+ *
+ * Errors (RTR_ERR_INVALID, nothing changes): no cloud; xyz and rgb both NULL; a bad stride for a non-NULL stream;
+ * nwords != (n + 31) / 32 with a selection; select_words NULL with nwords > 0; a selection on a sorted cloud without
+ * "point_ids" = 1.  2^32 points or more: RTR_ERR_UNSUPPORTED.  A failed allocation leaves the cloud as it was: every
+ * buffer, the device copy of host records included, is allocated before the first resident byte changes -- colours too,
+ * which are written with the commit and never before the rebuilt chunks have been measured.
+ *
+ * Scratch and cost: three arrays of (n + 31) / 32 words (the selection, its scan, the window's bits; also for "every
+ * point", 12.5 MB at 1e8 points); host records are copied to the device once, at the caller's stride --
+ * min(count, k - first) x stride bytes; device records are read where they lie.  A caller who wants bounded scratch
+ * writes in pieces through first / count; each piece is a commit of its own.  Kernel work is proportional to the chunks
+ * from the first to the last one that holds a written point (fp32 scratch for those chunks when the cloud is packed);
+ * for a packed cloud whose rebuilt chunks change size, add the device-to-device move of the blocks behind them, as in
+ * section 2d; and O(n / 256) passes over per-chunk arrays. */
+int rtr_write_points(rtr_ctx *ctx, const uint32_t *select_words, uint64_t nwords,
+                     uint64_t first, uint64_t count,
+                     const float *xyz, size_t xyz_stride_bytes,
+                     const uint8_t *rgb, size_t rgb_stride_bytes,
+                     uint64_t *total);
+
 /* ---- 3. camera (project_cloud.cu:318, project_cloud.h:50-59) -------------------- */
 /* P = K4 * E in fp32, row-major, exactly as the reference composes it with glm:
  * K row-major 3x3 intrinsics, E row-major 4x4 world->camera, both double. */

@@ -30,6 +30,8 @@
 // selectBox / selectPlanes / selectRect (section 6f) name the vertices of a region on the device; removeSelected,
 // hideSelected and transformSelected then act on them without a host array of flags.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
+// writeSelected / writePoints / colorSelected (section 2f) put edited vertices and colours back where they came from:
+// indices, the keep mask and the selection stay.
 //
 // computeFull (project_cloud.h:17-18, project_cloud.cu:437-493) needs libtorch: define RTR_WITH_TORCH
 // before including this header (and link libtorch); without it the class has the two projection
@@ -398,6 +400,45 @@ public:
         return extract(nullptr, 0, vertices, colors, nullptr);
     }
 
+    // Writing back (rtr.h section 2f), the mirror image of extractSelected: the selected vertices, in ascending vertex
+    // index, take the tight records of `vertices` (3 floats each) and `colors` (3 bytes each), as extractSelected returned
+    // and the caller edited them.  Either vector may be empty: that stream stays as it is resident.  A size that is not 3 k,
+    // or two non-empty vectors of different k, throws std::invalid_argument.  Vertex indices, the keep mask and the
+    // selection stay.  Returns the number of vertices written (0 without a selection): min(k, selected).
+    uint64_t writeSelected(const std::vector<float>& vertices, const std::vector<uint8_t>& colors) {
+        const uint64_t k = write_count(vertices, colors, "writeSelected");
+        if (!has_selection() || k == 0) return 0;
+        void* p = nullptr;
+        size_t bytes = 0;
+        check(ctx_, rtr_device_buffer(ctx_, RTR_BUF_SELECTION, &p, &bytes));
+        return write(static_cast<const uint32_t*>(p), (uint64_t)(bytes / 4), 0, k, vertices, colors);
+    }
+    // The vertices [first, first + count) take the records, as transformPoints names a range: count defaults to the
+    // records given; a range past the vertex count throws std::out_of_range, fewer records than `count` or a size that is
+    // not 3 k std::invalid_argument.  A cloud sorted without point_ids is addressed in its sorted order (extractAll's).
+    uint64_t writePoints(uint64_t first, uint64_t count, const std::vector<float>& vertices, const std::vector<uint8_t>& colors) {
+        const uint64_t k = write_count(vertices, colors, "writePoints");
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        if (count == UINT64_MAX) count = k;
+        if (first > n || count > n - first) throw std::out_of_range("writePoints: the range exceeds the vertex count");
+        if (count > k) throw std::invalid_argument("writePoints: fewer records than vertices in the range");
+        if (count == 0) return 0;
+        return write(nullptr, 0, first, count, vertices, colors);  // (every vertex: rank = vertex index)
+    }
+    // One colour for every selected vertex (a highlight); the selection stays.  Returns the number coloured.
+    uint64_t colorSelected(uint8_t c0, uint8_t c1, uint8_t c2) {
+        if (!has_selection()) return 0;
+        void* p = nullptr;
+        size_t bytes = 0;
+        check(ctx_, rtr_device_buffer(ctx_, RTR_BUF_SELECTION, &p, &bytes));
+        const uint8_t rgb[3] = {c0, c1, c2};
+        uint64_t total = 0;
+        check(ctx_, rtr_write_points(ctx_, static_cast<const uint32_t*>(p), (uint64_t)(bytes / 4), 0, UINT64_MAX, nullptr, 0, rgb, 0,
+                                     &total));
+        return total;
+    }
+
     // Renders the frame (computeRGBD / computeFilteredRGBD without host copies) and returns, per pixel (row-major
     // H x W), the vertex index of the point it shows, -1 for none (empty or prefiltered-away pixels).
     template <class Calibration, class Extrinsics>
@@ -457,6 +498,23 @@ private:
             check(ctx_, rtr_extract_points(ctx_, words, nwords, 0, k, vertices.data(), 12, colors.data(), 3,
                                            indices ? indices->data() : nullptr, nullptr));
         return k;
+    }
+    // the records of a write: tight triples, an empty vector = that stream stays; -> their number
+    static uint64_t write_count(const std::vector<float>& vertices, const std::vector<uint8_t>& colors, const char* fn) {
+        if (vertices.size() % 3 || colors.size() % 3)
+            throw std::invalid_argument(std::string(fn) + ": vertices and colors hold 3 values per vertex");
+        if (!vertices.empty() && !colors.empty() && vertices.size() != colors.size())
+            throw std::invalid_argument(std::string(fn) + ": vertices and colors name different numbers of vertices");
+        if (vertices.empty() && colors.empty())
+            throw std::invalid_argument(std::string(fn) + ": vertices and colors are both empty, nothing to write");
+        return (uint64_t)((vertices.empty() ? colors.size() : vertices.size()) / 3);
+    }
+    uint64_t write(const uint32_t* words, uint64_t nwords, uint64_t first, uint64_t count, const std::vector<float>& vertices,
+                   const std::vector<uint8_t>& colors) {
+        uint64_t total = 0;
+        check(ctx_, rtr_write_points(ctx_, words, nwords, first, count, vertices.empty() ? nullptr : vertices.data(), 12,
+                                     colors.empty() ? nullptr : colors.data(), 3, &total));
+        return first < total ? (count < total - first ? count : total - first) : 0;
     }
     template <class Calibration, class Extrinsics>
     static void projection(const Calibration& calibration, const Extrinsics& extrinsics, float P[16]) {

@@ -13,6 +13,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -1387,6 +1388,16 @@ hipError_t copy_blocks(hipStream_t s, uint32_t *planes, uint32_t *planes_b, cons
     return e != hipSuccess ? e : d2d(s, planes_b, c->pk_planes_b, units * 6 * 4);
 }
 
+// Where a caller's array lies (rtr_extract_points, rtr_write_points: each stream may be host or device memory)
+bool on_device(const void *p) {  // device (or managed) memory, as opposed to anything the host owns
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // (plain host memory is unknown to the runtime)
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+
 // Calls that take or return upload-order indices: a cloud sorted by the library must have kept its permutation.
 // `verb`: what the call would do with the indices; `or_else`: the call's own way round it, if it has one
 int need_upload_order(rtr_ctx *c, const char *verb = "mapped", const char *or_else = "") {
@@ -2009,15 +2020,104 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     return cloud_edited(c, true, tot + 3, "points of the rebuilt chunks");
 }
 
-// ---- moving points (rtr.h, section 2d) --------------------------------------------------------------------------
-// Points move where they lie: upload indices, the resident order, colours, the permutation and the keep mask stay.  A
-// selection pass names the first and last chunk holding a selected point, c0 and c1 (no pass for "every point"); only
-// chunks c0 .. c1 are rebuilt.  An unpacked cloud is moved in place (its SoA arrays, then the boxes of c0 .. c1).  A packed
-// one gets a window: chunks c0 .. c1 decoded (read from the SoA arrays with "keep_soa" = 1), the selected points moved.
-// Its commit is its own, because the blocks behind c1 are not decoded: when the window's units differ from the old ones by
+// ---- moving and writing points (rtr.h, sections 2d and 2f) -------------------------------------------------------
+// Points get new coordinates where they lie: upload indices, the resident order, the permutation and the keep mask stay.
+// A selection pass names the first and last chunk holding a point that changes, c0 and c1; only chunks c0 .. c1 are
+// rebuilt (rebuild_chunks).  `fill` queues the kernel that produces those chunks' new points (rtr_transform_points:
+// the selected ones moved; rtr_write_points: the written ones taken from the caller's records) into the arrays it is
+// handed, in_place or not.  An unpacked cloud is rebuilt in place (its SoA arrays, then the boxes of c0 .. c1).  A packed
+// one gets a window: chunks c0 .. c1 decoded (read from the SoA arrays with "keep_soa" = 1) with the new points in.  Its
+// commit is its own, because the blocks behind c1 are not decoded: when the window's units differ from the old ones by
 // delta, the tail's A and B blocks move by delta (through a scratch copy, or into fresh planes when the capacity changes;
 // `fitted`) and its headers' offsets with them.  Every buffer is allocated before the first resident byte changes, as in
-// commit_window.  The n-sized state stays: cloud_edited without `resized`.
+// commit_window; `also` queues what else the call changes in the resident arrays (rtr_write_points: the colours) and
+// runs in the commit phase, behind the last allocation.  tot: four device words -- the span (unused here), the window's
+// units, pack_verify's mismatches.  The n-sized state stays: the callers end in cloud_edited without `resized`.
+static int rebuild_chunks(rtr_ctx *c, DevBufs &buf, uint64_t c0, uint64_t c1, uint64_t *tot, const char *what,
+                          const std::function<void(float *, float *, float *, bool)> &fill, const std::function<void()> &also) {
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nch = (n + 255) / 256;
+    const uint64_t p0 = 256 * c0, wn = std::min(n, 256 * (c1 + 1)) - p0;
+    if (!c->pk_hdr) {  // (in place: nothing left to allocate)
+        fill(c->x + p0, c->y + p0, c->z + p0, true);
+        rtr::launch_chunk_bounds(s, window_view(c, c->x + p0, c->y + p0, c->z + p0, wn, c->spread + c0), c->bounds + 6 * c0,
+                                 c->spread + c0);
+        also();
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return launch_check(c, what);
+    }
+    // the window: chunks c0 .. c1 with the new points in; old_end: the tail's first unit
+    Window w;
+    uint64_t old_end = 0;
+    if (int rc = window_alloc(c, buf, w, c0, wn)) return rc;
+    fill(w.wx, w.wy, w.wz, false);
+    if (int rc = window_measure(c, buf, w, tot + 2, what, &old_end)) return rc;
+    const uint64_t new_end = w.units, tail = c->pk_units - old_end, units1 = new_end + tail;
+    const int64_t delta = (int64_t)(new_end - old_end);
+
+    // every buffer the commit needs, before anything resident changes
+    const uint64_t ucap1 = fitted(c->pk_units_cap, units1);
+    uint32_t *planes1 = c->pk_planes, *planes1_b = c->pk_planes_b, *tmp = nullptr;
+    if (ucap1 != c->pk_units_cap) {
+        HIP_TRY(c, buf.get(&planes1, rtr::pack_total_dwords(ucap1) * 4));
+        planes1_b = planes1 + rtr::pack_b_dwords(ucap1);
+    } else if (delta != 0 && tail) {
+        HIP_TRY(c, buf.get(&tmp, tail * 8 * 4));  // (the tail's A blocks, then its B blocks)
+    }
+
+    // commit: the tail's blocks to their new place, the window's headers and blocks, the tail's block offsets
+    if (planes1 != c->pk_planes) {  // (fresh planes: the prefix and the tail are copied, nothing overlaps)
+        HIP_TRY(c, copy_blocks(s, planes1, planes1_b, c, w.first_unit));
+        HIP_TRY(c, d2d(s, planes1 + new_end * 2, c->pk_planes + old_end * 2, tail * 2 * 4));
+        HIP_TRY(c, d2d(s, planes1_b + new_end * 6, c->pk_planes_b + old_end * 6, tail * 6 * 4));
+    } else if (tmp) {  // (source and destination overlap: through the scratch copy)
+        HIP_TRY(c, d2d(s, tmp, c->pk_planes + old_end * 2, tail * 2 * 4));
+        HIP_TRY(c, d2d(s, tmp + tail * 2, c->pk_planes_b + old_end * 6, tail * 6 * 4));
+        HIP_TRY(c, d2d(s, planes1 + new_end * 2, tmp, tail * 2 * 4));
+        HIP_TRY(c, d2d(s, planes1_b + new_end * 6, tmp + tail * 2, tail * 6 * 4));
+    }
+    HIP_TRY(c, d2d(s, c->pk_hdr + 2 * c0, w.whdr, w.wch * 2 * sizeof(uint4)));
+    rtr::launch_shift_units(s, c->pk_hdr, c1 + 1, nch, delta);
+    rtr::pack_write(s, w.cl, c->pk_hdr + 2 * c0, planes1, planes1_b);
+    HIP_TRY(c, zero_spare(s, planes1, planes1_b, units1));
+    if (c->opt_pack == 2) rtr::pack_verify(s, w.cl, c->pk_hdr + 2 * c0, planes1, planes1_b, tot + 3);
+    HIP_TRY(c, d2d(s, c->bounds + 6 * c0, w.wb, w.wch * 6 * sizeof(float)));
+    HIP_TRY(c, d2d(s, c->spread + c0, w.wsp, w.wch * sizeof(float)));
+    if (c->x) {  // ("keep_soa" = 1: the SoA arrays take the window as well)
+        HIP_TRY(c, d2d(s, c->x + p0, w.wx, w.wpad * 4)); HIP_TRY(c, d2d(s, c->y + p0, w.wy, w.wpad * 4));
+        HIP_TRY(c, d2d(s, c->z + p0, w.wz, w.wpad * 4));
+    }
+    also();
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = launch_check(c, what)) return rc;
+    if (planes1 != c->pk_planes) {
+        buf.swap_in(c->pk_planes, planes1);
+        c->pk_planes_b = planes1_b;
+        c->pk_units_cap = ucap1;
+    }
+    c->pk_units = units1;
+    c->pk_bytes = pack_bytes(units1, nch);
+    return RTR_OK;
+}
+
+// The first and last chunk holding a point of `sel` (upload-order words on the device; perm as for remove_gather) into
+// c0 / c1; *any = false: no point is selected.  tot[0 .. 1]: device scratch of the span.
+static int chunk_span(rtr_ctx *c, const uint32_t *sel, const uint32_t *perm, uint64_t *tot, const char *what, uint64_t *c0,
+                      uint64_t *c1, bool *any) {
+    hipStream_t s = c->stream;
+    const uint64_t nch = (c->n + 255) / 256;
+    HIP_TRY(c, hipMemsetAsync(tot, 0xFF, sizeof(uint64_t), s));
+    HIP_TRY(c, hipMemsetAsync(tot + 1, 0, sizeof(uint64_t), s));
+    rtr::launch_transform_span(s, sel, perm, c->n, tot);
+    uint64_t span[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(span, tot, sizeof span, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (int rc = launch_check(c, what)) return rc;
+    *any = span[0] < nch;
+    *c0 = span[0], *c1 = span[1];
+    return RTR_OK;
+}
+
 int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_words, uint64_t nwords) {
     if (!c) return RTR_ERR_INVALID;
     c->ov.other_call();
@@ -2031,7 +2131,7 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
     if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
     drop_soa(c);  // (SoA arrays decoded for a call in between are not kept: they would hold the old coordinates)
     hipStream_t s = c->stream;
-    const uint64_t n = c->n, nch = (n + 255) / 256;
+    const uint64_t nch = (c->n + 255) / 256;
     const uint32_t *perm0 = c->reordered ? c->perm : nullptr;
     rtr::Affine A;
     memcpy(A.m, M, sizeof A.m);
@@ -2046,76 +2146,107 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
     if (!every) {
         HIP_TRY(c, buf.get(&sel, nwords * 4));
         HIP_TRY(c, hipMemcpyAsync(sel, select_words, nwords * 4, hipMemcpyDefault, s));
-        HIP_TRY(c, hipMemsetAsync(tot, 0xFF, sizeof(uint64_t), s));
-        rtr::launch_transform_span(s, sel, perm0, n, tot);
-        uint64_t span[2] = {0, 0};
-        HIP_TRY(c, hipMemcpyAsync(span, tot, sizeof span, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (int rc = launch_check(c, "transform span")) return rc;
-        if (span[0] >= nch) return RTR_OK;  // (no point selected: nothing changes)
-        c0 = span[0], c1 = span[1];
+        bool any = false;
+        if (int rc = chunk_span(c, sel, perm0, tot, "transform span", &c0, &c1, &any)) return rc;
+        if (!any) return RTR_OK;  // (no point selected: nothing changes)
     }
-    const uint64_t p0 = 256 * c0, wn = std::min(n, 256 * (c1 + 1)) - p0;
     const rtr::Cloud cl = cloud_of(c);
-    if (!c->pk_hdr) {  // (in place: nothing left to allocate)
-        rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, c->x + p0, c->y + p0, c->z + p0, true);
-        rtr::launch_chunk_bounds(s, window_view(c, c->x + p0, c->y + p0, c->z + p0, wn, c->spread + c0), c->bounds + 6 * c0,
-                                 c->spread + c0);
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (int rc = launch_check(c, "transform")) return rc;
-    } else {
-        // the window: chunks c0 .. c1 with the selected points moved; old_end: the tail's first unit
-        Window w;
-        uint64_t old_end = 0;
-        if (int rc = window_alloc(c, buf, w, c0, wn)) return rc;
-        rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, w.wx, w.wy, w.wz, false);
-        if (int rc = window_measure(c, buf, w, tot + 2, "transform window", &old_end)) return rc;
-        const uint64_t new_end = w.units, tail = c->pk_units - old_end, units1 = new_end + tail;
-        const int64_t delta = (int64_t)(new_end - old_end);
-
-        // every buffer the commit needs, before anything resident changes
-        const uint64_t ucap1 = fitted(c->pk_units_cap, units1);
-        uint32_t *planes1 = c->pk_planes, *planes1_b = c->pk_planes_b, *tmp = nullptr;
-        if (ucap1 != c->pk_units_cap) {
-            HIP_TRY(c, buf.get(&planes1, rtr::pack_total_dwords(ucap1) * 4));
-            planes1_b = planes1 + rtr::pack_b_dwords(ucap1);
-        } else if (delta != 0 && tail) {
-            HIP_TRY(c, buf.get(&tmp, tail * 8 * 4));  // (the tail's A blocks, then its B blocks)
-        }
-
-        // commit: the tail's blocks to their new place, the window's headers and blocks, the tail's block offsets
-        if (planes1 != c->pk_planes) {  // (fresh planes: the prefix and the tail are copied, nothing overlaps)
-            HIP_TRY(c, copy_blocks(s, planes1, planes1_b, c, w.first_unit));
-            HIP_TRY(c, d2d(s, planes1 + new_end * 2, c->pk_planes + old_end * 2, tail * 2 * 4));
-            HIP_TRY(c, d2d(s, planes1_b + new_end * 6, c->pk_planes_b + old_end * 6, tail * 6 * 4));
-        } else if (tmp) {  // (source and destination overlap: through the scratch copy)
-            HIP_TRY(c, d2d(s, tmp, c->pk_planes + old_end * 2, tail * 2 * 4));
-            HIP_TRY(c, d2d(s, tmp + tail * 2, c->pk_planes_b + old_end * 6, tail * 6 * 4));
-            HIP_TRY(c, d2d(s, planes1 + new_end * 2, tmp, tail * 2 * 4));
-            HIP_TRY(c, d2d(s, planes1_b + new_end * 6, tmp + tail * 2, tail * 6 * 4));
-        }
-        HIP_TRY(c, d2d(s, c->pk_hdr + 2 * c0, w.whdr, w.wch * 2 * sizeof(uint4)));
-        rtr::launch_shift_units(s, c->pk_hdr, c1 + 1, nch, delta);
-        rtr::pack_write(s, w.cl, c->pk_hdr + 2 * c0, planes1, planes1_b);
-        HIP_TRY(c, zero_spare(s, planes1, planes1_b, units1));
-        if (c->opt_pack == 2) rtr::pack_verify(s, w.cl, c->pk_hdr + 2 * c0, planes1, planes1_b, tot + 3);
-        HIP_TRY(c, d2d(s, c->bounds + 6 * c0, w.wb, w.wch * 6 * sizeof(float)));
-        HIP_TRY(c, d2d(s, c->spread + c0, w.wsp, w.wch * sizeof(float)));
-        if (c->x) {  // ("keep_soa" = 1: the SoA arrays take the window as well)
-            HIP_TRY(c, d2d(s, c->x + p0, w.wx, w.wpad * 4)); HIP_TRY(c, d2d(s, c->y + p0, w.wy, w.wpad * 4));
-            HIP_TRY(c, d2d(s, c->z + p0, w.wz, w.wpad * 4));
-        }
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (int rc = launch_check(c, "transform")) return rc;
-        if (planes1 != c->pk_planes) {
-            buf.swap_in(c->pk_planes, planes1);
-            c->pk_planes_b = planes1_b;
-            c->pk_units_cap = ucap1;
-        }
-        c->pk_units = units1;
-        c->pk_bytes = pack_bytes(units1, nch);
-    }
+    auto fill = [&](float *wx, float *wy, float *wz, bool in_place) {
+        rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, wx, wy, wz, in_place);
+    };
+    if (int rc = rebuild_chunks(c, buf, c0, c1, tot, "transform", fill, [] {})) return rc;
     return cloud_edited(c, false, tot + 3, "moved points");
+}
+
+// ---- writing points back (rtr.h, section 2f) ------------------------------------------------------------------------
+// rtr_extract_points' ranks over rtr_transform_points' commit.  The selection's popcount scan gives k and every selected
+// point's rank; k_write_bits keeps the selection bits whose rank lies in [first, first + count) (for "every point" it
+// synthesises the words first), and those bits are the selection everything behind works on: the span c0 .. c1, the window
+// (rebuild_chunks with the caller's records as the source) and the colours (k_write_colors, queued in the commit phase:
+// a call that fails to allocate has changed no colour).  Host records are copied to the device once, at the caller's
+// stride, before anything resident changes.  A colour-only write rebuilds nothing: k_write_colors over the span.
+int rtr_write_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords, uint64_t first, uint64_t count, const float *xyz,
+                     size_t xs, const uint8_t *rgb, size_t rs, uint64_t *total) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->n > 0, "rtr_write_points: no cloud");
+    NEED(c, xyz || rgb, "rtr_write_points: nothing to write (xyz and rgb are both NULL)");
+    const bool every = select_words == nullptr && nwords == 0;
+    if (int rc = check_point_words(c, "rtr_write_points", "select_words", select_words, nwords, true, "", /*order_checked_later=*/true))
+        return rc;
+    NEED(c, !xyz || (xs >= 12 && xs % 4 == 0), "rtr_write_points: xyz_stride_bytes must be >= 12 and a multiple of 4");
+    NEED(c, !rgb || rs >= 3 || rs == 0, "rtr_write_points: rgb_stride_bytes must be >= 3, or 0 for one record for every point");
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    if (!every)
+        if (int rc = need_upload_order(c, "mapped", ", or write every point in the resident order (select_words NULL)")) return rc;
+    DevGuard g(c->device);
+    if (int rc = complete_all(c)) return rc;  // (frames issued before come out with the cloud they were issued with)
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nw = (n + 31) / 32;
+    const uint32_t *perm0 = c->reordered ? c->perm : nullptr;  // (sorted without point_ids, every point: rank = resident index)
+    DevBufs buf;
+
+    // the selection, its popcount scan and k, the number of selected points
+    uint32_t *sel, *wscan, *selw;
+    uint64_t *tot;  // span (first, last chunk), window units, pack mismatches, k
+    uint64_t k = n;
+    HIP_TRY(c, buf.get(&sel, nw * 4));
+    HIP_TRY(c, buf.get(&wscan, nw * 4));
+    HIP_TRY(c, buf.get(&selw, nw * 4));
+    HIP_TRY(c, buf.get(&tot, 5 * sizeof(uint64_t)));
+    HIP_TRY(c, hipMemsetAsync(tot, 0, 5 * sizeof(uint64_t), s));
+    if (!every) {
+        uint32_t *scratch;
+        HIP_TRY(c, buf.get(&scratch, rtr::scan_scratch_words(nw) * 4));
+        HIP_TRY(c, hipMemcpyAsync(sel, select_words, nw * 4, hipMemcpyDefault, s));
+        rtr::launch_scan_u32(s, sel, nw, n, wscan, scratch, tot + 4);
+        HIP_TRY(c, hipMemcpyAsync(&k, tot + 4, sizeof k, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (int rc = launch_check(c, "write scan")) return rc;
+    }
+    if (total) *total = k;
+    const uint64_t m = first < k ? std::min(count, k - first) : 0;
+    if (m == 0) return RTR_OK;  // (a sizing call, or a window behind the selection: nothing changes)
+
+    // the records on the device: only the bytes the call may read, a host stream copied once at the caller's stride
+    const uint8_t *dxyz = (const uint8_t *)xyz, *drgb = rgb;
+    if (xyz && !on_device(xyz)) {
+        uint8_t *d;
+        const size_t bytes = (m - 1) * xs + 12;
+        HIP_TRY(c, buf.get(&d, bytes));
+        HIP_TRY(c, hipMemcpyAsync(d, xyz, bytes, hipMemcpyHostToDevice, s));
+        dxyz = d;
+    }
+    if (rgb && !on_device(rgb)) {
+        uint8_t *d;
+        const size_t bytes = (m - 1) * rs + 3;
+        HIP_TRY(c, buf.get(&d, bytes));
+        HIP_TRY(c, hipMemcpyAsync(d, rgb, bytes, hipMemcpyHostToDevice, s));
+        drgb = d;
+    }
+
+    // the window's bits of the selection and the span of the chunks that hold them
+    rtr::launch_write_bits(s, sel, wscan, n, every, first, m, selw);
+    uint64_t c0 = 0, c1 = 0;
+    bool any = false;
+    if (int rc = chunk_span(c, selw, perm0, tot, "write span", &c0, &c1, &any)) return rc;
+    if (!any) return RTR_OK;
+    auto colours = [&] {
+        if (drgb) rtr::launch_write_colors(s, perm0, selw, sel, wscan, n, c0, c1, drgb, rs, first, c->rgba);
+    };
+    if (!dxyz) {  // (colours only: no chunk box, header or packed block changes)
+        colours();
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (int rc = launch_check(c, "write colours")) return rc;
+        return cloud_edited(c, false, tot + 3, "written points");
+    }
+    drop_soa(c);  // (SoA arrays decoded for a call in between are not kept: they would hold the old coordinates)
+    const rtr::Cloud cl = cloud_of(c);
+    auto fill = [&](float *wx, float *wy, float *wz, bool in_place) {
+        rtr::launch_write_window(s, cl, perm0, selw, sel, wscan, c0, c1, dxyz, xs, first, wx, wy, wz, in_place);
+    };
+    if (int rc = rebuild_chunks(c, buf, c0, c1, tot, "write", fill, colours)) return rc;
+    return cloud_edited(c, false, tot + 3, "written points");
 }
 
 int rtr_reorder_points(rtr_ctx *c) {
@@ -2189,17 +2320,6 @@ int rtr_download_points(rtr_ctx *c, float *xyzw, uint8_t *rgba, uint64_t first, 
 // destinations are written by the kernel; host destinations go through a device staging window (at the caller's stride
 // when every byte of a record is written -- 12 / 16 and 3 / 4 -- else tight, and the records are laid into the caller's
 // memory by the host, so that the bytes between them stay).  No fp32 SoA is built for a packed-only cloud.
-namespace {
-bool on_device(const void *p) {  // device (or managed) memory, as opposed to anything the host owns
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();  // (plain host memory is unknown to the runtime)
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-}  // namespace
-
 int rtr_extract_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords, uint64_t first, uint64_t count, float *xyz,
                        size_t xs, uint8_t *rgb, size_t rs, uint32_t *indices, uint64_t *total) {
     if (!c) return RTR_ERR_INVALID;

@@ -1,8 +1,9 @@
 // rtr_cloud_kernels.hip -- gfx950 kernels that edit or query the resident cloud outside a frame: iota, keep mask, remove,
-// scan, the packed headers' unit shift and wide-chunk count, select.  The arithmetic contract of rtr_kernels.hip holds
-// here too (-ffp-contract=off: the selection runs the frame's own project_point).
+// scan, the write bits, the packed headers' unit shift and wide-chunk count, select.  The arithmetic contract of
+// rtr_kernels.hip holds here too (-ffp-contract=off: the selection runs the frame's own project_point).
 #include "rtr_device.h"
 #include "rtr_remove_index.h"
+#include "rtr_write_index.h"
 
 #include <type_traits>
 
@@ -297,6 +298,26 @@ void launch_remove_renumber(hipStream_t s, const uint32_t *perm, uint64_t count,
     if (quads == 0) return;
     hipLaunchKernelGGL(k_remove_renumber, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(kBlock), 0, s, (const uint4 *)perm,
                        quads, keep, wscan, (uint4 *)out);
+}
+
+// ---- rtr_write_points (rtr.h section 2f) -------------------------------------------------------------------------
+// selw[w] = the bits of selection word w whose rank falls in the call's window [first, first + count) (write_word_bits),
+// a thread per word.  every: the selection is every point -- the words are synthesised here (all ones below n, their
+// scan 32 w) into sel / wscan, so that everything downstream reads sel, wscan and selw alike.
+__global__ __launch_bounds__(kBlock) void k_write_bits(uint32_t *__restrict__ sel, uint32_t *__restrict__ wscan, uint64_t n,
+                                                       int every, uint64_t first, uint64_t count, uint32_t *__restrict__ selw) {
+    const uint64_t nwords = (n + 31) / 32;
+    for (uint64_t w = (uint64_t)blockIdx.x * kBlock + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * kBlock) {
+        if (every) sel[w] = extract_word_mask(w, n), wscan[w] = (uint32_t)(32u * w);
+        selw[w] = write_word_bits(sel[w], wscan[w], w, first, count, n);
+    }
+}
+void launch_write_bits(hipStream_t s, uint32_t *sel, uint32_t *wscan, uint64_t n, bool every, uint64_t first, uint64_t count,
+                       uint32_t *selw) {
+    const uint64_t nwords = (n + 31) / 32, blocks = (nwords + kBlock - 1) / kBlock;
+    if (nwords == 0) return;
+    hipLaunchKernelGGL(k_write_bits, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, sel, wscan, n,
+                       every ? 1 : 0, first, count, selw);
 }
 
 __global__ __launch_bounds__(kBlock) void k_shift_units(uint4 *__restrict__ hdr, uint64_t c_from, uint64_t c_to, long long delta) {

@@ -404,6 +404,21 @@ void launch_transform_span(hipStream_t s, const uint32_t *sel, const uint32_t *p
 // in_place (wx = c.x + 256 c0 ...): only the quads holding a selected point are written
 void launch_transform_window(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *sel, uint64_t c0, uint64_t c1,
                              const Affine &M, float *wx, float *wy, float *wz, bool in_place);
+// rtr_write_points (section 2f): sel / wscan = the call's upload-order selection words and their exclusive popcount
+// scan, (n + 31) / 32 words each; the ranks [first, first + count) of the selection are written.
+// write_bits: selw[w] = the bits of sel[w] whose rank lies in that window (rtr_write_index.h); every: the selection is
+// every point, and sel / wscan are filled here first (all ones below n, scan 32 w)
+void launch_write_bits(hipStream_t s, uint32_t *sel, uint32_t *wscan, uint64_t n, bool every, uint64_t first, uint64_t count,
+                       uint32_t *selw);
+// launch_transform_window with another source: a point of selw takes the three floats at xyz + (rank - first) * stride
+// (device memory, stride a multiple of 4), bit for bit
+void launch_write_window(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *selw, const uint32_t *sel,
+                         const uint32_t *wscan, uint64_t c0, uint64_t c1, const uint8_t *xyz, uint64_t stride, uint64_t first,
+                         float *wx, float *wy, float *wz, bool in_place);
+// the colours of the points of selw in chunks c0 .. c1: rgba[resident index] = c0 | c1 << 8 | c2 << 16 | 0xFF000000 of the
+// three bytes at rgb + (rank - first) * stride (device memory; stride 0: one record for all)
+void launch_write_colors(hipStream_t s, const uint32_t *perm, const uint32_t *selw, const uint32_t *sel, const uint32_t *wscan,
+                         uint64_t n, uint64_t c0, uint64_t c1, const uint8_t *rgb, uint64_t stride, uint64_t first, uint32_t *rgba);
 // the block offsets hdr[2 c + 1].xy of chunks [c_from, c_to) move by delta units (the blocks behind a rebuilt window moved)
 void launch_shift_units(hipStream_t s, uint4 *hdr, uint64_t c_from, uint64_t c_to, int64_t delta);
 // out[0] / out[1] (device, zeroed by the caller) += the wide chunks of the packed form / those that carry a box word

@@ -4568,16 +4568,16 @@ void launch_extract(hipStream_t s, const ExtractArgs &a) {
 
 // ---- rtr_transform_points (rtr.h section 2d) ---------------------------------------------------------------------
 // sel: the caller's upload-order selection words (null: every point), perm as for remove_gather.  Lane l of the wave that
-// holds chunk c gathers the selection bits of its points 4 l .. 4 l + 3 (remove_gather; bits at or past n do not count).
+// holds chunk c gathers the selection bits of its points 4 l .. 4 l + 3 and, with sel, their upload indices u
+// (remove_gather; bits at or past n do not count).
 __device__ __forceinline__ void transform_gather(const uint32_t *__restrict__ sel, const uint32_t *__restrict__ perm, uint64_t n,
-                                                 uint64_t c, int lane, bool moved[4]) {
-    uint32_t u[4];
+                                                 uint64_t c, int lane, uint32_t u[4], bool moved[4]) {
     bool valid[4];
     if (sel) {
         remove_gather(sel, perm, n, c, lane, u, moved, valid);
-    } else {
+    } else {  // (no source reads u)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) moved[k] = c * 256u + 4u * (uint64_t)lane + (uint64_t)k < n;
+        for (int k = 0; k < 4; ++k) u[k] = 0u, moved[k] = c * 256u + 4u * (uint64_t)lane + (uint64_t)k < n;
     }
 }
 // span[0] / span[1] = the first / last chunk holding a selected point (the caller sets ~0 / 0).  A wave's chunks ascend,
@@ -4592,8 +4592,9 @@ __global__ __launch_bounds__(kBlock) void k_transform_span(const uint32_t *__res
     __syncthreads();
     unsigned long long lo = ~0ull, hi = 0ull;
     for (uint64_t c = ((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6; c < nchunks; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+        uint32_t u[4];
         bool moved[4];
-        transform_gather(sel, perm, n, c, lane, moved);
+        transform_gather(sel, perm, n, c, lane, u, moved);
         if (__ballot(moved[0] || moved[1] || moved[2] || moved[3]) != 0ull) {  // (wave-uniform)
             if (lo == ~0ull) lo = c;
             hi = c;
@@ -4611,20 +4612,42 @@ void launch_transform_span(hipStream_t s, const uint32_t *sel, const uint32_t *p
                        (unsigned long long *)span);
 }
 
-// Chunks c0 .. c1 with the selected points moved (affine_apply) into the window w* (quad q of the cloud at w*[q - 64 c0]).
-// Coordinates from the fp32 SoA when resident, else decoded from the packed form (bit for bit); unselected points and the
-// NaN pads pass through bit for bit.  in_place: w* are the SoA arrays themselves (from point 256 c0 on) -- the same thread
-// reads and writes a quad, so they are not __restrict__ -- and only quads holding a selected point are stored.
+// Chunks c0 .. c1 with the selected points given new coordinates into the window w* (quad q of the cloud at
+// w*[q - 64 c0]).  SRC says where a selected point's coordinates come from: AffineSource moves the resident ones
+// (affine_apply, rtr_transform_points), RecordSource takes the caller's record (rtr_write_points).  Coordinates from the
+// fp32 SoA when resident, else decoded from the packed form (bit for bit); unselected points and the NaN pads pass through
+// bit for bit.  in_place: w* are the SoA arrays themselves (from point 256 c0 on) -- the same thread reads and writes a
+// quad, so they are not __restrict__ -- and only quads holding a selected point are stored.
+struct AffineSource {
+    Affine M;
+    __device__ __forceinline__ void operator()(uint32_t, float &x, float &y, float &z) const { affine_apply(M, x, y, z); }
+};
+// The point of upload index u takes record rank(u) - first of xyz (three floats at `stride` bytes, a multiple of 4):
+// sel / wscan = the call's selection words and their popcount scan, the window's bits of which the kernel is given as
+// its selection.  No arithmetic: the bits are stored as they are read.  While the cloud is in upload order a chunk's
+// slots are consecutive, so neighbouring lanes read neighbouring records (48 bytes a lane at the tight stride).
+struct RecordSource {
+    const uint32_t *sel, *wscan;
+    const uint8_t *xyz;
+    uint64_t stride, first;
+    __device__ __forceinline__ void operator()(uint32_t u, float &x, float &y, float &z) const {
+        const uint64_t slot = (uint64_t)remove_rank(wscan[u >> 5], sel[u >> 5], u) - first;
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(xyz + slot * stride);
+        x = __uint_as_float(p[0]), y = __uint_as_float(p[1]), z = __uint_as_float(p[2]);
+    }
+};
+template <class SRC>
 __global__ __launch_bounds__(kBlock) void k_transform_window(const uint4 *__restrict__ hdr, const uint32_t *__restrict__ planes,
                                                              const uint32_t *__restrict__ planes_b, const float4 *x4,
                                                              const float4 *y4, const float4 *z4, const uint32_t *__restrict__ perm,
                                                              const uint32_t *__restrict__ sel, uint64_t n, uint64_t c0, uint64_t c1,
-                                                             Affine M, int in_place, float4 *wx4, float4 *wy4, float4 *wz4) {
+                                                             SRC src, int in_place, float4 *wx4, float4 *wy4, float4 *wz4) {
     const int lane = threadIdx.x & 63;
     const uint64_t n4 = (n + 3) / 4;
     for (uint64_t c = c0 + (((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6); c <= c1; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+        uint32_t u[4];
         bool moved[4];
-        transform_gather(sel, perm, n, c, lane, moved);
+        transform_gather(sel, perm, n, c, lane, u, moved);
         const bool mine = moved[0] || moved[1] || moved[2] || moved[3];
         if (in_place && __ballot(mine) == 0ull) continue;  // (wave-uniform)
         const uint64_t i = c * 64 + lane;
@@ -4638,22 +4661,67 @@ __global__ __launch_bounds__(kBlock) void k_transform_window(const uint4 *__rest
             unpack_chunk(raw_a, raw, h0.w, h0.x, h0.y, h0.z, X, Y, Z, lane);
         }
         if (i >= n4 || (in_place && !mine)) continue;
-        if (moved[0]) affine_apply(M, X.x, Y.x, Z.x);
-        if (moved[1]) affine_apply(M, X.y, Y.y, Z.y);
-        if (moved[2]) affine_apply(M, X.z, Y.z, Z.z);
-        if (moved[3]) affine_apply(M, X.w, Y.w, Z.w);
+        if (moved[0]) src(u[0], X.x, Y.x, Z.x);
+        if (moved[1]) src(u[1], X.y, Y.y, Z.y);
+        if (moved[2]) src(u[2], X.z, Y.z, Z.z);
+        if (moved[3]) src(u[3], X.w, Y.w, Z.w);
         const uint64_t o = i - c0 * 64;
         wx4[o] = X, wy4[o] = Y, wz4[o] = Z;
     }
 }
-void launch_transform_window(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *sel, uint64_t c0, uint64_t c1,
-                             const Affine &M, float *wx, float *wy, float *wz, bool in_place) {
+template <class SRC>
+static void launch_window(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *sel, uint64_t c0, uint64_t c1,
+                          const SRC &src, float *wx, float *wy, float *wz, bool in_place) {
     const uint64_t nchunks = (c.n + 255) / 256;
     if (c0 > c1 || c1 >= nchunks) return;
     const uint64_t blocks = (c1 - c0 + 1 + 3) / 4;  // (a wave per chunk)
-    hipLaunchKernelGGL(k_transform_window, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, c.pk.hdr,
+    hipLaunchKernelGGL(k_transform_window<SRC>, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, c.pk.hdr,
                        c.pk.planes, c.pk.planes_b, (const float4 *)c.x, (const float4 *)c.y, (const float4 *)c.z, perm, sel,
-                       c.n, c0, c1, M, in_place ? 1 : 0, (float4 *)wx, (float4 *)wy, (float4 *)wz);
+                       c.n, c0, c1, src, in_place ? 1 : 0, (float4 *)wx, (float4 *)wy, (float4 *)wz);
+}
+void launch_transform_window(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *sel, uint64_t c0, uint64_t c1,
+                             const Affine &M, float *wx, float *wy, float *wz, bool in_place) {
+    launch_window(s, c, perm, sel, c0, c1, AffineSource{M}, wx, wy, wz, in_place);
+}
+
+// ---- rtr_write_points (rtr.h section 2f) -------------------------------------------------------------------------
+// k_transform_window with the caller's records as the source (RecordSource): selw = the window's bits of the selection
+// (k_write_bits), sel / wscan = the selection and its scan, xyz = the records on the device, record 0 = rank `first`.
+void launch_write_window(hipStream_t s, const Cloud &c, const uint32_t *perm, const uint32_t *selw, const uint32_t *sel,
+                         const uint32_t *wscan, uint64_t c0, uint64_t c1, const uint8_t *xyz, uint64_t stride, uint64_t first,
+                         float *wx, float *wy, float *wz, bool in_place) {
+    launch_window(s, c, perm, selw, c0, c1, RecordSource{sel, wscan, xyz, stride, first}, wx, wy, wz, in_place);
+}
+// The colours of the written points of chunks c0 .. c1: rgba[resident index] = the record's first three bytes and an
+// opaque alpha, as k_aos_to_soa packs them; rgb_stride 0: every point takes record 0.  A chunk without a written point
+// is left wave-uniformly before anything else of it is read.
+__global__ __launch_bounds__(kBlock) void k_write_colors(const uint32_t *__restrict__ perm, const uint32_t *__restrict__ selw,
+                                                         const uint32_t *__restrict__ sel, const uint32_t *__restrict__ wscan,
+                                                         uint64_t n, uint64_t c0, uint64_t c1, const uint8_t *__restrict__ rgb,
+                                                         uint64_t stride, uint64_t first, uint32_t *__restrict__ rgba) {
+    const int lane = threadIdx.x & 63;
+    for (uint64_t c = c0 + (((uint64_t)blockIdx.x * kBlock + threadIdx.x) >> 6); c <= c1; c += ((uint64_t)gridDim.x * kBlock) >> 6) {
+        uint32_t u[4];
+        bool written[4], valid[4];
+        remove_gather(selw, perm, n, c, lane, u, written, valid);
+        if (__ballot(written[0] || written[1] || written[2] || written[3]) == 0ull) continue;  // (wave-uniform)
+        const uint64_t r0 = c * 256u + 4u * (uint64_t)lane;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!written[k]) continue;
+            const uint64_t slot = (uint64_t)remove_rank(wscan[u[k] >> 5], sel[u[k] >> 5], u[k]) - first;
+            const uint8_t *p = rgb + slot * stride;
+            rgba[r0 + k] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | 0xFF000000u;
+        }
+    }
+}
+void launch_write_colors(hipStream_t s, const uint32_t *perm, const uint32_t *selw, const uint32_t *sel, const uint32_t *wscan,
+                         uint64_t n, uint64_t c0, uint64_t c1, const uint8_t *rgb, uint64_t stride, uint64_t first, uint32_t *rgba) {
+    const uint64_t nchunks = (n + 255) / 256;
+    if (c0 > c1 || c1 >= nchunks) return;
+    const uint64_t blocks = (c1 - c0 + 1 + 3) / 4;  // (a wave per chunk)
+    hipLaunchKernelGGL(k_write_colors, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, s, perm, selw, sel,
+                       wscan, n, c0, c1, rgb, stride, first, rgba);
 }
 
 }  // namespace rtr

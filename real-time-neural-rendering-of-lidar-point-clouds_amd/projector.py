@@ -442,6 +442,84 @@ class Projector:
             return m
         return [dst[name] for name in ("xyz", "rgb", "indices") if name in dst]
 
+    # -- writing points back (rtr.h section 2f)
+    @staticmethod
+    def _write_source(arr, dtype, name):
+        """(pointer, row stride in bytes, rows, owner) of a stream of write_points: a numpy array (anything else numpy
+        converts is converted), a torch tensor (host or device) or an object with __cuda_array_interface__; 2-D with a
+        row per record and at least 3 contiguous columns of dtype."""
+        dt = np.dtype(dtype)
+        if hasattr(arr, "data_ptr"):  # a torch tensor (host or device)
+            if arr.element_size() != dt.itemsize or arr.dtype.is_floating_point != (dt.kind == "f"):
+                raise ValueError("%s must hold %s elements" % (name, dt))
+            if arr.is_cuda:
+                import torch
+                torch.cuda.current_stream(arr.device).synchronize()  # (the records may still be on their way)
+            shape, strides, ptr = tuple(arr.shape), tuple(st * dt.itemsize for st in arr.stride()), arr.data_ptr()
+        elif hasattr(arr, "__cuda_array_interface__"):
+            cai = arr.__cuda_array_interface__
+            if np.dtype(cai["typestr"]).itemsize != dt.itemsize:
+                raise ValueError("%s must hold %s elements" % (name, dt))
+            shape, ptr = tuple(cai["shape"]), cai["data"][0]
+            strides = cai.get("strides") or tuple(int(np.prod(shape[i + 1:])) * dt.itemsize for i in range(len(shape)))
+        else:
+            if not isinstance(arr, np.ndarray) or arr.dtype != dt:
+                arr = np.ascontiguousarray(arr, dtype=dt)
+            shape, strides, ptr = arr.shape, arr.strides, arr.ctypes.data
+        if len(shape) != 2 or shape[1] < 3:
+            raise ValueError("%s must be 2-D with a row per record and at least 3 columns" % name)
+        if shape[0] > 0 and (strides[1] != dt.itemsize or (shape[0] > 1 and strides[0] < 3 * dt.itemsize)):
+            raise ValueError("%s must have at least 3 contiguous columns per row" % name)
+        stride = strides[0] if shape[0] > 1 else max(strides[0], shape[1] * dt.itemsize)
+        return C.c_void_p(ptr), stride, shape[0], arr
+
+    def write_points(self, xyz=None, rgb=None, select=None, first=0, broadcast=False):
+        """Writes new coordinates and / or colours into resident points where they lie (include/rtr.h section 2f), the
+        mirror image of extract_points: of the k points `select` names (None = every point, else the forms of
+        set_point_keep, selection() included), in ascending upload index, the one of rank first + j takes row j.
+        xyz: float32 rows, rgb: uint8 rows -- numpy arrays, torch tensors (host or device) or objects with
+        __cuda_array_interface__, 2-D with a row per record and at least 3 columns (the row stride is the array's);
+        None leaves that stream as it is resident.  broadcast = True: rgb is one colour, of shape (3,) or (1, 3 | 4),
+        for every written point -- all of them from rank `first` on when xyz is None.  Coordinates are stored bit for
+        bit.  Indices, the resident order, the keep mask and the selection stay; frames equal, bit for bit, those of one
+        upload of the written cloud.  Returns the number of points written."""
+        if xyz is None and rgb is None:
+            raise ValueError("write_points: xyz and rgb are both None, nothing to write")
+        hold, count = [], None
+        px, sx, pc, sc = None, 0, None, 0
+        if xyz is not None:
+            px, sx, count, owner = self._write_source(xyz, np.float32, "xyz")
+            hold.append(owner)
+        if rgb is not None:
+            if broadcast:
+                if not (hasattr(rgb, "data_ptr") or hasattr(rgb, "__cuda_array_interface__")):
+                    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+                    if rgb.shape == (3,) or rgb.shape == (4,):
+                        rgb = rgb.reshape(1, -1)
+                elif len(tuple(rgb.shape)) == 1:
+                    rgb = rgb.reshape(1, -1)
+            pc, sc, rows, owner = self._write_source(rgb, np.uint8, "rgb")
+            hold.append(owner)
+            if broadcast:
+                if rows != 1:
+                    raise ValueError("a broadcast rgb is one record: shape (3,) or (1, 3 | 4)")
+                sc = 0
+                if count is None:
+                    count = 2 ** 64 - 1
+            elif count is not None and rows != count:
+                raise ValueError("xyz has %d rows and rgb %d: they must name the same points" % (count, rows))
+            else:
+                count = rows
+        elif broadcast:
+            raise ValueError("broadcast = True needs an rgb record")
+        ptr, nwords, _hold = (None, 0, None) if select is None else self._keep_words(select)
+        first = int(first)
+        if count == 0:  # (no record: nothing to write, and an empty array need not have an address)
+            return 0
+        k = C.c_uint64()
+        self._chk(self._lib.rtr_write_points(self._ctx, ptr, nwords, first, count, px, sx, pc, sc, C.byref(k)))
+        return min(count, max(0, k.value - first))
+
     # -- point pass (rtr.h section 6b)
     def point_pass(self, P, ids=True, visible=True):
         """Per-pixel point IDs (BUF_POINT_ID: upload index, NO_POINT for none) and / or the per-point visibility
