@@ -642,13 +642,26 @@ hipError_t sync_streams(rtr_ctx *c) {
     return hipStreamSynchronize(c->stream);
 }
 
+// Which of an overlapped frame's two events ride on a dispatch packet instead of a packet of their own behind the launch
+// (bit 0: `consumed` on the tile launch, bit 1: `binned` on T1); an A/B switch of the build, DESIGN.md section 4
+#ifndef RTR_DISPATCH_EVENTS
+#define RTR_DISPATCH_EVENTS 3
+#endif
+
+// the event the LAST reader of the active store -- one about to be launched on the tail stream -- signals from its
+// dispatch packet, or null where mark_consumed has to record it: only whole overlapped frames (rtr_render) ask
+hipEvent_t consumed_in_dispatch(rtr_ctx *c) {
+    if (!(RTR_DISPATCH_EVENTS & 1) || !c->front || !c->frame_overlapped) return nullptr;
+    return c->F().consumed;
+}
+
 // after the last reader of the active list / bin set has been queued on the tail stream
 // (with option "overlap" = 1 behind every reader, as ever; otherwise only behind overlapped frames -- a streak starts
-// by joining the two streams, bin_points)
-void mark_consumed(rtr_ctx *c) {
+// by joining the two streams, bin_points).  in_dispatch: that reader's launch carried the event (consumed_in_dispatch)
+void mark_consumed(rtr_ctx *c, bool in_dispatch = false) {
     if (!c->front || !(c->ov.mode == 1 || c->frame_overlapped)) return;
     auto &f = c->F();
-    if (hipEventRecord(f.consumed, c->stream) == hipSuccess) f.consumed_valid = true;
+    if (in_dispatch || hipEventRecord(f.consumed, c->stream) == hipSuccess) f.consumed_valid = true;
 }
 
 int collect_timing(rtr_ctx *c) {
@@ -2512,14 +2525,19 @@ static int bin_points(rtr_ctx *c, const float P[16], bool overlapped, bool clear
     const bool heavy_seen = c->split_cooldown > 0 || __atomic_load_n(c->split_host, __ATOMIC_RELAXED) != 0u;
     t.fill_shift = c->opt_fill_shift >= 0 ? c->opt_fill_shift : (heavy_seen ? 4 : 1);
     if (int rc = next_seq(c, c->F(), s1)) return rc;
+    bool binned_in_dispatch = false;
     {
         Timed tm(c, RTR_K_MIN_DEPTH, s1, true);
+        // (a dispatch has one stop event: a bracketed T1 gives it to the bracket, and a lean frame of an empty cloud
+        // launches nothing)
+        binned_in_dispatch = (RTR_DISPATCH_EVENTS & 2) && overlapped && !tm.a && (c->n > 0 || !lean);
         rtr::launch_project_bin(s1, cloud_of(c), make_proj(P), c->W, c->H, t, c->opt_cull ? c->bounds : nullptr,
-                                t1_flags(c, clear_split, no_split, lean), c->opt_phases, c->opt_xp, tm.a, tm.b);
+                                t1_flags(c, clear_split, no_split, lean), c->opt_phases, c->opt_xp, tm.a,
+                                binned_in_dispatch ? c->F().binned : tm.b);
         c->p2p.occ_from_scan = c->p2p.open;
     }
     if (overlapped) {
-        HIP_TRY(c, hipEventRecord(c->F().binned, c->front));
+        if (!binned_in_dispatch) HIP_TRY(c, hipEventRecord(c->F().binned, c->front));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->F().binned, 0));
     }
     memcpy(c->list_P, P, sizeof c->list_P);
@@ -2680,10 +2698,13 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
         // min / max partials (F1) while the finished depth tile is still in LDS
         fused = with_filter && c->prm.levels == 4;
         const rtr::TilePyr pyr = tile_pyr(c, c->frame, 0, fused);
+        // (the store's last reader is the split launch where the frame has one)
+        const hipEvent_t consumed = consumed_in_dispatch(c);
         {
             Timed t(c, RTR_K_TILE);
             rtr::launch_tile(c->stream, 0, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, c->frame.img,
-                             c->opt_keep_accum | (lean ? lean_bits(c, c->frame) : 0) | (c->F().parity << 4), fused ? &pyr : nullptr);
+                             c->opt_keep_accum | (lean ? lean_bits(c, c->frame) : 0) | (c->F().parity << 4), fused ? &pyr : nullptr,
+                             nullptr, split_launch ? nullptr : consumed);
             if (lean) c->list_valid = false;  // (the tile launch has consumed and reset the stream counters)
             // tiles heavier than option "split_threshold" are split over several workgroups: a second launch takes
             // the minimum over each slice (they meet in the depth buffer), then -- behind a barrier over its 256
@@ -2691,9 +2712,9 @@ int rtr_render(rtr_ctx *c, const float P[16], int with_filter) {
             // (no work item on ordinary frames: its workgroups leave at once)
             if (split_launch)  // (skipped while no frame has had a tile above the threshold: see rtr_ctx::split_host)
                 rtr::launch_tile(c->stream, 3, c->W, c->H, c->F().store, c->prm.depth_window, c->frame.depth, c->frame.acc, c->frame.img,
-                                 c->opt_keep_accum, fused ? &pyr : nullptr);
+                                 c->opt_keep_accum, fused ? &pyr : nullptr, nullptr, consumed);
         }
-        mark_consumed(c);
+        mark_consumed(c, consumed != nullptr);
         c->frame_overlapped = false;
         c->ov.frame_done(overlapped);
         if ((rc = launch_check(c, "tile frame"))) return rc;

@@ -252,7 +252,8 @@ int storage_tile_count(int W, int H);  // 32x16 storage tiles
 // bounds != NULL enables per-chunk frustum culling (see k_project_bin)
 void launch_project_bin(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, const TileStore &S,
                         const float *bounds, int clear_split, int phases, int xp = 0, hipEvent_t ev_start = nullptr,
-                        hipEvent_t ev_stop = nullptr);  // ev_*: time stamps taken by the dispatch itself (timing on)
+                        hipEvent_t ev_stop = nullptr);  // ev_*: signalled by the dispatch itself (time stamps with timing
+                                                        // on; ev_stop alone: an overlapped frame's `binned`)
 // rtr_render_views: ONE point-kernel launch serves `count` (<= kMaxViews) poses -- view v's in-frustum points go to the tile
 // store S[v], each of them a LEAN frame (see ts_off_order) for launch_tile.  tab_host: view_tab_bytes() of host memory
 // (pinned: it is copied to tab_dev, the same size of device memory, on the stream, and must not change before the copy
@@ -298,8 +299,10 @@ void launch_reset_split(hipStream_t s, int W, int H, const TileStore &S, uint32_
 // write_acc bit 3 (mode 0): a LEAN frame (see ts_off_order) -- T1 ran without epilogue (launch_project_bin's flag 8);
 // bit 4 (modes 0, 1): the frame's parity (which lcnt[] half its workgroups write, which order[] they read; the
 // launch's extra workgroup writes the OTHER order[])
+// ev_stop (modes 0, 3): an event the dispatch itself signals when the launch has ended, as launch_project_bin's
 void launch_tile(hipStream_t s, int mode, int W, int H, const TileStore &S, float window, uint32_t *depth,
-                 uint32_t *acc, uint8_t *img, int write_acc, const TilePyr *pyr, const Sliced *depth_slices = nullptr);
+                 uint32_t *acc, uint8_t *img, int write_acc, const TilePyr *pyr, const Sliced *depth_slices = nullptr,
+                 hipEvent_t ev_stop = nullptr);
 // folds the statistics of the lean frame of parity `parity` into the store's header now (rtr_frame_stats)
 void launch_lean_fold(hipStream_t s, int W, int H, const TileStore &S, int parity);
 void launch_stream_probe(hipStream_t s, const Cloud &c, const Proj &P, int W, int H, uint32_t *sink, int variant);

@@ -3145,7 +3145,7 @@ void unpack_to_soa(hipStream_t s, const PackedXyz &pk, uint64_t n, float *x, flo
 }
 
 void launch_tile(hipStream_t s, int mode, int W, int H, const TileStore &S, float window, uint32_t *depth,
-                 uint32_t *acc, uint8_t *img, int write_acc, const TilePyr *pyr, const Sliced *depth_slices) {
+                 uint32_t *acc, uint8_t *img, int write_acc, const TilePyr *pyr, const Sliced *depth_slices, hipEvent_t ev_stop) {
     TileGeom g = tile_geom(W, H);
     Sliced nosl{};
     nosl.chunk = 0;
@@ -3180,12 +3180,13 @@ void launch_tile(hipStream_t s, int mode, int W, int H, const TileStore &S, floa
                 if (cap >= g.ntiles + 1) flags |= 32;
             }
         }
-        hipLaunchKernelGGL(k_tile<0>, dim3(g.ntiles + 1), dim3(kTileThreadsCompact), lds0, s, S, g, W, H, window, depth, acc, img, flags,
-                           pyr ? *pyr : none, nosl);
+        // (ev_stop: the dispatch packet signals the event when the kernel has ended -- no packet of its own behind it)
+        hipExtLaunchKernelGGL(k_tile<0>, dim3(g.ntiles + 1), dim3(kTileThreadsCompact), lds0, s, nullptr, ev_stop, 0, S, g, W, H, window, depth,
+                              acc, img, flags, pyr ? *pyr : none, nosl);
     }
     else if (mode == 3)  // the split tiles' slices, min phase then second phase: every workgroup leaves at once on ordinary frames
-        hipLaunchKernelGGL(k_tile_split, dim3(kSplitGrid), block, 5 * tpix * sizeof(uint32_t) + 3 * tpix, s, S, g, W, H, window, depth,
-                           acc, img, write_acc & 1, pyr ? *pyr : none, nosl);
+        hipExtLaunchKernelGGL(k_tile_split, dim3(kSplitGrid), block, 5 * tpix * sizeof(uint32_t) + 3 * tpix, s, nullptr, ev_stop, 0, S, g, W, H,
+                              window, depth, acc, img, write_acc & 1, pyr ? *pyr : none, nosl);
     else if (mode == 4)  // owner-computes sharded frame: one workgroup per tile, the segment table behind the tile buffers
         hipLaunchKernelGGL(k_tile<4>, dim3(g.ntiles), block, lds + tpix * sizeof(uint32_t) + kSegCap4 * 16, s, S, g, W, H, window, depth,
                            acc, img, write_acc & 1, pyr ? *pyr : none, *depth_slices);
