@@ -201,7 +201,9 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *  "probe_variant": measurement aid of tools/probe_variants.py (selects the rtr_stream_probe kernel).
  *  rtr_get_option("views") reads the view count of the last rtr_render_views batch (section 6c; 0: none current).
  *  rtr_get_option("point_keep") reads 1 while a keep mask is set (section 6e).
- *  rtr_get_option("selection") reads 1 while a selection exists (section 6f). */
+ *  rtr_get_option("selection") reads 1 while a selection exists (section 6f).
+ *  rtr_get_option("voxel_keys_us" / "voxel_sort_us" / "voxel_heads_us") read the device time, in microseconds, that the last
+ *          rtr_select_voxel_grid (section 6g) spent in its key kernel, its sort and its head kernel (0 before the first). */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
 /* Reads an option back; also "p2p_open" (see "p2p_timeout_ms"), "reordered" (1: the resident cloud was sorted by the library),
  * "order_ratio_ppm" (mean chunk-box diagonal / cloud diagonal as uploaded, in millionths), "packed" and
@@ -747,6 +749,42 @@ int rtr_set_point_keep(rtr_ctx *ctx, const uint32_t *words, uint64_t nwords);
 int rtr_select_points(rtr_ctx *ctx, int plane_count, const float *planes, const float *P, const int rect[4],
                       int op, uint64_t stats[4]);
 int rtr_clear_selection(rtr_ctx *ctx);
+
+/* ---- 6g. selection by density: one point per cell of a voxel grid -------------------------------------------------
+ * rtr_select_voxel_grid thins the resident cloud on the device: of the points that fall into one cell of a regular grid
+ * it names one (PCL's VoxelGrid, spatial subsampling).  It writes into RTR_BUF_SELECTION exactly as rtr_select_points
+ * does -- the same buffer, the same life, the same op values with RTR_SELECT_OUTSIDE OR-ed in -- so the words feed
+ * rtr_remove_points, rtr_set_point_keep, rtr_transform_points, rtr_extract_points and rtr_write_points as they are.
+ * Cell of a point: inv[k] = 1.0f / cell[k], one IEEE fp32 division on the host; per axis t[k] = (p[k] - origin[k]) * inv[k]
+ * with the difference and the product each rounded to fp32 on its own (no FMA): numpy float32 in that order is an exact
+ * reference.  Point i is IN THE GRID iff on all three axes t[k] is finite and -2^20 <= t[k] < 2^20; its cell is then
+ * q[k] = floor(t[k]), three integers in [-2^20, 2^20).  Every other point -- a NaN or infinite coordinate, a difference
+ * or a product that overflows, a cell beyond +-2^20 -- is OUT OF THE GRID and counts as a cell of its own holding that
+ * one point.
+ * The representative of a cell is its point with the SMALLEST UPLOAD INDEX: it does not depend on the resident order,
+ * the library's sort, the packed form or any option.  hit(i) holds iff point i is the representative of its cell and the
+ * cell holds at least min_count (>= 1) points.  min_count = 1 is plain thinning; min_count = k also drops the cells with
+ * fewer than k returns (isolated stragglers).  Out-of-grid points are hits exactly when min_count == 1: thinning never
+ * silently loses a far-away point.  With RTR_SELECT_OUTSIDE hit = !hit for the points below n: thinning is this call with
+ * OUTSIDE followed by "remove / hide what is selected", or plain REPLACE with the words as rtr_remove_points' keep words.
+ * What it reads and leaves alone: section 6f's list.  The call reads the uploaded coordinates only; the context's clip
+ * planes and keep mask are ignored.  It changes no frame, frame buffer, tile store, pool, statistics, point-pass buffer
+ * or keep mask, and an open peer-to-peer exchange stays open.  Indices are the point pass's; a cloud sorted by the
+ * library needs option "point_ids" = 1.
+ * Ordering: queued on the context's stream behind everything issued before it.  Unlike rtr_select_points the call ALWAYS
+ * waits for its own work before it returns, stats or not: it frees its scratch.  It does not repeat frames whose extent
+ * pool overflowed: a frame's error stays pending for the next synchronising call, as in section 2e.
+ * stats (may be NULL): [0] the points selected after op, [1] occupied in-grid cells, [2] those of them holding at least
+ * min_count points, [3] out-of-grid points.  Without OUTSIDE and with op REPLACE, [0] == [2] + (min_count == 1 ? [3] : 0).
+ * Memory and cost: one sweep over the coordinates, a stable radix sort of n (64-bit key, 32-bit index) pairs and two
+ * passes over the sorted pairs and the words.  Scratch for the duration of the call: 24 B per point (the pairs, twice:
+ * the sort is out of place), the sort's temporary and (n + 31) / 32 words -- about 2.4 GB at 1e8 points.
+ * Errors: no cloud, origin or cell NULL, a non-finite origin, a cell size that is not finite and > 0 or whose fp32
+ * reciprocal is not, min_count == 0, an unknown op, a sorted cloud without point_ids -> RTR_ERR_INVALID;
+ * RTR_ERR_UNSUPPORTED for 2^32 points or more; a failed allocation -> RTR_ERR_HIP.  Every scratch buffer is allocated
+ * before the first selection word changes: after any of these the selection and everything else are as they were. */
+int rtr_select_voxel_grid(rtr_ctx *ctx, const float origin[3], const float cell[3], uint32_t min_count, int op,
+                          uint64_t stats[4]);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

@@ -29,6 +29,7 @@
 // transform where they lie: indices, order and the keep mask stay.
 // selectBox / selectPlanes / selectRect (section 6f) name the vertices of a region on the device; removeSelected,
 // hideSelected and transformSelected then act on them without a host array of flags.
+// selectVoxelGrid (section 6g) names one vertex per cell of a regular grid; thin removes all the others.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
 // writeSelected / writePoints / colorSelected (section 2f) put edited vertices and colours back where they came from:
 // indices, the keep mask and the selection stay.
@@ -346,6 +347,27 @@ public:
         uint64_t st[4] = {0, 0, 0, 0};
         check(ctx_, rtr_select_points(ctx_, 0, nullptr, P, rect, op, st));
         return st[0];
+    }
+    // One vertex per cell of a regular grid (section 6g): of the vertices that fall into one cell of size cell[0..2],
+    // counted from origin (nullptr: 0 0 0), the one with the smallest vertex index is selected where the cell holds at
+    // least min_count vertices; outside: every vertex but those.  Combined with the selection so far by op.  Returns
+    // the number selected afterwards.  point_ids = true when the cloud may be sorted.
+    uint64_t selectVoxelGrid(const float cell[3], const float origin[3] = nullptr, uint32_t min_count = 1,
+                             int op = RTR_SELECT_REPLACE, bool outside = false) {
+        const float zero[3] = {0.f, 0.f, 0.f};
+        uint64_t st[4];
+        check(ctx_, rtr_select_voxel_grid(ctx_, origin ? origin : zero, cell, min_count, op | (outside ? RTR_SELECT_OUTSIDE : 0), st));
+        return st[0];
+    }
+    // Thins the resident cloud to one vertex per cubic cell of size `cell` for good: every vertex but the cells'
+    // representatives is selected and removed.  Returns the number of vertices left.
+    uint64_t thin(float cell) {
+        const float c3[3] = {cell, cell, cell};
+        selectVoxelGrid(c3, nullptr, 1, RTR_SELECT_REPLACE, true);
+        removeSelected();
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        return n;
     }
     uint64_t selectedCount() {
         if (!has_selection()) return 0;

@@ -144,6 +144,7 @@ struct rtr_ctx {
     // everything that renumbers upload indices
     uint32_t *sel = nullptr;
     uint64_t *sel_stats = nullptr;
+    int voxel_us[3] = {0, 0, 0};  // the last rtr_select_voxel_grid: its key kernel, sort and head kernel, from their own events
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
     int opt_grid = rtr::kDefaultPointGrid;  // workgroups of the point kernels
 
@@ -1114,6 +1115,9 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "auto_reorder")) *value = c->opt_auto_reorder;
     else if (!strcmp(key, "reordered")) *value = c->reordered ? 1 : 0;
     else if (!strcmp(key, "selection")) *value = c->sel ? 1 : 0;  // a selection exists (rtr_select_points)
+    else if (!strcmp(key, "voxel_keys_us")) *value = c->voxel_us[0];  // the last rtr_select_voxel_grid, stage by stage
+    else if (!strcmp(key, "voxel_sort_us")) *value = c->voxel_us[1];
+    else if (!strcmp(key, "voxel_heads_us")) *value = c->voxel_us[2];
     else if (!strcmp(key, "point_keep")) *value = c->keep_up ? 1 : 0;  // a keep mask is set (rtr_set_point_keep)  // the resident cloud was sorted by the library
     else if (!strcmp(key, "order_ratio_ppm")) *value = (int)(c->order_ratio * 1e6f);  // chunk / cloud diagonal as uploaded
     else if (!strcmp(key, "cull")) *value = c->opt_cull;
@@ -3222,6 +3226,92 @@ int rtr_select_points(rtr_ctx *c, int plane_count, const float *planes, const fl
     HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, sizeof out, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- selection by a voxel grid (rtr.h, section 6g) ------------------------------------
+// Keys in upload-order slots (rtr::launch_voxel_keys), rocPRIM's stable sort by key, the head of every run of equal keys
+// into zeroed hit words, then selection := op(selection, hits).  Every buffer -- the selection's own when it does not
+// exist yet included -- is allocated before the first word changes, and the call waits for its work before the scratch
+// goes.  What rtr_select_points leaves alone stays as it is here too.
+namespace {
+struct EventSet {  // the stage boundaries of one call
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~EventSet() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+}  // namespace
+
+int rtr_select_voxel_grid(rtr_ctx *c, const float origin[3], const float cell[3], uint32_t min_count, int op, uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_select_voxel_grid: no cloud");
+    NEED(c, origin != nullptr, "rtr_select_voxel_grid: origin is NULL");
+    NEED(c, cell != nullptr, "rtr_select_voxel_grid: cell is NULL");
+    rtr::VoxelGrid grid{};
+    for (int k = 0; k < 3; ++k) {
+        NEED(c, std::isfinite(origin[k]), "rtr_select_voxel_grid: origin is not finite");
+        NEED(c, std::isfinite(cell[k]) && cell[k] > 0.f, "rtr_select_voxel_grid: cell must be finite and > 0");
+        const float inv = 1.0f / cell[k];  // (one IEEE fp32 division: the build has no fast-math)
+        NEED(c, std::isfinite(inv) && inv > 0.f, "rtr_select_voxel_grid: the reciprocal of cell is not finite and > 0 in fp32");
+        grid.origin[k] = origin[k];
+        grid.inv[k] = inv;
+    }
+    NEED(c, min_count >= 1u, "rtr_select_voxel_grid: min_count must be >= 1");
+    const int base = op & ~RTR_SELECT_OUTSIDE;
+    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_voxel_grid: unknown op");
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    if (int rc = need_upload_order(c, "formed")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nw = (n + 31) / 32;
+    const uint64_t words = std::max<uint64_t>((n + 255) / 256, 1) * 8;  // (the selection: 8 per 256-point chunk)
+    // every allocation first: a failure leaves the selection as it was
+    DevBufs buf;
+    uint64_t *k0, *k1, *st;
+    uint32_t *v0, *v1, *hit, *w = nullptr;
+    void *tmp;
+    size_t tmp_bytes = 0;
+    HIP_TRY(c, (hipError_t)rtr::voxel_sort_temp_bytes(n, &tmp_bytes));
+    HIP_TRY(c, buf.get(&k0, n * 8));
+    HIP_TRY(c, buf.get(&k1, n * 8));
+    HIP_TRY(c, buf.get(&v0, n * 4));
+    HIP_TRY(c, buf.get(&v1, n * 4));
+    HIP_TRY(c, buf.get(&hit, nw * 4));
+    HIP_TRY(c, buf.get(&tmp, tmp_bytes));
+    if (!c->sel) {
+        HIP_TRY(c, buf.get(&w, words * 4));
+        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
+    }
+    EventSet ev;
+    for (hipEvent_t &e : ev.e) HIP_TRY(c, hipEventCreate(&e));
+    if (w) {  // (a selection that does not exist yet is empty)
+        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
+        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
+    }
+    HIP_TRY(c, hipMemsetAsync(hit, 0, nw * 4, s));
+    HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
+    HIP_TRY(c, hipEventRecord(ev.e[0], s));
+    rtr::launch_voxel_keys(s, cloud_of(c), c->reordered ? c->perm : nullptr, grid, k0, v0);
+    if (int rc = launch_check(c, "voxel keys")) return rc;
+    HIP_TRY(c, hipEventRecord(ev.e[1], s));
+    if (n) HIP_TRY(c, (hipError_t)rtr::voxel_sort(s, tmp, tmp_bytes, k0, k1, v0, v1, n));
+    HIP_TRY(c, hipEventRecord(ev.e[2], s));
+    rtr::launch_voxel_heads(s, k1, v1, n, min_count, hit, c->sel_stats);
+    if (int rc = launch_check(c, "voxel heads")) return rc;
+    HIP_TRY(c, hipEventRecord(ev.e[3], s));
+    rtr::launch_voxel_combine(s, hit, n, base, (op & RTR_SELECT_OUTSIDE) != 0, c->sel);
+    if (int rc = launch_check(c, "voxel combine")) return rc;
+    rtr::launch_select_count(s, c->sel, n, c->sel_stats);
+    if (int rc = launch_check(c, "select count")) return rc;
+    uint64_t out[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, sizeof out, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+        c->voxel_us[k] = (int)(ms * 1000.f + 0.5f);
+    }
+    if (stats) memcpy(stats, out, sizeof out);
     return RTR_OK;
 }
 

@@ -438,4 +438,25 @@ void launch_select(hipStream_t s, const Cloud &c, const float *bounds, const Cli
 // *out (device) += the set bits of sel, all 8 words of every chunk of n points
 void launch_select_count(hipStream_t s, const uint32_t *sel, uint64_t n, uint64_t *out);
 
+// rtr_select_voxel_grid (rtr_voxel.hip; the cell arithmetic is rtr_voxel_key.h's): inv[k] = 1.0f / cell[k], host-rounded
+struct VoxelGrid {
+    float origin[3], inv[3];
+};
+// voxel_keys: keys[u] / vals[u] = voxel_key (kVoxelOut | u when out of the grid) / u for every resident point below n, u
+// its upload index (perm as for the point pass; null: the resident index); n pairs each, in ascending upload index
+void launch_voxel_keys(hipStream_t s, const Cloud &c, const uint32_t *perm, const VoxelGrid &g, uint64_t *keys, uint32_t *vals);
+// rocPRIM's stable radix sort of the n pairs by key, k0 / v0 -> k1 / v1; voxel_sort_temp_bytes: the temporary it asks
+// for.  Both return a hipError_t as int
+int voxel_sort_temp_bytes(uint64_t n, size_t *bytes);
+int voxel_sort(hipStream_t s, void *tmp, size_t tmp_bytes, const uint64_t *k0, uint64_t *k1, const uint32_t *v0, uint32_t *v1,
+               uint64_t n);
+// voxel_heads: over the sorted pairs, hit ((n + 31) / 32 words, zeroed by the caller) gets the bit vals[j] of the first
+// pair j of every run of equal keys that holds at least min_count (>= 1) pairs; stats (device, zeroed by the caller):
+// [1] / [2] / [3] += runs of in-grid keys / those of them with at least min_count pairs / out-of-grid pairs
+void launch_voxel_heads(hipStream_t s, const uint64_t *keys, const uint32_t *vals, uint64_t n, uint32_t min_count, uint32_t *hit,
+                        uint64_t *stats);
+// voxel_combine: sel (8 u32 per 256-point chunk) := op(sel, invert ? ~hit : hit), bits at or past n never set by it; op
+// as launch_select's
+void launch_voxel_combine(hipStream_t s, const uint32_t *hit, uint64_t n, int op, bool invert, uint32_t *sel);
+
 }  // namespace rtr

@@ -339,6 +339,28 @@ class Projector:
         self._chk(self._lib.rtr_select_points(self._ctx, k, _vp(pl) if k else None, _vp(Pm), _vp(rc4), code, _vp(out)))
         return tuple(int(v) for v in out) if stats else None
 
+    def select_voxel_grid(self, cell, origin=(0, 0, 0), min_count=1, op="replace", outside=False, stats=True):
+        """Selects on the device one point per cell of a regular grid (include/rtr.h section 6g) and combines the hits
+        with the selection so far, as select_points does.  cell: the cell size, a scalar or three values (> 0);
+        origin: a corner of cell (0, 0, 0).  The point of a cell with the smallest upload index is its representative,
+        and it is a hit when the cell holds at least min_count points; points out of the grid (non-finite, or beyond
+        2^20 cells from the origin) are cells of their own.  op / outside: as select_points.  The call always waits.
+        stats: returns (selected points after op, occupied cells, cells with at least min_count points, points out of
+        the grid); False: returns None."""
+        c3 = np.ascontiguousarray(np.broadcast_to(np.asarray(cell, dtype=np.float32), (3,)))
+        o3 = np.ascontiguousarray(origin, dtype=np.float32)
+        if o3.shape != (3,):
+            raise ValueError("origin must have three values")
+        mc = int(min_count)
+        if not 1 <= mc <= 0xFFFFFFFF:
+            raise ValueError("min_count must be in 1 .. 2^32 - 1")
+        code = self._SELECT_OPS[op] if isinstance(op, str) else int(op)
+        if outside:
+            code |= L.SELECT_OUTSIDE
+        out = np.zeros(4, np.uint64) if stats else None
+        self._chk(self._lib.rtr_select_voxel_grid(self._ctx, _vp(o3), _vp(c3), mc, code, _vp(out)))
+        return tuple(int(v) for v in out) if stats else None
+
     def selection(self):
         """The selection as a DeviceBuffer of upload-order words (pass it to remove_points, transform_points,
         set_point_keep or torch.as_tensor), or None when there is none."""
@@ -803,6 +825,19 @@ class ProjectCloud:
         self._p.set_resolution(calibration.getWidth(), calibration.getHeight())
         P = compose_projection(calibration.getIntrinsicsMatrix(), extrinsics)
         return self._p.select_points(P=P, rect=(x0, y0, x1, y1), op=op)[0]
+
+    def selectVoxelGrid(self, cell, origin=(0, 0, 0), min_count=1, op="replace", outside=False):
+        """Selects one vertex per cell of a regular grid of cell size `cell` (a scalar or three values) -- the one with
+        the smallest vertex index, where the cell holds at least min_count vertices (see Projector.select_voxel_grid).
+        Returns the number selected afterwards."""
+        return self._p.select_voxel_grid(cell, origin, min_count, op, outside)[0]
+
+    def thin(self, cell):
+        """Thins the resident cloud to one vertex per cell of size `cell` for good: selectVoxelGrid of everything but
+        the representatives, then removeSelected.  Returns the number of vertices left."""
+        self._p.select_voxel_grid(cell, outside=True, stats=False)
+        self.removeSelected()
+        return self._p.num_points
 
     def selectedCount(self):
         """The number of selected vertices (0 without a selection)."""
