@@ -203,7 +203,11 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *  rtr_get_option("point_keep") reads 1 while a keep mask is set (section 6e).
  *  rtr_get_option("selection") reads 1 while a selection exists (section 6f).
  *  rtr_get_option("voxel_keys_us" / "voxel_sort_us" / "voxel_heads_us") read the device time, in microseconds, that the last
- *          rtr_select_voxel_grid (section 6g) spent in its key kernel, its sort and its head kernel (0 before the first). */
+ *          rtr_select_voxel_grid (section 6g) spent in its key kernel, its sort and its head kernel (0 before the first).
+ *  rtr_get_option("neighbours_keys_us" / "neighbours_sort_us" / "neighbours_count_us") read the same for the last
+ *          rtr_select_neighbours (section 6h): its key kernel, its sort (with the wait for the key kernel's counters), and
+ *          its gather, work-list and count kernels together; "neighbours_pair_tests_k" reads the pair tests that call
+ *          made, in thousands (saturating at 2^31 - 1). */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
 /* Reads an option back; also "p2p_open" (see "p2p_timeout_ms"), "reordered" (1: the resident cloud was sorted by the library),
  * "order_ratio_ppm" (mean chunk-box diagonal / cloud diagonal as uploaded, in millionths), "packed" and
@@ -785,6 +789,53 @@ int rtr_clear_selection(rtr_ctx *ctx);
  * before the first selection word changes: after any of these the selection and everything else are as they were. */
 int rtr_select_voxel_grid(rtr_ctx *ctx, const float origin[3], const float cell[3], uint32_t min_count, int op,
                           uint64_t stats[4]);
+
+/* ---- 6h. selection by neighbour count: the radius outlier filter ---------------------------------------------------
+ * rtr_select_neighbours names the resident points that have at least min_neighbours OTHER points within `radius` (PCL's
+ * RadiusOutlierRemoval, Open3D's remove_radius_outlier).  It writes into RTR_BUF_SELECTION exactly as rtr_select_points
+ * does -- the same buffer, the same life, the same five op values with RTR_SELECT_OUTSIDE OR-ed in, bits past n clear --
+ * so the words feed rtr_remove_points, rtr_set_point_keep, rtr_transform_points, rtr_extract_points and
+ * rtr_write_points as they are.
+ * Neighbour relation: exact and symmetric.  r2 = radius * radius, rounded once to fp32 on the host.  Points i != j
+ * (upload indices) are NEIGHBOURS iff ((dx*dx + dy*dy) + dz*dz) <= r2 with dx = x[i] - x[j], dy = y[i] - y[j],
+ * dz = z[i] - z[j], every difference, product and sum rounded to fp32 on its own (no FMA): numpy float32 in that order
+ * is a bit-for-bit reference.  The comparison is inclusive; coincident points are neighbours of each other (d2 == 0); a
+ * point is never its own neighbour (by index, not by position).
+ * Non-finite points: a point with a NaN or infinite coordinate has no neighbours and is nobody's neighbour.  (A
+ * difference that overflows to infinity fails the comparison by itself.)
+ * hit(i) holds iff point i has at least min_neighbours (>= 1) neighbours.  With RTR_SELECT_OUTSIDE hit = !hit for the
+ * points below n: the outliers, non-finite points included -- what a clean-up removes (select with OUTSIDE, then
+ * rtr_remove_points with the complement as keep words, or rtr_set_point_keep, or rtr_extract_points).
+ * Independence: the result depends on the coordinates and the upload indices alone -- not on the resident order, the
+ * library's sort, the packed form, any option or the internal grid.
+ * The internal grid: cubic cells of edge h = radius * (1 + 2^-10), anchored at the world origin, a coordinate's cell
+ * floor(p / h) in fp64; two neighbours never lie more than one cell apart on an axis (the proof: csrc/rtr_neighbour_cell.h).
+ * Its SPAN is the cells -(2^20 - 1) .. 2^20 - 2 per axis, i.e. -(2^20 - 1) h <= p < (2^20 - 1) h: every cloud whose finite
+ * coordinates lie within +-2^20 * radius of the world origin is covered.  (Since r2 must be finite, +-FLT_MAX is always
+ * beyond the span.)
+ * What it reads and leaves alone: section 6f's list.  The call reads the uploaded coordinates only; the context's clip
+ * planes and keep mask are ignored.  It changes no frame, frame buffer, tile store, pool, statistics, point-pass buffer
+ * or keep mask, and an open peer-to-peer exchange stays open.  Indices are the point pass's; a cloud sorted by the
+ * library needs option "point_ids" = 1.  A sharded context selects among its own points.
+ * Ordering: as section 6g.  Queued on the context's stream behind everything issued before it; the call ALWAYS waits
+ * for its own work before it returns, stats or not: it frees its scratch (and it waits twice on the way, for the key
+ * sweep's counters and for the number of occupied cells).  It does not repeat frames whose extent pool overflowed.
+ * stats (may be NULL): [0] the points selected after op, [1] points with at least min_neighbours neighbours, [2] finite
+ * points with no neighbour at all, [3] non-finite points.
+ * Memory and cost: one sweep over the coordinates, a stable radix sort of n (64-bit key, 32-bit index) pairs, a gather
+ * of 16-byte records into cell order, and the pair tests.  Scratch for the duration of the call: 56 B per point (the
+ * pairs and the records, twice each), the sort's temporary, (n + 31) / 32 words and 80 B per work item -- one item per
+ * occupied cell and 64-point slice of it, at most min(cells + n / 64, n) -- about 6 to 14 GB at 1e8 points.  The work is
+ * proportional to the candidate pairs actually tested: a query point is tested against the points of the 27 cells
+ * around it, 64 at a time, and its wave stops as soon as all of its up to 64 query points have min_neighbours
+ * neighbours.  A pile of m coincident or near-coincident points with min_neighbours > m therefore costs O(m^2) pair
+ * tests; so does a radius far larger than the point spacing.
+ * Errors, with nothing changed: no cloud, a radius that is not finite and > 0, an r2 that is not a finite normal fp32
+ * number, min_neighbours == 0, an unknown op, a sorted cloud without point_ids -> RTR_ERR_INVALID; 2^32 points or more ->
+ * RTR_ERR_UNSUPPORTED; a finite coordinate beyond the span -> RTR_ERR_UNSUPPORTED (found by a counter of the key sweep,
+ * before any selection word changes); a failed allocation -> RTR_ERR_HIP.  Every scratch buffer is allocated before the
+ * first selection word changes: after any of these the selection and everything else are as they were. */
+int rtr_select_neighbours(rtr_ctx *ctx, float radius, uint32_t min_neighbours, int op, uint64_t stats[4]);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

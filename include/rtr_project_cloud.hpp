@@ -30,6 +30,7 @@
 // selectBox / selectPlanes / selectRect (section 6f) name the vertices of a region on the device; removeSelected,
 // hideSelected and transformSelected then act on them without a host array of flags.
 // selectVoxelGrid (section 6g) names one vertex per cell of a regular grid; thin removes all the others.
+// selectNeighbours (section 6h) names the vertices with enough others within a radius; removeOutliers removes the rest.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
 // writeSelected / writePoints / colorSelected (section 2f) put edited vertices and colours back where they came from:
 // indices, the keep mask and the selection stay.
@@ -368,6 +369,22 @@ public:
         uint64_t n = 0;
         check(ctx_, rtr_num_points(ctx_, &n));
         return n;
+    }
+    // The vertices with at least min_neighbours other vertices within `radius` (section 6h, the radius outlier filter;
+    // the distance test is exact fp32, inclusive, and a vertex is never its own neighbour); outside: every vertex but
+    // those -- the outliers, non-finite vertices included.  Combined with the selection so far by op.  Returns the
+    // number selected afterwards.  point_ids = true when the cloud may be sorted.
+    uint64_t selectNeighbours(float radius, uint32_t min_neighbours, int op = RTR_SELECT_REPLACE, bool outside = false) {
+        uint64_t st[4];
+        check(ctx_, rtr_select_neighbours(ctx_, radius, min_neighbours, op | (outside ? RTR_SELECT_OUTSIDE : 0), st));
+        return st[0];
+    }
+    // Takes the vertices with fewer than min_neighbours others within `radius` out of the resident cloud for good: they
+    // are selected (replacing the selection) and removed.  Returns the number removed.
+    uint64_t removeOutliers(float radius, uint32_t min_neighbours) {
+        const uint64_t gone = selectNeighbours(radius, min_neighbours, RTR_SELECT_REPLACE, true);
+        removeSelected();
+        return gone;
     }
     uint64_t selectedCount() {
         if (!has_selection()) return 0;

@@ -25,7 +25,7 @@ SYMBOLS = [
     "rtr_p2p_render", "rtr_frame_stats", "rtr_get_option", "rtr_host_output_buffers", "rtr_project_async", "rtr_wait",
     "rtr_p2p_render_owned", "rtr_point_pass", "rtr_render_views", "rtr_set_clip_planes", "rtr_get_clip_planes",
     "rtr_set_point_keep", "rtr_append_points", "rtr_remove_points", "rtr_transform_points", "rtr_select_points",
-    "rtr_clear_selection", "rtr_extract_points", "rtr_write_points", "rtr_select_voxel_grid",
+    "rtr_clear_selection", "rtr_extract_points", "rtr_write_points", "rtr_select_voxel_grid", "rtr_select_neighbours",
 ]
 
 RTR_OK, RTR_ERR_INVALID, RTR_ERR_HIP, RTR_ERR_NO_OUTPUT, RTR_ERR_UNSUPPORTED, RTR_ERR_INTERNAL = 0, -1, -2, -3, -4, -5
@@ -141,6 +141,7 @@ def lib():
     L.rtr_select_points.argtypes = [vp, i32, vp, vp, vp, i32, vp]
     L.rtr_clear_selection.argtypes = [vp]
     L.rtr_select_voxel_grid.argtypes = [vp, vp, vp, C.c_uint32, i32, vp]
+    L.rtr_select_neighbours.argtypes = [vp, C.c_float, C.c_uint32, i32, vp]
     L.rtr_extract_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, vp, C.POINTER(u64)]
     L.rtr_write_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, C.POINTER(u64)]
     for name in SYMBOLS:

@@ -1,7 +1,8 @@
 // rtr_device.h -- device-side helpers shared by the kernel files (rtr_kernels.hip: the frame path, the upload, the
-// point pass, extract and transform; rtr_cloud_kernels.hip: keep mask, remove, scan, select; rtr_voxel.hip: the voxel
-// grid's keys).  Device-only: every function is __device__ __forceinline__, so no device call crosses a translation unit
-// and no relocatable device code is needed.  Included by those three files and nothing else; the arithmetic contract of
+// point pass, extract and transform; rtr_cloud_kernels.hip: keep mask, remove, scan, select; rtr_voxel.hip and
+// rtr_neighbours.hip, through rtr_key_sweep.h: the key sweeps of the voxel grid and the neighbour search).
+// Device-only: every function is __device__ __forceinline__, so no device call crosses a translation unit and no
+// relocatable device code is needed.  Included by those files and nothing else; the arithmetic contract of
 // rtr_kernels.hip (-ffp-contract=off) holds for all.
 #pragma once
 #include "rtr_kernels.h"

@@ -459,4 +459,23 @@ void launch_voxel_heads(hipStream_t s, const uint64_t *keys, const uint32_t *val
 // as launch_select's
 void launch_voxel_combine(hipStream_t s, const uint32_t *hit, uint64_t n, int op, bool invert, uint32_t *sel);
 
+// rtr_select_neighbours (rtr_neighbours.hip; the cell arithmetic is rtr_neighbour_cell.h's, the sweep rtr_key_sweep.h's,
+// the sort and the combine rtr_voxel.hip's).
+// neighbour_keys: voxel_keys with the internal grid of `radius`; also rec[u] = (x, y, z, bits of u) for every point, and
+// counters (device, zeroed by the caller) [0] / [1] += points that are not finite / finite but beyond the grid's span
+void launch_neighbour_keys(hipStream_t s, const Cloud &c, const uint32_t *perm, float radius, uint64_t *keys, uint32_t *vals, float4 *rec,
+                           uint64_t *counters);
+// out[j] = rec[vals[j]] for the first m sorted pairs (those with a cell)
+void launch_neighbour_gather(hipStream_t s, const uint32_t *vals, const float4 *rec, uint64_t m, float4 *out);
+// *cells (device) += the runs of equal keys among the first m sorted keys
+void launch_neighbour_cells(hipStream_t s, const uint64_t *keys, uint64_t m, uint64_t *cells);
+// the work list: 20 words per item, one item per (run, 64-pair slice of it), *cursor (device, zeroed by the caller) items,
+// at most cap (min(cells + m / 64, m) always suffices)
+void launch_neighbour_items(hipStream_t s, const uint64_t *keys, uint64_t m, uint32_t *items, uint32_t *cursor, uint64_t cap);
+// the pair tests over the sorted records: hit ((n + 31) / 32 words, zeroed by the caller) gets the bit of every point
+// with at least min_neighbours (>= 1) others at ((dx dx + dy dy) + dz dz) <= r2; stats (device, zeroed) [1] / [2] +=
+// those points / the points of the list with no neighbour at all; *tests (device, zeroed) += the pair tests made
+void launch_neighbour_count(hipStream_t s, const float4 *rec, const uint32_t *items, const uint32_t *cursor, uint64_t cap, float r2,
+                            uint32_t min_neighbours, uint32_t *hit, uint64_t *stats, uint64_t *tests);
+
 }  // namespace rtr

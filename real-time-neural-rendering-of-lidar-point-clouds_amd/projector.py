@@ -361,6 +361,26 @@ class Projector:
         self._chk(self._lib.rtr_select_voxel_grid(self._ctx, _vp(o3), _vp(c3), mc, code, _vp(out)))
         return tuple(int(v) for v in out) if stats else None
 
+    def select_neighbours(self, radius, min_neighbours, op="replace", outside=False, stats=True):
+        """Selects on the device the points with at least min_neighbours other points within `radius` (include/rtr.h
+        section 6h, the radius outlier filter) and combines the hits with the selection so far, as select_points does.
+        Neighbours: ((dx*dx + dy*dy) + dz*dz) <= radius*radius in float32, inclusive; never the point itself; a
+        non-finite point has none.  outside: the outliers instead.  The call always waits.  stats: returns (selected
+        points after op, points with at least min_neighbours neighbours, finite points with no neighbour at all,
+        non-finite points); False: returns None."""
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        k = int(min_neighbours)
+        if not 1 <= k <= 0xFFFFFFFF:
+            raise ValueError("min_neighbours must be in 1 .. 2^32 - 1")
+        code = self._SELECT_OPS[op] if isinstance(op, str) else int(op)
+        if outside:
+            code |= L.SELECT_OUTSIDE
+        out = np.zeros(4, np.uint64) if stats else None
+        self._chk(self._lib.rtr_select_neighbours(self._ctx, r, k, code, _vp(out)))
+        return tuple(int(v) for v in out) if stats else None
+
     def selection(self):
         """The selection as a DeviceBuffer of upload-order words (pass it to remove_points, transform_points,
         set_point_keep or torch.as_tensor), or None when there is none."""
@@ -838,6 +858,18 @@ class ProjectCloud:
         self._p.select_voxel_grid(cell, outside=True, stats=False)
         self.removeSelected()
         return self._p.num_points
+
+    def selectNeighbours(self, radius, min_neighbours, op="replace", outside=False):
+        """Selects the vertices with at least min_neighbours other vertices within `radius` (outside: every vertex but
+        those; see Projector.select_neighbours).  Returns the number selected afterwards."""
+        return self._p.select_neighbours(radius, min_neighbours, op, outside)[0]
+
+    def removeOutliers(self, radius, min_neighbours):
+        """Takes the vertices with fewer than min_neighbours others within `radius` out of the resident cloud for good:
+        selectNeighbours of the outliers, then removeSelected.  Returns the number removed."""
+        gone = self._p.select_neighbours(radius, min_neighbours, outside=True)[0]
+        self.removeSelected()
+        return gone
 
     def selectedCount(self):
         """The number of selected vertices (0 without a selection)."""
