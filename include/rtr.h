@@ -207,7 +207,11 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *  rtr_get_option("neighbours_keys_us" / "neighbours_sort_us" / "neighbours_count_us") read the same for the last
  *          rtr_select_neighbours (section 6h): its key kernel, its sort (with the wait for the key kernel's counters), and
  *          its gather, work-list and count kernels together; "neighbours_pair_tests_k" reads the pair tests that call
- *          made, in thousands (saturating at 2^31 - 1). */
+ *          made, in thousands (saturating at 2^31 - 1).
+ *  rtr_get_option("clusters_keys_us" / "clusters_sort_us" / "clusters_label_us") read the same for the last
+ *          rtr_select_clusters (section 6i): its key kernel, its sort (with the wait for the key kernel's counters), and
+ *          its gather, work-list, union-find, flatten and hit kernels together; "clusters_pair_tests_k" reads that call's
+ *          pair tests, in thousands (saturating at 2^31 - 1). */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
 /* Reads an option back; also "p2p_open" (see "p2p_timeout_ms"), "reordered" (1: the resident cloud was sorted by the library),
  * "order_ratio_ppm" (mean chunk-box diagonal / cloud diagonal as uploaded, in millionths), "packed" and
@@ -836,6 +840,68 @@ int rtr_select_voxel_grid(rtr_ctx *ctx, const float origin[3], const float cell[
  * before any selection word changes); a failed allocation -> RTR_ERR_HIP.  Every scratch buffer is allocated before the
  * first selection word changes: after any of these the selection and everything else are as they were. */
 int rtr_select_neighbours(rtr_ctx *ctx, float radius, uint32_t min_neighbours, int op, uint64_t stats[4]);
+
+/* ---- 6i. selection by connected cluster: Euclidean clustering -------------------------------------------------------
+ * rtr_select_clusters names the resident points by the size of the cluster they belong to (PCL's
+ * EuclideanClusterExtraction, Open3D's cluster_dbscan with min_points = 1, "label connected components"): drop every
+ * floating blob of fewer than 50 returns, keep the largest structure, grow the selection to everything connected to it,
+ * label the segments.  It writes into RTR_BUF_SELECTION exactly as rtr_select_points does -- the same buffer, the same
+ * life, the same five op values with RTR_SELECT_OUTSIDE OR-ed in, bits past n clear -- so the words feed
+ * rtr_remove_points, rtr_set_point_keep, rtr_transform_points, rtr_extract_points and rtr_write_points as they are.
+ * Neighbour relation: exactly section 6h's, with the same rounding.  r2 = radius * radius, rounded once to fp32 on the
+ * host; points i != j are neighbours iff ((dx*dx + dy*dy) + dz*dz) <= r2 in fp32, every difference, product and sum
+ * rounded on its own (no FMA), inclusive; coincident points are neighbours of each other; a point is never its own
+ * neighbour (by index, not by position); a non-finite point has no neighbours and is nobody's neighbour.
+ * Clusters: the connected components of that relation over the n resident points.  A point without neighbours is a
+ * cluster of one -- every non-finite point among them.  The LABEL of a cluster is the smallest upload index among its
+ * members; its size is its member count.  numpy float32 in section 6h's order with any correct component labelling is
+ * a bit-for-bit reference: nothing here has a tolerance.
+ * Independence: clusters, labels and sizes depend on the coordinates and the upload indices alone -- not on the
+ * resident order, the library's sort, the packed form, any option or the internal grid.
+ * hit(i) holds iff all of
+ *   1. size(cluster(i)) >= min_points (>= 1);
+ *   2. max_points == 0 (unbounded) or size(cluster(i)) <= max_points;
+ *   3. flags has no RTR_CLUSTER_SEEDED, or the cluster of i contains at least one point that was selected BEFORE this
+ *      call (the seeds are read before op is applied; a selection that does not exist yet is empty, so nothing hits --
+ *      and the call creates an empty selection).  Seeded with op REPLACE grows the selection to everything connected to
+ *      it; with SUBTRACT or INTERSECT the seeds are likewise the selection as it was before the call.
+ * With RTR_SELECT_OUTSIDE hit = !hit for the points below n: "remove the small blobs" is min_points = k with OUTSIDE,
+ * then "remove what is selected".  op combines the hits with the selection so far as in section 6f.
+ * labels (may be NULL): room for n uint32_t, in host memory or in device memory of the context's device -- told apart
+ * as rtr_extract_points tells its outputs apart.  labels[i] = the label of point i's cluster, in upload order, for
+ * every point (hit or not, finite or not: a non-finite point's label is its own index).  It is written only when the
+ * call succeeds; after any error every element is as it was.  There is no resident label buffer.
+ * stats (may be NULL): [0] the points selected after op, [1] clusters, [2] clusters that hit (before OUTSIDE),
+ * [3] the points of the largest cluster.
+ * The internal grid and its SPAN: section 6h's -- every cloud whose finite coordinates lie within +-2^20 * radius of the
+ * world origin is covered.
+ * What it reads and leaves alone: section 6f's list.  The call reads the uploaded coordinates and, when seeded, the
+ * selection; the context's clip planes and keep mask are ignored.  It changes no frame, frame buffer, tile store, pool,
+ * statistics, point-pass buffer or keep mask, and an open peer-to-peer exchange stays open.  Indices are the point
+ * pass's; a cloud sorted by the library needs option "point_ids" = 1.  A sharded context clusters its own points.
+ * Ordering: as section 6h.  Queued on the context's stream behind everything issued before it; the call ALWAYS waits
+ * for its own work before it returns, stats or not (and it waits twice on the way, for the key sweep's counters and for
+ * the number of occupied cells).  It does not repeat frames whose extent pool overflowed.
+ * Memory and cost: section 6h's sweep, sort, gather and work list, then a lock-free union-find over the sorted
+ * positions (every accepted pair unites two sets; the larger root is hooked under the smaller, so a parent never
+ * exceeds its child and no wave ever waits for another), a pass that flattens it and gathers size, label and seed flag
+ * at the roots, and a pass that writes hits and labels.  Scratch for the duration of the call: section 6h's and nothing
+ * on top -- 56 B per point, the sort's temporary, (n + 31) / 32 words and 80 B per work item; the union-find's 16 B per
+ * point and the labels' 4 B per point reuse buffers that the sort and the gather have finished with -- about 6 to 14 GB
+ * at 1e8 points.  Every candidate pair of the 27 cells around a point is tested once per direction at most (the
+ * library tests a pair only from its end later in cell order, and skips the 64-candidate tiles that lie wholly behind
+ * the querying slice).  There is NO early exit: unlike section 6h every edge matters, so a pile of m coincident or
+ * near-coincident points costs O(m^2) pair tests whatever the arguments are; so does a radius far larger than the point
+ * spacing.
+ * Errors, with nothing changed: no cloud, a radius that is not finite and > 0, an r2 that is not a finite normal fp32
+ * number, min_points == 0, max_points != 0 && max_points < min_points, unknown bits in flags, an unknown op, a sorted
+ * cloud without point_ids -> RTR_ERR_INVALID; 2^32 points or more -> RTR_ERR_UNSUPPORTED; a finite coordinate beyond the
+ * span -> RTR_ERR_UNSUPPORTED (found by a counter of the key sweep, before any selection word or any element of labels
+ * changes, and before a selection is created); a failed allocation -> RTR_ERR_HIP.  Every scratch buffer is allocated
+ * before the first selection word changes: after any of these the selection and everything else are as they were. */
+#define RTR_CLUSTER_SEEDED 1   /* flags: only clusters holding a currently selected point */
+int rtr_select_clusters(rtr_ctx *ctx, float radius, uint32_t min_points, uint32_t max_points,
+                        int flags, int op, uint32_t *labels, uint64_t stats[4]);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

@@ -31,6 +31,7 @@
 // hideSelected and transformSelected then act on them without a host array of flags.
 // selectVoxelGrid (section 6g) names one vertex per cell of a regular grid; thin removes all the others.
 // selectNeighbours (section 6h) names the vertices with enough others within a radius; removeOutliers removes the rest.
+// selectClusters (section 6i) names them by the size of their connected cluster; growSelection, removeSmallClusters.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
 // writeSelected / writePoints / colorSelected (section 2f) put edited vertices and colours back where they came from:
 // indices, the keep mask and the selection stay.
@@ -383,6 +384,28 @@ public:
     // are selected (replacing the selection) and removed.  Returns the number removed.
     uint64_t removeOutliers(float radius, uint32_t min_neighbours) {
         const uint64_t gone = selectNeighbours(radius, min_neighbours, RTR_SELECT_REPLACE, true);
+        removeSelected();
+        return gone;
+    }
+    // The vertices whose connected cluster within `radius` (section 6i, Euclidean clustering over section 6h's exact
+    // relation) holds at least min_points and, unless max_points is 0, at most max_points vertices; seeded: only the
+    // clusters that hold a vertex selected before the call; outside: every vertex but those.  Combined with the
+    // selection so far by op.  labels (nullptr: none; host or device memory, one uint32_t per vertex): the label of every
+    // vertex's cluster, the smallest vertex index among its members.  Returns the number selected afterwards.
+    // point_ids = true when the cloud may be sorted.
+    uint64_t selectClusters(float radius, uint32_t min_points = 1, uint32_t max_points = 0, bool seeded = false,
+                            int op = RTR_SELECT_REPLACE, bool outside = false, uint32_t* labels = nullptr) {
+        uint64_t st[4];
+        check(ctx_, rtr_select_clusters(ctx_, radius, min_points, max_points, seeded ? RTR_CLUSTER_SEEDED : 0,
+                                        op | (outside ? RTR_SELECT_OUTSIDE : 0), labels, st));
+        return st[0];
+    }
+    // Grows the selection to every vertex connected to it by steps of at most `radius`.  Returns the number selected.
+    uint64_t growSelection(float radius) { return selectClusters(radius, 1, 0, true); }
+    // Takes the clusters of fewer than min_points vertices within `radius` out of the resident cloud for good: their
+    // vertices are selected (replacing the selection) and removed.  Returns the number removed.
+    uint64_t removeSmallClusters(float radius, uint32_t min_points) {
+        const uint64_t gone = selectClusters(radius, min_points, 0, false, RTR_SELECT_REPLACE, true);
         removeSelected();
         return gone;
     }

@@ -147,6 +147,8 @@ struct rtr_ctx {
     int voxel_us[3] = {0, 0, 0};  // the last rtr_select_voxel_grid: its key kernel, sort and head kernel, from their own events
     int neighbours_us[3] = {0, 0, 0};  // the last rtr_select_neighbours: key kernel, sort, gather + work list + count kernel
     int neighbours_tests_k = 0;        // ... and its pair tests in thousands (saturating)
+    int clusters_us[3] = {0, 0, 0};    // the last rtr_select_clusters: key kernel, sort, gather + work list + union-find + hits
+    int clusters_tests_k = 0;          // ... and its pair tests in thousands (saturating)
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
     int opt_grid = rtr::kDefaultPointGrid;  // workgroups of the point kernels
 
@@ -1124,6 +1126,10 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "neighbours_sort_us")) *value = c->neighbours_us[1];
     else if (!strcmp(key, "neighbours_count_us")) *value = c->neighbours_us[2];
     else if (!strcmp(key, "neighbours_pair_tests_k")) *value = c->neighbours_tests_k;
+    else if (!strcmp(key, "clusters_keys_us")) *value = c->clusters_us[0];  // the last rtr_select_clusters
+    else if (!strcmp(key, "clusters_sort_us")) *value = c->clusters_us[1];
+    else if (!strcmp(key, "clusters_label_us")) *value = c->clusters_us[2];
+    else if (!strcmp(key, "clusters_pair_tests_k")) *value = c->clusters_tests_k;
     else if (!strcmp(key, "point_keep")) *value = c->keep_up ? 1 : 0;  // a keep mask is set (rtr_set_point_keep)  // the resident cloud was sorted by the library
     else if (!strcmp(key, "order_ratio_ppm")) *value = (int)(c->order_ratio * 1e6f);  // chunk / cloud diagonal as uploaded
     else if (!strcmp(key, "cull")) *value = c->opt_cull;
@@ -3321,12 +3327,106 @@ int rtr_select_voxel_grid(rtr_ctx *c, const float origin[3], const float cell[3]
     return RTR_OK;
 }
 
-// ---- selection by neighbour count (rtr.h, section 6h) ---------------------------------
-// rtr_select_voxel_grid's pattern with a neighbour search between the sort and the combine (rtr_neighbours.hip).  The
-// call waits twice on the way -- for the key sweep's two counters (a point beyond the span fails the call; the points
-// with a cell are the first n - nonfinite sorted pairs) and for the number of occupied cells, which sizes the work list
-// -- and both lie before the first selection word changes, as does every allocation; a selection that does not exist
-// yet is only created once nothing can fail any more but a launch.
+// ---- selection by neighbour count and by cluster (rtr.h, sections 6h and 6i) ----------
+// rtr_select_voxel_grid's pattern with a neighbour search between the sort and the combine (rtr_neighbours.hip,
+// rtr_clusters.hip).  Both calls share everything up to the work list (neighbour_search): it waits twice on the way --
+// for the key sweep's two counters (a point beyond the span fails the call; the points with a cell are the first
+// n - nonfinite sorted pairs) and for the number of occupied cells, which sizes the work list -- and both lie before the
+// first selection word changes, as does every allocation; a selection that does not exist yet is only created once
+// nothing can fail any more but a launch.
+namespace {
+struct NeighbourSearch {  // the scratch of one call and what the search found
+    DevBufs buf;
+    EventSet ev;
+    uint64_t *k0, *k1, *cn;  // cn: [0] non-finite points, [1] finite points beyond the span, [2] pair tests, [3] cells, [4] the list's cursor
+    uint32_t *v0, *v1, *hit, *items;
+    float4 *rec0, *rec1;
+    uint64_t n, m, cap;  // points, those of them with a cell (the first m sorted pairs), the work list's slots
+};
+
+// Allocates, sweeps, sorts, gathers and lists; leaves hit and sel_stats zeroed, the selection in existence and
+// ev.e[0 .. 2] recorded (before the keys, behind them, behind the sort).
+int neighbour_search(rtr_ctx *c, const char *who, float radius, NeighbourSearch &q) {
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nw = (n + 31) / 32;
+    const uint64_t words = std::max<uint64_t>((n + 255) / 256, 1) * 8;  // (the selection: 8 per 256-point chunk)
+    DevBufs &buf = q.buf;
+    uint64_t *st;
+    uint32_t *w = nullptr;
+    void *tmp;
+    size_t tmp_bytes = 0;
+    HIP_TRY(c, (hipError_t)rtr::voxel_sort_temp_bytes(n, &tmp_bytes));
+    HIP_TRY(c, buf.get(&q.k0, n * 8));
+    HIP_TRY(c, buf.get(&q.k1, n * 8));
+    HIP_TRY(c, buf.get(&q.v0, n * 4));
+    HIP_TRY(c, buf.get(&q.v1, n * 4));
+    HIP_TRY(c, buf.get(&q.rec0, n * 16));
+    HIP_TRY(c, buf.get(&q.rec1, n * 16));
+    HIP_TRY(c, buf.get(&q.hit, nw * 4));
+    HIP_TRY(c, buf.get(&q.cn, 5 * sizeof(uint64_t)));
+    HIP_TRY(c, buf.get(&tmp, tmp_bytes));
+    if (!c->sel) {
+        HIP_TRY(c, buf.get(&w, words * 4));
+        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
+    }
+    for (hipEvent_t &e : q.ev.e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipMemsetAsync(q.hit, 0, nw * 4, s));
+    HIP_TRY(c, hipMemsetAsync(q.cn, 0, 5 * sizeof(uint64_t), s));
+    HIP_TRY(c, hipEventRecord(q.ev.e[0], s));
+    rtr::launch_neighbour_keys(s, cloud_of(c), c->reordered ? c->perm : nullptr, radius, q.k0, q.v0, q.rec0, q.cn);
+    if (int rc = launch_check(c, "neighbour keys")) return rc;
+    HIP_TRY(c, hipEventRecord(q.ev.e[1], s));
+    uint64_t host[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(host, q.cn, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (host[1])
+        return fail(c, RTR_ERR_UNSUPPORTED, "%s: %llu finite points lie beyond the span of the internal grid (about 2^20 "
+                    "radius from the world origin on an axis)", who, (unsigned long long)host[1]);
+    const uint64_t nonfinite = host[0], m = n - nonfinite;  // (the pairs with a cell sort to the front)
+    if (n) HIP_TRY(c, (hipError_t)rtr::voxel_sort(s, tmp, tmp_bytes, q.k0, q.k1, q.v0, q.v1, n));
+    HIP_TRY(c, hipEventRecord(q.ev.e[2], s));
+    rtr::launch_neighbour_gather(s, q.v1, q.rec0, m, q.rec1);
+    if (int rc = launch_check(c, "neighbour gather")) return rc;
+    rtr::launch_neighbour_cells(s, q.k1, m, q.cn + 3);
+    if (int rc = launch_check(c, "neighbour cells")) return rc;
+    HIP_TRY(c, hipMemcpyAsync(host + 3, q.cn + 3, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t cap = std::min<uint64_t>(host[3] + m / 64, m);  // (a cell of len points: ceil(len / 64) <= 1 + len / 64 items, each of >= 1 point)
+    HIP_TRY(c, buf.get(&q.items, cap * 80));
+    if (w) {  // (a selection that does not exist yet is empty)
+        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
+        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
+    }
+    HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
+    rtr::launch_neighbour_items(s, q.k1, m, q.items, (uint32_t *)(q.cn + 4), cap);
+    if (int rc = launch_check(c, "neighbour items")) return rc;
+    q.n = n, q.m = m, q.cap = cap;
+    return RTR_OK;
+}
+
+// selection := op(selection, hits), the count, the wait; out: the four statistics, *tests: the pair tests; us[0 .. 2]:
+// the stage times between the search's events and ev.e[3], which the caller has recorded
+int neighbour_finish(rtr_ctx *c, const char *what, NeighbourSearch &q, int op, uint64_t out[4], int us[3], int *tests_k) {
+    hipStream_t s = c->stream;
+    const int base = op & ~RTR_SELECT_OUTSIDE;
+    rtr::launch_voxel_combine(s, q.hit, q.n, base, (op & RTR_SELECT_OUTSIDE) != 0, c->sel);
+    if (int rc = launch_check(c, what)) return rc;
+    rtr::launch_select_count(s, c->sel, q.n, c->sel_stats);
+    if (int rc = launch_check(c, "select count")) return rc;
+    uint64_t tests = 0;
+    HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&tests, q.cn + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
+    for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, q.ev.e[k], q.ev.e[k + 1]));
+        us[k] = (int)(ms * 1000.f + 0.5f);
+    }
+    *tests_k = (int)std::min<uint64_t>(tests / 1000, 0x7FFFFFFF);
+    return RTR_OK;
+}
+}  // namespace
+
 int rtr_select_neighbours(rtr_ctx *c, float radius, uint32_t min_neighbours, int op, uint64_t stats[4]) {
     if (!c) return RTR_ERR_INVALID;
     c->ov.other_call();
@@ -3341,78 +3441,61 @@ int rtr_select_neighbours(rtr_ctx *c, float radius, uint32_t min_neighbours, int
     if (int rc = need_upload_order(c, "formed")) return rc;
     DevGuard g(c->device);
     hipStream_t s = c->stream;
-    const uint64_t n = c->n, nw = (n + 31) / 32;
-    const uint64_t words = std::max<uint64_t>((n + 255) / 256, 1) * 8;  // (the selection: 8 per 256-point chunk)
-    DevBufs buf;
-    uint64_t *k0, *k1, *st, *cn;  // cn: [0] non-finite points, [1] finite points beyond the span, [2] pair tests, [3] cells, [4] the list's cursor
-    uint32_t *v0, *v1, *hit, *items, *w = nullptr;
-    float4 *rec0, *rec1;
-    void *tmp;
-    size_t tmp_bytes = 0;
-    HIP_TRY(c, (hipError_t)rtr::voxel_sort_temp_bytes(n, &tmp_bytes));
-    HIP_TRY(c, buf.get(&k0, n * 8));
-    HIP_TRY(c, buf.get(&k1, n * 8));
-    HIP_TRY(c, buf.get(&v0, n * 4));
-    HIP_TRY(c, buf.get(&v1, n * 4));
-    HIP_TRY(c, buf.get(&rec0, n * 16));
-    HIP_TRY(c, buf.get(&rec1, n * 16));
-    HIP_TRY(c, buf.get(&hit, nw * 4));
-    HIP_TRY(c, buf.get(&cn, 5 * sizeof(uint64_t)));
-    HIP_TRY(c, buf.get(&tmp, tmp_bytes));
-    if (!c->sel) {
-        HIP_TRY(c, buf.get(&w, words * 4));
-        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
-    }
-    EventSet ev;
-    for (hipEvent_t &e : ev.e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, hipMemsetAsync(hit, 0, nw * 4, s));
-    HIP_TRY(c, hipMemsetAsync(cn, 0, 5 * sizeof(uint64_t), s));
-    HIP_TRY(c, hipEventRecord(ev.e[0], s));
-    rtr::launch_neighbour_keys(s, cloud_of(c), c->reordered ? c->perm : nullptr, radius, k0, v0, rec0, cn);
-    if (int rc = launch_check(c, "neighbour keys")) return rc;
-    HIP_TRY(c, hipEventRecord(ev.e[1], s));
-    uint64_t host[5] = {0, 0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(host, cn, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (host[1])
-        return fail(c, RTR_ERR_UNSUPPORTED, "rtr_select_neighbours: %llu finite points lie beyond the span of the internal grid (about 2^20 "
-                    "radius from the world origin on an axis)", (unsigned long long)host[1]);
-    const uint64_t nonfinite = host[0], m = n - nonfinite;  // (the pairs with a cell sort to the front)
-    if (n) HIP_TRY(c, (hipError_t)rtr::voxel_sort(s, tmp, tmp_bytes, k0, k1, v0, v1, n));
-    HIP_TRY(c, hipEventRecord(ev.e[2], s));
-    rtr::launch_neighbour_gather(s, v1, rec0, m, rec1);
-    if (int rc = launch_check(c, "neighbour gather")) return rc;
-    rtr::launch_neighbour_cells(s, k1, m, cn + 3);
-    if (int rc = launch_check(c, "neighbour cells")) return rc;
-    HIP_TRY(c, hipMemcpyAsync(host + 3, cn + 3, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    const uint64_t cap = std::min<uint64_t>(host[3] + m / 64, m);  // (a cell of len points: ceil(len / 64) <= 1 + len / 64 items, each of >= 1 point)
-    HIP_TRY(c, buf.get(&items, cap * 80));
-    if (w) {  // (a selection that does not exist yet is empty)
-        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
-        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
-    }
-    HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
-    rtr::launch_neighbour_items(s, k1, m, items, (uint32_t *)(cn + 4), cap);
-    if (int rc = launch_check(c, "neighbour items")) return rc;
-    rtr::launch_neighbour_count(s, rec1, items, (const uint32_t *)(cn + 4), cap, r2, min_neighbours, hit, c->sel_stats, cn + 2);
+    NeighbourSearch q;
+    if (int rc = neighbour_search(c, "rtr_select_neighbours", radius, q)) return rc;
+    rtr::launch_neighbour_count(s, q.rec1, q.items, (const uint32_t *)(q.cn + 4), q.cap, r2, min_neighbours, q.hit, c->sel_stats, q.cn + 2);
     if (int rc = launch_check(c, "neighbour count")) return rc;
-    HIP_TRY(c, hipEventRecord(ev.e[3], s));
-    HIP_TRY(c, d2d(s, c->sel_stats + 3, cn, sizeof(uint64_t)));
-    rtr::launch_voxel_combine(s, hit, n, base, (op & RTR_SELECT_OUTSIDE) != 0, c->sel);
-    if (int rc = launch_check(c, "neighbour combine")) return rc;
-    rtr::launch_select_count(s, c->sel, n, c->sel_stats);
-    if (int rc = launch_check(c, "select count")) return rc;
+    HIP_TRY(c, hipEventRecord(q.ev.e[3], s));
+    HIP_TRY(c, d2d(s, c->sel_stats + 3, q.cn, sizeof(uint64_t)));
     uint64_t out[4] = {0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, sizeof out, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(host + 2, cn + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-        c->neighbours_us[k] = (int)(ms * 1000.f + 0.5f);
+    if (int rc = neighbour_finish(c, "neighbour combine", q, op, out, c->neighbours_us, &c->neighbours_tests_k)) return rc;
+    if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- selection by connected cluster (rtr.h, section 6i) -------------------------------
+// The union-find's four arrays (parent, size, smallest upload index, seed flag: n words each) live in the unsorted
+// records' buffer, which is dead once the gather has run; the labels are written into the unsorted keys' buffer, dead
+// since the sort, and copied to the caller's array -- host or device memory, told apart as rtr_extract_points does --
+// once everything else has succeeded.
+int rtr_select_clusters(rtr_ctx *c, float radius, uint32_t min_points, uint32_t max_points, int flags, int op, uint32_t *labels,
+                        uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_select_clusters: no cloud");
+    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_select_clusters: radius must be finite and > 0");
+    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
+    NEED(c, std::isnormal(r2), "rtr_select_clusters: the square of radius is not a finite normal fp32 number");
+    NEED(c, min_points >= 1u, "rtr_select_clusters: min_points must be >= 1");
+    NEED(c, max_points == 0u || max_points >= min_points, "rtr_select_clusters: max_points must be 0 (unbounded) or >= min_points");
+    NEED(c, (flags & ~RTR_CLUSTER_SEEDED) == 0, "rtr_select_clusters: unknown bits in flags");
+    const int base = op & ~RTR_SELECT_OUTSIDE;
+    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_clusters: unknown op");
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    if (int rc = need_upload_order(c, "formed")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const bool seeded = (flags & RTR_CLUSTER_SEEDED) != 0, labels_dev = labels && on_device(labels);
+    NeighbourSearch q;
+    if (int rc = neighbour_search(c, "rtr_select_clusters", radius, q)) return rc;
+    const uint64_t n = q.n;
+    uint32_t *parent = reinterpret_cast<uint32_t *>(q.rec0), *size = parent + n, *minu = size + n, *seed = minu + n;
+    uint32_t *lab = labels ? reinterpret_cast<uint32_t *>(q.k0) : nullptr;
+    rtr::launch_cluster_init(s, n, parent, size, minu, seed);
+    if (int rc = launch_check(c, "cluster init")) return rc;
+    rtr::launch_cluster_link(s, q.rec1, q.items, (const uint32_t *)(q.cn + 4), q.cap, r2, parent, q.cn + 2);
+    if (int rc = launch_check(c, "cluster link")) return rc;
+    rtr::launch_cluster_flatten(s, q.v1, n, seeded ? c->sel : nullptr, parent, size, minu, seed);
+    if (int rc = launch_check(c, "cluster flatten")) return rc;
+    rtr::launch_cluster_hits(s, q.v1, n, parent, size, minu, seed, min_points, max_points, seeded, q.hit, lab, c->sel_stats);
+    if (int rc = launch_check(c, "cluster hits")) return rc;
+    HIP_TRY(c, hipEventRecord(q.ev.e[3], s));
+    uint64_t out[4] = {0, 0, 0, 0};
+    if (int rc = neighbour_finish(c, "cluster combine", q, op, out, c->clusters_us, &c->clusters_tests_k)) return rc;
+    if (lab) {  // (behind everything that can fail: the caller's array changes only when the call succeeds)
+        HIP_TRY(c, hipMemcpyAsync(labels, lab, n * 4, labels_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
     }
-    c->neighbours_tests_k = (int)std::min<uint64_t>(host[2] / 1000, 0x7FFFFFFF);
     if (stats) memcpy(stats, out, sizeof out);
     return RTR_OK;
 }

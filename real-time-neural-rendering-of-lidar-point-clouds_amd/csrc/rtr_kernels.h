@@ -471,11 +471,31 @@ void launch_neighbour_gather(hipStream_t s, const uint32_t *vals, const float4 *
 void launch_neighbour_cells(hipStream_t s, const uint64_t *keys, uint64_t m, uint64_t *cells);
 // the work list: 20 words per item, one item per (run, 64-pair slice of it), *cursor (device, zeroed by the caller) items,
 // at most cap (min(cells + m / 64, m) always suffices)
+constexpr int kNbItemWords = 20;  // {q0, qn, lo_0, hi_0, .. lo_8, hi_8}
 void launch_neighbour_items(hipStream_t s, const uint64_t *keys, uint64_t m, uint32_t *items, uint32_t *cursor, uint64_t cap);
 // the pair tests over the sorted records: hit ((n + 31) / 32 words, zeroed by the caller) gets the bit of every point
 // with at least min_neighbours (>= 1) others at ((dx dx + dy dy) + dz dz) <= r2; stats (device, zeroed) [1] / [2] +=
 // those points / the points of the list with no neighbour at all; *tests (device, zeroed) += the pair tests made
 void launch_neighbour_count(hipStream_t s, const float4 *rec, const uint32_t *items, const uint32_t *cursor, uint64_t cap, float r2,
                             uint32_t min_neighbours, uint32_t *hit, uint64_t *stats, uint64_t *tests);
+
+// rtr_select_clusters (rtr_clusters.hip; everything up to the work list is rtr_select_neighbours').  The union-find runs
+// over the n sorted positions: parent, size, minu, seed are n words each.
+// cluster_init: parent[j] = j, size[j] = 0, minu[j] = 2^32 - 1, seed[j] = 0
+void launch_cluster_init(hipStream_t s, uint64_t n, uint32_t *parent, uint32_t *size, uint32_t *minu, uint32_t *seed);
+// cluster_link: the pair tests of neighbour_count without its early exit; every pair at ((dx dx + dy dy) + dz dz) <= r2
+// unites its two sorted positions' sets in parent (parent[v] <= v throughout); *tests (device, zeroed) += the pair tests
+void launch_cluster_link(hipStream_t s, const float4 *rec, const uint32_t *items, const uint32_t *cursor, uint64_t cap, float r2,
+                         uint32_t *parent, uint64_t *tests);
+// cluster_flatten: parent[j] = the root of j; at the root size += 1, minu = min(minu, vals[j]), and, with sel (the
+// selection words; null: not asked for), seed |= the bit vals[j] of sel
+void launch_cluster_flatten(hipStream_t s, const uint32_t *vals, uint64_t n, const uint32_t *sel, uint32_t *parent, uint32_t *size,
+                            uint32_t *minu, uint32_t *seed);
+// cluster_hits: hit ((n + 31) / 32 words, zeroed by the caller) gets the bit vals[j] of every position whose root's size
+// lies in min_points .. max_points (0: unbounded) and, if seeded, whose root's seed is set; labels (device, n words, may
+// be null) [vals[j]] = the root's minu; stats (device, zeroed) [1] / [2] += roots / roots that hit, [3] = the largest size
+void launch_cluster_hits(hipStream_t s, const uint32_t *vals, uint64_t n, const uint32_t *parent, const uint32_t *size, const uint32_t *minu,
+                         const uint32_t *seed, uint32_t min_points, uint32_t max_points, bool seeded, uint32_t *hit, uint32_t *labels,
+                         uint64_t *stats);
 
 }  // namespace rtr

@@ -76,7 +76,7 @@ __device__ __forceinline__ uint32_t bcast(uint32_t v, int lane) { return (uint32
 // one atomic cursor (their order is arbitrary; nothing downstream depends on it) and are written by as many lanes.
 // An item: 20 words {q0, qn, lo_0, hi_0, .. lo_8, hi_8}: query points q0 .. q0 + qn - 1 (qn <= 64) of the sorted
 // records, candidates [lo_t, hi_t).  cap: the slots of `items` (never reached: cells + m / 64 bounds the sum).
-constexpr int kItemWords = 20;
+constexpr int kItemWords = kNbItemWords;
 
 __global__ __launch_bounds__(kBlock) void k_nb_items(const uint64_t *__restrict__ keys, uint32_t m, uint32_t *__restrict__ items,
                                                      uint32_t *__restrict__ cursor, uint32_t cap) {

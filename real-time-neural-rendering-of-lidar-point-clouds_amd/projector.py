@@ -381,6 +381,36 @@ class Projector:
         self._chk(self._lib.rtr_select_neighbours(self._ctx, r, k, code, _vp(out)))
         return tuple(int(v) for v in out) if stats else None
 
+    def select_clusters(self, radius, min_points=1, max_points=0, seeded=False, op="replace", outside=False, labels=False,
+                        stats=True):
+        """Selects on the device the points whose connected cluster within `radius` (include/rtr.h section 6i, Euclidean
+        clustering) holds at least min_points and, unless max_points is 0, at most max_points points, and combines the
+        hits with the selection so far, as select_points does.  Clusters are the connected components of
+        select_neighbours' relation; a point without neighbours (every non-finite one too) is a cluster of one.
+        seeded: only the clusters that hold a point selected before the call.  outside: every other point instead.
+        The call always waits.  labels: also the label of every point's cluster -- the smallest upload index among its
+        members -- as a uint32 array in upload order.  stats: (selected points after op, clusters, clusters that hit,
+        points of the largest cluster).  Returns the stats, (stats, labels) with labels, the labels alone with
+        stats=False, or None with neither."""
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        lo, hi = int(min_points), int(max_points)
+        if not 1 <= lo <= 0xFFFFFFFF:
+            raise ValueError("min_points must be in 1 .. 2^32 - 1")
+        if not 0 <= hi <= 0xFFFFFFFF or (hi != 0 and hi < lo):
+            raise ValueError("max_points must be 0 (unbounded) or in min_points .. 2^32 - 1")
+        code = self._SELECT_OPS[op] if isinstance(op, str) else int(op)
+        if outside:
+            code |= L.SELECT_OUTSIDE
+        out = np.zeros(4, np.uint64) if stats else None
+        lab = np.empty(self.num_points, np.uint32) if labels else None
+        self._chk(self._lib.rtr_select_clusters(self._ctx, r, lo, hi, L.CLUSTER_SEEDED if seeded else 0, code, _vp(lab), _vp(out)))
+        st = tuple(int(v) for v in out) if stats else None
+        if labels:
+            return (st, lab) if stats else lab
+        return st
+
     def selection(self):
         """The selection as a DeviceBuffer of upload-order words (pass it to remove_points, transform_points,
         set_point_keep or torch.as_tensor), or None when there is none."""
@@ -868,6 +898,24 @@ class ProjectCloud:
         """Takes the vertices with fewer than min_neighbours others within `radius` out of the resident cloud for good:
         selectNeighbours of the outliers, then removeSelected.  Returns the number removed."""
         gone = self._p.select_neighbours(radius, min_neighbours, outside=True)[0]
+        self.removeSelected()
+        return gone
+
+    def selectClusters(self, radius, min_points=1, max_points=0, seeded=False, op="replace", outside=False):
+        """Selects the vertices whose connected cluster within `radius` holds min_points .. max_points vertices (0: no
+        upper bound; seeded: only clusters holding a selected vertex; see Projector.select_clusters).  Returns the
+        number selected afterwards."""
+        return self._p.select_clusters(radius, min_points, max_points, seeded, op, outside)[0]
+
+    def growSelection(self, radius):
+        """Grows the selection to every vertex connected to it by steps of at most `radius`.  Returns the number
+        selected afterwards."""
+        return self._p.select_clusters(radius, seeded=True)[0]
+
+    def removeSmallClusters(self, radius, min_points):
+        """Takes the clusters of fewer than min_points vertices within `radius` out of the resident cloud for good:
+        selectClusters of everything else's complement, then removeSelected.  Returns the number removed."""
+        gone = self._p.select_clusters(radius, min_points, outside=True)[0]
         self.removeSelected()
         return gone
 
