@@ -211,7 +211,9 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *  rtr_get_option("clusters_keys_us" / "clusters_sort_us" / "clusters_label_us") read the same for the last
  *          rtr_select_clusters (section 6i): its key kernel, its sort (with the wait for the key kernel's counters), and
  *          its gather, work-list, union-find, flatten and hit kernels together; "clusters_pair_tests_k" reads that call's
- *          pair tests, in thousands (saturating at 2^31 - 1). */
+ *          pair tests, in thousands (saturating at 2^31 - 1).
+ *  rtr_get_option("plane_sample_us" / "plane_count_us") read the host time, in microseconds and with its waits, that the
+ *          last rtr_fit_plane (section 6j) spent drawing and extracting its sample and counting its candidates. */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
 /* Reads an option back; also "p2p_open" (see "p2p_timeout_ms"), "reordered" (1: the resident cloud was sorted by the library),
  * "order_ratio_ppm" (mean chunk-box diagonal / cloud diagonal as uploaded, in millionths), "packed" and
@@ -902,6 +904,75 @@ int rtr_select_neighbours(rtr_ctx *ctx, float radius, uint32_t min_neighbours, i
 #define RTR_CLUSTER_SEEDED 1   /* flags: only clusters holding a currently selected point */
 int rtr_select_clusters(rtr_ctx *ctx, float radius, uint32_t min_points, uint32_t max_points,
                         int flags, int op, uint32_t *labels, uint64_t stats[4]);
+
+/* ---- 6j. fitting the dominant plane: counting points in bands, RANSAC on top -----------------------------------------
+ * The ground-plane stage of a LiDAR pipeline (PCL's SACSegmentation with SACMODEL_PLANE, Open3D's segment_plane):
+ * rtr_fit_plane finds the plane that has the most resident points within `dist` of it, rtr_count_in_bands is the
+ * primitive it is built on.  Neither writes the selection: the facades' selectPlane turns a fitted plane into one with
+ * rtr_select_points (section 6f), and from there section 6i can cluster what is left.
+ *
+ * rtr_count_in_bands.  A BAND is five floats {a, b, c, d_lo, d_hi}.  Point i is IN band k iff
+ *     u + d_lo >= 0  and  (-u) + d_hi >= 0,   u = (a*x + b*y) + c*z,
+ * every product and every sum rounded to fp32 on its own (no FMA); NaN is in no band.  This is bit for bit the section
+ * 6d test of the two planes {a, b, c, d_lo} and {-a, -b, -c, d_hi}: negation commutes with round-to-nearest, so the
+ * second plane's sum is exactly -u and sharing u is no approximation.  Hence numpy float32 in that order is a
+ * bit-for-bit reference, and counts[k] equals stats[0] of rtr_select_points(ctx, 2, those two planes, NULL, NULL,
+ * RTR_SELECT_REPLACE, stats).  counts[k] = the number of points of the POPULATION in band k, k < count <= RTR_MAX_BANDS.
+ * Population: every resident point, or, with RTR_BANDS_SELECTED in flags, the points selected now (RTR_BUF_SELECTION as
+ * it is; a selection that does not exist counts as empty, and the call does not create one).
+ * What it reads and leaves alone: the uploaded coordinates and, with the flag, the selection; the context's clip planes
+ * and keep mask are ignored.  It changes NOTHING in the context -- section 6f's list, and the selection too: no frame,
+ * frame buffer, tile store, pool, statistics, point-pass buffer, keep mask or selection word, and an open peer-to-peer
+ * exchange stays open.  Indices are the point pass's: with the flag a cloud sorted by the library needs option
+ * "point_ids" = 1; without it no index is involved and every cloud works.  A sharded context counts its own points;
+ * counts are plain sums, so the ranks may all-reduce them (which is why the primitive is public).
+ * Ordering: queued on the context's stream behind everything issued before it; the call ALWAYS waits for its own work,
+ * since the counts go to the host.  It does not repeat frames whose extent pool overflowed.
+ * stats (may be NULL): [0] the population size, [1] (chunk, band) pairs decided on the chunk's box as wholly outside the
+ * band, [2] pairs decided on the box as wholly inside, [3] pairs tested point by point; [1] + [2] + [3] =
+ * ((n + 255) / 256) * count.  With the flag a chunk without a selected point is outside for every band.
+ * Memory and cost: the bands are taken 64 at a time (one launch each).  In a pass every 256-point chunk is classified
+ * on its box against all bands of the pass; a chunk that is neither outside nor inside for some band is decoded ONCE
+ * and tested against those bands only; an inside decision adds the chunk's population without its coordinates.
+ * Scratch: 8 * count bytes, and with the flag on a sorted cloud 32 bytes per 256 points (the selection in resident
+ * order, gathered once per call).
+ * Errors, with counts and stats untouched: no cloud, count outside 1..RTR_MAX_BANDS, bands or counts NULL, a non-finite
+ * value in a band or a = b = c = 0, unknown bits in flags, the flag on a sorted cloud without point_ids ->
+ * RTR_ERR_INVALID; 2^32 points or more -> RTR_ERR_UNSUPPORTED; a failed allocation -> RTR_ERR_HIP.
+ *
+ * rtr_fit_plane.  RANSAC with `iterations` candidates, each the plane through three points of the population, scored by
+ * rtr_count_in_bands.  Every host step is csrc/rtr_plane_fit.h, in fp64 / uint64 with one rounding per operation: a
+ * numpy float64 / uint64 program is an exact reference.
+ *   Sampler: m = the population size (n, or the selected count with RTR_BANDS_SELECTED).  Draw t = 3 c + j (candidate c,
+ *     j = 0..2) is z = seed + (t + 1) * 0x9E3779B97F4A7C15 followed by z ^= z >> 30; z *= 0xBF58476D1CE4E5B9;
+ *     z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (splitmix64, modulo 2^64).  Its rank is z % m, its point the
+ *     rank-th point of the population in upload order (with the flag: the rank-th selected index).  The sample's
+ *     coordinates come through rtr_extract_points' path.
+ *   Candidate, from the fp32 points p0, p1, p2 widened to double: e1 = p1 - p0, e2 = p2 - p0, nv = e1 x e2 with each
+ *     component (f*g) - (h*k), both products rounded on their own; len = sqrt((nx*nx + ny*ny) + nz*nz).  The candidate is
+ *     DEGENERATE if two of its ranks coincide, a sample coordinate is not finite, len is not finite and > 0, or the
+ *     offset below does not fit fp32.  Otherwise A = nv / len per component, negated if needed so that (c, b, a) is
+ *     lexicographically positive (the normal points up in a z-up cloud); D = -((A.x*x0 + A.y*y0) + A.z*z0);
+ *     plane = {(float)A.x, (float)A.y, (float)A.z, (float)D}; its band = {a, b, c, d + dist, dist - d} in fp32 (a band
+ *     with a non-finite bound makes the candidate DEGENERATE too).
+ *   Result: the winner is the non-degenerate candidate with the largest count, ties to the smallest c; plane[4] is its
+ *     plane.  stats (may be NULL): [0] its count, [1] non-degenerate candidates, [2] the winner's c, [3] m.  If every
+ *     candidate is degenerate (m < 3 among other cases) the call returns RTR_OK with plane = {0, 0, 0, 0} and stats[0]
+ *     = [1] = [2] = 0: the facades raise / throw.  There is no least-squares refit.
+ * It changes nothing in the context and neither changes nor creates the selection; ordering as rtr_count_in_bands (it
+ * waits for the sample, then for the counts).  The sample is drawn by upload index, so a cloud sorted by the library
+ * needs option "point_ids" = 1 with or without the flag.
+ * Memory and cost: (n + 31) / 32 words of scratch for the sample's bits (set on the device), one extract of at most
+ * 3 * iterations points, then rtr_count_in_bands over the non-degenerate candidates.  With the flag the selection words
+ * are copied to the host once (the rank-th selected index is found there).
+ * Errors, with plane and stats untouched: those of rtr_count_in_bands (plane NULL in place of bands / counts), dist not
+ * finite or < 0 (dist = 0 is allowed), iterations outside 1..RTR_MAX_BANDS, a sorted cloud without point_ids. */
+#define RTR_MAX_BANDS 4096
+#define RTR_BANDS_SELECTED 1   /* flags: count only the currently selected points */
+int rtr_count_in_bands(rtr_ctx *ctx, uint32_t count, const float *bands /* count x 5, host */, int flags,
+                       uint64_t *counts /* count, host */, uint64_t stats[4]);
+int rtr_fit_plane(rtr_ctx *ctx, float dist, uint32_t iterations, uint64_t seed, int flags, float plane[4],
+                  uint64_t stats[4]);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

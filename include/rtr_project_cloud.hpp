@@ -32,6 +32,7 @@
 // selectVoxelGrid (section 6g) names one vertex per cell of a regular grid; thin removes all the others.
 // selectNeighbours (section 6h) names the vertices with enough others within a radius; removeOutliers removes the rest.
 // selectClusters (section 6i) names them by the size of their connected cluster; growSelection, removeSmallClusters.
+// fitPlane (section 6j) finds the plane with the most vertices within a distance of it; selectPlane, segmentPlane.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
 // writeSelected / writePoints / colorSelected (section 2f) put edited vertices and colours back where they came from:
 // indices, the keep mask and the selection stay.
@@ -408,6 +409,49 @@ public:
         const uint64_t gone = selectClusters(radius, min_points, 0, false, RTR_SELECT_REPLACE, true);
         removeSelected();
         return gone;
+    }
+    // -- the dominant plane (rtr.h section 6j) --
+    struct Plane {
+        float abcd[4];     // unit normal with (c, b, a) lexicographically positive, and the offset
+        uint64_t inliers;  // the vertices of the population within dist of it
+    };
+    // Counts, for each of `count` bands {a, b, c, d_lo, d_hi}, the vertices with u + d_lo >= 0 and -u + d_hi >= 0,
+    // u = (a x + b y) + c z in fp32; selected: among the selected vertices only.  The selection stays as it is.
+    std::vector<uint64_t> countInBands(const float* bands, uint32_t count, bool selected = false, uint64_t stats[4] = nullptr) {
+        std::vector<uint64_t> counts(count);
+        check(ctx_, rtr_count_in_bands(ctx_, count, bands, selected ? RTR_BANDS_SELECTED : 0, counts.data(), stats));
+        return counts;
+    }
+    // RANSAC fit of the plane with the most vertices within `dist`: `iterations` candidates through three sampled
+    // vertices each (seed: the sampler's stream); selected: among the selected vertices only.  The selection stays as
+    // it is.  Throws std::runtime_error when every candidate is degenerate (fewer than three vertices, all samples
+    // collinear or coincident).  stats: rtr_fit_plane's.
+    Plane fitPlane(float dist, uint32_t iterations = 256, uint64_t seed = 0, bool selected = false, uint64_t stats[4] = nullptr) {
+        Plane p{};
+        uint64_t st[4] = {0, 0, 0, 0};
+        check(ctx_, rtr_fit_plane(ctx_, dist, iterations, seed, selected ? RTR_BANDS_SELECTED : 0, p.abcd, st));
+        if (stats) std::memcpy(stats, st, sizeof st);
+        if (st[1] == 0) throw std::runtime_error("rtr: fitPlane: every candidate was degenerate");
+        p.inliers = st[0];
+        return p;
+    }
+    // Selects the vertices within `dist` of `plane` {a, b, c, d}: rtr_select_points with the two planes {a, b, c, d + dist}
+    // and {-a, -b, -c, dist - d} of the fit's band (each sum one fp32 operation), so that with REPLACE the count is
+    // exactly fitPlane's.  Returns the number selected afterwards.
+    uint64_t selectPlane(const float plane[4], float dist, int op = RTR_SELECT_REPLACE, bool outside = false) {
+        volatile float lo = plane[3] + dist, hi = dist - plane[3];  // (volatile: rounded to fp32 whatever the build's flags)
+        const float two[8] = {plane[0], plane[1], plane[2], lo, -plane[0], -plane[1], -plane[2], hi};
+        uint64_t st[4];
+        check(ctx_, rtr_select_points(ctx_, 2, two, nullptr, nullptr, op | (outside ? RTR_SELECT_OUTSIDE : 0), st));
+        return st[0];
+    }
+    // Open3D's segment_plane: fitPlane, then selectPlane of it with REPLACE -- the inliers are the selection.  Peeling a
+    // second plane off the rest: segmentPlane, rtr_select_points with no plane and RTR_SELECT_TOGGLE, then
+    // fitPlane(dist, iterations, seed, true).
+    Plane segmentPlane(float dist, uint32_t iterations = 256, uint64_t seed = 0) {
+        const Plane p = fitPlane(dist, iterations, seed);
+        selectPlane(p.abcd, dist);
+        return p;
     }
     uint64_t selectedCount() {
         if (!has_selection()) return 0;

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include "rtr_kernels.h"
 #include "rtr_extract_index.h"
 #include "rtr_overlap_policy.h"
+#include "rtr_plane_fit.h"
 
 constexpr int kSplitCooldown = 8;  // whole frames keep launching k_tile_split this long after the last report of a tile above the threshold
 
@@ -144,6 +146,7 @@ struct rtr_ctx {
     // everything that renumbers upload indices
     uint32_t *sel = nullptr;
     uint64_t *sel_stats = nullptr;
+    int plane_us[2] = {0, 0};     // the last rtr_fit_plane: sampling + extract, counting (host clock, the waits included)
     int voxel_us[3] = {0, 0, 0};  // the last rtr_select_voxel_grid: its key kernel, sort and head kernel, from their own events
     int neighbours_us[3] = {0, 0, 0};  // the last rtr_select_neighbours: key kernel, sort, gather + work list + count kernel
     int neighbours_tests_k = 0;        // ... and its pair tests in thousands (saturating)
@@ -1130,6 +1133,8 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "clusters_sort_us")) *value = c->clusters_us[1];
     else if (!strcmp(key, "clusters_label_us")) *value = c->clusters_us[2];
     else if (!strcmp(key, "clusters_pair_tests_k")) *value = c->clusters_tests_k;
+    else if (!strcmp(key, "plane_sample_us")) *value = c->plane_us[0];  // the last rtr_fit_plane
+    else if (!strcmp(key, "plane_count_us")) *value = c->plane_us[1];
     else if (!strcmp(key, "point_keep")) *value = c->keep_up ? 1 : 0;  // a keep mask is set (rtr_set_point_keep)  // the resident cloud was sorted by the library
     else if (!strcmp(key, "order_ratio_ppm")) *value = (int)(c->order_ratio * 1e6f);  // chunk / cloud diagonal as uploaded
     else if (!strcmp(key, "cull")) *value = c->opt_cull;
@@ -3496,6 +3501,175 @@ int rtr_select_clusters(rtr_ctx *c, float radius, uint32_t min_points, uint32_t 
         HIP_TRY(c, hipMemcpyAsync(labels, lab, n * 4, labels_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
+    if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- counting points in bands, fitting a plane (rtr.h, section 6j) --------------------
+// Both calls read the coordinates (and, flagged, the selection) and change nothing.  count_bands is the part they share:
+// the counters, the selection in resident order when the cloud is sorted (rtr::launch_sel_gather into scratch, once per
+// call), the passes of rtr::launch_count_bands, one copy and one wait.  Results reach the caller's arrays only on success.
+namespace {
+int check_bands_call(rtr_ctx *c, const char *who, int flags) {
+    char msg[160];
+    if (c->cap == 0) { snprintf(msg, sizeof msg, "%s: no cloud", who); NEED(c, false, msg); }
+    if ((flags & ~RTR_BANDS_SELECTED) != 0) { snprintf(msg, sizeof msg, "%s: unknown bits in flags", who); NEED(c, false, msg); }
+    return RTR_OK;
+}
+// counts[count] and st[4] (host, both written only on success) for `count` valid bands
+int count_bands(rtr_ctx *c, uint32_t count, const float *bands, bool selected, uint64_t *counts, uint64_t st[4]) {
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nch = (n + 255) / 256;
+    std::vector<uint64_t> host(4 + (size_t)count, 0);
+    if (selected && !c->sel) {  // (an empty population: every chunk is outside for every band)
+        host[1] = nch * count;
+    } else {
+        DevBufs buf;
+        uint64_t *dev;
+        const uint32_t *res = nullptr;
+        HIP_TRY(c, buf.get(&dev, host.size() * sizeof(uint64_t)));
+        if (selected && c->reordered) {
+            uint32_t *r;
+            HIP_TRY(c, buf.get(&r, std::max<uint64_t>(nch, 1) * 8 * 4));
+            rtr::launch_sel_gather(s, c->sel, c->perm, n, r);
+            if (int rc = launch_check(c, "bands gather")) return rc;
+            res = r;
+        } else if (selected) {
+            res = c->sel;  // (upload order is the resident order)
+        }
+        HIP_TRY(c, hipMemsetAsync(dev, 0, host.size() * sizeof(uint64_t), s));
+        if (res) {
+            rtr::launch_select_count(s, res, n, dev);
+            if (int rc = launch_check(c, "bands population")) return rc;
+        }
+        rtr::launch_count_bands(s, cloud_of(c), c->bounds, bands, count, res, dev + 4, dev);
+        if (int rc = launch_check(c, "count bands")) return rc;
+        HIP_TRY(c, hipMemcpyAsync(host.data(), dev, host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));  // (always: the counts go to the host, the scratch with this call)
+        if (!res) host[0] = n;
+    }
+    memcpy(counts, host.data() + 4, (size_t)count * sizeof(uint64_t));
+    memcpy(st, host.data(), 4 * sizeof(uint64_t));
+    return RTR_OK;
+}
+}  // namespace
+
+int rtr_count_in_bands(rtr_ctx *c, uint32_t count, const float *bands, int flags, uint64_t *counts, uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    if (int rc = check_bands_call(c, "rtr_count_in_bands", flags)) return rc;
+    NEED(c, count >= 1u && count <= RTR_MAX_BANDS, "rtr_count_in_bands: count outside 1..RTR_MAX_BANDS");
+    NEED(c, bands != nullptr, "rtr_count_in_bands: bands is NULL");
+    NEED(c, counts != nullptr, "rtr_count_in_bands: counts is NULL");
+    for (uint32_t k = 0; k < count; ++k) {
+        const float *b = bands + 5 * (size_t)k;
+        for (int j = 0; j < 5; ++j) NEED(c, std::isfinite(b[j]), "rtr_count_in_bands: a value in bands is not finite");
+        NEED(c, b[0] != 0.f || b[1] != 0.f || b[2] != 0.f, "rtr_count_in_bands: a band of bands has a = b = c = 0");
+    }
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    const bool selected = (flags & RTR_BANDS_SELECTED) != 0;
+    if (selected)
+        if (int rc = need_upload_order(c, "read from the selection", " (flags = RTR_BANDS_SELECTED)")) return rc;
+    DevGuard g(c->device);
+    uint64_t st[4];
+    std::vector<uint64_t> out(count);
+    if (int rc = count_bands(c, count, bands, selected, out.data(), st)) return rc;
+    memcpy(counts, out.data(), (size_t)count * sizeof(uint64_t));
+    if (stats) memcpy(stats, st, sizeof st);
+    return RTR_OK;
+}
+
+// The sample: ranks from rtr_plane_fit.h's sampler, their upload indices (flagged: through the selection words copied to
+// the host and the prefix sums of their popcounts), one bit per distinct index into zeroed device words
+// (rtr::launch_set_bits), and those points through rtr_extract_points -- in ascending index order, so a draw finds its
+// coordinates by binary search among the sorted distinct indices.
+int rtr_fit_plane(rtr_ctx *c, float dist, uint32_t iterations, uint64_t seed, int flags, float plane[4], uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    if (int rc = check_bands_call(c, "rtr_fit_plane", flags)) return rc;
+    NEED(c, std::isfinite(dist) && dist >= 0.f, "rtr_fit_plane: dist must be finite and >= 0");
+    NEED(c, iterations >= 1u && iterations <= RTR_MAX_BANDS, "rtr_fit_plane: iterations outside 1..RTR_MAX_BANDS");
+    NEED(c, plane != nullptr, "rtr_fit_plane: plane is NULL");
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    if (int rc = need_upload_order(c, "sampled")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool selected = (flags & RTR_BANDS_SELECTED) != 0;
+    const uint64_t n = c->n, nw = (n + 31) / 32;
+    uint64_t m = n;
+    std::vector<uint32_t> selw, pre;  // flagged: the selection words and pre[w] = the selected points below word w
+    if (selected) {
+        m = 0;
+        if (c->sel && nw) {
+            selw.resize(nw), pre.resize(nw + 1);
+            HIP_TRY(c, hipMemcpyAsync(selw.data(), c->sel, nw * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+            pre[0] = 0;
+            for (uint64_t w = 0; w < nw; ++w) pre[w + 1] = pre[w] + (uint32_t)__builtin_popcount(selw[w]);
+            m = pre[nw];
+        }
+    }
+    const uint32_t draws = 3u * iterations;
+    std::vector<uint64_t> rank(draws), cnt;
+    std::vector<uint32_t> idx(draws), uniq;
+    std::vector<float> xyz, planes(4 * (size_t)iterations), bands;
+    std::vector<uint32_t> cand;  // the non-degenerate candidates, ascending
+    if (m >= 3) {
+        for (uint32_t t = 0; t < draws; ++t) {
+            rank[t] = rtr::plane_draw(seed, t) % m;
+            uint32_t u = (uint32_t)rank[t];
+            if (selected) {  // the rank-th set bit
+                const uint64_t w = (uint64_t)(std::upper_bound(pre.begin(), pre.end(), (uint32_t)rank[t]) - pre.begin()) - 1;
+                uint32_t bits = selw[w];
+                for (uint32_t k = (uint32_t)rank[t] - pre[w]; k > 0; --k) bits &= bits - 1;
+                u = (uint32_t)(32 * w) + (uint32_t)__builtin_ctz(bits);
+            }
+            idx[t] = u;
+        }
+        uniq = idx;
+        std::sort(uniq.begin(), uniq.end());
+        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+        const uint64_t k = uniq.size();
+        DevBufs buf;  // the sample's bits are set on the device: no word of them crosses the bus
+        uint32_t *dw, *di;
+        HIP_TRY(c, buf.get(&dw, nw * 4));
+        HIP_TRY(c, buf.get(&di, k * 4));
+        HIP_TRY(c, hipMemsetAsync(dw, 0, nw * 4, s));
+        HIP_TRY(c, hipMemcpyAsync(di, uniq.data(), k * 4, hipMemcpyHostToDevice, s));
+        rtr::launch_set_bits(s, di, k, dw);
+        if (int rc = launch_check(c, "sample bits")) return rc;
+        xyz.resize(3 * k);
+        if (int rc = rtr_extract_points(c, dw, nw, 0, k, xyz.data(), 12, nullptr, 0, nullptr, nullptr)) return rc;
+        for (uint32_t q = 0; q < iterations; ++q) {
+            const float *p[3];
+            for (int j = 0; j < 3; ++j)
+                p[j] = xyz.data() + 3 * (size_t)(std::lower_bound(uniq.begin(), uniq.end(), idx[3 * q + j]) - uniq.begin());
+            float band[5];
+            if (!rtr::plane_candidate(p[0], p[1], p[2], &rank[3 * (size_t)q], &planes[4 * (size_t)q])) continue;
+            rtr::plane_band(&planes[4 * (size_t)q], dist, band);
+            if (!std::isfinite(band[3]) || !std::isfinite(band[4])) continue;
+            cand.push_back(q);
+            bands.insert(bands.end(), band, band + 5);
+        }
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    uint64_t out[4] = {0, 0, 0, m};
+    float win[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!cand.empty()) {
+        uint64_t st[4];
+        cnt.resize(cand.size());
+        if (int rc = count_bands(c, (uint32_t)cand.size(), bands.data(), selected, cnt.data(), st)) return rc;
+        size_t best = 0;
+        for (size_t j = 1; j < cand.size(); ++j)
+            if (cnt[j] > cnt[best]) best = j;  // (ties: the smallest c stays)
+        out[0] = cnt[best], out[1] = cand.size(), out[2] = cand[best];
+        memcpy(win, &planes[4 * (size_t)cand[best]], sizeof win);
+    }
+    const auto t2 = std::chrono::steady_clock::now();
+    c->plane_us[0] = (int)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
+    c->plane_us[1] = (int)std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count();
+    memcpy(plane, win, sizeof win);
     if (stats) memcpy(stats, out, sizeof out);
     return RTR_OK;
 }

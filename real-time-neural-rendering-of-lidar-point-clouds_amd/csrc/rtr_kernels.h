@@ -498,4 +498,19 @@ void launch_cluster_hits(hipStream_t s, const uint32_t *vals, uint64_t n, const 
                          const uint32_t *seed, uint32_t min_points, uint32_t max_points, bool seeded, uint32_t *hit, uint32_t *labels,
                          uint64_t *stats);
 
+// rtr_count_in_bands (rtr_planes.hip; rtr.h section 6j).  counts[k] (device, zeroed by the caller) += the points of the
+// population in band k of `bands` (HOST memory, count x {a, b, c, d_lo, d_hi}), kBandPass bands per launch: every chunk is
+// classified on its box against all bands of a pass and decoded at most once per pass.  c / bounds as for launch_select.
+// res: null = every resident point, else the selection in RESIDENT order (8 words per chunk, no bit at or past n).
+// stats (device, zeroed by the caller): [1] / [2] / [3] += (chunk, band) pairs decided outside / inside on the box / tested
+// point by point.
+// res (8 words per 256-point chunk, every word written) = the upload-order words `up` (read only; bits at or past n
+// ignored) in RESIDENT order through perm (resident index -> upload index)
+void launch_sel_gather(hipStream_t s, const uint32_t *up, const uint32_t *perm, uint64_t n, uint32_t *res);
+// words (device, (n + 31) / 32, zeroed by the caller) |= the bit of every idx[0 .. count) (device; each below n)
+void launch_set_bits(hipStream_t s, const uint32_t *idx, uint64_t count, uint32_t *words);
+constexpr int kBandPass = 64;  // (a lane's band mask is one 64-bit word, the not-packed path's one ballot)
+void launch_count_bands(hipStream_t s, const Cloud &c, const float *bounds, const float *bands, uint32_t count, const uint32_t *res,
+                        uint64_t *counts, uint64_t *stats);
+
 }  // namespace rtr

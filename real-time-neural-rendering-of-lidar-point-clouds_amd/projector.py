@@ -411,6 +411,61 @@ class Projector:
             return (st, lab) if stats else lab
         return st
 
+    # -- bands and the dominant plane (rtr.h section 6j)
+    def count_in_bands(self, bands, selected=False, stats=True):
+        """Counts on the device, for each band {a, b, c, d_lo, d_hi} of `bands` ((k, 5), 1 <= k <= MAX_BANDS), the points
+        with u + d_lo >= 0 and -u + d_hi >= 0, u = (a*x + b*y) + c*z in float32 (include/rtr.h section 6j) -- the two
+        planes {a, b, c, d_lo} and {-a, -b, -c, d_hi} of select_points, without touching the selection.  selected: only
+        the currently selected points are counted (none without a selection).  The call always waits.  Returns a uint64
+        array of k counts, or with stats (counts, (population size, (chunk, band) pairs decided outside on the chunk's
+        box, pairs decided inside, pairs tested point by point))."""
+        with np.errstate(over="ignore"):
+            b = np.ascontiguousarray(bands, dtype=np.float32)
+        if b.ndim != 2 or b.shape[1] != 5:
+            raise ValueError("bands must have shape (k, 5)")
+        if not 1 <= b.shape[0] <= L.MAX_BANDS:
+            raise ValueError("bands must hold 1 .. %d bands" % L.MAX_BANDS)
+        if not np.isfinite(b).all():
+            raise ValueError("bands must be finite")
+        if (b[:, :3] == 0).all(axis=1).any():
+            raise ValueError("a band of bands has a = b = c = 0")
+        counts = np.zeros(b.shape[0], np.uint64)
+        out = np.zeros(4, np.uint64) if stats else None
+        self._chk(self._lib.rtr_count_in_bands(self._ctx, b.shape[0], _vp(b), L.BANDS_SELECTED if selected else 0, _vp(counts),
+                                               _vp(out)))
+        return (counts, tuple(int(v) for v in out)) if stats else counts
+
+    def fit_plane(self, dist, iterations=256, seed=0, selected=False):
+        """Fits the dominant plane of the resident cloud by RANSAC on the device (include/rtr.h section 6j): `iterations`
+        candidates through three sampled points each, scored by the points within `dist` (count_in_bands).  seed: the
+        sampler's stream, any integer modulo 2^64.  selected: sample and count only the currently selected points.
+        Neither changes the selection.  Returns (plane, inliers, stats): plane = float32 (a, b, c, d) with a unit normal
+        whose (c, b, a) is lexicographically positive, inliers = its count, stats = (inliers, non-degenerate candidates,
+        the winner's candidate number, population size).  Raises RuntimeError when every candidate is degenerate (fewer
+        than three points, all samples collinear or coincident)."""
+        with np.errstate(over="ignore"):
+            d = float(np.float32(dist))  # (as the library takes it)
+        if not (np.isfinite(d) and d >= 0):
+            raise ValueError("dist must be finite and >= 0 in float32")
+        it = int(iterations)
+        if not 1 <= it <= L.MAX_BANDS:
+            raise ValueError("iterations must be in 1 .. %d" % L.MAX_BANDS)
+        plane = np.zeros(4, np.float32)
+        out = np.zeros(4, np.uint64)
+        self._chk(self._lib.rtr_fit_plane(self._ctx, d, it, int(seed) & 0xFFFFFFFFFFFFFFFF, L.BANDS_SELECTED if selected else 0,
+                                          _vp(plane), _vp(out)))
+        st = tuple(int(v) for v in out)
+        if st[1] == 0:
+            raise RuntimeError("fit_plane: every candidate was degenerate (population of %d points)" % st[3])
+        return plane, st[0], st
+
+    @staticmethod
+    def plane_band(plane, dist):
+        """The band {a, b, c, d + dist, dist - d} of fit_plane's plane, in float32 as the library forms it."""
+        p = np.asarray(plane, dtype=np.float32).reshape(4)
+        d = np.float32(dist)
+        return np.array([p[0], p[1], p[2], p[3] + d, d - p[3]], dtype=np.float32)
+
     def selection(self):
         """The selection as a DeviceBuffer of upload-order words (pass it to remove_points, transform_points,
         set_point_keep or torch.as_tensor), or None when there is none."""
@@ -918,6 +973,37 @@ class ProjectCloud:
         gone = self._p.select_clusters(radius, min_points, outside=True)[0]
         self.removeSelected()
         return gone
+
+    # -- the dominant plane (rtr.h section 6j)
+    def fitPlane(self, dist, iterations=256, seed=0, selected=False):
+        """RANSAC fit of the plane with the most vertices within `dist` (see Projector.fit_plane).  Returns
+        (plane, inliers): float32 (a, b, c, d), unit normal pointing up, and the number of vertices within dist of it.
+        selected: among the selected vertices only.  The selection stays as it is."""
+        plane, inliers, _ = self._p.fit_plane(dist, iterations, seed, selected)
+        return plane, inliers
+
+    def countInBands(self, bands, selected=False):
+        """The number of vertices in each band {a, b, c, d_lo, d_hi} of `bands` ((k, 5); see Projector.count_in_bands), as a
+        uint64 array; selected: among the selected vertices only.  The selection stays as it is."""
+        return self._p.count_in_bands(bands, selected, stats=False)
+
+    def selectPlane(self, plane, dist, op="replace", outside=False):
+        """Selects the vertices within `dist` of `plane` -- select_points with the two planes {a, b, c, d + dist} and
+        {-a, -b, -c, dist - d} of the fit's band, so that with op "replace" the count is exactly fitPlane's -- and combines
+        them with the selection so far by op; outside: every other vertex.  Returns the number selected afterwards."""
+        b = Projector.plane_band(plane, dist)
+        planes = np.array([[b[0], b[1], b[2], b[3]], [-b[0], -b[1], -b[2], b[4]]], dtype=np.float32)
+        return self._p.select_points(planes=planes, op=op, outside=outside)[0]
+
+    def segmentPlane(self, dist, iterations=256, seed=0):
+        """Open3D's segment_plane: fitPlane, then selectPlane of it with "replace".  Returns (plane, inliers); the
+        inliers are the selection.  Peeling a second plane off the rest:
+            ground, _ = cloud.segmentPlane(0.03)
+            cloud.selectPlanes(None, op="toggle")            # everything but the ground
+            wall, _ = cloud.fitPlane(0.03, selected=True)"""
+        plane, inliers = self.fitPlane(dist, iterations, seed)
+        self.selectPlane(plane, dist)
+        return plane, inliers
 
     def selectedCount(self):
         """The number of selected vertices (0 without a selection)."""
