@@ -212,6 +212,11 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          rtr_select_clusters (section 6i): its key kernel, its sort (with the wait for the key kernel's counters), and
  *          its gather, work-list, union-find, flatten and hit kernels together; "clusters_pair_tests_k" reads that call's
  *          pair tests, in thousands (saturating at 2^31 - 1).
+ *  rtr_get_option("near_given_us" / "near_sweep_us") read the device time, in microseconds, that the last rtr_select_near
+ *          (section 6k) spent on the given points (their copy, key kernel, sort and gather) and on the resident sweep with
+ *          the combine and the counts; "near_pair_tests_k" reads that call's pair tests, in thousands, and
+ *          "near_chunks_skipped" / "near_chunks_decoded" its resident chunks decided without reading their coordinates /
+ *          decoded (all three saturating at 2^31 - 1).
  *  rtr_get_option("plane_sample_us" / "plane_count_us") read the host time, in microseconds and with its waits, that the
  *          last rtr_fit_plane (section 6j) spent drawing and extracting its sample and counting its candidates. */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
@@ -973,6 +978,80 @@ int rtr_count_in_bands(rtr_ctx *ctx, uint32_t count, const float *bands /* count
                        uint64_t *counts /* count, host */, uint64_t stats[4]);
 int rtr_fit_plane(rtr_ctx *ctx, float dist, uint32_t iterations, uint64_t seed, int flags, float plane[4],
                   uint64_t stats[4]);
+
+/* ---- 6k. selection by distance to given points: what a new scan touches ------------------------------------------------
+ * rtr_select_near relates the resident cloud to ANOTHER set of points: it names the resident points that have a given
+ * point within `radius` and, in near_words, the given points that have a resident point within it -- merging a scan
+ * without piling up duplicates ("append only the returns with no resident point within 2 cm"), change detection in
+ * both directions, brush and trajectory selection.  It writes into RTR_BUF_SELECTION exactly as rtr_select_points does
+ * -- the same buffer, the same life, the same five op values with RTR_SELECT_OUTSIDE OR-ed in, bits past n clear, a
+ * selection that does not exist yet counts as empty and is created -- so the words feed rtr_remove_points,
+ * rtr_set_point_keep, rtr_transform_points, rtr_extract_points and rtr_write_points as they are.
+ * Given points: `count` points at xyz + j * xyz_stride_bytes, three floats each; strides as rtr_upload_points takes them
+ * (12 for tight points, 16 for float4).  The memory is host memory or device memory of the context's device, told
+ * apart as rtr_extract_points tells its outputs apart.  The call copies or reads the given points before it returns.
+ * count == 0 is legal: xyz may then be NULL and nothing is near anything.
+ * Relation: exactly section 6h's, between a resident point i and a given point j.  r2 = radius * radius, rounded once
+ * to fp32 on the host.  The pair is NEAR iff ((dx*dx + dy*dy) + dz*dz) <= r2 with dx = x[i] - gx[j], dy = y[i] - gy[j],
+ * dz = z[i] - gz[j], every difference, product and sum rounded to fp32 on its own (no FMA): numpy float32 in that order
+ * is a bit-for-bit reference, nothing has a tolerance.  The comparison is inclusive.  The direction of the subtraction
+ * does not matter: negation is exact and the squares are equal.  There is no self-exclusion: the two sets are distinct,
+ * and a given point coincident with a resident one is near it.  A non-finite point on either side is near nothing.
+ * Resident side: hit(i) holds iff resident point i is near at least one given point.  With RTR_SELECT_OUTSIDE hit = !hit
+ * for the points below n.  op combines the hits with the selection so far as in section 6f.
+ * Given side: near_words may be NULL.  Otherwise (count + 31) / 32 words, in host or device memory: bit j % 32 of word
+ * j / 32 set iff given point j is near at least one resident point -- EVERY resident point counts: the keep mask, the
+ * clip planes and the selection are ignored.  Bits past count are clear.  The words are written only when the call
+ * succeeds.
+ * RTR_NEAR_GIVEN_ONLY: only near_words and stats[2..3]; the selection is neither read, changed nor created.  op must be
+ * 0 and near_words must not be NULL.  ("Append only what is new": a scan that adds nothing leaves the selection alone.)
+ * Independence: the results depend on the coordinates and on the upload and given indices alone -- not on the resident
+ * order, the library's sort, the packed form, any option, the internal grid or the order of the given points.
+ * The internal grid and its SPAN: section 6h's grid (csrc/rtr_neighbour_cell.h).  Only the GIVEN points must lie inside
+ * the span, every given point within +-2^20 * radius of the world origin does; a finite given coordinate beyond it ->
+ * RTR_ERR_UNSUPPORTED before anything changes.  RESIDENT points may lie anywhere -- unlike section 6h, because chunks
+ * rejected on their boxes are never looked at --: a resident point is tested exactly wherever it is; one whose cell on
+ * some axis lies more than one cell beyond the span is near no given point, and one a single cell beyond the span can
+ * be near a given point in the last cell, and then hits.
+ * stats (may be NULL): [0] the points selected after op, [1] the resident points with hit (before OUTSIDE and op),
+ * [2] the given points whose near bit is set (0 when near_words is NULL), [3] the non-finite given points.  With
+ * RTR_NEAR_GIVEN_ONLY [0] = [1] = 0.  All four are exact and independent of the form of the cloud.
+ * What it reads and leaves alone: section 6f's list.  The call reads the uploaded coordinates only; the context's clip
+ * planes and keep mask are ignored.  It changes no frame, frame buffer, tile store, pool, statistics, point-pass buffer
+ * or keep mask, and an open peer-to-peer exchange stays open.  Indices are the point pass's; a cloud sorted by the
+ * library needs option "point_ids" = 1 -- but not with RTR_NEAR_GIVEN_ONLY, which needs no upload index: near bits go by
+ * given index.  A sharded context works on its own points.
+ * Ordering: as section 6h.  Queued on the context's stream behind everything issued before it; the call ALWAYS waits
+ * for its own work before it returns, stats or not: it frees its scratch (and it waits once on the way, for the given
+ * points' counters and bounding box).  It does not repeat frames whose extent pool overflowed.
+ * Memory and cost: set by the GIVEN points.  They are keyed, sorted (a stable radix sort of count (64-bit key, 32-bit
+ * index) pairs) and gathered into 16-byte records in cell order; the resident cloud is neither sorted nor gathered.
+ * Scratch for the duration of the call: 56 B per GIVEN point (the pairs and the records, twice each), the sort's
+ * temporary, a copy of a host array at its stride, plus (n + 31) / 32 hit words, plus (count + 31) / 32 near words
+ * (rounded up to 8 per 256): nothing is proportional to n beyond the hit words.  One sweep over the resident chunks: a
+ * chunk of 256 points whose box, grown by a cell, does not meet the given points' bounding box, or whose cells have no
+ * given point in or next to them (up to 64 cell columns looked up in the sorted keys), is decided on its header and
+ * never decoded; the work is proportional to the chunks near a given point and to the candidate pairs tested.  A
+ * decoded chunk is tested against the given points of the cells around its box, 64 at a time, leaving out the cells
+ * that lie more than one cell from all four points of every lane (up to 4096 cell columns).  Without near_words a
+ * wave stops testing a chunk once all its points hit; with near_words every candidate pair is tested, because the given
+ * side needs them.  A pile of m coincident given points next to a chunk costs O(256 m) pair tests, a pile on both sides
+ * O(pile x candidates), as in section 6h; so does a radius far larger than the point spacing.  Chunks without a box (a
+ * non-finite coordinate among their points, or -- packed -- mixed signs on more than one axis without a box word) and
+ * chunks whose box covers more than 4096 cell columns take a slower per-point path.
+ * Option keys, read by rtr_get_option after a call: "near_given_us" (key, sort and gather of the given points),
+ * "near_sweep_us" (the resident sweep, combine and count), "near_pair_tests_k" (pair tests in thousands),
+ * "near_chunks_skipped" (chunks decided without reading their coordinates) and "near_chunks_decoded";
+ * near_chunks_skipped + near_chunks_decoded = (n + 255) / 256.
+ * Errors, with nothing changed (the selection, the option "selection", near_words and stats): no cloud, a radius that
+ * is not finite and > 0, an r2 that is not a finite normal fp32 number, xyz NULL with count > 0, a stride below 12 or
+ * not a multiple of 4, unknown bits in flags, an unknown op, RTR_NEAR_GIVEN_ONLY with op != 0 or near_words NULL, a
+ * sorted cloud without point_ids (unless RTR_NEAR_GIVEN_ONLY) -> RTR_ERR_INVALID; n or count >= 2^32, or a finite given
+ * point beyond the span -> RTR_ERR_UNSUPPORTED; a failed allocation -> RTR_ERR_HIP.  Every scratch buffer is allocated,
+ * and every check that can fail is made, before the first selection word changes. */
+#define RTR_NEAR_GIVEN_ONLY 1   /* flags: only near_words and stats[2..3]; the selection is neither read, changed nor created */
+int rtr_select_near(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, uint64_t count, float radius,
+                    int flags, int op, uint32_t *near_words, uint64_t stats[4]);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

@@ -32,6 +32,8 @@
 // selectVoxelGrid (section 6g) names one vertex per cell of a regular grid; thin removes all the others.
 // selectNeighbours (section 6h) names the vertices with enough others within a radius; removeOutliers removes the rest.
 // selectClusters (section 6i) names them by the size of their connected cluster; growSelection, removeSmallClusters.
+// selectNear (section 6k) names the vertices within a radius of GIVEN points, and the given points near a vertex.
+// appendNewPoints appends only the given points with no vertex within a radius: a scan merged without duplicates.
 // fitPlane (section 6j) finds the plane with the most vertices within a distance of it; selectPlane, segmentPlane.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
 // writeSelected / writePoints / colorSelected (section 2f) put edited vertices and colours back where they came from:
@@ -403,6 +405,36 @@ public:
     }
     // Grows the selection to every vertex connected to it by steps of at most `radius`.  Returns the number selected.
     uint64_t growSelection(float radius) { return selectClusters(radius, 1, 0, true); }
+    // Distance to given points (rtr.h section 6k): selects the vertices that have one of the m given points (host memory,
+    // strides as appendPoints takes them) within `radius` (outside: every vertex but those).  near_words: resized to
+    // (m + 31) / 32 words, bit j set = given point j has a vertex within radius.  Returns the number selected afterwards.
+    uint64_t selectNear(const float* xyz, size_t xyz_stride_bytes, size_t m, float radius, int op = RTR_SELECT_REPLACE,
+                        bool outside = false, std::vector<uint32_t>* near_words = nullptr) {
+        uint64_t st[4];
+        if (near_words) near_words->assign((m + 31) / 32, 0u);
+        check(ctx_, rtr_select_near(ctx_, xyz, xyz_stride_bytes, m, radius, 0, op | (outside ? RTR_SELECT_OUTSIDE : 0),
+                                    near_words ? near_words->data() : nullptr, st));
+        return st[0];
+    }
+    // Appends of the m given points exactly those with no vertex within `radius`, in their order (the selection stays as
+    // it is).  A scan is not thinned against itself: thin it first, or the cloud afterwards (selectVoxelGrid, thin).
+    // Returns the number appended.
+    size_t appendNewPoints(const float* xyz, size_t xyz_stride_bytes, const uint8_t* rgb, size_t rgb_stride_bytes, size_t m,
+                           float radius) {
+        std::vector<uint32_t> near((m + 31) / 32 + 1, 0u);
+        check(ctx_, rtr_select_near(ctx_, xyz, xyz_stride_bytes, m, radius, RTR_NEAR_GIVEN_ONLY, 0, near.data(), nullptr));
+        std::vector<float> v;
+        std::vector<uint8_t> c;
+        for (size_t j = 0; j < m; ++j) {
+            if ((near[j / 32] >> (j % 32)) & 1u) continue;
+            const float* p = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(xyz) + j * xyz_stride_bytes);
+            const uint8_t* q = rgb + j * rgb_stride_bytes;
+            v.insert(v.end(), p, p + 3);
+            c.insert(c.end(), q, q + 3);
+        }
+        if (!c.empty()) appendPoints(v.data(), 12, c.data(), 3, c.size() / 3);
+        return c.size() / 3;
+    }
     // Takes the clusters of fewer than min_points vertices within `radius` out of the resident cloud for good: their
     // vertices are selected (replacing the selection) and removed.  Returns the number removed.
     uint64_t removeSmallClusters(float radius, uint32_t min_points) {

@@ -150,6 +150,9 @@ struct rtr_ctx {
     int voxel_us[3] = {0, 0, 0};  // the last rtr_select_voxel_grid: its key kernel, sort and head kernel, from their own events
     int neighbours_us[3] = {0, 0, 0};  // the last rtr_select_neighbours: key kernel, sort, gather + work list + count kernel
     int neighbours_tests_k = 0;        // ... and its pair tests in thousands (saturating)
+    int near_us[2] = {0, 0};           // the last rtr_select_near: the given points' keys, sort and gather; the sweep, combine and counts
+    int near_tests_k = 0;              // ... its pair tests in thousands (saturating)
+    int near_chunks[2] = {0, 0};       // ... and its resident chunks decided without their coordinates / decoded (saturating)
     int clusters_us[3] = {0, 0, 0};    // the last rtr_select_clusters: key kernel, sort, gather + work list + union-find + hits
     int clusters_tests_k = 0;          // ... and its pair tests in thousands (saturating)
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
@@ -1129,6 +1132,11 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "neighbours_sort_us")) *value = c->neighbours_us[1];
     else if (!strcmp(key, "neighbours_count_us")) *value = c->neighbours_us[2];
     else if (!strcmp(key, "neighbours_pair_tests_k")) *value = c->neighbours_tests_k;
+    else if (!strcmp(key, "near_given_us")) *value = c->near_us[0];  // the last rtr_select_near
+    else if (!strcmp(key, "near_sweep_us")) *value = c->near_us[1];
+    else if (!strcmp(key, "near_pair_tests_k")) *value = c->near_tests_k;
+    else if (!strcmp(key, "near_chunks_skipped")) *value = c->near_chunks[0];
+    else if (!strcmp(key, "near_chunks_decoded")) *value = c->near_chunks[1];
     else if (!strcmp(key, "clusters_keys_us")) *value = c->clusters_us[0];  // the last rtr_select_clusters
     else if (!strcmp(key, "clusters_sort_us")) *value = c->clusters_us[1];
     else if (!strcmp(key, "clusters_label_us")) *value = c->clusters_us[2];
@@ -3499,6 +3507,134 @@ int rtr_select_clusters(rtr_ctx *c, float radius, uint32_t min_points, uint32_t 
     if (int rc = neighbour_finish(c, "cluster combine", q, op, out, c->clusters_us, &c->clusters_tests_k)) return rc;
     if (lab) {  // (behind everything that can fail: the caller's array changes only when the call succeeds)
         HIP_TRY(c, hipMemcpyAsync(labels, lab, n * 4, labels_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- selection by distance to given points (rtr.h, section 6k) ------------------------
+// The given points go through section 6h's key, sort and gather (rtr_near.hip's k_near_keys over the plain strided
+// array); the resident side is ONE sweep over the chunks that sorts and gathers nothing.  One wait on the way, for the
+// given points' counters and box: a point beyond the span fails the call there, before anything has changed.  Every
+// allocation lies before it too; a selection that does not exist yet is only created once nothing can fail any more but
+// a launch; the caller's near words and stats are written last.
+int rtr_select_near(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, float radius, int flags, int op, uint32_t *near_words,
+                    uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_select_near: no cloud");
+    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_select_near: radius must be finite and > 0");
+    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
+    NEED(c, std::isnormal(r2), "rtr_select_near: the square of radius is not a finite normal fp32 number");
+    NEED(c, count == 0 || xyz != nullptr, "rtr_select_near: xyz is NULL");
+    NEED(c, xs >= 12 && xs % 4 == 0, "rtr_select_near: xyz_stride_bytes must be >= 12 and a multiple of 4");
+    NEED(c, (flags & ~RTR_NEAR_GIVEN_ONLY) == 0, "rtr_select_near: unknown bits in flags");
+    const bool given_only = (flags & RTR_NEAR_GIVEN_ONLY) != 0;
+    const int base = op & ~RTR_SELECT_OUTSIDE;
+    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_near: unknown op");
+    NEED(c, !given_only || op == 0, "rtr_select_near: op must be 0 with RTR_NEAR_GIVEN_ONLY");
+    NEED(c, !given_only || near_words != nullptr, "rtr_select_near: near_words is NULL with RTR_NEAR_GIVEN_ONLY");
+    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    if (count >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "rtr_select_near: given indices are 32-bit: count is %llu", (unsigned long long)count);
+    if (!given_only)  // (the near bits go by GIVEN index: they need no upload order)
+        if (int rc = need_upload_order(c, "formed", ", or ask for the given side alone (flags = RTR_NEAR_GIVEN_ONLY)")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nw = (n + 31) / 32, gw = (count + 31) / 32;
+    const uint64_t words = std::max<uint64_t>((n + 255) / 256, 1) * 8;   // (the selection: 8 per 256-point chunk)
+    const uint64_t gwords = std::max<uint64_t>((count + 255) / 256, 1) * 8;  // (the near words, padded for launch_select_count)
+    const bool xyz_dev = count && on_device(xyz), near_dev = near_words && on_device(near_words);
+    // every allocation first: a failure leaves everything as it was
+    DevBufs buf;
+    EventSet ev;
+    uint64_t *k0, *k1, *cn, *st = nullptr;  // cn: [0] non-finite given points, [1] those beyond the span, [2] near bits, [4 .. 7] the sweep's, [8 .. 10] the box
+    uint32_t *v0, *v1, *hit = nullptr, *nearw = nullptr, *w = nullptr;
+    float4 *rec0, *rec1;
+    const uint8_t *gxyz = (const uint8_t *)xyz;
+    uint8_t *stage = nullptr;
+    void *tmp;
+    size_t tmp_bytes = 0;
+    const size_t gbytes = count ? (size_t)(count - 1) * xs + 12 : 0;
+    HIP_TRY(c, (hipError_t)rtr::voxel_sort_temp_bytes(std::max<uint64_t>(count, 1), &tmp_bytes));
+    HIP_TRY(c, buf.get(&k0, count * 8));
+    HIP_TRY(c, buf.get(&k1, count * 8));
+    HIP_TRY(c, buf.get(&v0, count * 4));
+    HIP_TRY(c, buf.get(&v1, count * 4));
+    HIP_TRY(c, buf.get(&rec0, count * 16));
+    HIP_TRY(c, buf.get(&rec1, count * 16));
+    HIP_TRY(c, buf.get(&cn, 12 * sizeof(uint64_t)));
+    HIP_TRY(c, buf.get(&tmp, tmp_bytes));
+    if (count && !xyz_dev) HIP_TRY(c, buf.get(&stage, gbytes));
+    if (!given_only) HIP_TRY(c, buf.get(&hit, nw * 4));
+    if (near_words) HIP_TRY(c, buf.get(&nearw, gwords * 4));
+    if (!given_only && !c->sel) {
+        HIP_TRY(c, buf.get(&w, words * 4));
+        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
+    }
+    for (int k = 0; k < 3; ++k) HIP_TRY(c, hipEventCreate(&ev.e[k]));
+    HIP_TRY(c, hipMemsetAsync(cn, 0, 12 * sizeof(uint64_t), s));
+    HIP_TRY(c, hipMemsetAsync(cn + 8, 0xFF, 3 * sizeof(uint32_t), s));  // (box: the minima start at 2^32 - 1, the maxima at 0)
+    if (hit) HIP_TRY(c, hipMemsetAsync(hit, 0, nw * 4, s));
+    if (nearw) HIP_TRY(c, hipMemsetAsync(nearw, 0, gwords * 4, s));
+    HIP_TRY(c, hipEventRecord(ev.e[0], s));
+    if (stage) {  // (the given points are read before the call returns: one copy at the caller's stride)
+        HIP_TRY(c, hipMemcpyAsync(stage, xyz, gbytes, hipMemcpyHostToDevice, s));
+        gxyz = stage;
+    }
+    rtr::launch_near_keys(s, gxyz, xs, count, radius, k0, v0, rec0, cn, reinterpret_cast<uint32_t *>(cn + 8));
+    if (int rc = launch_check(c, "near keys")) return rc;
+    uint64_t host[12] = {};
+    HIP_TRY(c, hipMemcpyAsync(host, cn, sizeof host, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (host[1])
+        return fail(c, RTR_ERR_UNSUPPORTED, "rtr_select_near: %llu finite given points lie beyond the span of the internal grid (about "
+                    "2^20 radius from the world origin on an axis)", (unsigned long long)host[1]);
+    const uint64_t nonfinite = host[0], m = count - nonfinite;  // (the pairs with a cell sort to the front)
+    if (count) HIP_TRY(c, (hipError_t)rtr::voxel_sort(s, tmp, tmp_bytes, k0, k1, v0, v1, count));
+    rtr::launch_neighbour_gather(s, v1, rec0, m, rec1);
+    if (int rc = launch_check(c, "near gather")) return rc;
+    HIP_TRY(c, hipEventRecord(ev.e[1], s));
+    if (w) {  // (a selection that does not exist yet is empty)
+        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
+        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
+    }
+    if (!given_only) HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
+    uint64_t sweep[4] = {0, 0, (n + 255) / 256, 0};  // (no given point has a cell: every chunk is decided without a launch)
+    if (m) {
+        double glo[3], ghi[3];
+        uint32_t box[6];
+        memcpy(box, host + 8, sizeof box);
+        rtr::near_box_from_keys(box, glo, ghi);
+        rtr::launch_near_sweep(s, cloud_of(c), c->bounds, c->reordered ? c->perm : nullptr, k1, rec1, m, radius, r2, glo, ghi, hit, nearw, cn + 4);
+        if (int rc = launch_check(c, "near sweep")) return rc;
+    }
+    uint64_t out[4] = {0, 0, 0, nonfinite};
+    if (!given_only) {
+        rtr::launch_voxel_combine(s, hit, n, base, (op & RTR_SELECT_OUTSIDE) != 0, c->sel);
+        if (int rc = launch_check(c, "near combine")) return rc;
+        rtr::launch_select_count(s, c->sel, n, c->sel_stats);
+        if (int rc = launch_check(c, "select count")) return rc;
+        HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    }
+    if (nearw && count) {
+        rtr::launch_select_count(s, nearw, count, cn + 2);
+        if (int rc = launch_check(c, "near count")) return rc;
+        HIP_TRY(c, hipMemcpyAsync(out + 2, cn + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipEventRecord(ev.e[2], s));
+    if (m) HIP_TRY(c, hipMemcpyAsync(sweep, cn + 4, sizeof sweep, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
+    out[1] = sweep[0];
+    for (int k = 0; k < 2; ++k) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+        c->near_us[k] = (int)(ms * 1000.f + 0.5f);
+    }
+    c->near_tests_k = (int)std::min<uint64_t>(sweep[1] / 1000, 0x7FFFFFFF);
+    c->near_chunks[0] = (int)std::min<uint64_t>(sweep[2], 0x7FFFFFFF), c->near_chunks[1] = (int)std::min<uint64_t>(sweep[3], 0x7FFFFFFF);
+    if (near_words && gw) {  // (behind everything that can fail: the caller's words change only when the call succeeds)
+        HIP_TRY(c, hipMemcpyAsync(near_words, nearw, gw * 4, near_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
     if (stats) memcpy(stats, out, sizeof out);

@@ -498,6 +498,26 @@ void launch_cluster_hits(hipStream_t s, const uint32_t *vals, uint64_t n, const 
                          const uint32_t *seed, uint32_t min_points, uint32_t max_points, bool seeded, uint32_t *hit, uint32_t *labels,
                          uint64_t *stats);
 
+// rtr_select_near (rtr_near.hip; rtr.h section 6k; the cell arithmetic is rtr_neighbour_cell.h's, the sort rtr_voxel.hip's,
+// the gather rtr_neighbours.hip's).
+// near_keys: the `count` (< 2^32) given points at xyz + j * stride (DEVICE memory, stride a multiple of 4): keys[j] / vals[j] =
+// the cell key in the internal grid of `radius` (kNbOut | j without a cell) / j, rec[j] = (x, y, z, bits of j); counters
+// (device, zeroed by the caller) [0] / [1] += points that are not finite / finite but beyond the span; box (device, preset
+// to three words of 2^32 - 1 and three of 0) = the float_order_key of the smallest / largest x, y, z among the points
+// with a cell
+void launch_near_keys(hipStream_t s, const uint8_t *xyz, uint64_t stride, uint64_t count, float radius, uint64_t *keys, uint32_t *vals,
+                      float4 *rec, uint64_t *counters, uint32_t *box);
+// that box on the host (only when some point has a cell)
+void near_box_from_keys(const uint32_t box[6], double lo[3], double hi[3]);
+// near_sweep: keys / rec = the m sorted given points with a cell, glo / ghi their box.  hit (upload order, (n + 31) / 32
+// words, zeroed by the caller; null: not asked for) gets the bit of every resident point at ((dx dx + dy dy) + dz dz) <=
+// r2 from a given point, near (zeroed; null: not asked for) the bit rec.w of every given point at that distance from a
+// resident one.  c / bounds as for launch_select, perm as for the point pass.  counters (device, zeroed) [0] += resident
+// points that hit, [1] += pair tests, [2] / [3] += chunks decided without their coordinates / decoded
+void launch_near_sweep(hipStream_t s, const Cloud &c, const float *bounds, const uint32_t *perm, const uint64_t *keys, const float4 *rec,
+                       uint64_t m, float radius, float r2, const double glo[3], const double ghi[3], uint32_t *hit, uint32_t *near,
+                       uint64_t *counters);
+
 // rtr_count_in_bands (rtr_planes.hip; rtr.h section 6j).  counts[k] (device, zeroed by the caller) += the points of the
 // population in band k of `bands` (HOST memory, count x {a, b, c, d_lo, d_hi}), kBandPass bands per launch: every chunk is
 // classified on its box against all bands of a pass and decoded at most once per pass.  c / bounds as for launch_select.

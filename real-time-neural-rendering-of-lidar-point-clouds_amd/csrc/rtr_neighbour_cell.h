@@ -12,6 +12,14 @@
 // span, so the two computed quotients differ by less than 1 - 2^-11 + 2^-32 < 1, and the floors of two numbers less
 // than 1 apart differ by at most 1.  The same holds for y and z.  (The 6g arithmetic, t = fl32(fl32(p - origin) inv), is
 // off by up to 2^20 2^-23 cells and more near the end of the span: not safe here.)
+//
+// Across the span's edge (rtr_select_near, section 6k: only the GIVEN point of a pair must have a cell).  The argument
+// above asks nothing of the span but the size of the quotients: a resident point near a given one has |t| <= 2^20 + 1, so
+// the division still moves it by at most 2^-53 |t| < 2^-32, far below the 2^-11 margin, and its floor -- taken without the
+// span check -- differs from the given point's cell by at most 1.  A resident point whose floor lies more than one cell
+// beyond the span is therefore near no given point, and the cells to look at around any other are q - 1 .. q + 1 cut to
+// kNbCellMin .. kNbCellMax BY CELL INDEX: neighbour_key_offset must not be used there, a key field has no room for
+// a cell beyond the span.
 #pragma once
 #include <stdint.h>
 

@@ -411,6 +411,43 @@ class Projector:
             return (st, lab) if stats else lab
         return st
 
+    def select_near(self, xyz, radius, op="replace", outside=False, near=False, given_only=False, stats=True):
+        """Selects on the device the resident points that have one of the GIVEN points `xyz` within `radius` (include/rtr.h
+        section 6k) and combines the hits with the selection so far, as select_points does.  xyz: float32 rows, (m, 3) or
+        (m, 4) -- a numpy array, a torch tensor (host or device) or an object with __cuda_array_interface__, as
+        write_points takes them; m = 0 is legal.  Near: ((dx*dx + dy*dy) + dz*dz) <= radius*radius in float32, inclusive,
+        select_neighbours' relation between a resident and a given point; a non-finite point on either side is near
+        nothing.  outside: the resident points near no given point instead.  near: also a bool array of m, True where
+        the given point has a resident point within radius (every resident point counts).  given_only: only that
+        array, the selection is neither read nor changed (op must be "replace", outside False).  The call always waits.
+        stats: (selected points after op, resident points with a given point within radius, given points with a
+        resident one within radius -- 0 without near --, non-finite given points).  Returns the stats, (stats, near
+        array) with near or given_only, the array alone with stats=False, or None with neither."""
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        code = self._SELECT_OPS[op] if isinstance(op, str) else int(op)
+        if outside:
+            code |= L.SELECT_OUTSIDE
+        if given_only and code != 0:
+            raise ValueError("given_only leaves the selection alone: op must be 'replace' and outside False")
+        ptr, stride, m, hold = self._write_source(xyz, np.float32, "xyz")
+        if m >= 2 ** 32:
+            raise ValueError("at most 2^32 - 1 given points")
+        if m and (stride < 12 or stride % 4):
+            raise ValueError("xyz rows must be at least 12 bytes apart, by a multiple of 4")
+        want = bool(near or given_only)
+        out = np.zeros(4, np.uint64) if stats else None
+        words = np.zeros((m + 31) // 32, np.uint32) if want else None
+        self._chk(self._lib.rtr_select_near(self._ctx, ptr if m else None, stride if m else 12, m, r,
+                                            L.NEAR_GIVEN_ONLY if given_only else 0, code, _vp(words), _vp(out)))
+        del hold
+        st = tuple(int(v) for v in out) if stats else None
+        if want:
+            bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:m].astype(bool)
+            return (st, bits) if stats else bits
+        return st
+
     # -- bands and the dominant plane (rtr.h section 6j)
     def count_in_bands(self, bands, selected=False, stats=True):
         """Counts on the device, for each band {a, b, c, d_lo, d_hi} of `bands` ((k, 5), 1 <= k <= MAX_BANDS), the points
@@ -973,6 +1010,28 @@ class ProjectCloud:
         gone = self._p.select_clusters(radius, min_points, outside=True)[0]
         self.removeSelected()
         return gone
+
+    # -- distance to given points (rtr.h section 6k)
+    def selectNear(self, vertices, radius, op='replace', outside=False):
+        """Selects the vertices that have one of the given `vertices` ((m, 3) or (m, 4) float32) within `radius`
+        (outside: every vertex but those; see Projector.select_near).  Returns the number selected afterwards."""
+        return self._p.select_near(vertices, radius, op, outside)[0]
+
+    def appendNewPoints(self, vertices, colors, radius):
+        """Appends of the given points (appendPoints' arrays) exactly those that have no resident vertex within `radius`,
+        in their order: merging an overlapping scan without piling up duplicates.  The selection stays as it is.  A
+        scan is not thinned against itself -- two new points closer than radius to each other are both appended: thin
+        the scan first, or the cloud afterwards (selectVoxelGrid, thin).  Returns the number appended."""
+        v = np.asarray(vertices)
+        c = np.asarray(colors)
+        if len(v) != len(c):
+            raise ValueError("vertices has %d rows and colors %d" % (len(v), len(c)))
+        near = self._p.select_near(v, radius, given_only=True, stats=False)
+        new = ~near
+        k = int(new.sum())
+        if k:
+            self.appendPoints(np.ascontiguousarray(v[new]), np.ascontiguousarray(c[new]))
+        return k
 
     # -- the dominant plane (rtr.h section 6j)
     def fitPlane(self, dist, iterations=256, seed=0, selected=False):
