@@ -2,7 +2,8 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py.  The product package never imports this module.
-PARITY UNPINNED (see rtr_oracle.c header): the reference has no fixtures.
+The reference has no fixtures; `ref(variant)` loads its own kernels compiled for the host
+(oracle/ref_build.py -> oracle/_ref/), which is what pins the oracle.
 """
 import ctypes as C
 import os
@@ -177,6 +178,14 @@ class MTProjector:
 MM_VARIANTS = {0: "contract (right products fused, left to right)", 1: "first add fused with the left product",
                2: "nothing contracted (-fmad=false)", 3: "re-associated: all fused, right to left",
                4: "re-associated: m3 folded into the first fma"}
+
+
+def mm_rows(mx, my, mz):
+    """The `mm` of project_variant() for a matmul whose rows x, y, z take forms mx, my, mz of MM_VARIANTS each."""
+    assert all(0 <= m <= 4 for m in (mx, my, mz))
+    return 8 + mx + 5 * my + 25 * mz
+
+
 DV_VARIANTS = {0: "contract: x * RN(1/z)", 1: "IEEE x / z", 2: "x * (RN(1/z) - 2 ulp)", 3: "x * (RN(1/z) - 1 ulp)",
                4: "x * (RN(1/z) + 1 ulp)", 5: "x * (RN(1/z) + 2 ulp)"}
 
@@ -194,7 +203,7 @@ def envelope_points(xyz, P, W, H, mm, dv, nthreads=8):
 
 
 def project_variant(xyz, rgb, P, W, H, mm, dv, params=None):
-    """A whole frame under arithmetic variant (mm, dv): same outputs as project()."""
+    """A whole frame under arithmetic variant (mm, dv): same outputs as project().  mm 0..4 or mm_rows(mx, my, mz)."""
     xyz, rgb = _cloud(xyz, rgb)
     P = _P(P)
     prm = params or default_params()
@@ -224,6 +233,134 @@ def filter(depth_bits, img, params=None, want_tensor=True):
         raise ValueError("orc_filter: unsupported dimensions (need W %% 2^levels == 0): %dx%d" % (W, H))
     return {"depth": d.view(np.float32).reshape(H, W), "img": im.reshape(H, W, 3), "mask": mask.reshape(H, W),
             "tensor": None if tensor is None else tensor.reshape(5, H, W), "minmax": mm}
+
+
+REF_VARIANTS = ("off_recip", "off_ieee", "fast_recip", "fast_ieee")
+REF_POISON = 0xA5
+_refs = {}
+
+
+class RefLib:
+    """One of oracle/_ref/libref_<variant>.so: the REFERENCE's kernels compiled for the host (oracle/ref_build.py),
+    run thread by thread by oracle/ref_host/ref_driver.cpp.  Elements that no kernel of the reference writes come back
+    holding the `poison` byte; `block_size` stands for project_cloud.cu:216 (it must not change any result)."""
+
+    def __init__(self, variant, path):
+        self.variant = variant
+        L = C.CDLL(path)
+        L.ref_abi.restype = C.c_int
+        L.ref_build_traits.restype = C.c_int
+        L.ref_config.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.ref_config.restype = None
+        pv = C.c_void_p
+        L.ref_project.restype = C.c_int
+        L.ref_project.argtypes = [pv, pv, C.c_size_t, pv, C.c_int, C.c_int, pv, pv, pv]
+        L.ref_filter.restype = C.c_int
+        L.ref_filter.argtypes = [pv, pv, C.c_int, C.c_int, pv, pv, pv, pv]
+        L.ref_resize.restype = C.c_int
+        L.ref_resize.argtypes = [pv, pv, pv, C.c_int, C.c_int]
+        L.ref_frame.restype = C.c_int
+        L.ref_frame.argtypes = [pv, pv, C.c_size_t, pv, C.c_int, C.c_int, pv, pv, pv, pv, pv, pv, pv, pv, pv]
+        assert L.ref_abi() == 1
+        self.L = L
+        self.contracted = bool(L.ref_build_traits() & 1)
+        self.ieee_quotient = bool(L.ref_build_traits() & 2)
+
+    @staticmethod
+    def _cloud4(xyzw, rgba):
+        xyzw = np.ascontiguousarray(xyzw, dtype=np.float32)
+        rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+        assert xyzw.ndim == 2 and xyzw.shape[1] == 4 and rgba.shape == (xyzw.shape[0], 4)
+        return xyzw, rgba
+
+    def _filtered(self, W, H, d, im, mask, dims, mm, tensor):
+        mw, mh = int(dims[0]), int(dims[1])
+        return {"depth": d.view(np.float32).reshape(H, W), "img": im.reshape(H, W, 3),
+                "mask": mask[:mw * mh].reshape(mh, mw).copy(), "minmax": mm, "tensor_raw": tensor,
+                "tensor": tensor[:5 * mw * mh].reshape(5, mh, mw).copy()}
+
+    def project(self, xyzw, rgba, P, W, H, block_size=1024, poison=REF_POISON, slack=1):
+        """computeRGBD (project_cloud.cu:268-329) -> dict(depth_bits [H,W], acc [H,W,4], img [H,W,3])"""
+        xyzw, rgba = self._cloud4(xyzw, rgba)
+        P = _P(P)
+        depth, acc, img = np.empty(W * H, np.uint32), np.empty(W * H * 4, np.uint32), np.empty(W * H * 3, np.uint8)
+        self.L.ref_config(block_size, slack, poison)
+        rc = self.L.ref_project(_ptr(xyzw), _ptr(rgba), xyzw.shape[0], _ptr(P), W, H, _ptr(depth), _ptr(acc), _ptr(img))
+        assert rc == 0
+        return {"depth_bits": depth.reshape(H, W), "acc": acc.reshape(H, W, 4), "img": img.reshape(H, W, 3)}
+
+    def filter(self, depth_bits, img, block_size=1024, poison=REF_POISON, slack=1):
+        """applyDepthFilter (project_cloud.cu:331-392) on copies of a given unfiltered frame.
+        -> dict(depth f32 [H,W], img [H,W,3], mask [H_eff,W_eff], minmax u32[2], tensor fp16 bits [5,H_eff,W_eff] -- the
+        reference's own layout, plane stride W_eff*H_eff --, tensor_raw [5*W*H]: the whole buffer, poison behind)"""
+        H, W = depth_bits.shape
+        d = np.ascontiguousarray(depth_bits, dtype=np.uint32).copy().reshape(-1)
+        im = np.ascontiguousarray(img, dtype=np.uint8).copy().reshape(-1)
+        mask, dims, mm = np.zeros(W * H, np.uint8), np.zeros(2, np.int32), np.zeros(2, np.uint32)
+        tensor = np.empty(5 * W * H, np.uint16)
+        self.L.ref_config(block_size, slack, poison)
+        rc = self.L.ref_filter(_ptr(d), _ptr(im), W, H, _ptr(mask), _ptr(dims), _ptr(mm), _ptr(tensor))
+        if rc != 0:
+            raise ValueError("ref_filter: unsupported dimensions %dx%d" % (W, H))
+        return self._filtered(W, H, d, im, mask, dims, mm, tensor)
+
+    def resize(self, lo, hi, mask, block_size=1024):
+        """One launch of resizeKernel (project_cloud.cu:128-161, launched as at :385): lo f32 [h,w], hi f32 [2h(+1),2w(+1)],
+        mask u8 like hi -> the new hi (blended where mask == 0)."""
+        oh, ow = hi.shape
+        assert lo.shape == (oh // 2, ow // 2) and mask.shape == hi.shape
+        lo = np.ascontiguousarray(lo, dtype=np.float32)
+        out = np.ascontiguousarray(hi, dtype=np.float32).copy()
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        self.L.ref_config(block_size, 1, REF_POISON)
+        rc = self.L.ref_resize(_ptr(lo), _ptr(out), _ptr(mask), ow, oh)
+        assert rc == 0
+        return out
+
+    def frame(self, xyzw, rgba, P, W, H, block_size=1024, poison=REF_POISON, slack=1):
+        """computeFilteredRGBD (project_cloud.cu:394-434) -> (project()'s dict, filter()'s dict)"""
+        xyzw, rgba = self._cloud4(xyzw, rgba)
+        P = _P(P)
+        du, acc, iu = np.empty(W * H, np.uint32), np.empty(W * H * 4, np.uint32), np.empty(W * H * 3, np.uint8)
+        d, im = np.empty(W * H, np.uint32), np.empty(W * H * 3, np.uint8)
+        mask, dims, mm = np.zeros(W * H, np.uint8), np.zeros(2, np.int32), np.zeros(2, np.uint32)
+        tensor = np.empty(5 * W * H, np.uint16)
+        self.L.ref_config(block_size, slack, poison)
+        rc = self.L.ref_frame(_ptr(xyzw), _ptr(rgba), xyzw.shape[0], _ptr(P), W, H, _ptr(du), _ptr(acc), _ptr(iu),
+                              _ptr(d), _ptr(im), _ptr(mask), _ptr(dims), _ptr(mm), _ptr(tensor))
+        assert rc == 0
+        return ({"depth_bits": du.reshape(H, W), "acc": acc.reshape(H, W, 4), "img": iu.reshape(H, W, 3)},
+                self._filtered(W, H, d, im, mask, dims, mm, tensor))
+
+
+def ref_builder():
+    """oracle/ref_build.py as a module (the recipe that makes oracle/_ref from the reference tree)."""
+    import importlib.util
+    import sys
+    if "rtr_ref_build" not in sys.modules:
+        spec = importlib.util.spec_from_file_location("rtr_ref_build", os.path.join(_HERE, "ref_build.py"))
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules["rtr_ref_build"] = mod
+        spec.loader.exec_module(mod)
+    return sys.modules["rtr_ref_build"]
+
+
+def ref_available():
+    """True when the reference tree is there (oracle/_ref can be built) or a built oracle/_ref is."""
+    rb = ref_builder()
+    return rb.have_reference() or rb.built()
+
+
+def ref(variant):
+    """-> RefLib for "off_recip" | "off_ieee" | "fast_recip" | "fast_ieee"; builds oracle/_ref when the reference tree
+    is there, otherwise loads what is already built.  Raises when neither is possible."""
+    assert variant in REF_VARIANTS, variant
+    if variant not in _refs:
+        rb = ref_builder()
+        if not rb.build():
+            raise RuntimeError("oracle/_ref is not built and there is no reference tree under %s" % rb.reference_dir())
+        _refs[variant] = RefLib(variant, rb.lib_path(variant))
+    return _refs[variant]
 
 
 def f32_to_f16(x):

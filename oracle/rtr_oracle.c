@@ -6,11 +6,13 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load
  * this library; the shipped HIP path never links, imports or calls it.
  *
- * PARITY UNPINNED: the reference ships no tests, golden vectors or fixtures for
- * this path and its CUDA sources cannot be built or
- * run in this image (no nvcc, glm, OpenCV, libtorch-CUDA).  The oracle is pinned
- * only by hand-derived known-answer tests (tests/test_oracle_kat.py) that follow
- * the cited reference lines.
+ * PARITY: the reference ships no tests, golden vectors or fixtures for this path
+ * (SURVEY.md section 4 / 8c), and its CUDA program cannot be built without nvcc,
+ * glm, OpenCV and libtorch-CUDA.  Its KERNELS can: oracle/ref_build.py compiles
+ * them for the host, unchanged, and tests/test_oracle_vs_reference.py pins this
+ * file to them bit for bit, next to the hand-derived
+ * known-answer tests (tests/test_oracle_kat.py) that follow the cited lines.
+ * Unpinned: nvcc's FMA contraction and __fdividef's approximate reciprocal.
  *
  * Arithmetic contract (binding for this oracle AND for the HIP kernels):
  *   every fp32 operation below is a single IEEE-754 round-to-nearest-even
@@ -343,9 +345,13 @@ static inline float quot_v(float a, float rz, int dv) {
     }
     return f_mul(a, inv);
 }
+/* mm 0..4: the same form in all three rows.  A compiler may also pick a form PER ROW (the host build of the reference's
+ * own text does, tests/test_oracle_vs_reference.py): mm = 8 + mx + 5 my + 25 mz, each digit one of the forms above.     */
+static inline int mm_valid(int mm) { return mm >= 0 && (mm <= 4 || (mm >= 8 && mm < 8 + 125)); }
 static inline int project_point_v(const float *P, float x, float y, float z, int W, int H, int mm, int dv,
                                   uint32_t *pix, float *depth) {
-    float rx = row_v(P, x, y, z, mm), ry = row_v(P + 4, x, y, z, mm), rz = row_v(P + 8, x, y, z, mm);
+    const int mx = mm < 8 ? mm : (mm - 8) % 5, my = mm < 8 ? mm : (mm - 8) / 5 % 5, mz = mm < 8 ? mm : (mm - 8) / 25;
+    float rx = row_v(P, x, y, z, mx), ry = row_v(P + 4, x, y, z, my), rz = row_v(P + 8, x, y, z, mz);
     if (!(rz > 0.0f)) return 0;
     float fu = rintf(quot_v(rx, rz, dv)), fv = rintf(quot_v(ry, rz, dv));
     if (!(fu >= 0.0f && fu < (float)W && fv >= 0.0f && fv < (float)H)) return 0;
@@ -399,7 +405,7 @@ int orc_envelope_points(const void *xyz, size_t xyz_stride, size_t n, const floa
 int orc_project_variant(const void *xyz, size_t xyz_stride, const uint8_t *rgb, size_t rgb_stride, size_t n,
                         const float P[16], int W, int H, const orc_params *prm, int mm, int dv,
                         uint32_t *depth, uint32_t *acc, uint8_t *img) {
-    if (mm < 0 || mm > 4 || dv < 0 || dv > 5) return -1;
+    if (!mm_valid(mm) || dv < 0 || dv > 5) return -1;
     const size_t npix = (size_t)W * H;
     orc_clear(depth, acc, npix);
     for (size_t i = 0; i < n; ++i) {

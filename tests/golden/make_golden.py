@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Writes tests/golden/*.npz: small input clouds + the frame buffers the CPU oracle produces
-for them.  The reference holds no golden vectors and cannot be built or run here (CUDA), so
-these are REGRESSION pins of the oracle (itself pinned by the hand-derived KATs and the
-exact-rational model), not outputs of the reference.  Re-run only on a deliberate contract
+for them.  The reference holds no golden vectors, so these are REGRESSION pins of the oracle
+(itself pinned by the reference's kernels compiled for the host, the hand-derived KATs and the
+exact-rational model), not outputs of the reference -- those are make_ref_golden.py's
+ref_*.npz.  Re-run only on a deliberate contract
 change:  python tests/golden/make_golden.py"""
 import os
 import sys

@@ -3,7 +3,9 @@
 oracle/rtr_oracle.c's structure: whole-array float32 operations (numpy rounds every float32
 operation once; the fused multiply-adds of the contract are formed in float64, whose 53-bit
 product of two float32 values is exact, then rounded once to float32).  Agreement with the C
-oracle pins the oracle's filter the way tests/pymodel.py pins its projection."""
+oracle pins the oracle's filter the way tests/pymodel.py pins its projection.  The one contractible expression, the
+bilinear blend, can also be stated unfused or with the other product fused (`blend`): those are what the reference's
+own kernels compute when built for the host without and with contraction (tests/test_oracle_vs_reference.py)."""
 import numpy as np
 
 F = np.float32
@@ -60,7 +62,22 @@ def compare(lo, hi, grad, strength):  # project_cloud.cu:88-126; lo: (lh, lw), h
     return np.where(keep, 255, 0).astype(np.uint8)
 
 
-def resize_into(lo, hi, mask):  # project_cloud.cu:128-161, in place where mask == 0
+def _blend(w, a, b, blend):
+    """(1 - w) * a + w * b (project_cloud.cu:157-160) in float32, the one contractible expression of the prefilter:
+      "fused"       the contract: fma(w, b, RN((1 - w) * a))
+      "unfused"     every operation rounded on its own: RN(RN((1 - w) * a) + RN(w * b))
+      "fused_left"  the other product fused: fma(1 - w, a, RN(w * b))"""
+    w = np.broadcast_to(w, a.shape)
+    u = (F(1) - w).astype(F)
+    if blend == "fused":
+        return _fma(w, b, (u * a).astype(F))
+    if blend == "unfused":
+        return ((u * a).astype(F) + (w * b).astype(F)).astype(F)
+    assert blend == "fused_left", blend
+    return _fma(u, a, (w * b).astype(F))
+
+
+def resize_into(lo, hi, mask, blend="fused"):  # project_cloud.cu:128-161, in place where mask == 0
     oh, ow = hi.shape
     lh, lw = lo.shape
     x = np.arange(ow, dtype=F)
@@ -76,16 +93,16 @@ def resize_into(lo, hi, mask):  # project_cloud.cu:128-161, in place where mask 
     wy = (iny - y0.astype(F)).astype(F)[:, None]
     with np.errstate(all="ignore"):
         def row(yy):
-            a, b = lo[yy][:, x0], lo[yy][:, x1]
-            return _fma(np.broadcast_to(wx, a.shape), b, ((F(1) - wx).astype(F) * a).astype(F))
+            return _blend(wx, lo[yy][:, x0], lo[yy][:, x1], blend)
         v0, v1 = row(y0), row(y1)
-        out = _fma(np.broadcast_to(wy, v0.shape), v1, ((F(1) - wy).astype(F) * v0).astype(F))
+        out = _blend(wy, v0, v1, blend)
     hi[mask == 0] = out[mask == 0]
 
 
-def apply_filter(depth_bits, img, strength=1.025, thr=0.03, levels=4):
+def apply_filter(depth_bits, img, strength=1.025, thr=0.03, levels=4, blend="fused"):
     """-> dict(depth f32, img, mask, tensor u16 [5,H,W], minmax u32[2]) under the rules of
-    DESIGN.md (rows >= H_eff: mask = non-empty; tensor plane stride W*H)."""
+    DESIGN.md (rows >= H_eff: mask = non-empty; tensor plane stride W*H).  `blend`: how the bilinear blend is
+    rounded (see _blend); "fused" is the contract, "unfused" what a build without contraction computes."""
     H, W = depth_bits.shape
     lv = [depth_bits.view(F).copy()]
     for i in range(1, levels + 1):
@@ -98,7 +115,7 @@ def apply_filter(depth_bits, img, strength=1.025, thr=0.03, levels=4):
         mask = compare(lv[i][:ch // 2, :cw // 2], lv[i - 1][:ch, :cw], grad, strength)
         if i > 1:
             sub = lv[i - 1][:ch, :cw]
-            resize_into(lv[i][:ch // 2, :cw // 2], sub, mask)
+            resize_into(lv[i][:ch // 2, :cw // 2], sub, mask, blend)
     bits = depth_bits[:ch, :cw]
     valid = bits[bits != EMPTY]
     mn = np.uint32(valid.min()) if valid.size else np.uint32(0xFFFFFFFF)

@@ -1,7 +1,8 @@
-"""How far the oracle's arithmetic contract can be from a CUDA build of the reference (PARITY UNPINNED, DESIGN.md
-section 2): render.cu:33-40 (`matmul` under nvcc's unspecified FMA contraction) and render.cu:65-66 (`__fdividef`, x
-times an approximate reciprocal) cannot be reproduced here, and the reference ships no golden frame.  These tests do
-not pin the oracle against the reference -- nothing can, here -- they BOUND the gap: every evaluation a CUDA build
+"""How far the oracle's arithmetic contract can be from a CUDA build of the reference:
+render.cu:33-40 (`matmul` under nvcc's unspecified FMA contraction) and render.cu:65-66 (`__fdividef`, x
+times an approximate reciprocal) cannot be reproduced off an NVIDIA toolchain, and the reference ships no golden frame.
+Everything else is pinned by tests/test_oracle_vs_reference.py (the reference's kernels compiled for the host); for
+these two, the tests here BOUND the gap: every evaluation a CUDA build
 could plausibly produce (oracle/rtr_oracle.c "ENVELOPE": other contractions / associations of matmul, IEEE division,
 the reciprocal perturbed by +-1 / +-2 ulp) against the contract, on BASELINE C3's cloud and poses (a sample: the full
 table in DESIGN.md is tools/oracle_envelope.py at 1e7 points x 100 poses).  CPU only."""

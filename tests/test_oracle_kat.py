@@ -1,6 +1,6 @@
 """CPU: known-answer tests pinning the oracle (hand-derived from the reference lines;
-SURVEY.md 8c items 1-9).  The reference ships no fixtures of its own: PARITY UNPINNED
-beyond these.  Camera: P = K * I, fx = fy = 100, cx = 32, cy = 24, 64 x 48."""
+SURVEY.md 8c items 1-9).  The reference ships no fixtures of its own; its kernels compiled
+for the host pin the oracle in tests/test_oracle_vs_reference.py.  Camera: P = K * I, fx = fy = 100, cx = 32, cy = 24, 64 x 48."""
 import numpy as np
 import pytest
 
