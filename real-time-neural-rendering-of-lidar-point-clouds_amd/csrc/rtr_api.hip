@@ -6,10 +6,11 @@
 // project_cloud.cu:346-390), every launch goes to one stream with no device-wide
 // synchronisation in between (the reference calls cudaDeviceSynchronize ten times
 // per frame), and the camera matrix travels as a kernel argument.
+// The selection and analysis calls (rtr.h sections 6f - 6k) are in rtr_select_api.hip;
+// rtr_host.h holds what both files share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -18,235 +19,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtr.h"
-#include "rtr_kernels.h"
+#include "rtr_host.h"
 #include "rtr_extract_index.h"
-#include "rtr_overlap_policy.h"
-#include "rtr_plane_fit.h"
 
 constexpr int kSplitCooldown = 8;  // whole frames keep launching k_tile_split this long after the last report of a tile above the threshold
 
-struct rtr_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    rtr_params prm{};
-    std::string err;
-
-    // resident cloud (SoA)
-    float *x = nullptr, *y = nullptr, *z = nullptr;
-    uint32_t *rgba = nullptr;
-    float *bounds = nullptr;    // bounding box per 256-point chunk (frustum culling option)
-    float *spread = nullptr;    // lane spread per 256-point chunk (rtr::Cloud::spread: T1's lane test)
-    float absmax[3] = {0.f, 0.f, 0.f};  // largest finite |x|, |y|, |z| of the resident cloud
-    int opt_lane_test = 1;      // T1 tests one point per lane first (option "lane_test")
-    int opt_chunk_test = 1;     // T1 tests packed chunks on their header boxes first (option "chunk_test")
-    int opt_keep_soa = 0;       // 1: the fp32 SoA arrays stay resident beside the packed form (option "keep_soa")
-    int opt_pool_worst = 0;     // 1: the extent pool is always sized for the worst case, 2 n entries (option "pool_worst_case")
-    int opt_lean = 1;           // whole single-GPU frames without split tiles end T1 without its epilogue (option "lean")
-    int opt_lean_identity = 1;  // lean frames: tile workgroup b takes tile b when the whole launch is resident (option "lean_identity")
-    int opt_lean_early = -1;    // lean frames: first batch of entries requested before the stream counters are known: 0 never,
-                                // 1 always, -1 when the previous frame's tiles were full (option "lean_early")
-    bool last_lean = false;     // the last binned frame was a lean one (its statistics are folded on demand; FrontSet::parity)
-    uint64_t n = 0, cap = 0;
-    uint4 *pk_hdr = nullptr;        // rtr::PackedXyz of the resident cloud (option "pack"); null: not in use
-    uint32_t *pk_planes = nullptr, *pk_planes_b = nullptr;  // (one allocation: A streams, then B streams)
-    uint64_t pk_bytes = 0;          // headers + planes
-    uint64_t pk_units = 0, pk_units_cap = 0;  // 32-byte units of the planes in use / allocated (rtr_append_points grows them)
-    uint64_t pk_hdr_chunks = 0;     // chunks the header array holds (+ the zero pair behind them)
-    int opt_pack = 1;               // 0 never, 1 when it saves >= 1/8 of the coordinate stream, 2 always + verified after packing
-
-    int W = 0, H = 0;  // resolution
-    rtr::Clip clip{};  // the user's clip planes (rtr_set_clip_planes; count 0: none): every point kernel of a frame honours them
-
-    // tile-binned pipeline: the tile store T1 appends to and T4 reads (rtr_kernels.h)
-    struct FrontSet {
-        rtr::TileStore store{};
-        uint64_t pool_n = 0;        // point count the dynamic extent pool was sized for
-        int nst = 0, ntiles = 0;    // tile counts the per-tile arrays were sized for
-        rtr::StoreConsts consts{};  // host copy of the store's header constants
-        uint64_t *dyn = nullptr;    // dynamic extent pool
-        uint64_t dyn_cap = 0;
-        hipEvent_t binned = nullptr, consumed = nullptr;  // T1 done (front stream) / T4 done (tail stream)
-        bool consumed_valid = false;
-        int parity = 0;             // lean-frame parity of this store: order[], lcnt[] and the lflag words live in it
-        bool lean_pending = false;  // its last frame was a lean one whose statistics no later frame has folded yet
-    };
-
-    // What a set of frames renders into: the single frame (rtr_render, the phase calls; with option "overlap" T1 of
-    // frame k+1 fills its second set on the front stream while the tail of frame k still reads the other) or a batch
-    // of views (rtr_render_views, one set per view).  depth / img / tensor hold `cap` frames (alloc_target); the
-    // accumulators, prefilter mask, min / max partials and pyramid levels are scratch that the frames take in turn.
-    // Stores are allocated per resolution and pools per cloud by the frames that use them; the minmax words and the
-    // mapped words live as long as the context.
-    struct Target {
-        int cap = 0;
-        uint32_t *depth = nullptr, *acc = nullptr, *part_min = nullptr, *part_max = nullptr;
-        uint8_t *img = nullptr, *mask = nullptr;
-        uint16_t *tensor = nullptr;
-        uint32_t *minmax = nullptr;  // 2 words per frame, RTR_MAX_VIEWS frames
-        float *lv[9] = {nullptr};    // pyramid levels 1..lv_levels (level 0 is a frame's depth)
-        int lv_levels = 0;
-        FrontSet fs[RTR_MAX_VIEWS];
-        int cur = 0;                 // the set of the last frame (the single frame alternates with option "overlap")
-        uint32_t *err_host = nullptr, *err_dev = nullptr;  // mapped word: tile-store error bits of frames since it was last read
-        uint32_t *entries_host = nullptr, *entries_dev = nullptr;  // mapped word: entries of the last frame whose statistics are complete
-        uint64_t entries_max = 0;    // the most entries a completed frame of this cloud has had
-        bool pool_worst = false;     // the pools are worst-case sized for this cloud: a frame overflowed them, or the peers map them
-    } frame, views;
-    FrontSet &F() { return frame.fs[frame.cur]; }
-    rtr::OverlapPolicy ov;      // option "overlap" and the streak of whole frames: which of them run T1 on `front`
-    bool frame_overlapped = false;  // the whole frame being queued runs overlapped (mark_consumed)
-    int opt_front_priority = 0; // stream priority `front` is created with: 0 default, 1 lowest, 2 highest (option "front_priority")
-    int opt_tail_cus = 0;       // CUs per XCD reserved for the tail stream when overlapping (0 = no CU masks)
-    hipStream_t front = nullptr;
-    hipStream_t masked_tail = nullptr;
-    hipEvent_t joined = nullptr;  // recorded on `stream` when a streak of overlapped frames begins: `front` waits for it
-    bool list_valid = false;    // bins match list_P / current cloud / resolution / window
-    float list_P[12] = {0};
-    int opt_mode = 1;           // 0 = two-pass global atomics (the reference's structure),
-                                // 1 = tile-binned LDS z-buffer (default)
-    int opt_keep_accum = 0;     // whole-frame calls also materialise RTR_BUF_ACCUM
-    bool force_atomic = false;       // set around a whole frame that takes the atomic form (> 4096 tiles)
-    int opt_heavy = 32768;           // tiles with more entries are split over several workgroups in T4 ...
-    int opt_slice = 16384;           // ... into slices of at least this many entries
-    int opt_p2p_timeout_ms = 2000;   // peer-to-peer flag barriers give up after this long (option "p2p_timeout_ms")
-    int opt_fill_shift = -1;         // spacing of the stream counters, 4 << value bytes; -1: by the frames seen (see "fill_shift")
-    int opt_debug_dyn_cap = -1;      // test aid: cap the dynamic extent pool at this many entries (-1: off)
-    int opt_debug_extract_window = -1;  // test aid: cap rtr_extract_points' internal window at this many points (-1: off)
-    // whole frames launch k_tile_split (an empty launch costs ~5 us) only while tiles above the split threshold have
-    // been seen: T1's epilogue stores their number here (mapped host word, read without a sync -- it describes the
-    // last frame whose T1 has COMPLETED, the host may be frames ahead), and the launch stays on for kSplitCooldown
-    // frames after the last such report, after an upload, a new resolution or new split options.  A frame that
-    // turns out to need it while it is off is still exact (bin_epilogue, `no_split`).
-    uint32_t *split_host = nullptr, *split_dev = nullptr;
-    int split_cooldown = 0;
-    int opt_xp = 0;                  // RTR_EXPERIMENT builds only (tools/kbench.py)
-    int opt_phases = 0;         // T1: phase groups of the grid stride (option "phases", see k_project_bin); 0 = automatic
-    int opt_probe = 0;          // rtr_stream_probe variant (experiments)
-    int opt_cull = 0;           // per-chunk frustum culling in T1
-    int opt_auto_reorder = 2;   // Morton-sort a cloud right after upload / generation: 0 never, 1 always, 2 when its
-                                // 256-point chunks are not spatially compact (default)
-    bool reordered = false;     // the resident cloud was sorted by the library
-    int opt_point_ids = 0;      // 1: a sorted cloud keeps its upload order as a resident permutation (option "point_ids")
-    uint32_t *perm = nullptr;   // [cap] upload index of every resident point (only while `reordered`)
-    // the keep mask (rtr_set_point_keep; keep_up null: none): the caller's upload-order words, and the resident-order
-    // copy with its chunk summary the point kernels read (rtr::Keep).  Cleared with every new cloud
-    uint32_t *keep_up = nullptr, *keep_res = nullptr;
-    uint8_t *keep_sum = nullptr;
-
-    // point pass (rtr_point_pass): per-pixel point IDs [H*W] (per resolution) and the visibility mask (8 words per
-    // 256-point chunk; (n + 31) / 32 of them are the buffer)
-    uint32_t *pp_ids = nullptr, *pp_vis = nullptr;
-    uint64_t pp_vis_words = 0;
-    bool pp_vis_current = false;  // the mask was computed for the resident cloud
-    hipEvent_t pp_done = nullptr;  // recorded behind the last point pass
-    // the selection (rtr_select_points; sel null: none): upload-order words, 8 per 256-point chunk of the cloud it was made
-    // for ((n + 31) / 32 of them are the buffer), and the four device words a call with `stats` counts into.  Dropped by
-    // everything that renumbers upload indices
-    uint32_t *sel = nullptr;
-    uint64_t *sel_stats = nullptr;
-    int plane_us[2] = {0, 0};     // the last rtr_fit_plane: sampling + extract, counting (host clock, the waits included)
-    int voxel_us[3] = {0, 0, 0};  // the last rtr_select_voxel_grid: its key kernel, sort and head kernel, from their own events
-    int neighbours_us[3] = {0, 0, 0};  // the last rtr_select_neighbours: key kernel, sort, gather + work list + count kernel
-    int neighbours_tests_k = 0;        // ... and its pair tests in thousands (saturating)
-    int near_us[2] = {0, 0};           // the last rtr_select_near: the given points' keys, sort and gather; the sweep, combine and counts
-    int near_tests_k = 0;              // ... its pair tests in thousands (saturating)
-    int near_chunks[2] = {0, 0};       // ... and its resident chunks decided without their coordinates / decoded (saturating)
-    int clusters_us[3] = {0, 0, 0};    // the last rtr_select_clusters: key kernel, sort, gather + work list + union-find + hits
-    int clusters_tests_k = 0;          // ... and its pair tests in thousands (saturating)
-    float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
-    int opt_grid = rtr::kDefaultPointGrid;  // workgroups of the point kernels
-
-    // peer-to-peer exchange (rtr_p2p_*): own exchange buffers, the peers' mappings, barrier state
-    struct P2P {
-        uint32_t *red = nullptr;          // [npix] reduced depth; this rank writes its slice, peers read it
-        uint8_t *ximg = nullptr;          // [3 * npix] resolved image; same (the prefilter rewrites RTR_BUF_IMAGE in place)
-        uint32_t *flags = nullptr;        // [RTR_P2P_MAX_RANKS] uncached: barrier counters written by the peers
-        uint32_t *occ = nullptr;          // [128] one bit per screen tile: this rank's frame has entries there
-        uint32_t *occ_all = nullptr;      // [kMaxPeers * 128] every rank's bitmap, gathered by the first barrier of a frame
-        bool depth_peers = false;         // rtr_p2p_render: the accumulate launch takes the MIN over the peers' depth itself
-        bool depth_in_red = false;        // ... and has left the completed depth in `red` (the peers were reading `depth`)
-        bool occ_current = false;         // occ was computed from the bins that are valid now
-        bool occ_from_scan = false;       // ... by the epilogue of this frame's T1 (no separate launch)
-        bool whole_frame = false;         // inside rtr_p2p_render: the tile launches are the only writers of depth /
-                                          // accumulators (no clear, no read-modify-write) and T4<2> emits the pyramid
-        bool pyramid_done = false;
-        bool depth_sliced = false;        // ... RTR_BUF_DEPTH is completed by the accumulate launch (no depth gather)
-        bool image_sliced = false;        // ... the prefilter reads the image from the ranks' slices (no image gather)
-        bool acc_from_bins = false;       // the last accumulate pass used exactly those bins
-        uint32_t *status_host = nullptr;  // mapped host word: barrier timeouts
-        uint32_t *status_dev = nullptr;
-        rtr::PeerSet depth{}, accum{}, image{}, reduced{}, flags_of{}, occ_of{}, meta_of{}, ext0_of{}, dyn_of{};
-        rtr::OwnedTab *tab = nullptr;     // device copy of the peers' tile-store / frame-buffer mappings (owner-computes form)
-        void *opened[9][RTR_P2P_MAX_RANKS] = {};
-        int rank = 0, world = 0;
-        uint32_t seq = 0;
-        bool open = false;
-    } p2p;
-
-    // asynchronous host outputs (rtr_project_async): per slot a device snapshot of depth + image (so the next
-    // frame's kernels may overwrite the frame buffers), pinned host buffers, and the events that order the two
-    // streams -- the device-to-host copies run on `copy_stream` beside the next frame's kernels
-    struct HostOut {
-        uint8_t *img = nullptr, *dimg = nullptr;
-        float *depth = nullptr;
-        uint32_t *ddepth = nullptr;
-        void *img_map = nullptr, *depth_map = nullptr;  // the pinned buffers as the device addresses them
-        hipEvent_t snap = nullptr, done = nullptr;  // snapshot taken (frame stream) / copies finished (copy stream)
-        bool busy = false;
-    } ho[RTR_ASYNC_SLOTS];
-    hipStream_t copy_stream = nullptr;
-
-    // timing
-    int timing = 0;  // 0 off, 1 every phase, 2 only the streaming kernel (RTR_K_MIN_DEPTH / ACCUMULATE), 3 = 2 on every 4th launch
-    uint32_t timing_tick = 0;
-    struct Span { hipEvent_t a, b; int k; };
-    std::vector<Span> pending;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-    double total_ms[RTR_K_COUNT] = {0};
-    uint64_t launches[RTR_K_COUNT] = {0};
-
-    uint64_t cloud_seq = 0;  // +1 per upload / generation (alloc_cloud)
-
-    // rtr::launch_project_bin_views' table (pinned / device); `copied`: the last copy of `host` has been read
-    struct ViewTab {
-        void *host = nullptr, *dev = nullptr;
-        hipEvent_t copied = nullptr;
-        bool pending = false;
-    } vtab;
-
-    // What a synchronising call renders again when it learns that the adaptive extent pool was too small (repair)
-    struct Journal {
-        struct Frames {
-            float P[RTR_MAX_VIEWS * 16] = {0};
-            int count = 0, filter = 0;
-            rtr::Clip clip{};  // the clip planes the frames were issued with
-        };
-        Frames frame;  // the last whole frame (rtr_render): count 0 or 1
-        Frames views;  // the last batch of views (rtr_render_views); count 0: none, or it is incomplete
-        struct Pass {  // the last point pass
-            float P[16] = {0};
-            int what = 0;
-            bool behind = false;     // queued right behind the last whole frame, nothing rendered since: repeated with it
-            bool unchecked = false;  // queued, and not yet known to have read a complete frame
-            bool invalid = false;    // its outputs came from a frame the tile store reported incomplete
-            rtr::Clip clip{};
-        } pass;
-        struct Slot {  // the frame queued into each async slot; `stale`: queued before the pool grew (rtr_wait repeats it)
-            float P[16] = {0};
-            int filter = 0;
-            bool stale = false;
-            bool sealed = false;  // finished and checked by rtr_set_point_keep: no later overflow makes it stale
-            uint64_t cloud = 0;  // cloud_seq when it was queued
-            rtr::Clip clip{};
-        } slot[RTR_ASYNC_SLOTS];
-    } jr;
-};
-
 static thread_local std::string g_create_err;
 
-static int fail(rtr_ctx *c, int code, const char *fmt, ...) {
+int fail(rtr_ctx *c, int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -256,29 +36,7 @@ static int fail(rtr_ctx *c, int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(c, expr)                                                                         \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail((c), RTR_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                     \
-    } while (0)
-
-#define NEED(c, cond, msg) \
-    do { if (!(cond)) return fail((c), RTR_ERR_INVALID, "%s", msg); } while (0)
-
 namespace {
-
-struct DevGuard {  // contexts pin their device for the duration of a call and hand the caller's back
-    int prev = -1;
-    explicit DevGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev); else prev = -1;
-    }
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-    DevGuard(const DevGuard &) = delete;
-    DevGuard &operator=(const DevGuard &) = delete;
-};
 
 template <class T>
 void dfree(T *&p) {
@@ -423,12 +181,6 @@ void free_pack(rtr_ctx *c) {
 
 void free_keep(rtr_ctx *c) {
     dfree(c->keep_up); dfree(c->keep_res); dfree(c->keep_sum);
-}
-
-void free_select(rtr_ctx *c) {
-    if (!c->sel) return;
-    (void)sync_streams(c);  // (a selection in flight may still write it)
-    dfree(c->sel); dfree(c->sel_stats);
 }
 
 void free_cloud(rtr_ctx *c) {
@@ -605,21 +357,6 @@ int alloc_cloud(rtr_ctx *c, uint64_t n) {
     return RTR_OK;
 }
 
-rtr::Proj make_proj(const float P[16]) {
-    rtr::Proj p;
-    for (int i = 0; i < 12; ++i) p.m[i] = P[i];
-    return p;
-}
-
-rtr::Cloud cloud_of(const rtr_ctx *c) {
-    // (a chunk of 256 points spanning more than half of the cloud: consecutive points are unrelated.  A hash-ordered
-    // cloud measures ~1.0; the reference loader's 0.25 m blocks in hash-map order, unordered inside, measure 0.28 for a
-    // 10 m room and must keep the wave-level claim groups: 0.33 ms instead of 0.66 ms per frame without them)
-    return rtr::Cloud{c->x, c->y, c->z, c->rgba, c->n, c->opt_grid, (!c->reordered && c->order_ratio > 0.5f) ? 1 : 0,
-                      rtr::PackedXyz{c->pk_hdr, c->pk_planes, c->pk_planes_b}, c->spread, {c->absmax[0], c->absmax[1], c->absmax[2]},
-                      c->clip, rtr::Keep{c->keep_up ? c->keep_res : nullptr, c->keep_sum}};
-}
-
 struct Timed {  // brackets one phase with hipEvents on the stream it is launched on
     rtr_ctx *c; int k; hipStream_t s; hipEvent_t a = nullptr, b = nullptr;
     bool in_dispatch;  // the launch itself carries the two events (hipExtLaunchKernelGGL): nothing to record here
@@ -695,12 +432,6 @@ int check_frame(rtr_ctx *c) {
     return RTR_OK;
 }
 
-int launch_check(rtr_ctx *c, const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, RTR_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return RTR_OK;
-}
-
 // The prefilter's conditions, checked before anything changes
 int check_prefilter(rtr_ctx *c) {
     const int L = c->prm.levels;
@@ -751,6 +482,54 @@ rtr::TilePyr tile_pyr(const rtr_ctx *c, const rtr_ctx::Target &t, int k, bool en
 }
 
 }  // namespace
+
+// ---- shared with rtr_select_api.hip (declared in rtr_host.h) -------------------------------------------------------
+void free_select(rtr_ctx *c) {
+    if (!c->sel) return;
+    (void)sync_streams(c);  // (a selection in flight may still write it)
+    dfree(c->sel); dfree(c->sel_stats);
+}
+
+rtr::Proj make_proj(const float P[16]) {
+    rtr::Proj p;
+    for (int i = 0; i < 12; ++i) p.m[i] = P[i];
+    return p;
+}
+
+rtr::Cloud cloud_of(const rtr_ctx *c) {
+    // (a chunk of 256 points spanning more than half of the cloud: consecutive points are unrelated.  A hash-ordered
+    // cloud measures ~1.0; the reference loader's 0.25 m blocks in hash-map order, unordered inside, measure 0.28 for a
+    // 10 m room and must keep the wave-level claim groups: 0.33 ms instead of 0.66 ms per frame without them)
+    return rtr::Cloud{c->x, c->y, c->z, c->rgba, c->n, c->opt_grid, (!c->reordered && c->order_ratio > 0.5f) ? 1 : 0,
+                      rtr::PackedXyz{c->pk_hdr, c->pk_planes, c->pk_planes_b}, c->spread, {c->absmax[0], c->absmax[1], c->absmax[2]},
+                      c->clip, rtr::Keep{c->keep_up ? c->keep_res : nullptr, c->keep_sum}};
+}
+
+int launch_check(rtr_ctx *c, const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, RTR_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+hipError_t d2d(hipStream_t s, void *dst, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
+}
+
+// Where a caller's array lies (rtr_extract_points, rtr_write_points: each stream may be host or device memory)
+bool on_device(const void *p) {  // device (or managed) memory, as opposed to anything the host owns
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // (plain host memory is unknown to the runtime)
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+
+int need_upload_order(rtr_ctx *c, const char *verb, const char *or_else) {
+    if (!c->reordered || c->perm) return RTR_OK;
+    return fail(c, RTR_ERR_INVALID, "the resident cloud was reordered without option point_ids = 1, so upload-order indices "
+                "cannot be %s: set point_ids = 1 before the upload (or upload with auto_reorder = 0)%s", verb, or_else);
+}
 
 static int set_overlap(rtr_ctx *c, int value);
 static void overlap_teardown(rtr_ctx *c);
@@ -1393,28 +1172,6 @@ int rtr_synchronize(rtr_ctx *c) {
 }  // extern "C"
 
 namespace {
-struct DevBufs {  // a call's device buffers: freed on every exit path unless a resident array has taken them (swap_in)
-    std::vector<void *> p;
-    ~DevBufs() { for (void *q : p) if (q) (void)hipFree(q); }
-    template <class T> hipError_t get(T **out, size_t bytes) {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 4);
-        if (e == hipSuccess) p.push_back(q);
-        *out = static_cast<T *>(q);
-        return e;
-    }
-    template <class T> void swap_in(T *&field, T *next) {  // a resident array replaced: the old one goes with the scratch
-        if (field == next) return;
-        p.push_back((void *)field);
-        for (auto &x : p) if (x == (void *)next) x = nullptr;
-        field = next;
-    }
-};
-
-hipError_t d2d(hipStream_t s, void *dst, const void *src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : hipSuccess;
-}
-
 // The packed form's invariants, each in one place (rtr::PackedXyz; `units`: 32-byte units of both plane streams).
 // Resident bytes: blocks + headers
 uint64_t pack_bytes(uint64_t units, uint64_t chunks) { return units * 32 + chunks * 32; }
@@ -1430,23 +1187,6 @@ hipError_t copy_blocks(hipStream_t s, uint32_t *planes, uint32_t *planes_b, cons
     return e != hipSuccess ? e : d2d(s, planes_b, c->pk_planes_b, units * 6 * 4);
 }
 
-// Where a caller's array lies (rtr_extract_points, rtr_write_points: each stream may be host or device memory)
-bool on_device(const void *p) {  // device (or managed) memory, as opposed to anything the host owns
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();  // (plain host memory is unknown to the runtime)
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-
-// Calls that take or return upload-order indices: a cloud sorted by the library must have kept its permutation.
-// `verb`: what the call would do with the indices; `or_else`: the call's own way round it, if it has one
-int need_upload_order(rtr_ctx *c, const char *verb = "mapped", const char *or_else = "") {
-    if (!c->reordered || c->perm) return RTR_OK;
-    return fail(c, RTR_ERR_INVALID, "the resident cloud was reordered without option point_ids = 1, so upload-order indices "
-                "cannot be %s: set point_ids = 1 before the upload (or upload with auto_reorder = 0)%s", verb, or_else);
-}
 // An upload-order bit-word argument (`words`, `nwords`; `fn` and `what` name the call and the argument in the messages):
 // one bit per resident point, so nwords must be (n + 31) / 32, and a cloud the library sorted must have kept its
 // permutation (need_upload_order with `or_else`) -- unless `order_checked_later`: the call asks that itself, behind its
@@ -2218,7 +1958,7 @@ int rtr_write_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords, 
         return rc;
     NEED(c, !xyz || (xs >= 12 && xs % 4 == 0), "rtr_write_points: xyz_stride_bytes must be >= 12 and a multiple of 4");
     NEED(c, !rgb || rs >= 3 || rs == 0, "rtr_write_points: rgb_stride_bytes must be >= 3, or 0 for one record for every point");
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    if (int rc = check_indexable(c)) return rc;
     if (!every)
         if (int rc = need_upload_order(c, "mapped", ", or write every point in the resident order (select_words NULL)")) return rc;
     DevGuard g(c->device);
@@ -2373,7 +2113,7 @@ int rtr_extract_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords
         return rc;
     NEED(c, !xyz || (xs >= 12 && xs % 4 == 0), "rtr_extract_points: xyz_stride_bytes must be >= 12 and a multiple of 4");
     NEED(c, !rgb || rs >= 3, "rtr_extract_points: rgb_stride_bytes must be >= 3");
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+    if (int rc = check_indexable(c)) return rc;
     const bool lost_order = c->reordered && !c->perm;
     if (!every)
         if (int rc = need_upload_order(c, "mapped", ", or extract every point (select_words NULL)")) return rc;
@@ -3192,629 +2932,6 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
     pass.unchecked = true;
     pass.invalid = false;
     pass.clip = c->clip;
-    return RTR_OK;
-}
-
-// ---- selection (rtr.h, section 6f) ----------------------------------------------------
-// One sweep over the resident coordinates on the context's stream (rtr::launch_select), nothing else read or written:
-// the cloud's own planes and mask, the frames, their journal and the point pass's buffers stay as they are.
-int rtr_select_points(rtr_ctx *c, int plane_count, const float *planes, const float *P, const int rect[4], int op,
-                      uint64_t stats[4]) {
-    if (!c) return RTR_ERR_INVALID;
-    c->ov.other_call();
-    NEED(c, c->cap > 0, "rtr_select_points: no cloud");
-    NEED(c, plane_count >= 0 && plane_count <= RTR_MAX_CLIP_PLANES, "rtr_select_points: plane_count outside 0..RTR_MAX_CLIP_PLANES");
-    NEED(c, plane_count == 0 || planes != nullptr, "rtr_select_points: planes is NULL");
-    rtr::Clip clip{};
-    for (int j = 0; j < plane_count; ++j) {
-        for (int k = 0; k < 4; ++k) {
-            NEED(c, std::isfinite(planes[4 * j + k]), "rtr_select_points: a coefficient is not finite");
-            clip.p[j][k] = planes[4 * j + k];
-        }
-        NEED(c, clip.p[j][0] != 0.f || clip.p[j][1] != 0.f || clip.p[j][2] != 0.f, "rtr_select_points: a = b = c = 0");
-    }
-    clip.count = plane_count;
-    if (P) {
-        NEED(c, c->W > 0 && c->H > 0, "rtr_select_points: a rectangle needs a resolution (rtr_set_resolution)");
-        NEED(c, rect != nullptr, "rtr_select_points: rect is NULL");
-        NEED(c, 0 <= rect[0] && rect[0] < rect[2] && rect[2] <= c->W && 0 <= rect[1] && rect[1] < rect[3] && rect[3] <= c->H,
-             "rtr_select_points: the rectangle must satisfy 0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H");
-    }
-    const int base = op & ~RTR_SELECT_OUTSIDE;
-    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_points: unknown op");
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    if (int rc = need_upload_order(c, "formed")) return rc;
-    DevGuard g(c->device);
-    hipStream_t s = c->stream;
-    const uint64_t words = std::max<uint64_t>((c->n + 255) / 256, 1) * 8;  // (8 per 256-point chunk: whole-chunk stores)
-    if (!c->sel) {  // (a selection that does not exist yet is empty)
-        DevBufs buf;
-        uint32_t *w;
-        uint64_t *st;
-        HIP_TRY(c, buf.get(&w, words * 4));
-        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
-        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
-        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
-    }
-    const uint32_t *perm = c->reordered ? c->perm : nullptr;
-    if (perm && base == RTR_SELECT_REPLACE) HIP_TRY(c, hipMemsetAsync(c->sel, 0, words * 4, s));
-    if (stats) HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
-    rtr::Proj proj{};
-    if (P) proj = make_proj(P);
-    rtr::launch_select(s, cloud_of(c), c->bounds, clip, P ? &proj : nullptr, c->W, c->H, rect, base, (op & RTR_SELECT_OUTSIDE) != 0,
-                       c->sel, perm, stats ? c->sel_stats : nullptr);
-    if (int rc = launch_check(c, "select")) return rc;
-    if (!stats) return RTR_OK;
-    rtr::launch_select_count(s, c->sel, c->n, c->sel_stats);
-    if (int rc = launch_check(c, "select count")) return rc;
-    uint64_t out[4] = {0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, sizeof out, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    memcpy(stats, out, sizeof out);
-    return RTR_OK;
-}
-
-// ---- selection by a voxel grid (rtr.h, section 6g) ------------------------------------
-// Keys in upload-order slots (rtr::launch_voxel_keys), rocPRIM's stable sort by key, the head of every run of equal keys
-// into zeroed hit words, then selection := op(selection, hits).  Every buffer -- the selection's own when it does not
-// exist yet included -- is allocated before the first word changes, and the call waits for its work before the scratch
-// goes.  What rtr_select_points leaves alone stays as it is here too.
-namespace {
-struct EventSet {  // the stage boundaries of one call
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~EventSet() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-}  // namespace
-
-int rtr_select_voxel_grid(rtr_ctx *c, const float origin[3], const float cell[3], uint32_t min_count, int op, uint64_t stats[4]) {
-    if (!c) return RTR_ERR_INVALID;
-    c->ov.other_call();
-    NEED(c, c->cap > 0, "rtr_select_voxel_grid: no cloud");
-    NEED(c, origin != nullptr, "rtr_select_voxel_grid: origin is NULL");
-    NEED(c, cell != nullptr, "rtr_select_voxel_grid: cell is NULL");
-    rtr::VoxelGrid grid{};
-    for (int k = 0; k < 3; ++k) {
-        NEED(c, std::isfinite(origin[k]), "rtr_select_voxel_grid: origin is not finite");
-        NEED(c, std::isfinite(cell[k]) && cell[k] > 0.f, "rtr_select_voxel_grid: cell must be finite and > 0");
-        const float inv = 1.0f / cell[k];  // (one IEEE fp32 division: the build has no fast-math)
-        NEED(c, std::isfinite(inv) && inv > 0.f, "rtr_select_voxel_grid: the reciprocal of cell is not finite and > 0 in fp32");
-        grid.origin[k] = origin[k];
-        grid.inv[k] = inv;
-    }
-    NEED(c, min_count >= 1u, "rtr_select_voxel_grid: min_count must be >= 1");
-    const int base = op & ~RTR_SELECT_OUTSIDE;
-    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_voxel_grid: unknown op");
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    if (int rc = need_upload_order(c, "formed")) return rc;
-    DevGuard g(c->device);
-    hipStream_t s = c->stream;
-    const uint64_t n = c->n, nw = (n + 31) / 32;
-    const uint64_t words = std::max<uint64_t>((n + 255) / 256, 1) * 8;  // (the selection: 8 per 256-point chunk)
-    // every allocation first: a failure leaves the selection as it was
-    DevBufs buf;
-    uint64_t *k0, *k1, *st;
-    uint32_t *v0, *v1, *hit, *w = nullptr;
-    void *tmp;
-    size_t tmp_bytes = 0;
-    HIP_TRY(c, (hipError_t)rtr::voxel_sort_temp_bytes(n, &tmp_bytes));
-    HIP_TRY(c, buf.get(&k0, n * 8));
-    HIP_TRY(c, buf.get(&k1, n * 8));
-    HIP_TRY(c, buf.get(&v0, n * 4));
-    HIP_TRY(c, buf.get(&v1, n * 4));
-    HIP_TRY(c, buf.get(&hit, nw * 4));
-    HIP_TRY(c, buf.get(&tmp, tmp_bytes));
-    if (!c->sel) {
-        HIP_TRY(c, buf.get(&w, words * 4));
-        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
-    }
-    EventSet ev;
-    for (hipEvent_t &e : ev.e) HIP_TRY(c, hipEventCreate(&e));
-    if (w) {  // (a selection that does not exist yet is empty)
-        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
-        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
-    }
-    HIP_TRY(c, hipMemsetAsync(hit, 0, nw * 4, s));
-    HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
-    HIP_TRY(c, hipEventRecord(ev.e[0], s));
-    rtr::launch_voxel_keys(s, cloud_of(c), c->reordered ? c->perm : nullptr, grid, k0, v0);
-    if (int rc = launch_check(c, "voxel keys")) return rc;
-    HIP_TRY(c, hipEventRecord(ev.e[1], s));
-    if (n) HIP_TRY(c, (hipError_t)rtr::voxel_sort(s, tmp, tmp_bytes, k0, k1, v0, v1, n));
-    HIP_TRY(c, hipEventRecord(ev.e[2], s));
-    rtr::launch_voxel_heads(s, k1, v1, n, min_count, hit, c->sel_stats);
-    if (int rc = launch_check(c, "voxel heads")) return rc;
-    HIP_TRY(c, hipEventRecord(ev.e[3], s));
-    rtr::launch_voxel_combine(s, hit, n, base, (op & RTR_SELECT_OUTSIDE) != 0, c->sel);
-    if (int rc = launch_check(c, "voxel combine")) return rc;
-    rtr::launch_select_count(s, c->sel, n, c->sel_stats);
-    if (int rc = launch_check(c, "select count")) return rc;
-    uint64_t out[4] = {0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, sizeof out, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-        c->voxel_us[k] = (int)(ms * 1000.f + 0.5f);
-    }
-    if (stats) memcpy(stats, out, sizeof out);
-    return RTR_OK;
-}
-
-// ---- selection by neighbour count and by cluster (rtr.h, sections 6h and 6i) ----------
-// rtr_select_voxel_grid's pattern with a neighbour search between the sort and the combine (rtr_neighbours.hip,
-// rtr_clusters.hip).  Both calls share everything up to the work list (neighbour_search): it waits twice on the way --
-// for the key sweep's two counters (a point beyond the span fails the call; the points with a cell are the first
-// n - nonfinite sorted pairs) and for the number of occupied cells, which sizes the work list -- and both lie before the
-// first selection word changes, as does every allocation; a selection that does not exist yet is only created once
-// nothing can fail any more but a launch.
-namespace {
-struct NeighbourSearch {  // the scratch of one call and what the search found
-    DevBufs buf;
-    EventSet ev;
-    uint64_t *k0, *k1, *cn;  // cn: [0] non-finite points, [1] finite points beyond the span, [2] pair tests, [3] cells, [4] the list's cursor
-    uint32_t *v0, *v1, *hit, *items;
-    float4 *rec0, *rec1;
-    uint64_t n, m, cap;  // points, those of them with a cell (the first m sorted pairs), the work list's slots
-};
-
-// Allocates, sweeps, sorts, gathers and lists; leaves hit and sel_stats zeroed, the selection in existence and
-// ev.e[0 .. 2] recorded (before the keys, behind them, behind the sort).
-int neighbour_search(rtr_ctx *c, const char *who, float radius, NeighbourSearch &q) {
-    hipStream_t s = c->stream;
-    const uint64_t n = c->n, nw = (n + 31) / 32;
-    const uint64_t words = std::max<uint64_t>((n + 255) / 256, 1) * 8;  // (the selection: 8 per 256-point chunk)
-    DevBufs &buf = q.buf;
-    uint64_t *st;
-    uint32_t *w = nullptr;
-    void *tmp;
-    size_t tmp_bytes = 0;
-    HIP_TRY(c, (hipError_t)rtr::voxel_sort_temp_bytes(n, &tmp_bytes));
-    HIP_TRY(c, buf.get(&q.k0, n * 8));
-    HIP_TRY(c, buf.get(&q.k1, n * 8));
-    HIP_TRY(c, buf.get(&q.v0, n * 4));
-    HIP_TRY(c, buf.get(&q.v1, n * 4));
-    HIP_TRY(c, buf.get(&q.rec0, n * 16));
-    HIP_TRY(c, buf.get(&q.rec1, n * 16));
-    HIP_TRY(c, buf.get(&q.hit, nw * 4));
-    HIP_TRY(c, buf.get(&q.cn, 5 * sizeof(uint64_t)));
-    HIP_TRY(c, buf.get(&tmp, tmp_bytes));
-    if (!c->sel) {
-        HIP_TRY(c, buf.get(&w, words * 4));
-        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
-    }
-    for (hipEvent_t &e : q.ev.e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, hipMemsetAsync(q.hit, 0, nw * 4, s));
-    HIP_TRY(c, hipMemsetAsync(q.cn, 0, 5 * sizeof(uint64_t), s));
-    HIP_TRY(c, hipEventRecord(q.ev.e[0], s));
-    rtr::launch_neighbour_keys(s, cloud_of(c), c->reordered ? c->perm : nullptr, radius, q.k0, q.v0, q.rec0, q.cn);
-    if (int rc = launch_check(c, "neighbour keys")) return rc;
-    HIP_TRY(c, hipEventRecord(q.ev.e[1], s));
-    uint64_t host[4] = {0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(host, q.cn, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (host[1])
-        return fail(c, RTR_ERR_UNSUPPORTED, "%s: %llu finite points lie beyond the span of the internal grid (about 2^20 "
-                    "radius from the world origin on an axis)", who, (unsigned long long)host[1]);
-    const uint64_t nonfinite = host[0], m = n - nonfinite;  // (the pairs with a cell sort to the front)
-    if (n) HIP_TRY(c, (hipError_t)rtr::voxel_sort(s, tmp, tmp_bytes, q.k0, q.k1, q.v0, q.v1, n));
-    HIP_TRY(c, hipEventRecord(q.ev.e[2], s));
-    rtr::launch_neighbour_gather(s, q.v1, q.rec0, m, q.rec1);
-    if (int rc = launch_check(c, "neighbour gather")) return rc;
-    rtr::launch_neighbour_cells(s, q.k1, m, q.cn + 3);
-    if (int rc = launch_check(c, "neighbour cells")) return rc;
-    HIP_TRY(c, hipMemcpyAsync(host + 3, q.cn + 3, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    const uint64_t cap = std::min<uint64_t>(host[3] + m / 64, m);  // (a cell of len points: ceil(len / 64) <= 1 + len / 64 items, each of >= 1 point)
-    HIP_TRY(c, buf.get(&q.items, cap * 80));
-    if (w) {  // (a selection that does not exist yet is empty)
-        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
-        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
-    }
-    HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
-    rtr::launch_neighbour_items(s, q.k1, m, q.items, (uint32_t *)(q.cn + 4), cap);
-    if (int rc = launch_check(c, "neighbour items")) return rc;
-    q.n = n, q.m = m, q.cap = cap;
-    return RTR_OK;
-}
-
-// selection := op(selection, hits), the count, the wait; out: the four statistics, *tests: the pair tests; us[0 .. 2]:
-// the stage times between the search's events and ev.e[3], which the caller has recorded
-int neighbour_finish(rtr_ctx *c, const char *what, NeighbourSearch &q, int op, uint64_t out[4], int us[3], int *tests_k) {
-    hipStream_t s = c->stream;
-    const int base = op & ~RTR_SELECT_OUTSIDE;
-    rtr::launch_voxel_combine(s, q.hit, q.n, base, (op & RTR_SELECT_OUTSIDE) != 0, c->sel);
-    if (int rc = launch_check(c, what)) return rc;
-    rtr::launch_select_count(s, c->sel, q.n, c->sel_stats);
-    if (int rc = launch_check(c, "select count")) return rc;
-    uint64_t tests = 0;
-    HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&tests, q.cn + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, q.ev.e[k], q.ev.e[k + 1]));
-        us[k] = (int)(ms * 1000.f + 0.5f);
-    }
-    *tests_k = (int)std::min<uint64_t>(tests / 1000, 0x7FFFFFFF);
-    return RTR_OK;
-}
-}  // namespace
-
-int rtr_select_neighbours(rtr_ctx *c, float radius, uint32_t min_neighbours, int op, uint64_t stats[4]) {
-    if (!c) return RTR_ERR_INVALID;
-    c->ov.other_call();
-    NEED(c, c->cap > 0, "rtr_select_neighbours: no cloud");
-    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_select_neighbours: radius must be finite and > 0");
-    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
-    NEED(c, std::isnormal(r2), "rtr_select_neighbours: the square of radius is not a finite normal fp32 number");
-    NEED(c, min_neighbours >= 1u, "rtr_select_neighbours: min_neighbours must be >= 1");
-    const int base = op & ~RTR_SELECT_OUTSIDE;
-    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_neighbours: unknown op");
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    if (int rc = need_upload_order(c, "formed")) return rc;
-    DevGuard g(c->device);
-    hipStream_t s = c->stream;
-    NeighbourSearch q;
-    if (int rc = neighbour_search(c, "rtr_select_neighbours", radius, q)) return rc;
-    rtr::launch_neighbour_count(s, q.rec1, q.items, (const uint32_t *)(q.cn + 4), q.cap, r2, min_neighbours, q.hit, c->sel_stats, q.cn + 2);
-    if (int rc = launch_check(c, "neighbour count")) return rc;
-    HIP_TRY(c, hipEventRecord(q.ev.e[3], s));
-    HIP_TRY(c, d2d(s, c->sel_stats + 3, q.cn, sizeof(uint64_t)));
-    uint64_t out[4] = {0, 0, 0, 0};
-    if (int rc = neighbour_finish(c, "neighbour combine", q, op, out, c->neighbours_us, &c->neighbours_tests_k)) return rc;
-    if (stats) memcpy(stats, out, sizeof out);
-    return RTR_OK;
-}
-
-// ---- selection by connected cluster (rtr.h, section 6i) -------------------------------
-// The union-find's four arrays (parent, size, smallest upload index, seed flag: n words each) live in the unsorted
-// records' buffer, which is dead once the gather has run; the labels are written into the unsorted keys' buffer, dead
-// since the sort, and copied to the caller's array -- host or device memory, told apart as rtr_extract_points does --
-// once everything else has succeeded.
-int rtr_select_clusters(rtr_ctx *c, float radius, uint32_t min_points, uint32_t max_points, int flags, int op, uint32_t *labels,
-                        uint64_t stats[4]) {
-    if (!c) return RTR_ERR_INVALID;
-    c->ov.other_call();
-    NEED(c, c->cap > 0, "rtr_select_clusters: no cloud");
-    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_select_clusters: radius must be finite and > 0");
-    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
-    NEED(c, std::isnormal(r2), "rtr_select_clusters: the square of radius is not a finite normal fp32 number");
-    NEED(c, min_points >= 1u, "rtr_select_clusters: min_points must be >= 1");
-    NEED(c, max_points == 0u || max_points >= min_points, "rtr_select_clusters: max_points must be 0 (unbounded) or >= min_points");
-    NEED(c, (flags & ~RTR_CLUSTER_SEEDED) == 0, "rtr_select_clusters: unknown bits in flags");
-    const int base = op & ~RTR_SELECT_OUTSIDE;
-    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_clusters: unknown op");
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    if (int rc = need_upload_order(c, "formed")) return rc;
-    DevGuard g(c->device);
-    hipStream_t s = c->stream;
-    const bool seeded = (flags & RTR_CLUSTER_SEEDED) != 0, labels_dev = labels && on_device(labels);
-    NeighbourSearch q;
-    if (int rc = neighbour_search(c, "rtr_select_clusters", radius, q)) return rc;
-    const uint64_t n = q.n;
-    uint32_t *parent = reinterpret_cast<uint32_t *>(q.rec0), *size = parent + n, *minu = size + n, *seed = minu + n;
-    uint32_t *lab = labels ? reinterpret_cast<uint32_t *>(q.k0) : nullptr;
-    rtr::launch_cluster_init(s, n, parent, size, minu, seed);
-    if (int rc = launch_check(c, "cluster init")) return rc;
-    rtr::launch_cluster_link(s, q.rec1, q.items, (const uint32_t *)(q.cn + 4), q.cap, r2, parent, q.cn + 2);
-    if (int rc = launch_check(c, "cluster link")) return rc;
-    rtr::launch_cluster_flatten(s, q.v1, n, seeded ? c->sel : nullptr, parent, size, minu, seed);
-    if (int rc = launch_check(c, "cluster flatten")) return rc;
-    rtr::launch_cluster_hits(s, q.v1, n, parent, size, minu, seed, min_points, max_points, seeded, q.hit, lab, c->sel_stats);
-    if (int rc = launch_check(c, "cluster hits")) return rc;
-    HIP_TRY(c, hipEventRecord(q.ev.e[3], s));
-    uint64_t out[4] = {0, 0, 0, 0};
-    if (int rc = neighbour_finish(c, "cluster combine", q, op, out, c->clusters_us, &c->clusters_tests_k)) return rc;
-    if (lab) {  // (behind everything that can fail: the caller's array changes only when the call succeeds)
-        HIP_TRY(c, hipMemcpyAsync(labels, lab, n * 4, labels_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
-    if (stats) memcpy(stats, out, sizeof out);
-    return RTR_OK;
-}
-
-// ---- selection by distance to given points (rtr.h, section 6k) ------------------------
-// The given points go through section 6h's key, sort and gather (rtr_near.hip's k_near_keys over the plain strided
-// array); the resident side is ONE sweep over the chunks that sorts and gathers nothing.  One wait on the way, for the
-// given points' counters and box: a point beyond the span fails the call there, before anything has changed.  Every
-// allocation lies before it too; a selection that does not exist yet is only created once nothing can fail any more but
-// a launch; the caller's near words and stats are written last.
-int rtr_select_near(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, float radius, int flags, int op, uint32_t *near_words,
-                    uint64_t stats[4]) {
-    if (!c) return RTR_ERR_INVALID;
-    c->ov.other_call();
-    NEED(c, c->cap > 0, "rtr_select_near: no cloud");
-    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_select_near: radius must be finite and > 0");
-    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
-    NEED(c, std::isnormal(r2), "rtr_select_near: the square of radius is not a finite normal fp32 number");
-    NEED(c, count == 0 || xyz != nullptr, "rtr_select_near: xyz is NULL");
-    NEED(c, xs >= 12 && xs % 4 == 0, "rtr_select_near: xyz_stride_bytes must be >= 12 and a multiple of 4");
-    NEED(c, (flags & ~RTR_NEAR_GIVEN_ONLY) == 0, "rtr_select_near: unknown bits in flags");
-    const bool given_only = (flags & RTR_NEAR_GIVEN_ONLY) != 0;
-    const int base = op & ~RTR_SELECT_OUTSIDE;
-    NEED(c, op >= 0 && (base <= RTR_SELECT_INTERSECT || base == RTR_SELECT_TOGGLE), "rtr_select_near: unknown op");
-    NEED(c, !given_only || op == 0, "rtr_select_near: op must be 0 with RTR_NEAR_GIVEN_ONLY");
-    NEED(c, !given_only || near_words != nullptr, "rtr_select_near: near_words is NULL with RTR_NEAR_GIVEN_ONLY");
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    if (count >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "rtr_select_near: given indices are 32-bit: count is %llu", (unsigned long long)count);
-    if (!given_only)  // (the near bits go by GIVEN index: they need no upload order)
-        if (int rc = need_upload_order(c, "formed", ", or ask for the given side alone (flags = RTR_NEAR_GIVEN_ONLY)")) return rc;
-    DevGuard g(c->device);
-    hipStream_t s = c->stream;
-    const uint64_t n = c->n, nw = (n + 31) / 32, gw = (count + 31) / 32;
-    const uint64_t words = std::max<uint64_t>((n + 255) / 256, 1) * 8;   // (the selection: 8 per 256-point chunk)
-    const uint64_t gwords = std::max<uint64_t>((count + 255) / 256, 1) * 8;  // (the near words, padded for launch_select_count)
-    const bool xyz_dev = count && on_device(xyz), near_dev = near_words && on_device(near_words);
-    // every allocation first: a failure leaves everything as it was
-    DevBufs buf;
-    EventSet ev;
-    uint64_t *k0, *k1, *cn, *st = nullptr;  // cn: [0] non-finite given points, [1] those beyond the span, [2] near bits, [4 .. 7] the sweep's, [8 .. 10] the box
-    uint32_t *v0, *v1, *hit = nullptr, *nearw = nullptr, *w = nullptr;
-    float4 *rec0, *rec1;
-    const uint8_t *gxyz = (const uint8_t *)xyz;
-    uint8_t *stage = nullptr;
-    void *tmp;
-    size_t tmp_bytes = 0;
-    const size_t gbytes = count ? (size_t)(count - 1) * xs + 12 : 0;
-    HIP_TRY(c, (hipError_t)rtr::voxel_sort_temp_bytes(std::max<uint64_t>(count, 1), &tmp_bytes));
-    HIP_TRY(c, buf.get(&k0, count * 8));
-    HIP_TRY(c, buf.get(&k1, count * 8));
-    HIP_TRY(c, buf.get(&v0, count * 4));
-    HIP_TRY(c, buf.get(&v1, count * 4));
-    HIP_TRY(c, buf.get(&rec0, count * 16));
-    HIP_TRY(c, buf.get(&rec1, count * 16));
-    HIP_TRY(c, buf.get(&cn, 12 * sizeof(uint64_t)));
-    HIP_TRY(c, buf.get(&tmp, tmp_bytes));
-    if (count && !xyz_dev) HIP_TRY(c, buf.get(&stage, gbytes));
-    if (!given_only) HIP_TRY(c, buf.get(&hit, nw * 4));
-    if (near_words) HIP_TRY(c, buf.get(&nearw, gwords * 4));
-    if (!given_only && !c->sel) {
-        HIP_TRY(c, buf.get(&w, words * 4));
-        HIP_TRY(c, buf.get(&st, 4 * sizeof(uint64_t)));
-    }
-    for (int k = 0; k < 3; ++k) HIP_TRY(c, hipEventCreate(&ev.e[k]));
-    HIP_TRY(c, hipMemsetAsync(cn, 0, 12 * sizeof(uint64_t), s));
-    HIP_TRY(c, hipMemsetAsync(cn + 8, 0xFF, 3 * sizeof(uint32_t), s));  // (box: the minima start at 2^32 - 1, the maxima at 0)
-    if (hit) HIP_TRY(c, hipMemsetAsync(hit, 0, nw * 4, s));
-    if (nearw) HIP_TRY(c, hipMemsetAsync(nearw, 0, gwords * 4, s));
-    HIP_TRY(c, hipEventRecord(ev.e[0], s));
-    if (stage) {  // (the given points are read before the call returns: one copy at the caller's stride)
-        HIP_TRY(c, hipMemcpyAsync(stage, xyz, gbytes, hipMemcpyHostToDevice, s));
-        gxyz = stage;
-    }
-    rtr::launch_near_keys(s, gxyz, xs, count, radius, k0, v0, rec0, cn, reinterpret_cast<uint32_t *>(cn + 8));
-    if (int rc = launch_check(c, "near keys")) return rc;
-    uint64_t host[12] = {};
-    HIP_TRY(c, hipMemcpyAsync(host, cn, sizeof host, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (host[1])
-        return fail(c, RTR_ERR_UNSUPPORTED, "rtr_select_near: %llu finite given points lie beyond the span of the internal grid (about "
-                    "2^20 radius from the world origin on an axis)", (unsigned long long)host[1]);
-    const uint64_t nonfinite = host[0], m = count - nonfinite;  // (the pairs with a cell sort to the front)
-    if (count) HIP_TRY(c, (hipError_t)rtr::voxel_sort(s, tmp, tmp_bytes, k0, k1, v0, v1, count));
-    rtr::launch_neighbour_gather(s, v1, rec0, m, rec1);
-    if (int rc = launch_check(c, "near gather")) return rc;
-    HIP_TRY(c, hipEventRecord(ev.e[1], s));
-    if (w) {  // (a selection that does not exist yet is empty)
-        HIP_TRY(c, hipMemsetAsync(w, 0, words * 4, s));
-        buf.swap_in(c->sel, w); buf.swap_in(c->sel_stats, st);
-    }
-    if (!given_only) HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
-    uint64_t sweep[4] = {0, 0, (n + 255) / 256, 0};  // (no given point has a cell: every chunk is decided without a launch)
-    if (m) {
-        double glo[3], ghi[3];
-        uint32_t box[6];
-        memcpy(box, host + 8, sizeof box);
-        rtr::near_box_from_keys(box, glo, ghi);
-        rtr::launch_near_sweep(s, cloud_of(c), c->bounds, c->reordered ? c->perm : nullptr, k1, rec1, m, radius, r2, glo, ghi, hit, nearw, cn + 4);
-        if (int rc = launch_check(c, "near sweep")) return rc;
-    }
-    uint64_t out[4] = {0, 0, 0, nonfinite};
-    if (!given_only) {
-        rtr::launch_voxel_combine(s, hit, n, base, (op & RTR_SELECT_OUTSIDE) != 0, c->sel);
-        if (int rc = launch_check(c, "near combine")) return rc;
-        rtr::launch_select_count(s, c->sel, n, c->sel_stats);
-        if (int rc = launch_check(c, "select count")) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out, c->sel_stats, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    }
-    if (nearw && count) {
-        rtr::launch_select_count(s, nearw, count, cn + 2);
-        if (int rc = launch_check(c, "near count")) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out + 2, cn + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(c, hipEventRecord(ev.e[2], s));
-    if (m) HIP_TRY(c, hipMemcpyAsync(sweep, cn + 4, sizeof sweep, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
-    out[1] = sweep[0];
-    for (int k = 0; k < 2; ++k) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-        c->near_us[k] = (int)(ms * 1000.f + 0.5f);
-    }
-    c->near_tests_k = (int)std::min<uint64_t>(sweep[1] / 1000, 0x7FFFFFFF);
-    c->near_chunks[0] = (int)std::min<uint64_t>(sweep[2], 0x7FFFFFFF), c->near_chunks[1] = (int)std::min<uint64_t>(sweep[3], 0x7FFFFFFF);
-    if (near_words && gw) {  // (behind everything that can fail: the caller's words change only when the call succeeds)
-        HIP_TRY(c, hipMemcpyAsync(near_words, nearw, gw * 4, near_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-    }
-    if (stats) memcpy(stats, out, sizeof out);
-    return RTR_OK;
-}
-
-// ---- counting points in bands, fitting a plane (rtr.h, section 6j) --------------------
-// Both calls read the coordinates (and, flagged, the selection) and change nothing.  count_bands is the part they share:
-// the counters, the selection in resident order when the cloud is sorted (rtr::launch_sel_gather into scratch, once per
-// call), the passes of rtr::launch_count_bands, one copy and one wait.  Results reach the caller's arrays only on success.
-namespace {
-int check_bands_call(rtr_ctx *c, const char *who, int flags) {
-    char msg[160];
-    if (c->cap == 0) { snprintf(msg, sizeof msg, "%s: no cloud", who); NEED(c, false, msg); }
-    if ((flags & ~RTR_BANDS_SELECTED) != 0) { snprintf(msg, sizeof msg, "%s: unknown bits in flags", who); NEED(c, false, msg); }
-    return RTR_OK;
-}
-// counts[count] and st[4] (host, both written only on success) for `count` valid bands
-int count_bands(rtr_ctx *c, uint32_t count, const float *bands, bool selected, uint64_t *counts, uint64_t st[4]) {
-    hipStream_t s = c->stream;
-    const uint64_t n = c->n, nch = (n + 255) / 256;
-    std::vector<uint64_t> host(4 + (size_t)count, 0);
-    if (selected && !c->sel) {  // (an empty population: every chunk is outside for every band)
-        host[1] = nch * count;
-    } else {
-        DevBufs buf;
-        uint64_t *dev;
-        const uint32_t *res = nullptr;
-        HIP_TRY(c, buf.get(&dev, host.size() * sizeof(uint64_t)));
-        if (selected && c->reordered) {
-            uint32_t *r;
-            HIP_TRY(c, buf.get(&r, std::max<uint64_t>(nch, 1) * 8 * 4));
-            rtr::launch_sel_gather(s, c->sel, c->perm, n, r);
-            if (int rc = launch_check(c, "bands gather")) return rc;
-            res = r;
-        } else if (selected) {
-            res = c->sel;  // (upload order is the resident order)
-        }
-        HIP_TRY(c, hipMemsetAsync(dev, 0, host.size() * sizeof(uint64_t), s));
-        if (res) {
-            rtr::launch_select_count(s, res, n, dev);
-            if (int rc = launch_check(c, "bands population")) return rc;
-        }
-        rtr::launch_count_bands(s, cloud_of(c), c->bounds, bands, count, res, dev + 4, dev);
-        if (int rc = launch_check(c, "count bands")) return rc;
-        HIP_TRY(c, hipMemcpyAsync(host.data(), dev, host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));  // (always: the counts go to the host, the scratch with this call)
-        if (!res) host[0] = n;
-    }
-    memcpy(counts, host.data() + 4, (size_t)count * sizeof(uint64_t));
-    memcpy(st, host.data(), 4 * sizeof(uint64_t));
-    return RTR_OK;
-}
-}  // namespace
-
-int rtr_count_in_bands(rtr_ctx *c, uint32_t count, const float *bands, int flags, uint64_t *counts, uint64_t stats[4]) {
-    if (!c) return RTR_ERR_INVALID;
-    c->ov.other_call();
-    if (int rc = check_bands_call(c, "rtr_count_in_bands", flags)) return rc;
-    NEED(c, count >= 1u && count <= RTR_MAX_BANDS, "rtr_count_in_bands: count outside 1..RTR_MAX_BANDS");
-    NEED(c, bands != nullptr, "rtr_count_in_bands: bands is NULL");
-    NEED(c, counts != nullptr, "rtr_count_in_bands: counts is NULL");
-    for (uint32_t k = 0; k < count; ++k) {
-        const float *b = bands + 5 * (size_t)k;
-        for (int j = 0; j < 5; ++j) NEED(c, std::isfinite(b[j]), "rtr_count_in_bands: a value in bands is not finite");
-        NEED(c, b[0] != 0.f || b[1] != 0.f || b[2] != 0.f, "rtr_count_in_bands: a band of bands has a = b = c = 0");
-    }
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    const bool selected = (flags & RTR_BANDS_SELECTED) != 0;
-    if (selected)
-        if (int rc = need_upload_order(c, "read from the selection", " (flags = RTR_BANDS_SELECTED)")) return rc;
-    DevGuard g(c->device);
-    uint64_t st[4];
-    std::vector<uint64_t> out(count);
-    if (int rc = count_bands(c, count, bands, selected, out.data(), st)) return rc;
-    memcpy(counts, out.data(), (size_t)count * sizeof(uint64_t));
-    if (stats) memcpy(stats, st, sizeof st);
-    return RTR_OK;
-}
-
-// The sample: ranks from rtr_plane_fit.h's sampler, their upload indices (flagged: through the selection words copied to
-// the host and the prefix sums of their popcounts), one bit per distinct index into zeroed device words
-// (rtr::launch_set_bits), and those points through rtr_extract_points -- in ascending index order, so a draw finds its
-// coordinates by binary search among the sorted distinct indices.
-int rtr_fit_plane(rtr_ctx *c, float dist, uint32_t iterations, uint64_t seed, int flags, float plane[4], uint64_t stats[4]) {
-    if (!c) return RTR_ERR_INVALID;
-    c->ov.other_call();
-    if (int rc = check_bands_call(c, "rtr_fit_plane", flags)) return rc;
-    NEED(c, std::isfinite(dist) && dist >= 0.f, "rtr_fit_plane: dist must be finite and >= 0");
-    NEED(c, iterations >= 1u && iterations <= RTR_MAX_BANDS, "rtr_fit_plane: iterations outside 1..RTR_MAX_BANDS");
-    NEED(c, plane != nullptr, "rtr_fit_plane: plane is NULL");
-    if (c->n >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
-    if (int rc = need_upload_order(c, "sampled")) return rc;
-    DevGuard g(c->device);
-    hipStream_t s = c->stream;
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool selected = (flags & RTR_BANDS_SELECTED) != 0;
-    const uint64_t n = c->n, nw = (n + 31) / 32;
-    uint64_t m = n;
-    std::vector<uint32_t> selw, pre;  // flagged: the selection words and pre[w] = the selected points below word w
-    if (selected) {
-        m = 0;
-        if (c->sel && nw) {
-            selw.resize(nw), pre.resize(nw + 1);
-            HIP_TRY(c, hipMemcpyAsync(selw.data(), c->sel, nw * 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(c, hipStreamSynchronize(s));
-            pre[0] = 0;
-            for (uint64_t w = 0; w < nw; ++w) pre[w + 1] = pre[w] + (uint32_t)__builtin_popcount(selw[w]);
-            m = pre[nw];
-        }
-    }
-    const uint32_t draws = 3u * iterations;
-    std::vector<uint64_t> rank(draws), cnt;
-    std::vector<uint32_t> idx(draws), uniq;
-    std::vector<float> xyz, planes(4 * (size_t)iterations), bands;
-    std::vector<uint32_t> cand;  // the non-degenerate candidates, ascending
-    if (m >= 3) {
-        for (uint32_t t = 0; t < draws; ++t) {
-            rank[t] = rtr::plane_draw(seed, t) % m;
-            uint32_t u = (uint32_t)rank[t];
-            if (selected) {  // the rank-th set bit
-                const uint64_t w = (uint64_t)(std::upper_bound(pre.begin(), pre.end(), (uint32_t)rank[t]) - pre.begin()) - 1;
-                uint32_t bits = selw[w];
-                for (uint32_t k = (uint32_t)rank[t] - pre[w]; k > 0; --k) bits &= bits - 1;
-                u = (uint32_t)(32 * w) + (uint32_t)__builtin_ctz(bits);
-            }
-            idx[t] = u;
-        }
-        uniq = idx;
-        std::sort(uniq.begin(), uniq.end());
-        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-        const uint64_t k = uniq.size();
-        DevBufs buf;  // the sample's bits are set on the device: no word of them crosses the bus
-        uint32_t *dw, *di;
-        HIP_TRY(c, buf.get(&dw, nw * 4));
-        HIP_TRY(c, buf.get(&di, k * 4));
-        HIP_TRY(c, hipMemsetAsync(dw, 0, nw * 4, s));
-        HIP_TRY(c, hipMemcpyAsync(di, uniq.data(), k * 4, hipMemcpyHostToDevice, s));
-        rtr::launch_set_bits(s, di, k, dw);
-        if (int rc = launch_check(c, "sample bits")) return rc;
-        xyz.resize(3 * k);
-        if (int rc = rtr_extract_points(c, dw, nw, 0, k, xyz.data(), 12, nullptr, 0, nullptr, nullptr)) return rc;
-        for (uint32_t q = 0; q < iterations; ++q) {
-            const float *p[3];
-            for (int j = 0; j < 3; ++j)
-                p[j] = xyz.data() + 3 * (size_t)(std::lower_bound(uniq.begin(), uniq.end(), idx[3 * q + j]) - uniq.begin());
-            float band[5];
-            if (!rtr::plane_candidate(p[0], p[1], p[2], &rank[3 * (size_t)q], &planes[4 * (size_t)q])) continue;
-            rtr::plane_band(&planes[4 * (size_t)q], dist, band);
-            if (!std::isfinite(band[3]) || !std::isfinite(band[4])) continue;
-            cand.push_back(q);
-            bands.insert(bands.end(), band, band + 5);
-        }
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    uint64_t out[4] = {0, 0, 0, m};
-    float win[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!cand.empty()) {
-        uint64_t st[4];
-        cnt.resize(cand.size());
-        if (int rc = count_bands(c, (uint32_t)cand.size(), bands.data(), selected, cnt.data(), st)) return rc;
-        size_t best = 0;
-        for (size_t j = 1; j < cand.size(); ++j)
-            if (cnt[j] > cnt[best]) best = j;  // (ties: the smallest c stays)
-        out[0] = cnt[best], out[1] = cand.size(), out[2] = cand[best];
-        memcpy(win, &planes[4 * (size_t)cand[best]], sizeof win);
-    }
-    const auto t2 = std::chrono::steady_clock::now();
-    c->plane_us[0] = (int)std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
-    c->plane_us[1] = (int)std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count();
-    memcpy(plane, win, sizeof win);
-    if (stats) memcpy(stats, out, sizeof out);
-    return RTR_OK;
-}
-
-int rtr_clear_selection(rtr_ctx *c) {
-    if (!c) return RTR_ERR_INVALID;
-    c->ov.other_call();
-    DevGuard g(c->device);
-    free_select(c);
     return RTR_OK;
 }
 

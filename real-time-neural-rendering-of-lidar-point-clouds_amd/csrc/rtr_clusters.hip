@@ -117,8 +117,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_link(const float4 *__restrict__ r
                 for (int j = 0; j < m; ++j) {
                     const float cx = __int_as_float(__builtin_amdgcn_readlane(cxi, j)), cy = __int_as_float(__builtin_amdgcn_readlane(cyi, j)),
                                 cz = __int_as_float(__builtin_amdgcn_readlane(czi, j));
-                    const float dx = f_sub(x, cx), dy = f_sub(y, cy), dz = f_sub(z, cz);
-                    const float d2 = f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
+                    const float d2 = pair_dist2(x, y, z, cx, cy, cz);
                     const uint32_t cp = c0 + (uint32_t)j;
                     const uint32_t par = (uint32_t)__builtin_amdgcn_readlane(cpi, j);  // parent[cp] a moment ago: an ancestor of cp
                     if (live && d2 <= r2 && cp < qp && par != mine) mine = cl_unite(parent, mine, par);

@@ -1,6 +1,7 @@
 // rtr_device.h -- device-side helpers shared by the kernel files (rtr_kernels.hip: the frame path, the upload, the
 // point pass, extract and transform; rtr_cloud_kernels.hip: keep mask, remove, scan, select; rtr_voxel.hip and
-// rtr_neighbours.hip, through rtr_key_sweep.h: the key sweeps of the voxel grid and the neighbour search).
+// rtr_neighbours.hip, through rtr_key_sweep.h: the key sweeps of the voxel grid and the neighbour search;
+// rtr_neighbours.hip, rtr_clusters.hip and rtr_near.hip: the pair test and the binary search in the sorted keys).
 // Device-only: every function is __device__ __forceinline__, so no device call crosses a translation unit and no
 // relocatable device code is needed.  Included by those files and nothing else; the arithmetic contract of
 // rtr_kernels.hip (-ffp-contract=off) holds for all.
@@ -20,6 +21,24 @@ constexpr int kBlock = 256;   // 4 waves
 __device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
 __device__ __forceinline__ float f_add(float a, float b) { return a + b; }
 __device__ __forceinline__ float f_sub(float a, float b) { return a - b; }
+
+// the pair test of the radius searches (neighbours, clusters, near): the squared distance of (x, y, z) and (cx, cy, cz) as
+// three differences, three products and two sums, each rounded on its own, in the order ((dx dx + dy dy) + dz dz)
+__device__ __forceinline__ float pair_dist2(float x, float y, float z, float cx, float cy, float cz) {
+    const float dx = f_sub(x, cx), dy = f_sub(y, cy), dz = f_sub(z, cz);
+    return f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
+}
+
+// the first index in [0, m) of the sorted keys whose key is >= target (m: none)
+__device__ __forceinline__ uint32_t key_lower_bound(const uint64_t *__restrict__ keys, uint32_t m, uint64_t target) {
+    uint32_t lo = 0, hi = m;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < target) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
 
 // ---------------------------------------------------------------------------------
 // projection of one point: render.cu:33-40 (matmul rows 0..2), :63 (z cull),

@@ -70,16 +70,6 @@ __global__ __launch_bounds__(kBlock) void k_near_keys(const uint8_t *__restrict_
     }
 }
 
-// the first index in [0, m) whose key is >= target (m: none)
-__device__ __forceinline__ uint32_t near_lower_bound(const uint64_t *__restrict__ keys, uint32_t m, uint64_t target) {
-    uint32_t lo = 0, hi = m;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < target) lo = mid + 1u;
-        else hi = mid;
-    }
-    return lo;
-}
 // the key of an IN-SPAN cell given by its three indices (kNbCellMin .. kNbCellMax each)
 __device__ __forceinline__ uint64_t near_cell_key(int32_t cx, int32_t cy, int32_t cz) {
     return ((uint64_t)(uint32_t)(cx + kNbBias) << 42) | ((uint64_t)(uint32_t)(cy + kNbBias) << 21) | (uint64_t)(uint32_t)(cz + kNbBias);
@@ -146,8 +136,7 @@ __device__ __forceinline__ uint32_t near_test4(const float xs[4], const float ys
     uint32_t acc = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float dx = f_sub(xs[k], cx), dy = f_sub(ys[k], cy), dz = f_sub(zs[k], cz);
-        const float d2 = f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
+        const float d2 = pair_dist2(xs[k], ys[k], zs[k], cx, cy, cz);
         acc |= (d2 <= r2 ? 1u : 0u) << k;
     }
     return acc;
@@ -182,7 +171,7 @@ __device__ __forceinline__ void near_chunk(const NearArgs &a, uint64_t chunk, bo
             bool any = false;  // slab t holds a key at all between its first and its last cell of the range (a superset of them)
             if ((uint32_t)lane < (uint32_t)nx) {
                 const int32_t cx = c0[0] + lane;
-                any = near_lower_bound(a.keys, a.m, near_cell_key(cx, c1[1], c1[2]) + 1u) > near_lower_bound(a.keys, a.m, near_cell_key(cx, c0[1], c0[2]));
+                any = key_lower_bound(a.keys, a.m, near_cell_key(cx, c1[1], c1[2]) + 1u) > key_lower_bound(a.keys, a.m, near_cell_key(cx, c0[1], c0[2]));
             }
             if (__ballot(any) == 0ull) {
                 w.skipped += 1u;
@@ -198,8 +187,8 @@ __device__ __forceinline__ void near_chunk(const NearArgs &a, uint64_t chunk, bo
         rlo = rhi = 0u;
         if (col < ncols) {
             colx = c0[0] + (int32_t)(col / ny), coly = c0[1] + (int32_t)(col % ny);
-            rlo = near_lower_bound(a.keys, a.m, near_cell_key(colx, coly, c0[2]));
-            rhi = near_lower_bound(a.keys, a.m, near_cell_key(colx, coly, c1[2]) + 1u);
+            rlo = key_lower_bound(a.keys, a.m, near_cell_key(colx, coly, c0[2]));
+            rhi = key_lower_bound(a.keys, a.m, near_cell_key(colx, coly, c1[2]) + 1u);
         }
     };
     if (!per_point) {
@@ -311,12 +300,11 @@ __device__ __forceinline__ void near_chunk(const NearArgs &a, uint64_t chunk, bo
                 const int32_t cx = q[0] + d / 3 - 1, cy = q[1] + d % 3 - 1;
                 if (cx < cmin || cx > cmax || cy < cmin || cy > cmax) continue;
                 if (!NEARW && ((hb >> k) & 1u)) break;
-                const uint32_t b = near_lower_bound(a.keys, a.m, near_cell_key(cx, cy, z0));
-                const uint32_t e = near_lower_bound(a.keys, a.m, near_cell_key(cx, cy, z1) + 1u);
+                const uint32_t b = key_lower_bound(a.keys, a.m, near_cell_key(cx, cy, z0));
+                const uint32_t e = key_lower_bound(a.keys, a.m, near_cell_key(cx, cy, z1) + 1u);
                 for (uint32_t j = b; j < e; ++j) {
                     const float4 cd = a.rec[j];
-                    const float dx = f_sub(p[0], cd.x), dy = f_sub(p[1], cd.y), dz = f_sub(p[2], cd.z);
-                    const float d2 = f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
+                    const float d2 = pair_dist2(p[0], p[1], p[2], cd.x, cd.y, cd.z);
                     w.lane_tests += 1u;
                     if (d2 <= a.r2) {
                         hb |= 1u << k;

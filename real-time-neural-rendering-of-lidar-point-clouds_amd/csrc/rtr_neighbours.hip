@@ -55,17 +55,6 @@ __global__ __launch_bounds__(kBlock) void k_nb_cells(const uint64_t *__restrict_
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(cells, (unsigned long long)cnt);
 }
 
-// the first index in [0, m) whose key is >= target (m: none)
-__device__ __forceinline__ uint32_t lower_bound(const uint64_t *__restrict__ keys, uint32_t m, uint64_t target) {
-    uint32_t lo = 0, hi = m;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < target) lo = mid + 1u;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ uint32_t bcast(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
 
 // ---------------------------------------------------------------------------------
@@ -102,7 +91,7 @@ __global__ __launch_bounds__(kBlock) void k_nb_items(const uint64_t *__restrict_
                 const int t = lane < 9 ? lane : lane - 9;
                 const uint64_t target = lane == 18 ? kh + 1u
                                                    : neighbour_key_offset(kh, t / 3 - 1, t % 3 - 1, lane < 9 ? -1 : 1) + (lane < 9 ? 0u : 1u);
-                r = lower_bound(keys, m, target);
+                r = key_lower_bound(keys, m, target);
             }
             const uint32_t len = bcast(r, 18) - jh, nsl = (len + 63u) / 64u;
             uint32_t base = 0;
@@ -172,8 +161,7 @@ __global__ __launch_bounds__(kBlock) void k_nb_count(const float4 *__restrict__ 
                     const float cx = __int_as_float(__builtin_amdgcn_readlane(cxi, j)), cy = __int_as_float(__builtin_amdgcn_readlane(cyi, j)),
                                 cz = __int_as_float(__builtin_amdgcn_readlane(czi, j));
                     const uint32_t cu = (uint32_t)__builtin_amdgcn_readlane(cui, j);
-                    const float dx = f_sub(x, cx), dy = f_sub(y, cy), dz = f_sub(z, cz);
-                    const float d2 = f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
+                    const float d2 = pair_dist2(x, y, z, cx, cy, cz);
                     cnt += (d2 <= r2 && cu != u) ? 1u : 0u;
                 }
                 n_tests += (uint64_t)m * nlive;
