@@ -217,6 +217,9 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          the combine and the counts; "near_pair_tests_k" reads that call's pair tests, in thousands, and
  *          "near_chunks_skipped" / "near_chunks_decoded" its resident chunks decided without reading their coordinates /
  *          decoded (all three saturating at 2^31 - 1).
+ *  rtr_get_option("nearest_given_us" / "nearest_sweep_us" / "nearest_pair_tests_k" / "nearest_chunks_skipped" /
+ *          "nearest_chunks_decoded") read the same five for the last rtr_nearest_points (section 6l): the sweep's time
+ *          includes the unpacking of the given side.
  *  rtr_get_option("plane_sample_us" / "plane_count_us") read the host time, in microseconds and with its waits, that the
  *          last rtr_fit_plane (section 6j) spent drawing and extracting its sample and counting its candidates. */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
@@ -1052,6 +1055,66 @@ int rtr_fit_plane(rtr_ctx *ctx, float dist, uint32_t iterations, uint64_t seed, 
 #define RTR_NEAR_GIVEN_ONLY 1   /* flags: only near_words and stats[2..3]; the selection is neither read, changed nor created */
 int rtr_select_near(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, uint64_t count, float radius,
                     int flags, int op, uint32_t *near_words, uint64_t stats[4]);
+
+/* ---- 6l. the nearest resident point to each given point: which one, and how far ----------------------------------------
+ * rtr_nearest_points answers what section 6k's bits cannot: for every GIVEN point the resident point closest to it within
+ * `radius` and its squared distance, and, the other way round, for every resident point the closest given one -- the
+ * correspondences of a scan registered against the map (with rtr_transform_points: one ICP step), cloud-to-cloud distance
+ * and change detection with a magnitude, colouring or labelling a scan from the map, snapping picked coordinates to real
+ * returns.  Everything it shares with rtr_select_near is section 6k's; only the differences are spelled out here.
+ * Given points: exactly as in section 6k -- strides, host or device memory, the span rule, non-finite points.  count == 0
+ * is legal: xyz may then be NULL.
+ * Relation: section 6k's.  d2 = ((dx*dx + dy*dy) + dz*dz), every operation rounded to fp32 on its own (no FMA); a pair
+ * is a CANDIDATE iff d2 <= r2, inclusive, r2 = radius * radius rounded once to fp32 on the host.  numpy float32 in that
+ * order is a bit-for-bit reference, nothing has a tolerance.  `radius` is the search bound (ICP's maximum correspondence
+ * distance), and the reason section 6k's sweep applies: a chunk nowhere near a given point is never decoded.
+ * Given side: given_index[j] = the upload index of the resident point with the smallest d2 among the candidates of given
+ * point j; of several candidates with the same d2 bits, the smallest upload index wins.  given_dist2[j] = that d2, bit
+ * for bit: subnormal values are kept as they are (the kernels do not flush denormals), a coincident point gives +0.  A
+ * given point with no candidate -- every non-finite one among them -- gets RTR_NEAREST_NONE and +inf (0x7F800000).  EVERY
+ * resident point counts, as in section 6k: the keep mask, the clip planes and the selection are ignored.
+ * Resident side: resident_index[i] = the given index with the smallest d2 among the candidates of resident point i, ties
+ * to the smallest given index; resident_dist2[i] = that d2.  A resident point with no candidate gets RTR_NEAREST_NONE
+ * and +inf; so does one more than a cell beyond the span, by section 6k's rule.  Both arrays hold n entries and are
+ * indexed by UPLOAD index.
+ * Outputs: each of the four pointers may be NULL on its own; all four NULL is legal (stats only; both sides are computed
+ * all the same).  Each is host or device memory, told apart as section 6k tells near_words.  They are written only when
+ * the call succeeds.  n and count are below 2^32, so RTR_NEAREST_NONE is never a real index.
+ * Coordinates are not returned: the library keeps no map from upload to resident index, and the 64 bits of the atomic
+ * that decides a given point's winner hold a distance and an index and nothing more.  Gather them with
+ * rtr_extract_points from the winning indices (rtr_project_cloud.hpp: matchPoints does).
+ * flags must be 0.
+ * stats (may be NULL): [0] the given points that have a nearest, [1] the resident points that have one, [2] the
+ * non-finite given points, [3] 0.  All are exact and independent of the form of the cloud; [0] equals rtr_select_near's
+ * stats[2] for the same arguments (with near_words), [1] its stats[1].
+ * Independence: the results depend on the coordinates and on the upload and given indices alone -- not on the resident
+ * order, the library's sort, the packed form, any option, the internal grid or the order of the given points: when the
+ * given points are permuted, the given outputs permute with them (and the resident indices map through the permutation).
+ * What it reads and leaves alone: section 6k's list, and the selection besides, which is neither read, changed nor
+ * created.  The call reads the uploaded coordinates only; it changes no frame, frame buffer, tile store, pool,
+ * statistics, point-pass buffer or keep mask, and an open peer-to-peer exchange stays open.  Indices are the point pass's:
+ * a cloud sorted by the library needs option "point_ids" = 1.  A sharded context works on its own points.
+ * Ordering: as section 6k.  Queued on the context's stream behind everything issued before it; the call ALWAYS waits for
+ * its own work before it returns (and once on the way, for the given points' counters and bounding box).
+ * Memory and cost: section 6k's sweep without its early exit -- every chunk near a given point is tested against every
+ * candidate around it --, keeping a minimum where section 6k ORs a bit: per tile of 64 candidates one 64-bit atomic
+ * minimum per candidate that some point of the chunk accepted.  Scratch for the duration of the call: section 6k's 56 B
+ * per given point, the sort's temporary and the copy of a host array, plus 8 B per GIVEN point for the given slots (and
+ * 4 B per given point and given output asked for), plus 8 B per RESIDENT point only when a resident output is asked for
+ * (the caller's arrays change only on success, so the kernel writes a scratch copy).  Everything is allocated before
+ * anything is written.
+ * Option keys, read by rtr_get_option after a call: "nearest_given_us", "nearest_sweep_us" (with the unpacking of the
+ * given side), "nearest_pair_tests_k", "nearest_chunks_skipped" and "nearest_chunks_decoded";
+ * nearest_chunks_skipped + nearest_chunks_decoded = (n + 255) / 256.
+ * Errors, with nothing changed (the four outputs and stats): no cloud, a radius that is not finite and > 0, an r2 that
+ * is not a finite normal fp32 number, xyz NULL with count > 0, a stride below 12 or not a multiple of 4, flags != 0, a
+ * sorted cloud without point_ids -> RTR_ERR_INVALID; n or count >= 2^32, or a finite given point beyond the span ->
+ * RTR_ERR_UNSUPPORTED; a failed allocation -> RTR_ERR_HIP. */
+#define RTR_NEAREST_NONE 0xFFFFFFFFu   /* the index of "no point within radius" */
+int rtr_nearest_points(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, uint64_t count, float radius, int flags,
+                       uint32_t *given_index, float *given_dist2,        /* count entries each, or NULL */
+                       uint32_t *resident_index, float *resident_dist2,  /* n entries each, upload order, or NULL */
+                       uint64_t stats[4]);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

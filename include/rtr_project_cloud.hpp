@@ -34,6 +34,8 @@
 // selectClusters (section 6i) names them by the size of their connected cluster; growSelection, removeSmallClusters.
 // selectNear (section 6k) names the vertices within a radius of GIVEN points, and the given points near a vertex.
 // appendNewPoints appends only the given points with no vertex within a radius: a scan merged without duplicates.
+// nearestPoints (section 6l) finds for every given point the nearest vertex within a radius and its squared distance;
+// matchPoints also returns the matched vertices' coordinates and colours: one ICP step with a fit and transformPoints.
 // fitPlane (section 6j) finds the plane with the most vertices within a distance of it; selectPlane, segmentPlane.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
 // writeSelected / writePoints / colorSelected (section 2f) put edited vertices and colours back where they came from:
@@ -43,12 +45,14 @@
 // before including this header (and link libtorch); without it the class has the two projection
 // methods and tensor(), the device pointer computeFull hands to the U-Net.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #ifdef RTR_WITH_TORCH
@@ -434,6 +438,59 @@ public:
         }
         if (!c.empty()) appendPoints(v.data(), 12, c.data(), 3, c.size() / 3);
         return c.size() / 3;
+    }
+    // The nearest vertex to each given point (rtr.h section 6l): for every one of the m given points (host memory, strides
+    // as appendPoints takes them) the upload index of the vertex closest to it within `radius` -- of equal distances the
+    // smallest index -- and its squared distance, float32 bit for bit; RTR_NEAREST_NONE and +inf where there is none.
+    struct Nearest {
+        std::vector<uint32_t> index;  // m: upload index, or RTR_NEAREST_NONE
+        std::vector<float> dist2;     // m: squared distance, or +inf
+    };
+    Nearest nearestPoints(const float* xyz, size_t xyz_stride_bytes, size_t m, float radius) {
+        Nearest r;
+        r.index.assign(m, RTR_NEAREST_NONE);
+        r.dist2.assign(m, 0.f);
+        check(ctx_, rtr_nearest_points(ctx_, xyz, xyz_stride_bytes, m, radius, 0, r.index.data(), r.dist2.data(), nullptr, nullptr, nullptr));
+        return r;
+    }
+    // nearestPoints with the matched vertices themselves: vertices / colors hold 3 values per given point, the resident
+    // coordinates and colours of its winner bit for bit, zero where there is no match.  One extract of the distinct
+    // winners.  With a rigid fit of the matched given points onto `vertices` and transformPoints: one ICP step.
+    struct Match {
+        std::vector<uint32_t> index;
+        std::vector<float> dist2;
+        std::vector<float> vertices;  // 3 m
+        std::vector<uint8_t> colors;  // 3 m
+    };
+    Match matchPoints(const float* xyz, size_t xyz_stride_bytes, size_t m, float radius) {
+        Nearest nn = nearestPoints(xyz, xyz_stride_bytes, m, radius);
+        Match r;
+        r.vertices.assign(3 * m, 0.f);
+        r.colors.assign(3 * m, (uint8_t)0);
+        uint64_t n = 0;
+        check(ctx_, rtr_num_points(ctx_, &n));
+        std::vector<uint32_t> words((size_t)((n + 31) / 32), 0u), idx;
+        bool any = false;
+        for (size_t j = 0; j < m; ++j) {
+            const uint32_t u = nn.index[j];
+            if (u == RTR_NEAREST_NONE) continue;
+            words[u / 32] |= 1u << (u % 32);
+            any = true;
+        }
+        if (any) {
+            std::vector<float> v;
+            std::vector<uint8_t> c;
+            extract(words.data(), words.size(), v, c, &idx);  // (ascending upload index: the distinct winners, sorted)
+            for (size_t j = 0; j < m; ++j) {
+                if (nn.index[j] == RTR_NEAREST_NONE) continue;
+                const size_t at = (size_t)(std::lower_bound(idx.begin(), idx.end(), nn.index[j]) - idx.begin());
+                std::memcpy(&r.vertices[3 * j], &v[3 * at], 12);
+                std::memcpy(&r.colors[3 * j], &c[3 * at], 3);
+            }
+        }
+        r.index = std::move(nn.index);
+        r.dist2 = std::move(nn.dist2);
+        return r;
     }
     // Takes the clusters of fewer than min_points vertices within `radius` out of the resident cloud for good: their
     // vertices are selected (replacing the selection) and removed.  Returns the number removed.

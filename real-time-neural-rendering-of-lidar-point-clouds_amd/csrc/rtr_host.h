@@ -1,5 +1,5 @@
 // rtr_host.h -- what the host translation units share (rtr_api.hip: contexts, the cloud and its edits, frames, buffers;
-// rtr_select_api.hip: the selection and analysis calls of rtr.h sections 6f - 6k): the context, the error path, a call's
+// rtr_select_api.hip: the selection and analysis calls of rtr.h sections 6f - 6l): the context, the error path, a call's
 // device guard and device buffers, and the handful of helpers of rtr_api.hip that the selection calls use too.  Every
 // function declared here is defined once, in rtr_api.hip unless noted, and stays out of the library's exported symbols.
 #pragma once
@@ -140,6 +140,9 @@ struct rtr_ctx {
     int near_us[2] = {0, 0};           // the last rtr_select_near: the given points' keys, sort and gather; the sweep, combine and counts
     int near_tests_k = 0;              // ... its pair tests in thousands (saturating)
     int near_chunks[2] = {0, 0};       // ... and its resident chunks decided without their coordinates / decoded (saturating)
+    int nearest_us[2] = {0, 0};        // the last rtr_nearest_points: the given points' keys, sort and gather; the sweep and the unpack
+    int nearest_tests_k = 0;           // ... its pair tests in thousands (saturating)
+    int nearest_chunks[2] = {0, 0};    // ... and its resident chunks decided without their coordinates / decoded (saturating)
     int clusters_us[3] = {0, 0, 0};    // the last rtr_select_clusters: key kernel, sort, gather + work list + union-find + hits
     int clusters_tests_k = 0;          // ... and its pair tests in thousands (saturating)
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded

@@ -518,6 +518,20 @@ void launch_near_sweep(hipStream_t s, const Cloud &c, const float *bounds, const
                        uint64_t m, float radius, float r2, const double glo[3], const double ghi[3], uint32_t *hit, uint32_t *near,
                        uint64_t *counters);
 
+// rtr_nearest_points (rtr_nearest.hip; rtr.h section 6l; the given points go through near_keys, the sort and the gather
+// above, the sweep is rtr_near_sweep.h's, shared with near_sweep).
+// nearest_sweep: keys / rec / glo / ghi / c / bounds / perm / counters as for near_sweep.  slots (m's `count` words of 64
+// bits, all ones before the launch) [rec.w] = the smallest (bits of d2) << 32 | upload index over the resident points at
+// ((dx dx + dy dy) + dz dz) <= r2 from that given point.  ridx / rd2 (both or neither; upload order, padded to a multiple
+// of 4 points, preset to 2^32 - 1 / the bits of +inf) [u] = the given index with the smallest (d2, given index) for
+// resident point u / the bits of that d2; a point with no given point at that distance is not written
+void launch_nearest_sweep(hipStream_t s, const Cloud &c, const float *bounds, const uint32_t *perm, const uint64_t *keys, const float4 *rec,
+                          uint64_t m, float radius, float r2, const double glo[3], const double ghi[3], uint64_t *slots, uint32_t *ridx,
+                          uint32_t *rd2, uint64_t *counters);
+// nearest_unpack: idx[j] / d2[j] (device, count words each, either may be null) = the low / high half of slots[j], or
+// 2^32 - 1 / the bits of +inf for a slot of all ones; *have (device, zeroed by the caller) += the slots that are not
+void launch_nearest_unpack(hipStream_t s, const uint64_t *slots, uint64_t count, uint32_t *idx, uint32_t *d2, uint64_t *have);
+
 // rtr_count_in_bands (rtr_planes.hip; rtr.h section 6j).  counts[k] (device, zeroed by the caller) += the points of the
 // population in band k of `bands` (HOST memory, count x {a, b, c, d_lo, d_hi}), kBandPass bands per launch: every chunk is
 // classified on its box against all bands of a pass and decoded at most once per pass.  c / bounds as for launch_select.

@@ -1,7 +1,7 @@
-// rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6k) on top of the kernels of
-// rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip and rtr_planes.hip.  The rules
-// the calls share are stated once each, in the helpers below; DESIGN.md ("The selection calls in their own file") has
-// the order of events every call follows and why an error leaves the selection as it was.
+// rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6l) on top of the kernels of
+// rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip, rtr_nearest.hip and
+// rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
+// calls in their own file") has the order of events every call follows and why an error leaves the selection as it was.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -94,6 +94,53 @@ struct EventSet {  // the stage boundaries of one call
             float ms = 0.f;
             HIP_TRY(c, hipEventElapsedTime(&ms, e[first + k], e[first + k + 1]));
             out[k] = (int)(ms * 1000.f + 0.5f);
+        }
+        return RTR_OK;
+    }
+};
+
+// The GIVEN points of rtr_select_near and rtr_nearest_points (rtr.h sections 6k and 6l): section 6h's key, sort and gather
+// over a plain strided array in host or device memory.  alloc: the scratch, among the call's other allocations; run:
+// everything up to the sorted records ks.k1 / ks.rec1 of the m points with a cell and their box, with ONE wait on the
+// way, for the counters and the box: a finite point beyond the span fails the call there, before anything has changed.
+// cn (device, 12 words): [0] non-finite given points, [1] those beyond the span, [2] the caller's, [4 .. 7] the sweep's,
+// [8 .. 10] the box
+struct GivenPoints {
+    KeyedScratch ks;
+    uint64_t *cn = nullptr;
+    uint8_t *stage = nullptr;
+    size_t gbytes = 0;
+    uint64_t nonfinite = 0, m = 0;
+    double glo[3] = {0, 0, 0}, ghi[3] = {0, 0, 0};
+    int alloc(rtr_ctx *c, DevBufs &buf, const float *xyz, size_t xs, uint64_t count) {
+        gbytes = count ? (size_t)(count - 1) * xs + 12 : 0;
+        if (int rc = ks.alloc(c, buf, count, true)) return rc;
+        HIP_TRY(c, buf.get(&cn, 12 * sizeof(uint64_t)));
+        if (count && !on_device(xyz)) HIP_TRY(c, buf.get(&stage, gbytes));
+        return RTR_OK;
+    }
+    int run(rtr_ctx *c, const char *who, hipStream_t s, const float *xyz, size_t xs, uint64_t count, float radius) {
+        HIP_TRY(c, hipMemsetAsync(cn, 0, 12 * sizeof(uint64_t), s));
+        HIP_TRY(c, hipMemsetAsync(cn + 8, 0xFF, 3 * sizeof(uint32_t), s));  // (box: the minima start at 2^32 - 1, the maxima at 0)
+        const uint8_t *gxyz = (const uint8_t *)xyz;
+        if (stage) {  // (the given points are read before the call returns: one copy at the caller's stride)
+            HIP_TRY(c, hipMemcpyAsync(stage, xyz, gbytes, hipMemcpyHostToDevice, s));
+            gxyz = stage;
+        }
+        rtr::launch_near_keys(s, gxyz, xs, count, radius, ks.k0, ks.v0, ks.rec0, cn, reinterpret_cast<uint32_t *>(cn + 8));
+        if (int rc = launch_check(c, "given keys")) return rc;
+        uint64_t host[12] = {};
+        HIP_TRY(c, hipMemcpyAsync(host, cn, sizeof host, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (host[1]) return fail_span(c, who, "given points", host[1]);
+        nonfinite = host[0], m = count - nonfinite;  // (the pairs with a cell sort to the front)
+        HIP_TRY(c, ks.sort(s, count));
+        rtr::launch_neighbour_gather(s, ks.v1, ks.rec0, m, ks.rec1);
+        if (int rc = launch_check(c, "given gather")) return rc;
+        if (m) {
+            uint32_t box[6];
+            memcpy(box, host + 8, sizeof box);
+            rtr::near_box_from_keys(box, glo, ghi);
         }
         return RTR_OK;
     }
@@ -367,9 +414,9 @@ int rtr_select_clusters(rtr_ctx *c, float radius, uint32_t min_points, uint32_t 
 }
 
 // ---- selection by distance to given points (rtr.h, section 6k) ------------------------
-// The given points go through section 6h's key, sort and gather (rtr_near.hip's k_near_keys over the plain strided
-// array); the resident side is ONE sweep over the chunks that sorts and gathers nothing.  One wait on the way, for the
-// given points' counters and box: a point beyond the span fails the call there, before anything has changed.  The
+// The given points go through section 6h's key, sort and gather (GivenPoints: rtr_near.hip's k_near_keys over the plain
+// strided array); the resident side is ONE sweep over the chunks that sorts and gathers nothing.  One wait on the way,
+// for the given points' counters and box: a point beyond the span fails the call there, before anything has changed.  The
 // caller's near words and stats are written last.
 int rtr_select_near(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, float radius, int flags, int op, uint32_t *near_words,
                     uint64_t stats[4]) {
@@ -395,53 +442,31 @@ int rtr_select_near(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, flo
     hipStream_t s = c->stream;
     const uint64_t n = c->n, nw = (n + 31) / 32, gw = (count + 31) / 32;
     const uint64_t gwords = sel_words(count);  // (the near words, padded for launch_select_count)
-    const bool xyz_dev = count && on_device(xyz), near_dev = near_words && on_device(near_words);
+    const bool near_dev = near_words && on_device(near_words);
     DevBufs buf;
     EventSet ev;
-    KeyedScratch ks;
+    GivenPoints gp;  // (cn[2]: the near bits)
     NewSelection fresh;
-    uint64_t *cn;  // [0] non-finite given points, [1] those beyond the span, [2] near bits, [4 .. 7] the sweep's, [8 .. 10] the box
     uint32_t *hit = nullptr, *nearw = nullptr;
-    const uint8_t *gxyz = (const uint8_t *)xyz;
-    uint8_t *stage = nullptr;
-    const size_t gbytes = count ? (size_t)(count - 1) * xs + 12 : 0;
-    if (int rc = ks.alloc(c, buf, count, true)) return rc;
-    HIP_TRY(c, buf.get(&cn, 12 * sizeof(uint64_t)));
-    if (count && !xyz_dev) HIP_TRY(c, buf.get(&stage, gbytes));
+    if (int rc = gp.alloc(c, buf, xyz, xs, count)) return rc;
+    uint64_t *cn = gp.cn;
     if (!given_only) HIP_TRY(c, buf.get(&hit, nw * 4));
     if (near_words) HIP_TRY(c, buf.get(&nearw, gwords * 4));
     if (!given_only)
         if (int rc = fresh.reserve(c, buf)) return rc;
     if (int rc = ev.create(c, 3)) return rc;
-    HIP_TRY(c, hipMemsetAsync(cn, 0, 12 * sizeof(uint64_t), s));
-    HIP_TRY(c, hipMemsetAsync(cn + 8, 0xFF, 3 * sizeof(uint32_t), s));  // (box: the minima start at 2^32 - 1, the maxima at 0)
     if (hit) HIP_TRY(c, hipMemsetAsync(hit, 0, nw * 4, s));
     if (nearw) HIP_TRY(c, hipMemsetAsync(nearw, 0, gwords * 4, s));
     if (int rc = ev.record(c, 0, s)) return rc;
-    if (stage) {  // (the given points are read before the call returns: one copy at the caller's stride)
-        HIP_TRY(c, hipMemcpyAsync(stage, xyz, gbytes, hipMemcpyHostToDevice, s));
-        gxyz = stage;
-    }
-    rtr::launch_near_keys(s, gxyz, xs, count, radius, ks.k0, ks.v0, ks.rec0, cn, reinterpret_cast<uint32_t *>(cn + 8));
-    if (int rc = launch_check(c, "near keys")) return rc;
-    uint64_t host[12] = {};
-    HIP_TRY(c, hipMemcpyAsync(host, cn, sizeof host, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (host[1]) return fail_span(c, "rtr_select_near", "given points", host[1]);
-    const uint64_t nonfinite = host[0], m = count - nonfinite;  // (the pairs with a cell sort to the front)
-    HIP_TRY(c, ks.sort(s, count));
-    rtr::launch_neighbour_gather(s, ks.v1, ks.rec0, m, ks.rec1);
-    if (int rc = launch_check(c, "near gather")) return rc;
+    if (int rc = gp.run(c, "rtr_select_near", s, xyz, xs, count, radius)) return rc;
+    const uint64_t nonfinite = gp.nonfinite, m = gp.m;
     if (int rc = ev.record(c, 1, s)) return rc;
     if (int rc = fresh.create(c, buf, s)) return rc;
     if (!given_only) HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
     uint64_t sweep[4] = {0, 0, (n + 255) / 256, 0};  // (no given point has a cell: every chunk is decided without a launch)
     if (m) {
-        double glo[3], ghi[3];
-        uint32_t box[6];
-        memcpy(box, host + 8, sizeof box);
-        rtr::near_box_from_keys(box, glo, ghi);
-        rtr::launch_near_sweep(s, cloud_of(c), c->bounds, c->reordered ? c->perm : nullptr, ks.k1, ks.rec1, m, radius, r2, glo, ghi, hit, nearw, cn + 4);
+        rtr::launch_near_sweep(s, cloud_of(c), c->bounds, c->reordered ? c->perm : nullptr, gp.ks.k1, gp.ks.rec1, m, radius, r2, gp.glo, gp.ghi, hit,
+                               nearw, cn + 4);
         if (int rc = launch_check(c, "near sweep")) return rc;
     }
     uint64_t out[4] = {0, 0, 0, nonfinite};
@@ -465,6 +490,82 @@ int rtr_select_near(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, flo
         HIP_TRY(c, hipMemcpyAsync(near_words, nearw, gw * 4, near_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
+    if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- the nearest resident point to each given point (rtr.h, section 6l) ---------------
+// rtr_select_near's order of events with minima in place of bits (rtr_nearest.hip): the given points are keyed, sorted
+// and gathered as there (GivenPoints), with the same wait and the same failure for a point beyond the span; the sweep
+// fills one 64-bit slot per given point and, when a resident output is asked for, scratch copies of the two resident
+// arrays.  The selection plays no part.  The caller's four arrays and stats are written last.
+int rtr_nearest_points(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, float radius, int flags, uint32_t *given_index,
+                       float *given_dist2, uint32_t *resident_index, float *resident_dist2, uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_nearest_points: no cloud");
+    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_nearest_points: radius must be finite and > 0");
+    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
+    NEED(c, std::isnormal(r2), "rtr_nearest_points: the square of radius is not a finite normal fp32 number");
+    NEED(c, count == 0 || xyz != nullptr, "rtr_nearest_points: xyz is NULL");
+    NEED(c, xs >= 12 && xs % 4 == 0, "rtr_nearest_points: xyz_stride_bytes must be >= 12 and a multiple of 4");
+    NEED(c, flags == 0, "rtr_nearest_points: flags must be 0");
+    if (int rc = check_indexable(c)) return rc;
+    if (count >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "rtr_nearest_points: given indices are 32-bit: count is %llu", (unsigned long long)count);
+    if (int rc = need_upload_order(c, "returned")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, n4 = (n + 3) & ~3ull;  // (the resident arrays hold whole quads)
+    const bool want_res = resident_index || resident_dist2;
+    DevBufs buf;
+    EventSet ev;
+    GivenPoints gp;  // (cn[2]: the given points with a nearest)
+    uint64_t *slots;
+    uint32_t *gi = nullptr, *gd = nullptr, *ri = nullptr, *rd = nullptr;
+    if (int rc = gp.alloc(c, buf, xyz, xs, count)) return rc;
+    uint64_t *cn = gp.cn;
+    HIP_TRY(c, buf.get(&slots, count * 8));
+    if (given_index) HIP_TRY(c, buf.get(&gi, count * 4));
+    if (given_dist2) HIP_TRY(c, buf.get(&gd, count * 4));
+    if (want_res) HIP_TRY(c, buf.get(&ri, n4 * 4));
+    if (want_res) HIP_TRY(c, buf.get(&rd, n4 * 4));
+    if (int rc = ev.create(c, 3)) return rc;
+    if (count) HIP_TRY(c, hipMemsetAsync(slots, 0xFF, count * 8, s));
+    if (want_res) {
+        HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)ri, (int)RTR_NEAREST_NONE, n4, s));
+        HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)rd, 0x7F800000, n4, s));
+    }
+    if (int rc = ev.record(c, 0, s)) return rc;
+    if (int rc = gp.run(c, "rtr_nearest_points", s, xyz, xs, count, radius)) return rc;
+    const uint64_t nonfinite = gp.nonfinite, m = gp.m;
+    if (int rc = ev.record(c, 1, s)) return rc;
+    uint64_t sweep[4] = {0, 0, (n + 255) / 256, 0};  // (no given point has a cell: every chunk is decided without a launch)
+    if (m) {
+        rtr::launch_nearest_sweep(s, cloud_of(c), c->bounds, c->reordered ? c->perm : nullptr, gp.ks.k1, gp.ks.rec1, m, radius, r2, gp.glo, gp.ghi,
+                                  slots, ri, rd, cn + 4);
+        if (int rc = launch_check(c, "nearest sweep")) return rc;
+    }
+    rtr::launch_nearest_unpack(s, slots, count, gi, gd, cn + 2);
+    if (int rc = launch_check(c, "nearest unpack")) return rc;
+    if (int rc = ev.record(c, 2, s)) return rc;
+    uint64_t have = 0;
+    HIP_TRY(c, hipMemcpyAsync(&have, cn + 2, sizeof have, hipMemcpyDeviceToHost, s));
+    if (m) HIP_TRY(c, hipMemcpyAsync(sweep, cn + 4, sizeof sweep, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
+    if (int rc = ev.stage_us(c, 0, 2, c->nearest_us)) return rc;
+    c->nearest_tests_k = saturate_k(sweep[1]);
+    c->nearest_chunks[0] = saturate_int(sweep[2]), c->nearest_chunks[1] = saturate_int(sweep[3]);
+    // behind everything that can fail: the caller's arrays change only when the call succeeds
+    struct Out { void *dst; const uint32_t *src; uint64_t words; };
+    const Out outs[4] = {{given_index, gi, count}, {given_dist2, gd, count}, {resident_index, ri, n}, {resident_dist2, rd, n}};
+    bool copied = false;
+    for (const Out &o : outs) {
+        if (!o.dst || !o.words) continue;
+        HIP_TRY(c, hipMemcpyAsync(o.dst, o.src, o.words * 4, on_device(o.dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        copied = true;
+    }
+    if (copied) HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t out[4] = {have, sweep[0], nonfinite, 0};
     if (stats) memcpy(stats, out, sizeof out);
     return RTR_OK;
 }

@@ -448,6 +448,61 @@ class Projector:
             return (st, bits) if stats else bits
         return st
 
+    def nearest_points(self, xyz, radius, given=True, resident=False, stats=True):
+        """Finds on the device, for every GIVEN point of `xyz`, the nearest resident point within `radius`, and for every
+        resident point the nearest given one (include/rtr.h section 6l).  xyz: as select_near takes it -- float32 rows,
+        (m, 3) or (m, 4), a numpy array, a torch tensor (host or device) or an object with __cuda_array_interface__;
+        m = 0 is legal.  Candidates: ((dx*dx + dy*dy) + dz*dz) <= radius*radius in float32, inclusive, select_near's
+        relation; of the candidates the smallest d2 wins, of equal d2 bits the smallest index.  given: (index, dist2)
+        of m entries, the upload index of the nearest resident point and its squared distance bit for bit; resident:
+        (index, dist2) of num_points entries in upload order, the given index of the nearest given point.  An entry
+        without a candidate (every non-finite point) holds NEAREST_NONE and +inf.  Indices are uint32, distances
+        float32; device input gives torch tensors on that device, anything else numpy arrays.  The selection, the keep
+        mask and the clip planes play no part.  The call always waits.  stats: (given points with a nearest, resident
+        points with one, non-finite given points, 0).  Returns the requested pairs and the stats flattened in the order
+        given index, given dist2, resident index, resident dist2, stats; a single item alone; None with nothing."""
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        with np.errstate(over="ignore", under="ignore"):
+            r2 = np.float32(r) * np.float32(r)
+        if not (np.isfinite(r2) and r2 >= np.finfo(np.float32).tiny):
+            raise ValueError("the square of radius must be a finite normal float32 number")
+        ptr, stride, m, hold = self._write_source(xyz, np.float32, "xyz")
+        if m >= 2 ** 32:
+            raise ValueError("at most 2^32 - 1 given points")
+        if m and (stride < 12 or stride % 4):
+            raise ValueError("xyz rows must be at least 12 bytes apart, by a multiple of 4")
+        n = self.num_points
+        device = None
+        if hasattr(xyz, "data_ptr"):
+            device = xyz.device if xyz.is_cuda else None
+        elif hasattr(xyz, "__cuda_array_interface__"):
+            device = "cuda:%d" % self.device
+        arrays, ptrs = [], []
+        for want, rows in ((given, m), (given, m), (resident, n), (resident, n)):
+            dt = (np.uint32, np.float32)[len(ptrs) % 2]
+            if not want:
+                ptrs.append(None)
+            elif device is not None:
+                import torch
+                a = torch.empty(rows, dtype=torch.uint32 if dt is np.uint32 else torch.float32, device=device)
+                arrays.append(a)
+                ptrs.append(C.c_void_p(a.data_ptr()))
+            else:
+                a = np.empty(rows, dt)
+                arrays.append(a)
+                ptrs.append(_vp(a))
+        out = np.zeros(4, np.uint64) if stats else None
+        self._chk(self._lib.rtr_nearest_points(self._ctx, ptr if m else None, stride if m else 12, m, r, 0, ptrs[0], ptrs[1],
+                                               ptrs[2], ptrs[3], _vp(out)))
+        del hold
+        if stats:
+            arrays.append(tuple(int(v) for v in out))
+        if not arrays:
+            return None
+        return arrays[0] if len(arrays) == 1 else tuple(arrays)
+
     # -- bands and the dominant plane (rtr.h section 6j)
     def count_in_bands(self, bands, selected=False, stats=True):
         """Counts on the device, for each band {a, b, c, d_lo, d_hi} of `bands` ((k, 5), 1 <= k <= MAX_BANDS), the points
@@ -1032,6 +1087,36 @@ class ProjectCloud:
         if k:
             self.appendPoints(np.ascontiguousarray(v[new]), np.ascontiguousarray(c[new]))
         return k
+
+    # -- the nearest vertex to given points (rtr.h section 6l)
+    def nearestPoints(self, vertices, radius):
+        """For every given vertex ((m, 3) or (m, 4) float32) the resident vertex closest to it within `radius` (see
+        Projector.nearest_points).  Returns (index, dist2): the upload index (NEAREST_NONE: none within radius) and the
+        squared distance (+inf then), float32 bit for bit."""
+        return self._p.nearest_points(vertices, radius, stats=False)
+
+    def matchPoints(self, vertices, radius):
+        """nearestPoints with the matched vertices themselves: returns (index, dist2, xyz, rgb), xyz (m, 3) float32 and
+        rgb (m, 3) uint8 the resident coordinates and colours of every winner, bit for bit; rows without a match are
+        zero.  One extract of the distinct winners.  With a rigid fit of vertices[matched] onto xyz[matched] and
+        transformPoints this is one ICP step."""
+        index, dist2 = self.nearestPoints(vertices, radius)
+        if hasattr(index, "cpu"):
+            index, dist2 = index.cpu().numpy(), dist2.cpu().numpy()
+        return (index, dist2) + self._gather_matched(index)
+
+    def _gather_matched(self, index):
+        m = index.shape[0]
+        xyz, rgb = np.zeros((m, 3), np.float32), np.zeros((m, 3), np.uint8)
+        matched = index != L.NEAREST_NONE
+        if matched.any():
+            words = np.zeros((self._p.num_points + 31) // 32, np.uint32)
+            win = np.unique(index[matched])
+            np.bitwise_or.at(words, win >> 5, np.uint32(1) << (win & 31).astype(np.uint32))
+            x, c, idx = self._p.extract_points(words, indices=True)  # (ascending upload index: idx equals win)
+            at = np.searchsorted(idx, index[matched])
+            xyz[matched], rgb[matched] = x[at, :3], c[at, :3]
+        return xyz, rgb
 
     # -- the dominant plane (rtr.h section 6j)
     def fitPlane(self, dist, iterations=256, seed=0, selected=False):
