@@ -220,6 +220,10 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *  rtr_get_option("nearest_given_us" / "nearest_sweep_us" / "nearest_pair_tests_k" / "nearest_chunks_skipped" /
  *          "nearest_chunks_decoded") read the same five for the last rtr_nearest_points (section 6l): the sweep's time
  *          includes the unpacking of the given side.
+ *  rtr_get_option("nearest_k_given_us" / "nearest_k_sweep_us" / "nearest_k_pair_tests_k" / "nearest_k_chunks_skipped" /
+ *          "nearest_k_chunks_decoded") read the same five for the last rtr_nearest_k_points (section 6m), and
+ *          "nearest_k_cascades_k" the row insertions its sweep started, in thousands (saturating at 2^31 - 1): that one
+ *          depends on the timing of the waves and differs from run to run.
  *  rtr_get_option("plane_sample_us" / "plane_count_us") read the host time, in microseconds and with its waits, that the
  *          last rtr_fit_plane (section 6j) spent drawing and extracting its sample and counting its candidates. */
 int rtr_set_option(rtr_ctx *ctx, const char *key, int value);
@@ -1115,6 +1119,54 @@ int rtr_nearest_points(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, 
                        uint32_t *given_index, float *given_dist2,        /* count entries each, or NULL */
                        uint32_t *resident_index, float *resident_dist2,  /* n entries each, upload order, or NULL */
                        uint64_t stats[4]);
+
+/* ---- 6m. the k nearest resident points to each given point ---------------------------------------------------------------
+ * rtr_nearest_k_points is section 6l's given side with k answers per given point in place of one: the input of normal
+ * and curvature estimation (PCA over k neighbours), of the statistical outlier filter (mean distance to k neighbours),
+ * of local density, of colouring a scan from several map points.  It runs section 6k's sweep: a chunk nowhere near a
+ * given point is never decoded.
+ * Section 6l's rules apply unchanged to: the given points (strides, host or device memory, the span rule, non-finite
+ * points; count == 0 is legal); the relation (fp32 ((dx*dx + dy*dy) + dz*dz) <= r2, inclusive, no FMA, denormals kept);
+ * EVERY resident point counts; the independence from the resident order, the library's sort, the packed form, any
+ * option, the internal grid and the order of the given points (the rows permute with them); what the call reads and
+ * leaves alone; the ordering (the call ALWAYS waits for its own work); "point_ids" = 1 for a cloud sorted by the library.
+ * Row j of `index` and `dist2` (k entries each, at [j * k]): the CANDIDATES of given point j in ascending order of (d2
+ * bits, upload index), the first min(k, candidates) of them; the remaining entries of the row are RTR_NEAREST_NONE and
+ * +inf (0x7F800000).  found[j] = the number of real entries of row j.  numpy float32 plus a stable sort on (bits, index)
+ * is a bit-for-bit reference; nothing has a tolerance.  With k = 1 the row equals rtr_nearest_points' given_index[j] and
+ * given_dist2[j] bit for bit.
+ * Self queries: a given point coincident with a resident one is its own neighbour at +0.  For the k neighbours of the
+ * resident points themselves: extract them (rtr_extract_points), ask for k + 1, and drop from each row the entry whose
+ * index is the point's own -- not the row's first entry: a coincident duplicate with a smaller upload index sorts before
+ * the point itself.
+ * There is no resident side: it would be n * k entries, and section 6l serves k = 1 there.
+ * k is 1 .. RTR_NEAREST_MAX_K.  flags must be 0.  Each of the three outputs may be NULL on its own; all three NULL is
+ * legal (stats only).  Each is host or device memory, told apart as in section 6l.  Outputs and stats are written only
+ * when the call succeeds.
+ * stats (may be NULL): [0] the given points with found > 0 (= rtr_select_near's stats[2] for the same arguments), [1] the
+ * sum of found, [2] the non-finite given points, [3] the given points with found == k.  All four are exact and
+ * independent of the form of the cloud.
+ * Memory and cost: section 6l's sweep; every given point has a ROW of k 64-bit slots, and an accepted pair's key walks
+ * the row by returning 64-bit atomic minima, each slot keeping the smaller and passing the larger on, so that the row
+ * ends sorted for any interleaving: no lock, no retry, no wave waiting for another.  A key that does not beat the row's
+ * last slot is dropped unread.  Scratch for the duration of the call: section 6k's 56 B per given point, the sort's
+ * temporary and the copy of a host array, plus 8 * k B per given point for the rows, plus a staging copy of every output
+ * that lies in host memory (4 * k B per given point for index and for dist2, 4 B for found).  Everything is allocated
+ * before anything is written.
+ * Option keys, read by rtr_get_option after a call: "nearest_k_given_us", "nearest_k_sweep_us" (with the unpacking),
+ * "nearest_k_pair_tests_k", "nearest_k_chunks_skipped" and "nearest_k_chunks_decoded" (their sum is (n + 255) / 256), and
+ * "nearest_k_cascades_k", the row insertions started, in thousands: it depends on timing, not on the inputs alone.
+ * Errors, with nothing changed (the three outputs and stats): section 6l's list as it is -- no cloud, a radius that is
+ * not finite and > 0, an r2 that is not a finite normal fp32 number, xyz NULL with count > 0, a stride below 12 or not a
+ * multiple of 4, flags != 0, a sorted cloud without point_ids -> RTR_ERR_INVALID; n or count >= 2^32, or a finite given
+ * point beyond the span -> RTR_ERR_UNSUPPORTED; a failed allocation -> RTR_ERR_HIP --, and k == 0 or
+ * k > RTR_NEAREST_MAX_K -> RTR_ERR_INVALID.  rtr_last_error names the argument. */
+#define RTR_NEAREST_MAX_K 64
+int rtr_nearest_k_points(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, uint64_t count, float radius,
+                         uint32_t k, int flags,
+                         uint32_t *index, float *dist2,   /* count * k entries each, row j at [j * k], or NULL */
+                         uint32_t *found,                 /* count entries, or NULL */
+                         uint64_t stats[4]);
 
 /* ---- 7. measurement -------------------------------------------------------------- */
 typedef enum {

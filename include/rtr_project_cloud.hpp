@@ -36,6 +36,7 @@
 // appendNewPoints appends only the given points with no vertex within a radius: a scan merged without duplicates.
 // nearestPoints (section 6l) finds for every given point the nearest vertex within a radius and its squared distance;
 // matchPoints also returns the matched vertices' coordinates and colours: one ICP step with a fit and transformPoints.
+// nearestKPoints (section 6m) finds the k nearest vertices within a radius, sorted: the input of normals and density.
 // fitPlane (section 6j) finds the plane with the most vertices within a distance of it; selectPlane, segmentPlane.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
 // writeSelected / writePoints / colorSelected (section 2f) put edited vertices and colours back where they came from:
@@ -451,6 +452,26 @@ public:
         r.index.assign(m, RTR_NEAREST_NONE);
         r.dist2.assign(m, 0.f);
         check(ctx_, rtr_nearest_points(ctx_, xyz, xyz_stride_bytes, m, radius, 0, r.index.data(), r.dist2.data(), nullptr, nullptr, nullptr));
+        return r;
+    }
+    // The k nearest vertices to each given point (rtr.h section 6m): row j of index / dist2 (k entries at [j * k]) holds the
+    // vertices within `radius` of given point j in ascending order of (squared distance bits, upload index), the first
+    // min(k, candidates) of them, RTR_NEAREST_NONE and +inf behind them; found[j] is the number of real entries.
+    // 1 <= k <= RTR_NEAREST_MAX_K.  For the neighbours of the vertices themselves ask for k + 1 and drop the entry whose
+    // index is the vertex's own.
+    struct NearestK {
+        std::vector<uint32_t> index;  // m * k: upload index, or RTR_NEAREST_NONE
+        std::vector<float> dist2;     // m * k: squared distance, or +inf
+        std::vector<uint32_t> found;  // m: real entries of the row
+        uint32_t k;
+    };
+    NearestK nearestKPoints(const float* xyz, size_t xyz_stride_bytes, size_t m, uint32_t k, float radius) {
+        NearestK r;
+        r.k = k;
+        r.index.assign(m * (size_t)k, RTR_NEAREST_NONE);
+        r.dist2.assign(m * (size_t)k, 0.f);
+        r.found.assign(m, 0u);
+        check(ctx_, rtr_nearest_k_points(ctx_, xyz, xyz_stride_bytes, m, radius, k, 0, r.index.data(), r.dist2.data(), r.found.data(), nullptr));
         return r;
     }
     // nearestPoints with the matched vertices themselves: vertices / colors hold 3 values per given point, the resident

@@ -26,7 +26,8 @@ SYMBOLS = [
     "rtr_p2p_render_owned", "rtr_point_pass", "rtr_render_views", "rtr_set_clip_planes", "rtr_get_clip_planes",
     "rtr_set_point_keep", "rtr_append_points", "rtr_remove_points", "rtr_transform_points", "rtr_select_points",
     "rtr_clear_selection", "rtr_extract_points", "rtr_write_points", "rtr_select_voxel_grid", "rtr_select_neighbours",
-    "rtr_select_clusters", "rtr_count_in_bands", "rtr_fit_plane", "rtr_nearest_points", "rtr_select_near",
+    "rtr_select_clusters", "rtr_count_in_bands", "rtr_fit_plane", "rtr_nearest_k_points",
+    "rtr_nearest_points", "rtr_select_near",
 ]
 
 RTR_OK, RTR_ERR_INVALID, RTR_ERR_HIP, RTR_ERR_NO_OUTPUT, RTR_ERR_UNSUPPORTED, RTR_ERR_INTERNAL = 0, -1, -2, -3, -4, -5
@@ -40,6 +41,7 @@ SELECT_TOGGLE = 8  # ... and sel ^= hit (with no region: inverts the selection)
 CLUSTER_SEEDED = 1  # rtr_select_clusters' flag: only clusters holding a currently selected point
 NEAR_GIVEN_ONLY = 1  # rtr_select_near's flag: only the given side, the selection is left alone
 NEAREST_NONE = 0xFFFFFFFF  # RTR_NEAREST_NONE: rtr_nearest_points' index of "no point within radius"
+NEAREST_MAX_K = 64  # RTR_NEAREST_MAX_K: rtr_nearest_k_points' largest k
 BANDS_SELECTED = 1  # rtr_count_in_bands / rtr_fit_plane flag: only the currently selected points
 MAX_BANDS = 4096  # RTR_MAX_BANDS
 MAX_VIEWS = 8  # RTR_MAX_VIEWS
@@ -152,6 +154,7 @@ def lib():
     L.rtr_count_in_bands.argtypes = [vp, C.c_uint32, vp, i32, vp, vp]
     L.rtr_select_near.argtypes = [vp, vp, sz, u64, C.c_float, i32, i32, vp, vp]
     L.rtr_nearest_points.argtypes = [vp, vp, sz, u64, C.c_float, i32, vp, vp, vp, vp, vp]
+    L.rtr_nearest_k_points.argtypes = [vp, vp, sz, u64, C.c_float, C.c_uint32, i32, vp, vp, vp, vp]
     L.rtr_fit_plane.argtypes = [vp, C.c_float, C.c_uint32, u64, i32, vp, vp]
     L.rtr_extract_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, vp, C.POINTER(u64)]
     L.rtr_write_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, C.POINTER(u64)]

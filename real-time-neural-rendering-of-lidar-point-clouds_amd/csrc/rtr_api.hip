@@ -921,6 +921,12 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "nearest_pair_tests_k")) *value = c->nearest_tests_k;
     else if (!strcmp(key, "nearest_chunks_skipped")) *value = c->nearest_chunks[0];
     else if (!strcmp(key, "nearest_chunks_decoded")) *value = c->nearest_chunks[1];
+    else if (!strcmp(key, "nearest_k_given_us")) *value = c->nearest_k_us[0];  // the last rtr_nearest_k_points
+    else if (!strcmp(key, "nearest_k_sweep_us")) *value = c->nearest_k_us[1];
+    else if (!strcmp(key, "nearest_k_pair_tests_k")) *value = c->nearest_k_tests_k;
+    else if (!strcmp(key, "nearest_k_chunks_skipped")) *value = c->nearest_k_chunks[0];
+    else if (!strcmp(key, "nearest_k_chunks_decoded")) *value = c->nearest_k_chunks[1];
+    else if (!strcmp(key, "nearest_k_cascades_k")) *value = c->nearest_k_cascades_k;
     else if (!strcmp(key, "clusters_keys_us")) *value = c->clusters_us[0];  // the last rtr_select_clusters
     else if (!strcmp(key, "clusters_sort_us")) *value = c->clusters_us[1];
     else if (!strcmp(key, "clusters_label_us")) *value = c->clusters_us[2];

@@ -143,6 +143,10 @@ struct rtr_ctx {
     int nearest_us[2] = {0, 0};        // the last rtr_nearest_points: the given points' keys, sort and gather; the sweep and the unpack
     int nearest_tests_k = 0;           // ... its pair tests in thousands (saturating)
     int nearest_chunks[2] = {0, 0};    // ... and its resident chunks decided without their coordinates / decoded (saturating)
+    int nearest_k_us[2] = {0, 0};      // the last rtr_nearest_k_points: the same five ...
+    int nearest_k_tests_k = 0;
+    int nearest_k_chunks[2] = {0, 0};
+    int nearest_k_cascades_k = 0;      // ... and the cascades its sweep started, in thousands (saturating; depends on timing)
     int clusters_us[3] = {0, 0, 0};    // the last rtr_select_clusters: key kernel, sort, gather + work list + union-find + hits
     int clusters_tests_k = 0;          // ... and its pair tests in thousands (saturating)
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded

@@ -532,6 +532,20 @@ void launch_nearest_sweep(hipStream_t s, const Cloud &c, const float *bounds, co
 // 2^32 - 1 / the bits of +inf for a slot of all ones; *have (device, zeroed by the caller) += the slots that are not
 void launch_nearest_unpack(hipStream_t s, const uint64_t *slots, uint64_t count, uint32_t *idx, uint32_t *d2, uint64_t *have);
 
+// rtr_nearest_k_points (rtr_nearest_k.hip; rtr.h section 6m; given points and sweep as for rtr_nearest_points).
+// nearest_k_sweep: as nearest_sweep with a ROW of k slots per given point: rows (count * k words of 64 bits, all ones before
+// the launch) [rec.w * k + s] = the (s + 1)-th smallest (bits of d2) << 32 | upload index over the resident points within
+// r2 of that given point, all ones past their number (rtr_topk_cascade.h).  1 <= k <= 64.  *cascades (device, zeroed by
+// the caller) += the cascades started: it depends on timing
+void launch_nearest_k_sweep(hipStream_t s, const Cloud &c, const float *bounds, const uint32_t *perm, const uint64_t *keys, const float4 *rec,
+                            uint64_t m, float radius, float r2, const double glo[3], const double ghi[3], uint64_t *rows, uint32_t k,
+                            uint64_t *cascades, uint64_t *counters);
+// nearest_k_unpack: idx / d2 (device, count * k words each) = the low / high halves of the rows, 2^32 - 1 / the bits of
+// +inf for a slot of all ones; found[j] (count words) = row j's real entries; any of the three may be null.  tally (device,
+// zeroed by the caller) [0] += rows with an entry, [1] += entries, [2] += full rows
+void launch_nearest_k_unpack(hipStream_t s, const uint64_t *rows, uint64_t count, uint32_t k, uint32_t *idx, uint32_t *d2, uint32_t *found,
+                             uint64_t *tally);
+
 // rtr_count_in_bands (rtr_planes.hip; rtr.h section 6j).  counts[k] (device, zeroed by the caller) += the points of the
 // population in band k of `bands` (HOST memory, count x {a, b, c, d_lo, d_hi}), kBandPass bands per launch: every chunk is
 // classified on its box against all bands of a pass and decoded at most once per pass.  c / bounds as for launch_select.

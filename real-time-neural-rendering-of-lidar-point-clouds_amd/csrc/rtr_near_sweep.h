@@ -1,7 +1,7 @@
-// rtr_near_sweep.h -- the sweep over the RESIDENT chunks that rtr_near.hip (rtr_select_near, rtr.h section 6k) and
-// rtr_nearest.hip (rtr_nearest_points, section 6l) share: the box rejection on headers, the column lookup, the reach test
-// and the per-point fallback, written once.  What a call does with an accepted pair is its OP (see "OP" below): 6k ORs
-// bits, 6l keeps minima.  Device-only, as rtr_device.h: included by those two files and nothing else.
+// rtr_near_sweep.h -- the sweep over the RESIDENT chunks that rtr_near.hip (rtr_select_near, rtr.h section 6k), rtr_nearest.hip
+// (rtr_nearest_points, 6l) and rtr_nearest_k.hip (rtr_nearest_k_points, 6m) share: the box rejection on headers, the column
+// lookup, the reach test and the per-point fallback, written once.  What a call does with an accepted pair is its OP (see "OP"
+// below): 6k ORs bits, 6l keeps minima, 6m the k smallest.  Device-only, as rtr_device.h: included by those three files only.
 #pragma once
 #include "rtr_device.h"
 #include "rtr_neighbour_cell.h"

@@ -1,6 +1,6 @@
-// rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6l) on top of the kernels of
-// rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip, rtr_nearest.hip and
-// rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
+// rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6m) on top of the kernels of
+// rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip, rtr_nearest.hip, rtr_nearest_k.hip
+// and rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
 // calls in their own file") has the order of events every call follows and why an error leaves the selection as it was.
 #include <algorithm>
 #include <chrono>
@@ -99,8 +99,8 @@ struct EventSet {  // the stage boundaries of one call
     }
 };
 
-// The GIVEN points of rtr_select_near and rtr_nearest_points (rtr.h sections 6k and 6l): section 6h's key, sort and gather
-// over a plain strided array in host or device memory.  alloc: the scratch, among the call's other allocations; run:
+// The GIVEN points of rtr_select_near, rtr_nearest_points and rtr_nearest_k_points (rtr.h sections 6k - 6m): section 6h's
+// key, sort and gather over a plain strided array in host or device memory.  alloc: the scratch, among the call's other allocations; run:
 // everything up to the sorted records ks.k1 / ks.rec1 of the m points with a cell and their box, with ONE wait on the
 // way, for the counters and the box: a finite point beyond the span fails the call there, before anything has changed.
 // cn (device, 12 words): [0] non-finite given points, [1] those beyond the span, [2] the caller's, [4 .. 7] the sweep's,
@@ -566,6 +566,79 @@ int rtr_nearest_points(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, 
     }
     if (copied) HIP_TRY(c, hipStreamSynchronize(s));
     const uint64_t out[4] = {have, sweep[0], nonfinite, 0};
+    if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- the k nearest resident points to each given point (rtr.h, section 6m) ------------
+// rtr_nearest_points' order of events with a row of k slots per given point in place of one (rtr_nearest_k.hip).  The
+// unpack kernel writes an output in device memory where it lies and one in host memory into a staging copy; it is the
+// last thing queued that can fail, so the caller's arrays and stats change only when the call succeeds.
+int rtr_nearest_k_points(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, float radius, uint32_t k, int flags, uint32_t *index,
+                         float *dist2, uint32_t *found, uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_nearest_k_points: no cloud");
+    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_nearest_k_points: radius must be finite and > 0");
+    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
+    NEED(c, std::isnormal(r2), "rtr_nearest_k_points: the square of radius is not a finite normal fp32 number");
+    NEED(c, count == 0 || xyz != nullptr, "rtr_nearest_k_points: xyz is NULL");
+    NEED(c, xs >= 12 && xs % 4 == 0, "rtr_nearest_k_points: xyz_stride_bytes must be >= 12 and a multiple of 4");
+    NEED(c, k >= 1 && k <= RTR_NEAREST_MAX_K, "rtr_nearest_k_points: k outside 1..RTR_NEAREST_MAX_K");
+    NEED(c, flags == 0, "rtr_nearest_k_points: flags must be 0");
+    if (int rc = check_indexable(c)) return rc;
+    if (count >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "rtr_nearest_k_points: given indices are 32-bit: count is %llu", (unsigned long long)count);
+    if (int rc = need_upload_order(c, "returned")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, slots = count * k;
+    DevBufs buf;
+    EventSet ev;
+    GivenPoints gp;
+    uint64_t *rows, *tally;  // tally: the unpack's three counts, [3] the cascades
+    struct Out { void *dst; uint32_t *dev; uint64_t words; };  // dev: where the unpack writes -- dst itself, or its staging copy
+    Out outs[3] = {{index, nullptr, slots}, {dist2, nullptr, slots}, {found, nullptr, count}};
+    if (int rc = gp.alloc(c, buf, xyz, xs, count)) return rc;
+    uint64_t *cn = gp.cn;
+    HIP_TRY(c, buf.get(&rows, slots * 8));
+    HIP_TRY(c, buf.get(&tally, 4 * sizeof(uint64_t)));
+    for (Out &o : outs) {
+        if (!o.dst || !o.words) continue;
+        if (on_device(o.dst)) o.dev = (uint32_t *)o.dst;
+        else HIP_TRY(c, buf.get(&o.dev, o.words * 4));
+    }
+    if (int rc = ev.create(c, 3)) return rc;
+    if (slots) HIP_TRY(c, hipMemsetAsync(rows, 0xFF, slots * 8, s));
+    HIP_TRY(c, hipMemsetAsync(tally, 0, 4 * sizeof(uint64_t), s));
+    if (int rc = ev.record(c, 0, s)) return rc;
+    if (int rc = gp.run(c, "rtr_nearest_k_points", s, xyz, xs, count, radius)) return rc;
+    const uint64_t nonfinite = gp.nonfinite, m = gp.m;
+    if (int rc = ev.record(c, 1, s)) return rc;
+    uint64_t sweep[4] = {0, 0, (n + 255) / 256, 0};  // (no given point has a cell: every chunk is decided without a launch)
+    if (m) {
+        rtr::launch_nearest_k_sweep(s, cloud_of(c), c->bounds, c->reordered ? c->perm : nullptr, gp.ks.k1, gp.ks.rec1, m, radius, r2, gp.glo, gp.ghi,
+                                    rows, k, tally + 3, cn + 4);
+        if (int rc = launch_check(c, "nearest k sweep")) return rc;
+    }
+    rtr::launch_nearest_k_unpack(s, rows, count, k, outs[0].dev, outs[1].dev, outs[2].dev, tally);
+    if (int rc = launch_check(c, "nearest k unpack")) return rc;
+    if (int rc = ev.record(c, 2, s)) return rc;
+    uint64_t t[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(t, tally, sizeof t, hipMemcpyDeviceToHost, s));
+    if (m) HIP_TRY(c, hipMemcpyAsync(sweep, cn + 4, sizeof sweep, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
+    if (int rc = ev.stage_us(c, 0, 2, c->nearest_k_us)) return rc;
+    bool copied = false;
+    for (const Out &o : outs) {  // (behind everything else that can fail)
+        if (!o.dev || o.dev == o.dst) continue;
+        HIP_TRY(c, hipMemcpyAsync(o.dst, o.dev, o.words * 4, hipMemcpyDeviceToHost, s));
+        copied = true;
+    }
+    if (copied) HIP_TRY(c, hipStreamSynchronize(s));
+    c->nearest_k_tests_k = saturate_k(sweep[1]);
+    c->nearest_k_chunks[0] = saturate_int(sweep[2]), c->nearest_k_chunks[1] = saturate_int(sweep[3]);
+    c->nearest_k_cascades_k = saturate_k(t[3]);
+    const uint64_t out[4] = {t[0], t[1], nonfinite, t[2]};
     if (stats) memcpy(stats, out, sizeof out);
     return RTR_OK;
 }

@@ -503,6 +503,57 @@ class Projector:
             return None
         return arrays[0] if len(arrays) == 1 else tuple(arrays)
 
+    def nearest_k_points(self, xyz, k, radius, stats=True):
+        """Finds on the device, for every GIVEN point of `xyz`, its `k` nearest resident points within `radius`
+        (include/rtr.h section 6m).  xyz: as nearest_points takes it -- float32 rows, (m, 3) or (m, 4), a numpy array, a
+        torch tensor (host or device) or an object with __cuda_array_interface__; m = 0 is legal.  k: 1 .. NEAREST_MAX_K.
+        Candidates: nearest_points' relation.  Returns (index, dist2, found): index (m, k) uint32 and dist2 (m, k)
+        float32, row j the candidates of given point j in ascending order of (dist2 bits, upload index), the first
+        min(k, candidates) of them, NEAREST_NONE and +inf behind them; found (m,) uint32 the number of real entries of
+        each row.  A given point coincident with a resident one finds it at +0.  Device input gives torch tensors on
+        that device, anything else numpy arrays.  The selection, the keep mask and the clip planes play no part.  The
+        call always waits.  stats: also, as a fourth item, (given points with found > 0, the sum of found, non-finite
+        given points, given points with found == k)."""
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        with np.errstate(over="ignore", under="ignore"):
+            r2 = np.float32(r) * np.float32(r)
+        if not (np.isfinite(r2) and r2 >= np.finfo(np.float32).tiny):
+            raise ValueError("the square of radius must be a finite normal float32 number")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError("k must be an integer")
+        k = int(k)
+        if not 1 <= k <= L.NEAREST_MAX_K:
+            raise ValueError("k must be in 1 .. NEAREST_MAX_K (%d)" % L.NEAREST_MAX_K)
+        ptr, stride, m, hold = self._write_source(xyz, np.float32, "xyz")
+        if m >= 2 ** 32:
+            raise ValueError("at most 2^32 - 1 given points")
+        if m and (stride < 12 or stride % 4):
+            raise ValueError("xyz rows must be at least 12 bytes apart, by a multiple of 4")
+        device = None
+        if hasattr(xyz, "data_ptr"):
+            device = xyz.device if xyz.is_cuda else None
+        elif hasattr(xyz, "__cuda_array_interface__"):
+            device = "cuda:%d" % self.device
+        arrays, ptrs = [], []
+        for shape, dt in (((m, k), np.uint32), ((m, k), np.float32), ((m,), np.uint32)):
+            if device is not None:
+                import torch
+                a = torch.empty(shape, dtype=torch.uint32 if dt is np.uint32 else torch.float32, device=device)
+                ptrs.append(C.c_void_p(a.data_ptr()))
+            else:
+                a = np.empty(shape, dt)
+                ptrs.append(_vp(a))
+            arrays.append(a)
+        out = np.zeros(4, np.uint64) if stats else None
+        self._chk(self._lib.rtr_nearest_k_points(self._ctx, ptr if m else None, stride if m else 12, m, r, k, 0, ptrs[0], ptrs[1],
+                                                 ptrs[2], _vp(out)))
+        del hold
+        if stats:
+            arrays.append(tuple(int(v) for v in out))
+        return tuple(arrays)
+
     # -- bands and the dominant plane (rtr.h section 6j)
     def count_in_bands(self, bands, selected=False, stats=True):
         """Counts on the device, for each band {a, b, c, d_lo, d_hi} of `bands` ((k, 5), 1 <= k <= MAX_BANDS), the points
@@ -1094,6 +1145,12 @@ class ProjectCloud:
         Projector.nearest_points).  Returns (index, dist2): the upload index (NEAREST_NONE: none within radius) and the
         squared distance (+inf then), float32 bit for bit."""
         return self._p.nearest_points(vertices, radius, stats=False)
+
+    def nearestKPoints(self, vertices, k, radius):
+        """The k nearest vertices to each row of `vertices` within `radius`, on the device (include/rtr.h section 6m,
+        Projector.nearest_k_points).  Returns (index, dist2, found): (m, k) upload indices (NEAREST_NONE behind the real
+        entries) and squared distances (+inf there), ascending by (dist2 bits, index), and the real entries per row."""
+        return self._p.nearest_k_points(vertices, k, radius, stats=False)
 
     def matchPoints(self, vertices, radius):
         """nearestPoints with the matched vertices themselves: returns (index, dist2, xyz, rgb), xyz (m, 3) float32 and
