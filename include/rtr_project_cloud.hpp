@@ -421,8 +421,8 @@ public:
                                     near_words ? near_words->data() : nullptr, st));
         return st[0];
     }
-    // Appends of the m given points exactly those with no vertex within `radius`, in their order (the selection stays as
-    // it is).  A scan is not thinned against itself: thin it first, or the cloud afterwards (selectVoxelGrid, thin).
+    // Appends of the m given points exactly those with no vertex within `radius`, in their order (the search leaves
+    // the selection as it is; appending even one point drops it, as appendPoints does).  A scan is not thinned against itself: thin it first, or the cloud afterwards (selectVoxelGrid, thin).
     // Returns the number appended.
     size_t appendNewPoints(const float* xyz, size_t xyz_stride_bytes, const uint8_t* rgb, size_t rgb_stride_bytes, size_t m,
                            float radius) {

@@ -1125,7 +1125,8 @@ class ProjectCloud:
 
     def appendNewPoints(self, vertices, colors, radius):
         """Appends of the given points (appendPoints' arrays) exactly those that have no resident vertex within `radius`,
-        in their order: merging an overlapping scan without piling up duplicates.  The selection stays as it is.  A
+        in their order: merging an overlapping scan without piling up duplicates.  The search leaves the selection as
+        it is; appending even one point drops it, as appendPoints does (it stays when nothing is new).  A
         scan is not thinned against itself -- two new points closer than radius to each other are both appended: thin
         the scan first, or the cloud afterwards (selectVoxelGrid, thin).  Returns the number appended."""
         v = np.asarray(vertices)

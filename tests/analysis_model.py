@@ -278,10 +278,11 @@ class _Gen(wm._Gen):
                 dist.append(float(np.sqrt(d2.min())))
         return np.array(out, np.int64)
 
-    def _radius(self, kmax=16):
+    def _radius(self, kmax=16, rank=None):
         """(radius, q, k): float32(1.0001 x the distance from a finite point q to its k-th nearest finite point), k in
-        {1, 4, 16} and at most kmax; None where the cloud has no such radius whose square is a normal float32.  Where q
-        was taken next to a hot position, the distance is stretched to reach that position if eight times it does."""
+        {1, 4, 16} and at most kmax (or `rank`, where nearest_model.py names one: nothing is drawn for k then); None where
+        the cloud has no such radius whose square is a normal float32.  Where q was taken next to a hot position, the
+        distance is stretched to reach that position if eight times it does."""
         fin = self._finite()
         if fin.size < 2:
             return None
@@ -290,7 +291,7 @@ class _Gen(wm._Gen):
             reach = []
             i = int(self._near_hot(1, reach)[0])
             q = self.model.xyz[i].astype(np.float64)
-            k = max(1, min(int(self.arng.choice([1, 4, 16])), fin.size - 1, kmax))
+            k = max(1, min(int(self.arng.choice([1, 4, 16])) if rank is None else rank, fin.size - 1, kmax))
             d = np.sqrt(np.sort(((p - q) ** 2).sum(axis=1))[k])  # ([0] is q itself)
             if reach and d < reach[0] <= 8 * d:
                 d = reach[0]
