@@ -519,7 +519,12 @@ int rtr_project(rtr_ctx *ctx, const float P[16], uint8_t *host_img, float *host_
  * prefilter; masked pixels read depth -1 and colour 0; also fills the fp16
  * {1,5,H,W} device tensor consumed by the U-Net (project_cloud.cu:471). */
 int rtr_project_filtered(rtr_ctx *ctx, const float P[16], uint8_t *host_img, float *host_depth);
-/* Same frame sequences without any host copy or host sync (outputs stay in HBM). */
+/* Same frame sequences without any host copy or host sync (outputs stay in HBM).
+ * P may be any finite 3x4 (row 3 is never read) -- off-axis, rolled, skewed, mirrored, left-handed, rescaled,
+ * composed for a cloud far from the origin: the frame is the oracle's for it, bit for bit; what the library
+ * rejects early (chunk boxes, lanes, quads) is speed only and never changes a pixel.  Tested for row magnitudes
+ * from 2^-104 to 2^40 times a pixel camera's and coordinates up to 2.4e6; not for r.z above 2^126 (the exact
+ * test's reciprocal is subnormal there) nor for rows x coordinates below ~4e-40 (tests/README_cameras.md). */
 int rtr_render(rtr_ctx *ctx, const float P[16], int with_filter);
 
 /* ---- 4b. the same frames with the host copies off the critical path ---------------

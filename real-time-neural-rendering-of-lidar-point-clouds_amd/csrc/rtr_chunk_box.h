@@ -42,8 +42,23 @@ RTR_HD FrustumPlanes rect_planes(const float m[12], float x0, float y0, float x1
     }
     return f;
 }
-// The box [lo, hi] lies entirely on the wrong side of one half-space by more than 1e-4 x the magnitude of the terms
+// The box [lo, hi] lies entirely on the wrong side of one half-space by more than kBoxSlack x the magnitude of the terms
 // involved: no point in it can pass the exact test (see "CULL" in rtr_kernels.hip).  NaN / inf boxes never do.
+//   Error argument (u = 2^-24; p a point of the box that the exact test keeps; T the sum of the term magnitudes of the
+// rows involved at p, weighted as the half-space weights them; M the real value of m, >= T and >= sum |pl_k p_k| + |pl_3|):
+//   - the exact test: each row is one product, two fused multiply-adds and one sum, four roundings of at most u of the
+//     row's term magnitudes; a kept point has r.z > 0 and a rounded quotient in [-0.5, W - 0.5] (1 + 3u) on those rows, which
+//     lies half a pixel inside the half-spaces' -1 and W: the half-space's real value at p is >= -4.01 u T;
+//   - the coefficients pl are sums of up to two rounded terms: <= 2 u of plm each, 2 u M in all;
+//   - the box arithmetic: its products round the real ones monotonically, so max(fl(pl lo), fl(pl hi)) >= pl p_k - u |pl p_k|,
+//     and the three sums of those maxima err by <= 3.01 u M: v >= -10.1 u M (6.0e-7 M), the computed m >= M (1 - 8 u);
+//   - rejection needs v < -2e-6 m, 3.3 times that distance.  The factor is small on purpose: m is the size of the
+//     coordinates times the row, so for a cloud kilometres from the origin every further factor in the slack is that many
+//     scene units through which the test rejects nothing (tests/README_cameras.md has the counts).  Whoever adds a
+//     rounding to the exact test or to the lines below has to add it to this sum.
+//   - not covered: a product in the subnormal range carries 2^-150 of absolute error that no multiple of m pays for;
+//     it counts where m itself is below ~2^-131 (4e-40).  No matrix and cloud that the tests run come near it.
+constexpr float kBoxSlack = 2e-6f;
 RTR_HD bool box_outside(const FrustumPlanes &f, const float lo[3], const float hi[3]) {
     bool culled = false;
     for (int q = 0; q < 5; ++q) {
@@ -54,7 +69,7 @@ RTR_HD bool box_outside(const FrustumPlanes &f, const float lo[3], const float h
             const float e0 = __builtin_fabsf(lo[k]), e1 = __builtin_fabsf(hi[k]);
             m += f.plm[q][k] * (e0 > e1 ? e0 : e1);
         }
-        culled = culled || (v < -1e-4f * m);
+        culled = culled || (v < -kBoxSlack * m);
     }
     return culled;
 }
@@ -89,7 +104,7 @@ RTR_HD bool chunk_box(uint32_t bx, uint32_t by, uint32_t bz, uint32_t widths, fl
 // truncated pattern moves it away from zero past the original (patterns of one sign are ordered like their magnitudes,
 // denormals included), so lo16 <= min and hi16 >= max EXACTLY: the interval holds every value, and at most 2^-7 of an
 // end's magnitude is given away.  box_outside / clip_box_outside ask no more of a box than that it contains the points
-// (see there: the 1e-4 slack covers the arithmetic of the test, and is unchanged).
+// (see there: the slack covers the arithmetic of the test, and is unchanged).
 // (total order of the finite patterns as unsigned keys: -max < ... < -0 < +0 < ... < +max)
 RTR_HD uint32_t float_order_key(uint32_t bits) { return bits ^ ((bits >> 31) != 0u ? 0xFFFFFFFFu : 0x80000000u); }
 RTR_HD uint32_t float_order_bits(uint32_t key) { return key ^ ((key >> 31) != 0u ? 0x80000000u : 0xFFFFFFFFu); }
@@ -148,7 +163,7 @@ RTR_HD bool clip_keep(const Clip &c, float x, float y, float z) {
     return keep;
 }
 // The box [lo, hi] lies entirely on the wrong side of one clip plane: no point in it can pass clip_keep.  Same form as
-// box_outside -- the largest value of a.p + d over the box, v, against a slack of 1e-4 x the magnitude of its terms, m,
+// box_outside -- the largest value of a.p + d over the box, v, against a slack (here 1e-4) x the magnitude of its terms, m,
 // plus 2^-126 for products that leave the normal range.  Why no box holding a point p that clip_keep keeps is rejected
 // (u = 2^-24, T = |a x| + |b y| + |c z| + |d| of the plane at p, all <= m's real value M):
 //   - the point test: each of its three products errs by <= u |term| + 2^-150 (2^-150: a product in the subnormal range;

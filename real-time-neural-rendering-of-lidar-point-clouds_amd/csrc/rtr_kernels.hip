@@ -6,6 +6,7 @@
 // divide / sqrt.  Nothing here is GEMM-shaped: the path is an HBM-bound stream plus
 // a scatter, so the work goes into coalescing, atomic traffic and launch count.
 #include "rtr_device.h"
+#include "rtr_lane_test.h"
 #include "rtr_remove_index.h"
 #include "rtr_extract_index.h"
 
@@ -938,7 +939,7 @@ void launch_lean_fold(hipStream_t s, int W, int H, const TileStore &S, int parit
 // r.y + r.z >= 0, H r.z - r.y >= 0 -- supersets of the exact acceptance region (a kept point
 // has its fp32 quotient in [-0.5, W - 0.5], up to 2^-22 relative) -- and skips the chunk,
 // loads included, when the box lies entirely on the wrong side of one of them by more than
-// 1e-4 x the magnitude of the terms involved (the fp32 evaluation of r.x, r.y, r.z errs by
+// 2e-6 x the magnitude of the terms involved (kBoxSlack; the fp32 evaluation of r.x, r.y, r.z errs by
 // < 3e-7 x that magnitude, so no point the exact arithmetic would keep is ever skipped).
 // Only spatially coherent point orders have tight chunk boxes (rtr_reorder_points).
 // GROUPS = false: a cloud whose consecutive points are unrelated (measured at upload: its 256-point chunks
@@ -972,29 +973,10 @@ void launch_lean_fold(hipStream_t s, int W, int H, const TileStore &S, int parit
 // again: a lane is rejected only when r.z(p_0) + lz s <= -zfront, zfront = 2^-20 x T over the cloud's bounding box, twice
 // the 2^-21 T needed (before round 5 the comparison was with 0: a lane within rounding of the camera plane could go).
 // The CHUNK TEST in front of it (packed clouds, option "chunk_test") rejects a chunk whose header box (chunk_box) lies
-// outside one of the five half-spaces of CULL below by more than 1e-4 x the magnitude of its terms; for r.z >= 0 that
+// outside one of the five half-spaces of CULL below by more than 2e-6 x the magnitude of its terms; for r.z >= 0 that
 // is the same argument: a kept point has a real r.z > -4 u T, the box's computed maximum of r.z errs by a few u of the
-// box's magnitude sum, and 1e-4 x that sum is thousands of times more.
-struct LaneTest {
-    float lz, lall, zsafe, zfront;
-};
-static LaneTest lane_test_consts(const Proj &P, int W, int H, const float absmax[3]) {
-    LaneTest t;
-    const float *m = P.m;
-    const float l1x = fabsf(m[0]) + fabsf(m[1]) + fabsf(m[2]), l1y = fabsf(m[4]) + fabsf(m[5]) + fabsf(m[6]);
-    const float l1z = fabsf(m[8]) + fabsf(m[9]) + fabsf(m[10]);
-    const float hi = (float)(W > H ? W : H) + 0.25f;
-    t.lz = l1z * 1.001f;
-    t.lall = ((l1x > l1y ? l1x : l1y) + hi * l1z) * 1.001f;
-    auto mag = [&](int r) { return fabsf(m[4 * r]) * absmax[0] + fabsf(m[4 * r + 1]) * absmax[1] + fabsf(m[4 * r + 2]) * absmax[2] + fabsf(m[4 * r + 3]); };
-    const float rx = mag(0), ry = mag(1), rz = mag(2);
-    t.zsafe = 0x1p-18f * ((rx > ry ? rx : ry) + hi * rz);
-    t.zfront = 0x1p-20f * rz;
-    if (!(t.zsafe >= 1e-30f)) t.zsafe = __builtin_inff();  // (NaN / no finite box: the margin step never applies)
-    if (!(t.zfront < 3e38f)) t.zfront = __builtin_inff();  // (... nor does the front step)
-    if (!(t.lz < 3e38f) || !(t.lall < 3e38f)) t.zsafe = t.zfront = __builtin_inff(), t.lz = t.lall = 3e38f;
-    return t;
-}
+// box's magnitude sum, and 2e-6 x that sum is three times their total (box_outside has the argument).
+// (struct LaneTest and lane_test_consts: rtr_lane_test.h, which the host checks compile as well)
 
 // SEVERAL VIEWS (MV, rtr_render_views).  One launch streams the cloud once for up to kMaxViews poses: the pose-free work
 // -- the header stream, the decode of the bit-packed coordinates, the colour loads -- is done once per chunk, the pose
@@ -2799,7 +2781,7 @@ void launch_project_bin(hipStream_t s, const Cloud &c, const Proj &P, int W, int
     // (hipExtLaunchKernelGGL with null events is a plain launch; with events the dispatch packet itself carries
     // the start / stop time stamps: no extra packets around the kernel, unlike hipEventRecord pairs)
     const bool packed = c.pk.hdr != nullptr;
-    const LaneTest lt = lane_test_consts(P, W, H, c.absmax);
+    const LaneTest lt = lane_test_consts(P.m, W, H, c.absmax);
     const dim3 block(kBlock);
     const float4 *x = packed ? (const float4 *)c.pk.hdr : (const float4 *)c.x;
     const float4 *y = packed ? (const float4 *)c.pk.planes : (const float4 *)c.y;
@@ -2837,7 +2819,7 @@ hipError_t launch_project_bin_views(hipStream_t s, const Cloud &c, const Proj *P
     t = ViewTab{};
     for (int v = 0; v < count; ++v) {
         t.P[v] = P[v];
-        t.lt[v] = lane_test_consts(P[v], W, H, c.absmax);
+        t.lt[v] = lane_test_consts(P[v].m, W, H, c.absmax);
         t.S[v] = S[v];
     }
     const bool packed = c.pk.hdr != nullptr;

@@ -98,7 +98,7 @@ def box_outside(planes, lo, hi):
             for k in range(3):
                 v = v + np.maximum(pl[q, k] * lo[:, k], pl[q, k] * hi[:, k])
                 m = m + plm[q, k] * mag[:, k]
-            culled |= v < np.float32(-1e-4) * m
+            culled |= v < np.float32(-2e-6) * m
     return culled
 
 
