@@ -196,6 +196,20 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *  "debug_dyn_cap": test aid -- caps the pool of dynamic stream extents at this many entries (-1 = off), so that a
  *          heavy tile overflows it and the error path (RTR_ERR_INTERNAL) can be exercised.
  *  "debug_extract_window": test aid -- caps the points per internal window of rtr_extract_points (section 2e; -1 = off).
+ *  "debug_store_stamp": test aid, frames never depend on it -- sets the 24-bit frame stamp (0 .. 0xFFFFFF) of every tile
+ *          store the context holds (both sets of the single frame, every view's store) and of the stores it creates
+ *          later, so that the stamp's wrap -- reached after 2^24 frames into one store -- can be had within a few frames.
+ *          Forward only: a value below the stamp of a store is RTR_ERR_INVALID and changes nothing.  Host state only:
+ *          nothing is launched or written to the device.  rtr_get_option reads the stamp of the single frame's current
+ *          store: that of its last frame, never 0 once it has rendered one.
+ *  "debug_p2p_barrier": test aid, frames never depend on it -- the barrier number the peer-to-peer exchange starts at,
+ *          as the 32 bits of the value (-1 = off: it starts at 0), so that the wrap of the barrier counter -- reached after
+ *          2^32 barriers -- can be had within a few frames.  Read once per exchange, by the rtr_p2p_export that allocates
+ *          this rank's flag words (the first for a resolution and cloud, or after rtr_p2p_close): the words start
+ *          there, and rtr_p2p_open starts the counter at the same number; a value set later waits for the next such
+ *          export.  Set it before rtr_p2p_export, to the same value on every rank.
+ *          rtr_get_option reads, while the exchange is open, the 32 bits of the number of the last barrier queued
+ *          (otherwise the value set), so that a test can see the counter pass 0.
  *  "xp": only in RTR_EXPERIMENT builds (make experiment): switches parts of the point kernel off for
  *          timing attribution -- frames are WRONG while it is non-zero; the shipped library rejects it.
  *  "probe_variant": measurement aid of tools/probe_variants.py (selects the rtr_stream_probe kernel).

@@ -59,7 +59,7 @@ void p2p_release(rtr_ctx *c) {  // the peers' mappings and this rank's exchange 
     dfree(q.tab);
     q.open = false;
     q.world = 0;
-    q.seq = 0;
+    q.seq = q.start = 0;
 }
 
 struct Slice { size_t chunk, first, count; };
@@ -213,7 +213,7 @@ int ensure_store(rtr_ctx *c, rtr_ctx::Target &t, rtr_ctx::FrontSet &f, int k, hi
         HIP_TRY(c, hipMalloc((void **)&st.ext0, ((size_t)nst * rtr::kS0 + 16) * sizeof(uint64_t)));
         HIP_TRY(c, hipMalloc((void **)&st.meta, meta_bytes));
         HIP_TRY(c, hipMemsetAsync(st.meta, 0, meta_bytes, s));  // stream lengths 0, directory stamps 0 (never current)
-        st.seq = 0;
+        st.seq = c->debug_store_stamp;  // (0 unless option "debug_store_stamp" was set)
         st.nst = f.nst = nst;
         st.ntiles = f.ntiles = nt;
         {   // launch order of the tile kernel: identity until a frame has been rendered
@@ -241,14 +241,13 @@ int ensure_store(rtr_ctx *c, rtr_ctx::Target &t, rtr_ctx::FrontSet &f, int k, hi
     return RTR_OK;
 }
 
-// the store's next 24-bit frame stamp; when it wraps every directory entry is forgotten once
+// the store's next 24-bit frame stamp (rtr_stamp_rule.h); when it wraps every directory entry is forgotten once, on
+// the stream the frame's point kernel will run on: behind everything that still reads the directory, ahead of that kernel
 int next_seq(rtr_ctx *c, rtr_ctx::FrontSet &f, hipStream_t s) {
     auto &t = f.store;
-    t.seq = (t.seq + 1u) & 0xFFFFFFu;
-    if (t.seq == 0u) {
-        HIP_TRY(c, hipMemsetAsync(rtr::ts_dir(t), 0, (size_t)f.nst * rtr::kDirK * sizeof(unsigned long long), s));
-        t.seq = 1u;
-    }
+    const rtr::StampStep step = rtr::next_stamp(t.seq);
+    if (step.clear) HIP_TRY(c, hipMemsetAsync(rtr::ts_dir(t), 0, rtr::dir_bytes(f.nst), s));
+    t.seq = step.stamp;
     return RTR_OK;
 }
 
@@ -797,6 +796,22 @@ int rtr_set_option(rtr_ctx *c, const char *key, int value) {
         c->opt_debug_extract_window = value;
         return RTR_OK;
     }
+    if (!strcmp(key, "debug_store_stamp")) {  // test aid: the 24-bit frame stamp's wrap (next_seq) within a few frames
+        NEED(c, value >= 0 && value <= (int)rtr::kStampMask, "debug_store_stamp must be in 0..0xFFFFFF");
+        // (forward only: a stamp moved backwards could make stale directory words current, which the library never does)
+        for (const auto *t : {&c->frame, &c->views})
+            for (const auto &f : t->fs)
+                NEED(c, !f.store.ext0 || (uint32_t)value >= f.store.seq, "debug_store_stamp is below the stamp of a tile store (forward only)");
+        for (auto *t : {&c->frame, &c->views})
+            for (auto &f : t->fs)
+                if (f.store.ext0) f.store.seq = (uint32_t)value;
+        c->debug_store_stamp = (uint32_t)value;  // (host state only: the kernels get the stamp as an argument)
+        return RTR_OK;
+    }
+    if (!strcmp(key, "debug_p2p_barrier")) {  // test aid: the barrier counter's wrap; read where the flag words are allocated (p2p_alloc)
+        c->opt_debug_p2p_barrier = value;     // (-1: off; anything else is the counter's 32 bits)
+        return RTR_OK;
+    }
     if (!strcmp(key, "p2p_timeout_ms")) {
         NEED(c, value >= 1 && value <= 60000, "p2p_timeout_ms must be in 1..60000");
         c->opt_p2p_timeout_ms = value;
@@ -996,6 +1011,10 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "split_slice")) *value = c->opt_slice;
     else if (!strcmp(key, "point_grid")) *value = c->opt_grid;
     else if (!strcmp(key, "debug_extract_window")) *value = c->opt_debug_extract_window;
+    // (while the exchange is open: the 32 bits of its barrier counter, the number of the last barrier queued)
+    else if (!strcmp(key, "debug_p2p_barrier")) *value = c->p2p.open ? (int)c->p2p.seq : c->opt_debug_p2p_barrier;
+    // (the stamp of the single frame's current store -- of its last frame, or what its first frame will start from)
+    else if (!strcmp(key, "debug_store_stamp")) *value = (int)(c->F().store.ext0 ? c->F().store.seq : c->debug_store_stamp);
     else return fail(c, RTR_ERR_INVALID, "unknown option '%s'", key);
     return RTR_OK;
 }
@@ -2641,7 +2660,13 @@ static int p2p_alloc(rtr_ctx *c) {  // this rank's exchange buffers (per resolut
     if (!q.occ_all) HIP_TRY(c, hipMalloc((void **)&q.occ_all, (size_t)rtr::kMaxPeers * rtr::kP2POccBytes));
     if (!q.flags) {
         HIP_TRY(c, hipExtMallocWithFlags((void **)&q.flags, 4096, hipDeviceMallocUncached));
-        HIP_TRY(c, hipMemsetAsync(q.flags, 0, 4096, c->stream));
+        // (every word starts at the barrier number the exchange starts at -- 0, or option "debug_p2p_barrier" -- and is
+        // filled HERE, before the handles leave rtr_p2p_export: a peer that opens first may already have written its
+        // first barrier into them by the time this rank opens)
+        // (the option is read HERE only: rtr_p2p_open starts the counter at what the words were filled with)
+        if (c->opt_debug_p2p_barrier == -1) HIP_TRY(c, hipMemsetAsync(q.flags, 0, 4096, c->stream));
+        else HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)q.flags, c->opt_debug_p2p_barrier, 4096 / 4, c->stream));
+        q.start = c->opt_debug_p2p_barrier == -1 ? 0u : (uint32_t)c->opt_debug_p2p_barrier;
         HIP_TRY(c, sync_streams(c));
     }
     if (!q.status_host) HIP_TRY(c, mapped_word(&q.status_host, &q.status_dev));
@@ -2727,7 +2752,7 @@ int rtr_p2p_open(rtr_ctx *c, int rank, int world, const rtr_p2p_handles *all) {
     }
     q.rank = rank;
     q.world = world;
-    q.seq = 0;
+    q.seq = q.start;  // (0, or option "debug_p2p_barrier" as it was when this rank's flag words were filled)
     q.open = true;
     *q.status_host = 0;
     return RTR_OK;

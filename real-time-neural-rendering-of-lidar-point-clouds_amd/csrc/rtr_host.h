@@ -101,6 +101,8 @@ struct rtr_ctx {
     int opt_fill_shift = -1;         // spacing of the stream counters, 4 << value bytes; -1: by the frames seen (see "fill_shift")
     int opt_debug_dyn_cap = -1;      // test aid: cap the dynamic extent pool at this many entries (-1: off)
     int opt_debug_extract_window = -1;  // test aid: cap rtr_extract_points' internal window at this many points (-1: off)
+    uint32_t debug_store_stamp = 0;  // test aid (option "debug_store_stamp"): the frame stamp tile stores created from now on start at
+    int opt_debug_p2p_barrier = -1;  // test aid: the barrier number the next peer-to-peer exchange starts at (-1: off, i.e. 0)
     // whole frames launch k_tile_split (an empty launch costs ~5 us) only while tiles above the split threshold have
     // been seen: T1's epilogue stores their number here (mapped host word, read without a sync -- it describes the
     // last frame whose T1 has COMPLETED, the host may be frames ahead), and the launch stays on for kSplitCooldown
@@ -176,6 +178,7 @@ struct rtr_ctx {
         void *opened[9][RTR_P2P_MAX_RANKS] = {};
         int rank = 0, world = 0;
         uint32_t seq = 0;
+        uint32_t start = 0;               // the barrier number the flag words were filled with (p2p_alloc): where seq starts at open
         bool open = false;
     } p2p;
 

@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rtr_barrier_rule.h"
 #include "rtr_chunk_box.h"
+#include "rtr_stamp_rule.h"
 
 namespace rtr {
 
@@ -112,7 +114,7 @@ struct TilePyr {  // F1 folded into T4 (whole-frame calls with the default 4 lev
 // handed out on demand from `dyn` (extent k >= 1 holds stream positions [kS0 << (k-1), kS0 << k)).
 constexpr int kS0Shift = 12;             // static extent: 4096 entries = 32 KB per storage tile
 constexpr uint32_t kS0 = 1u << kS0Shift;
-constexpr int kDirK = 21;                // extents 1..20 reach 2^32 entries per storage tile
+// (kDirK, the directory words per storage tile, and the frame stamp's rule: rtr_stamp_rule.h)
 constexpr int kHeavyExtra = 512;         // extra tile-kernel workgroups available for split tiles
 struct TileStore {   // what travels as kernel argument (the point kernel is short of scalar registers)
     uint64_t *ext0;  // [nst * kS0]

@@ -3809,8 +3809,11 @@ void launch_filter(hipStream_t s, const FilterLevels &L, uint32_t *depth_bits, u
 // with system-scope atomics.
 //
 // Barrier: every rank owns flags[world]; a rank entering barrier number `seq` stores seq into
-// flags[rank] of every peer and then waits until its own flags[r] >= seq for all r.  All ranks run
-// the same sequence of barriers, so the counter can simply increase.  The wait is bounded
+// flags[rank] of every peer and then waits until its own flags[r] has reached seq for all r.  All ranks
+// run the same sequence of barriers, so one counter per rank, incremented per barrier, names them; it is
+// 32 bits wide and wraps after 2^32 barriers, so "has reached" is the serial-number comparison of
+// rtr_barrier_rule.h (a plain flag < seq does not wait for a peer that has not passed 0 yet once seq is small again:
+// around the wrap a rank could run barriers ahead of such a peer, unflagged).  The wait is bounded
 // (wall_clock64 ticks): a rank that never arrives makes the others give up, count the event in
 // `status` (mapped host memory) and go on -- the host then drops back to the collectives.
 __global__ void k_p2p_sync(uint32_t *__restrict__ my_flags, PeerSet peer_flags, int rank, int world, uint32_t seq,
@@ -3819,7 +3822,7 @@ __global__ void k_p2p_sync(uint32_t *__restrict__ my_flags, PeerSet peer_flags, 
     if (t >= world || t == rank) return;
     __hip_atomic_store(static_cast<uint32_t *>(peer_flags.p[t]) + rank, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     const unsigned long long t0 = wall_clock64();
-    while (__hip_atomic_load(my_flags + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < seq) {
+    while (barrier_not_arrived(__hip_atomic_load(my_flags + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM), seq)) {
         if (wall_clock64() - t0 > timeout_ticks) {
             *reinterpret_cast<volatile uint32_t *>(status) = 1u;  // plain store: the word lives in host memory
             break;
@@ -3838,7 +3841,7 @@ __global__ void k_p2p_sync_gather(uint32_t *__restrict__ my_flags, PeerSet peer_
     if (t < world && t != rank) {
         __hip_atomic_store(static_cast<uint32_t *>(peer_flags.p[t]) + rank, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         const unsigned long long t0 = wall_clock64();
-        while (__hip_atomic_load(my_flags + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < seq) {
+        while (barrier_not_arrived(__hip_atomic_load(my_flags + t, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM), seq)) {
             if (wall_clock64() - t0 > timeout_ticks) {
                 *reinterpret_cast<volatile uint32_t *>(status) = 1u;
                 break;

@@ -19,6 +19,10 @@ def main():
     scene, mode = sys.argv[5], int(sys.argv[6])
     stall_rank = int(sys.argv[7]) if len(sys.argv) > 7 else -1  # this rank sleeps past the barrier timeout once
     form = sys.argv[8] if len(sys.argv) > 8 else "p2p"          # "owned": rtr_p2p_render_owned, the frame owner rotates
+    # test aids of the two counters that wrap (include/rtr.h), set on every rank before rtr_p2p_export; -1: not set
+    store_stamp = int(sys.argv[9]) if len(sys.argv) > 9 else -1     # "debug_store_stamp": the exported store's frame stamp
+    barrier_start = int(sys.argv[10]) if len(sys.argv) > 10 else -1  # "debug_p2p_barrier": the barrier counter's 32 bits
+    stall_frame = int(sys.argv[11]) if len(sys.argv) > 11 else 3    # the frame in front of which `stall_rank` sleeps
     dist.init_process_group("gloo")
     rank, world = dist.get_rank(), dist.get_world_size()
     pkg, orc = entry.load_package(), entry.load_oracle()
@@ -27,6 +31,33 @@ def main():
     proj.set_option("mode", mode)   # 0: the atomic form, no bins: every tile counts as occupied
     proj.generate_synthetic(scene, 11, lo, hi - lo, n)
     proj.set_resolution(W, H)
+    if store_stamp >= 0:
+        proj.set_option("debug_store_stamp", store_stamp)
+    if barrier_start != -1:
+        proj.set_option("debug_p2p_barrier", barrier_start - (1 << 32) if barrier_start >= (1 << 31) else barrier_start)
+    pose = lambda k: pkg.orbit_projection(7 * k, W, H)  # noqa: E731
+    if store_stamp >= 0:
+        # (the stamp runs use the poses of stamp_wrap_scenes.py: this rank's own store then uses dynamic extents in every frame)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import stamp_wrap_scenes as sw
+        pose = lambda k: sw.pose(orc, k % len(sw.POSE_SPECS))  # noqa: E731
+    stamps, barriers = [], []  # with a test aid set, read back after every frame: the store's stamp, the exchange's barrier counter
+
+    def read_back():
+        if store_stamp >= 0 or barrier_start != -1:
+            stamps.append(proj.get_option("debug_store_stamp"))
+            barriers.append(proj.get_option("debug_p2p_barrier") & 0xFFFFFFFF)
+
+    def own_store():
+        """This rank's store after the last frame: its heaviest tile against the oracle's count for this rank's shard."""
+        if store_stamp < 0:
+            return None
+        mine = orc.generate(scene, 11, lo, hi - lo, n)
+        counts = sw.tile_counts(orc, mine[0], mine[1], pose(frames - 1), W, H)
+        st = proj.frame_stats()
+        return {"heaviest": st["heaviest_tile"], "want": sw.heaviest_tile(counts), "errors": st["errors"],
+                "dynamic": all(sw.uses_dynamic_extents(sw.tile_counts(orc, mine[0], mine[1], pose(k), W, H))
+                               for k in range(min(frames, len(sw.POSE_SPECS))))}
     local = pkg.sharded.HipLocal(proj)
     local.bind_stream()
     if stall_rank >= 0:
@@ -39,10 +70,11 @@ def main():
         # occupying ranks' entries out of their tile stores); only the frame's owner ends with the whole frame
         local.p2p_setup(rank, world, None)
         for k in range(frames):
-            P = pkg.orbit_projection(7 * k, W, H)
+            P = pose(k)
             filt = (k % 2 == 1) and W % 16 == 0
             owner = (k + 1) % world
             proj.p2p_render_owned(P, filt, owner)
+            read_back()
             if rank == owner:
                 ref = orc.project(xyzw, rgba, P, W, H)
                 rd, ri, rt = ref["depth_bits"], ref["img"], None
@@ -58,7 +90,8 @@ def main():
             else:
                 proj.synchronize()
         out = {"rank": rank, "ok": ok, "exchange": "owned", "p2p_note": None, "timeouts": proj.p2p_timeouts(),
-               "notes": notes, "suspect": None, "errors": proj.frame_stats()["errors"]}
+               "notes": notes, "suspect": None, "errors": proj.frame_stats()["errors"], "stamps": stamps,
+               "barriers": barriers, "store": own_store()}
         gathered = [None] * world
         dist.all_gather_object(gathered, out)
         if rank == 0:
@@ -68,13 +101,14 @@ def main():
         dist.destroy_process_group()
         return
     for k in range(frames):
-        P = pkg.orbit_projection(7 * k, W, H)
+        P = pose(k)
         filt = (k % 2 == 1) and W % 16 == 0
-        if k == 3 and rank == stall_rank:
+        if k == stall_frame and rank == stall_rank:
             import time
             proj.synchronize()
             time.sleep(1.0)  # the other ranks' barriers give up after 150 ms
         sp.render(P, filt)
+        read_back()
         ref = orc.project(xyzw, rgba, P, W, H)
         rd, ri = ref["depth_bits"], ref["img"]
         if filt:
@@ -85,7 +119,7 @@ def main():
             ok = False
             notes.append("frame %d differs on rank %d" % (k, rank))
     out = {"rank": rank, "ok": ok, "exchange": sp.exchange, "p2p_note": sp.p2p_note, "timeouts": proj.p2p_timeouts(),
-           "notes": notes, "suspect": sp.p2p_suspect_frames}
+           "notes": notes, "suspect": sp.p2p_suspect_frames, "stamps": stamps, "barriers": barriers, "store": own_store()}
     gathered = [None] * world
     dist.all_gather_object(gathered, out)
     if rank == 0:

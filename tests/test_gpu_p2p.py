@@ -80,6 +80,89 @@ def test_p2p_barrier_timeout_falls_back_to_the_collectives():
     assert any(r["timeouts"] != 0 for r in out if r["rank"] != 1), out  # a rank that waited saw it
 
 
+def _run_worker(ranks, *args):
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "p2p_worker.py")] + [str(a) for a in args]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stderr[-3000:]
+    out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("[")][-1])
+    assert len(out) == ranks
+    return out
+
+
+STAMP_MAX = 0xFFFFFF
+BARRIER_START = 0xFFFFFFF0
+
+
+def _wrapped_once(values, top, what):
+    """A counter read back after every frame: it starts near `top`, never decreases except for ONE drop from near
+    `top` to a small value (the wrap), and at least four frames follow the drop.  -> the index of the first small one."""
+    drops = [k for k in range(1, len(values)) if values[k] < values[k - 1]]
+    assert len(drops) == 1, (what, values)
+    k = drops[0]
+    assert values[0] > top - 64 and top - 64 < values[k - 1] <= top and values[k] < 64, (what, values)
+    assert len(values) - k >= 4, (what, values)
+    return k
+
+
+@pytest.mark.parametrize("ranks,form", [(2, "p2p"), (3, "owned")])
+def test_p2p_store_stamp_wraps_under_the_peers(ranks, form):
+    """The exported tile store's 24-bit frame stamp wraps while the peers have the store mapped (option
+    "debug_store_stamp" on every rank before rtr_p2p_export; tests/stamp_wrap_scenes.py: every rank's store uses dynamic
+    extents in every frame, in other tiles than the frame before).  rtr_p2p_render on 2 ranks, rtr_p2p_render_owned with
+    a rotating owner on 3: the clear of the directory is ordered against the peers' reads by the frame's barriers, so
+    every frame ≡ oracle on every rank that holds it, with no fallback and no barrier timeout."""
+    import stamp_wrap_scenes as sw
+    out = _run_worker(ranks, sw.W, sw.H, sw.P2P_N[ranks], 12, "uniform_box", 1, -1, form, STAMP_MAX - 4)
+    for r in out:
+        assert r["ok"] and r["timeouts"] == 0, r
+        assert r["exchange"] == ("p2p" if form == "p2p" else "owned"), r
+        assert 0 not in r["stamps"], r
+        _wrapped_once(r["stamps"], STAMP_MAX, r)
+        st = r["store"]  # dynamic extents in use after the wrap: this rank's statistics against the oracle's counts
+        assert st["dynamic"] and st["errors"] == 0 and st["heaviest"] == st["want"] > 2 * 8192, r
+
+
+@pytest.mark.parametrize("ranks,form", [(2, "p2p"), (3, "owned")])
+def test_p2p_barrier_counter_wraps(ranks, form):
+    """Every rank's barrier counter starts at 0xFFFFFFF0 (option "debug_p2p_barrier") and passes 0 within the run: at
+    two or more barriers a frame, by frame 8 of 16.  The fixed barriers go on ordering the ranks through the wrap --
+    frames ≡ oracle on every rank, no timeout, no fallback.  This is a run of the code as it is, not a test that tells
+    the comparisons apart: with ranks in step the old `flag < seq` mis-orders little more than barrier 0 and would very
+    likely pass here too.  What tells them apart is the host check (tests/test_cpp_wrap_rules.py) and the stalled rank
+    of the next test."""
+    out = _run_worker(ranks, 208, 120, 100000, 16, "room_shell", 1, -1, form, -1, BARRIER_START)
+    for r in out:
+        assert r["ok"] and r["timeouts"] == 0, r
+        assert form != "owned" or r["errors"] == 0, r
+        assert r["exchange"] == ("p2p" if form == "p2p" else "owned"), r
+        b = r["barriers"]
+        assert len(b) == 16 and all(((y - x) & 0xFFFFFFFF) >= 2 for x, y in zip(b, b[1:])), r  # >= 2 barriers a frame
+        _wrapped_once(b, 0xFFFFFFFF, r)
+
+
+def test_p2p_barrier_timeout_at_the_counter_wrap():
+    """The stalled-rank run of test_p2p_barrier_timeout_falls_back_to_the_collectives placed ON the counter's wrap: the
+    first barrier of the stalled frame is number 0, and the stalled rank's word on the waiting ranks still reads
+    0xFFFFFFFF.  This is where the old `flag < seq` fails -- 0xFFFFFFFF < 0 is false, and so is 0xFFFFFFFF < 1, < 2:
+    the waiting ranks would run through the whole frame's barriers without waiting, flag no timeout and read the
+    stalled rank's buffers unordered.  The serial-number comparison waits, so the ranks that waited must report the
+    timeout and every rank falls back to the collectives with exact frames, exactly as before the wrap.
+
+    The placement is asserted from the read-back counters: the tile form of rtr_p2p_render runs three barriers a
+    frame, so from 0xFFFFFFF0 the counter reads 0xFFFFFFFF behind frame 4, on every rank (check_every = 1: every rank
+    has finished frame 4 before any begins frame 5)."""
+    ranks, stall_frame = 3, 5
+    out = _run_worker(ranks, 208, 120, 100000, 9, "room_shell", 1, 1, "p2p", -1, BARRIER_START, stall_frame)
+    for r in out:
+        assert r["ok"], r
+        assert r["exchange"] == "collective" and "timed out" in (r["p2p_note"] or ""), r
+        assert r["suspect"] is not None, r
+        b = r["barriers"][:stall_frame]
+        assert b == [BARRIER_START + 3 * (k + 1) for k in range(stall_frame)] and b[-1] == 0xFFFFFFFF, r  # the next barrier is number 0
+    assert any(r["timeouts"] != 0 for r in out if r["rank"] != 1), out  # a rank that waited saw it
+
+
 def test_p2p_single_rank_and_misuse(pkg, orc):
     """world = 1 needs no peer mapping: the p2p calls must then leave the frame of the plain phase
     sequence; and the documented misuse cases return errors instead of touching memory."""
