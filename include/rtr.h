@@ -141,6 +141,9 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          used when it saves at least 1/8 of the stream; 0: never; 2: always, and the packed form is
  *          decoded and compared with the SoA arrays once (an error if a single point differs).  rtr_get_option:
  *          "packed" (1: in use), "packed_millibytes_per_point" (coordinate stream incl. headers, 12000 = raw).
+ *          Applied to the resident cloud, a failed allocation of the fp32 arrays a packed-only cloud is decoded into
+ *          -> RTR_ERR_HIP, and the cloud keeps its form and the option its previous value; where the packed form
+ *          itself does not fit the cloud stays (or becomes) unpacked and the call returns RTR_OK ("packed" 0).
  *  "keep_soa": 0 (default) = a packed cloud is resident in packed form ONLY: the fp32 SoA arrays (12 B per point) are
  *          freed once the cloud has been packed and decoded again -- bit for bit -- by the calls that read fp32
  *          coordinates (mode 0 and the phase calls with another matrix, rtr_reorder_points, rtr_download_points,
@@ -210,6 +213,17 @@ int rtr_get_params(const rtr_ctx *ctx, rtr_params *p);
  *          export.  Set it before rtr_p2p_export, to the same value on every rank.
  *          rtr_get_option reads, while the exchange is open, the 32 bits of the number of the last barrier queued
  *          (otherwise the value set), so that a test can see the counter pass 0.
+ *  "debug_alloc_fail": test aid -- N >= 1: the N-th device or pinned-host allocation the library attempts from now on
+ *          fails, once, as if the device had run out of memory, and the switch disarms itself; 0 disarms it.  The
+ *          library does not ask HIP for that allocation at all: nothing absurd is requested, nothing is launched, HIP's
+ *          last error stays clean.  Every allocation of the library goes through the switch.  rtr_get_option reads the
+ *          attempts still to go, 0 once it has fired or is off (so a test can tell that it fired from a call
+ *          that made fewer than N allocations).  Process-wide, not per context, like the two counters below; setting it
+ *          does not end a streak of option "overlap".  What each call leaves behind after a failed allocation is stated
+ *          with the call.
+ *  "debug_alloc_count" (rtr_get_option only): the allocation attempts of the process so far, failed ones included.
+ *  "debug_alloc_live" (rtr_get_option only): the allocations of the process made through the library and not yet freed,
+ *          over all its contexts (both saturate at 2^31 - 1).
  *  "xp": only in RTR_EXPERIMENT builds (make experiment): switches parts of the point kernel off for
  *          timing attribution -- frames are WRONG while it is non-zero; the shipped library rejects it.
  *  "probe_variant": measurement aid of tools/probe_variants.py (selects the rtr_stream_probe kernel).
@@ -257,21 +271,33 @@ int rtr_synchronize(rtr_ctx *ctx);
  * colour.  xyz_stride_bytes = 16 for the reference's float4 (x,y,z,1) layout
  * (Octreegrid.h:162-170), 12 for tight xyz.  rgb_stride_bytes = 4 for uchar4
  * (c0,c1,c2,255) (Octreegrid.h:172-180), 3 for tight triples; channel order is
- * preserved end to end (B,G,R in the reference).  Replaces any previous cloud. */
+ * preserved end to end (B,G,R in the reference).  Replaces any previous cloud.
+ * A failed allocation -> RTR_ERR_HIP, and the context holds either the previous cloud, untouched, with its keep mask
+ * and selection (only when the call fails before anything of that cloud has gone), or no points at all, as after an
+ * upload of 0 points: rtr_num_points reads 0, no keep mask, no selection, "packed" and "reordered" read 0; clip planes,
+ * options and resolution stay.  Never part of one cloud and part of the other: the previous cloud's arrays are given
+ * back or overwritten first (two clouds may not fit), so the new one cannot be had all-or-nothing beside it.
+ * The sort of option "auto_reorder" and the packing of option "pack" behind the upload are best effort: where their
+ * scratch does not fit the call returns RTR_OK with the cloud unsorted ("reordered" 0) / unpacked ("packed" 0). */
 int rtr_upload_points(rtr_ctx *ctx, const float *xyz, size_t xyz_stride_bytes, const uint8_t *rgb,
                       size_t rgb_stride_bytes, size_t n);
 /* Synthesises points [first, first+count) of a `total`-point scene directly in
- * HBM (counter-based generator; bit-identical to the oracle's). */
+ * HBM (counter-based generator; bit-identical to the oracle's).  A failed allocation: as for
+ * rtr_upload_points -- RTR_ERR_HIP, and the previous cloud untouched or no points at all. */
 int rtr_generate_synthetic(rtr_ctx *ctx, int scene, uint64_t seed, uint64_t first, uint64_t count,
                            uint64_t total);
 /* One-off Morton (Z-order) sort of the resident cloud: consecutive points become spatial
  * neighbours, like the reference loader's 0.25 m block order (cloudreader.cpp:8-82).  Never
  * changes a frame (min and integer sums commute); it changes rtr_download_points' order and
- * makes the per-tile appends long runs and option "cull" effective. */
+ * makes the per-tile appends long runs and option "cull" effective.
+ * A failed allocation up to and including the sort -> RTR_ERR_HIP and the cloud is as it was (order, "reordered", the
+ * permutation of "point_ids", the packed form): the sort writes nothing back before it holds all its scratch.  Behind
+ * the sort the packing is best effort, as after an upload: RTR_OK with "packed" 0. */
 int rtr_reorder_points(rtr_ctx *ctx);
 int rtr_num_points(const rtr_ctx *ctx, uint64_t *n);
 /* Copies the resident cloud back as float4 / uchar4 AoS (tests, debugging), in the RESIDENT order (see
- * option "auto_reorder"). */
+ * option "auto_reorder").  A cloud resident in packed form only is decoded for the copy; a failed allocation ->
+ * RTR_ERR_HIP, the cloud stays as it was (in packed form only) and the outputs hold nothing defined. */
 int rtr_download_points(rtr_ctx *ctx, float *xyzw, uint8_t *rgba, uint64_t first, uint64_t count);
 
 /* ---- 2b. appending points to the resident cloud ------------------------------------------------------------------
@@ -451,7 +477,8 @@ int rtr_transform_points(rtr_ctx *ctx, const float M[12], const uint32_t *select
  * Errors (RTR_ERR_INVALID, nothing is written): no cloud; nwords != (n + 31) / 32 with a selection; select_words NULL
  * with nwords > 0; a bad stride for a non-NULL stream; a selection on a sorted cloud without "point_ids" = 1; indices on
  * a sorted cloud without "point_ids" = 1; xyz, rgb, indices and total all NULL.  2^32 points or more:
- * RTR_ERR_UNSUPPORTED. */
+ * RTR_ERR_UNSUPPORTED.  A failed allocation -> RTR_ERR_HIP: the call only reads, so the cloud and the context are as
+ * they were; what the outputs and *total hold is not defined. */
 int rtr_extract_points(rtr_ctx *ctx, const uint32_t *select_words, uint64_t nwords,
                        uint64_t first, uint64_t count,
                        float *xyz, size_t xyz_stride_bytes,
@@ -520,25 +547,35 @@ int rtr_write_points(rtr_ctx *ctx, const uint32_t *select_words, uint64_t nwords
 /* P = K4 * E in fp32, row-major, exactly as the reference composes it with glm:
  * K row-major 3x3 intrinsics, E row-major 4x4 world->camera, both double. */
 int rtr_compose_projection(const double K[9], const double E[16], float P[16]);
-/* (Re)allocates the frame buffers; cheap no-op when unchanged (project_cloud.cu:275-298). */
+/* (Re)allocates the frame buffers; cheap no-op when unchanged (project_cloud.cu:275-298).  The buffers of the previous
+ * resolution are given back first (and an exported peer-to-peer exchange with them), so a failed allocation ->
+ * RTR_ERR_HIP leaves the context with NO resolution, as rtr_create left it: the calls that need one return
+ * RTR_ERR_INVALID until rtr_set_resolution succeeds.  The cloud, its mask, selection and clip planes are untouched. */
 int rtr_set_resolution(rtr_ctx *ctx, int width, int height);
 
 /* ---- 4. whole-frame calls (the reference's public methods) ---------------------- */
 /* computeRGBD (project_cloud.cu:268-312): clear, min-depth pass, accumulate pass,
  * resolve.  host_img: W*H*3 u8 or NULL; host_depth: W*H float or NULL (empty
  * pixel = FLT_MAX).  Both NULL -> RTR_ERR_NO_OUTPUT like the reference's -1;
- * use rtr_render() for device-resident output. */
+ * use rtr_render() for device-resident output.  A failed allocation: see rtr_render. */
 int rtr_project(rtr_ctx *ctx, const float P[16], uint8_t *host_img, float *host_depth);
 /* computeFilteredRGBD (project_cloud.cu:394-434): rtr_project + depth-heuristic
  * prefilter; masked pixels read depth -1 and colour 0; also fills the fp16
- * {1,5,H,W} device tensor consumed by the U-Net (project_cloud.cu:471). */
+ * {1,5,H,W} device tensor consumed by the U-Net (project_cloud.cu:471).  A failed allocation: see rtr_render. */
 int rtr_project_filtered(rtr_ctx *ctx, const float P[16], uint8_t *host_img, float *host_depth);
 /* Same frame sequences without any host copy or host sync (outputs stay in HBM).
  * P may be any finite 3x4 (row 3 is never read) -- off-axis, rolled, skewed, mirrored, left-handed, rescaled,
  * composed for a cloud far from the origin: the frame is the oracle's for it, bit for bit; what the library
  * rejects early (chunk boxes, lanes, quads) is speed only and never changes a pixel.  Tested for row magnitudes
  * from 2^-104 to 2^40 times a pixel camera's and coordinates up to 2.4e6; not for r.z above 2^126 (the exact
- * test's reciprocal is subnormal there) nor for rows x coordinates below ~4e-40 (tests/README_cameras.md). */
+ * test's reciprocal is subnormal there) nor for rows x coordinates below ~4e-40 (tests/README_cameras.md).
+ * The three calls of this section make what they need on first use and keep it: a tile store per resolution, an extent
+ * pool per cloud (both again for the second set of option "overlap"), the prefilter's pyramid levels.  A failed
+ * allocation of one of them -> RTR_ERR_HIP: the frame buffers hold nothing defined, the cloud, mask, selection, clip
+ * planes and resolution are untouched, a resource is either complete or absent, and the same call made again starts
+ * from there and renders the exact frame.  A frame that a synchronising call (rtr_synchronize, rtr_wait,
+ * rtr_download_buffer, the host copies of rtr_project) renders again after an overflow of the adaptive pool allocates
+ * the larger pool: if that fails the synchronising call returns RTR_ERR_HIP and the frame must be rendered again. */
 int rtr_render(rtr_ctx *ctx, const float P[16], int with_filter);
 
 /* ---- 4b. the same frames with the host copies off the critical path ---------------
@@ -552,7 +589,10 @@ int rtr_render(rtr_ctx *ctx, const float P[16], int with_filter);
  * (option "pool_worst_case"), every slot still queued is rendered again with the grown pool, synchronously,
  * before RTR_OK is returned; a slot whose cloud has been replaced since fails instead.  The buffers (rtr_host_output_buffers: W*H*3 u8, W*H float,
  * valid until the next rtr_set_resolution) may be read until the slot is used again.  A caller that needs the
- * frame in its own arrays copies from there (or keeps using the synchronous calls). */
+ * frame in its own arrays copies from there (or keeps using the synchronous calls).
+ * The slots' pinned buffers and device snapshots are made by the first rtr_project_async / rtr_host_output_buffers at a
+ * resolution, slot by slot; a failed allocation -> RTR_ERR_HIP, nothing is queued, a slot is either complete or absent
+ * (no slot is marked busy), and the cloud and the frame resources of section 4 are as they were. */
 #define RTR_ASYNC_SLOTS 2
 int rtr_host_output_buffers(rtr_ctx *ctx, int slot, uint8_t **img, float **depth);
 int rtr_project_async(rtr_ctx *ctx, const float P[16], int slot, int with_filter);
@@ -584,7 +624,11 @@ int rtr_filter(rtr_ctx *ctx);                          /* project_cloud.cu:331-3
  * within the barrier timeout (option "p2p_timeout_ms", default 2 s) is flagged in rtr_p2p_status on the
  * ranks that waited for it; their frames since then are undefined.  The caller polls rtr_p2p_status
  * (a host word, no synchronisation), agrees with the other ranks and falls back to the collectives --
- * sharded.ShardedProjector does that every `check_every` frames.  rtr_set_resolution closes the mapping. */
+ * sharded.ShardedProjector does that every `check_every` frames.  rtr_set_resolution closes the mapping.
+ * rtr_p2p_export allocates this rank's tile store, worst-case extent pool and exchange buffers; a failed allocation ->
+ * RTR_ERR_HIP, the handle block holds nothing defined, the exchange buffers are all given back (nothing is exported:
+ * rtr_p2p_open refuses until an export succeeds), and the cloud and the frame buffers are untouched.  rtr_p2p_open
+ * after a failed allocation of its own has closed every mapping it made and dropped the export. */
 #define RTR_P2P_MAX_RANKS 16
 typedef struct rtr_p2p_handles {
     unsigned char depth[64], accum[64], image[64], reduced[64], flags[64], tiles[64];
@@ -665,7 +709,9 @@ int rtr_download_buffer(rtr_ctx *ctx, int which, void *host, size_t bytes);
  * with the point pass queued right behind it; a point pass that read a frame reported incomplete otherwise makes
  * rtr_download_buffer of its outputs fail with RTR_ERR_INTERNAL.
  * Errors: RTR_ERR_INVALID without a cloud or a resolution, for `what` outside 1..3, and when the cloud was sorted
- * without option "point_ids" (rtr_last_error says so); RTR_ERR_UNSUPPORTED for 2^32 points or more.
+ * without option "point_ids" (rtr_last_error says so); RTR_ERR_UNSUPPORTED for 2^32 points or more.  The two buffers
+ * are made on first use; a failed allocation -> RTR_ERR_HIP, nothing is launched, the frame and the cloud are
+ * untouched, and a buffer the call could not make reads as before any pass (RTR_ERR_INVALID from rtr_device_buffer).
  * Sharded frames: on a rank the indices are rank-local (its own upload), and only its own points are tested against
  * the depth buffer it holds; a global ID needs the rank's offset and a MIN across ranks, which the library does not do. */
 #define RTR_POINTS_IDS 1
@@ -689,7 +735,10 @@ int rtr_point_pass(rtr_ctx *ctx, const float P[16], int what);
  * rtr_synchronize or rtr_download_buffer(RTR_BUF_VIEW_*), with every view's pool worst-case sized (16 B per point and
  * view) from then on for this cloud; a caller who consumes batches on the stream without such a call sets option
  * "pool_worst_case" 1.
- * Errors: count outside 1..RTR_MAX_VIEWS, P NULL, no cloud or no resolution -> RTR_ERR_INVALID, nothing changed. */
+ * Errors: count outside 1..RTR_MAX_VIEWS, P NULL, no cloud or no resolution -> RTR_ERR_INVALID, nothing changed.
+ * A failed allocation (batch buffers, pyramid levels, a view's store or pool, the views' table) -> RTR_ERR_HIP: no batch
+ * is current ("views" reads 0, RTR_BUF_VIEW_* hold nothing defined), every resource is complete or absent, the single
+ * frame and the cloud are untouched, and the same call made again renders the exact batch. */
 #define RTR_MAX_VIEWS 8
 int rtr_render_views(rtr_ctx *ctx, int count, const float *P, int with_filter);
 
@@ -741,7 +790,8 @@ int rtr_get_clip_planes(rtr_ctx *ctx, int *count, float *planes);
  * Memory: while a mask is set, 2 bits per point (upload-order and resident-order copies) + 1 byte per 256 points; none
  * without one.
  * Errors: no cloud, nwords != (n + 31) / 32, words NULL with nwords > 0, a sorted cloud without point_ids
- * -> RTR_ERR_INVALID, nothing changed. */
+ * -> RTR_ERR_INVALID, nothing changed.  A failed allocation -> RTR_ERR_HIP and the old mask (or none) stays in force:
+ * the new words are built in buffers of their own and swapped in at the end. */
 int rtr_set_point_keep(rtr_ctx *ctx, const uint32_t *words, uint64_t nwords);
 
 /* ---- 6f. selection: name the points of a region on the device -----------------------------------------------------
@@ -779,7 +829,8 @@ int rtr_set_point_keep(rtr_ctx *ctx, const uint32_t *words, uint64_t nwords);
  * Errors: no cloud, plane_count outside 0..RTR_MAX_CLIP_PLANES, planes NULL with plane_count > 0, a non-finite
  * coefficient or a = b = c = 0, P given without a resolution or with rect NULL, a rectangle not within 0 <= x0 < x1 <= W
  * and 0 <= y0 < y1 <= H, an unknown op, a sorted cloud without point_ids -> RTR_ERR_INVALID, nothing changed;
- * RTR_ERR_UNSUPPORTED for 2^32 points or more. */
+ * RTR_ERR_UNSUPPORTED for 2^32 points or more.  The call allocates only when no selection exists yet: a failed
+ * allocation -> RTR_ERR_HIP, there is still no selection ("selection" reads 0) and stats is untouched. */
 #define RTR_SELECT_REPLACE   0   /* sel  = hit          */
 #define RTR_SELECT_ADD       1   /* sel |= hit          */
 #define RTR_SELECT_SUBTRACT  2   /* sel &= ~hit         */
@@ -823,7 +874,8 @@ int rtr_clear_selection(rtr_ctx *ctx);
  * Errors: no cloud, origin or cell NULL, a non-finite origin, a cell size that is not finite and > 0 or whose fp32
  * reciprocal is not, min_count == 0, an unknown op, a sorted cloud without point_ids -> RTR_ERR_INVALID;
  * RTR_ERR_UNSUPPORTED for 2^32 points or more; a failed allocation -> RTR_ERR_HIP.  Every scratch buffer is allocated
- * before the first selection word changes: after any of these the selection and everything else are as they were. */
+ * before the first selection word changes: after any of these the selection and everything else are as they were, the
+ * caller's stats included (they are written by a call that succeeds, and by no other). */
 int rtr_select_voxel_grid(rtr_ctx *ctx, const float origin[3], const float cell[3], uint32_t min_count, int op,
                           uint64_t stats[4]);
 
@@ -871,7 +923,8 @@ int rtr_select_voxel_grid(rtr_ctx *ctx, const float origin[3], const float cell[
  * number, min_neighbours == 0, an unknown op, a sorted cloud without point_ids -> RTR_ERR_INVALID; 2^32 points or more ->
  * RTR_ERR_UNSUPPORTED; a finite coordinate beyond the span -> RTR_ERR_UNSUPPORTED (found by a counter of the key sweep,
  * before any selection word changes); a failed allocation -> RTR_ERR_HIP.  Every scratch buffer is allocated before the
- * first selection word changes: after any of these the selection and everything else are as they were. */
+ * first selection word changes: after any of these the selection and everything else are as they were, the caller's
+ * stats included. */
 int rtr_select_neighbours(rtr_ctx *ctx, float radius, uint32_t min_neighbours, int op, uint64_t stats[4]);
 
 /* ---- 6i. selection by connected cluster: Euclidean clustering -------------------------------------------------------
@@ -931,7 +984,8 @@ int rtr_select_neighbours(rtr_ctx *ctx, float radius, uint32_t min_neighbours, i
  * cloud without point_ids -> RTR_ERR_INVALID; 2^32 points or more -> RTR_ERR_UNSUPPORTED; a finite coordinate beyond the
  * span -> RTR_ERR_UNSUPPORTED (found by a counter of the key sweep, before any selection word or any element of labels
  * changes, and before a selection is created); a failed allocation -> RTR_ERR_HIP.  Every scratch buffer is allocated
- * before the first selection word changes: after any of these the selection and everything else are as they were. */
+ * before the first selection word changes: after any of these the selection and everything else are as they were, the
+ * caller's labels and stats included. */
 #define RTR_CLUSTER_SEEDED 1   /* flags: only clusters holding a currently selected point */
 int rtr_select_clusters(rtr_ctx *ctx, float radius, uint32_t min_points, uint32_t max_points,
                         int flags, int op, uint32_t *labels, uint64_t stats[4]);

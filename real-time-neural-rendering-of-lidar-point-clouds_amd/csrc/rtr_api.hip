@@ -40,7 +40,7 @@ namespace {
 
 template <class T>
 void dfree(T *&p) {
-    if (p) (void)hipFree(p);
+    (void)rtr::dev_free(p);
     p = nullptr;
 }
 
@@ -75,8 +75,8 @@ Slice p2p_slice(const rtr_ctx *c) {  // pixels owned by this rank: slices are mu
 void free_host_out(rtr_ctx *c) {
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     for (auto &h : c->ho) {
-        if (h.img) (void)hipHostFree(h.img);
-        if (h.depth) (void)hipHostFree(h.depth);
+        (void)rtr::host_free(h.img);
+        (void)rtr::host_free(h.depth);
         dfree(h.dimg); dfree(h.ddepth);
         if (h.snap) (void)hipEventDestroy(h.snap);
         if (h.done) (void)hipEventDestroy(h.done);
@@ -88,7 +88,7 @@ hipError_t sync_streams(rtr_ctx *c);
 
 // One zeroed word of pinned host memory that the device writes through its mapping (error bits, statistics)
 hipError_t mapped_word(uint32_t **host, uint32_t **dev) {
-    hipError_t e = hipHostMalloc((void **)host, sizeof(uint32_t), hipHostMallocMapped);
+    hipError_t e = rtr::host_malloc(host, sizeof(uint32_t), hipHostMallocMapped);
     if (e != hipSuccess) {
         *host = nullptr;
         return e;
@@ -98,7 +98,7 @@ hipError_t mapped_word(uint32_t **host, uint32_t **dev) {
     e = hipHostGetDevicePointer(&d, *host, 0);
     *dev = static_cast<uint32_t *>(d);
     if (e != hipSuccess) {
-        (void)hipHostFree(*host);
+        (void)rtr::host_free(*host);
         *host = nullptr;
     }
     return e;
@@ -116,13 +116,13 @@ int alloc_target(rtr_ctx *c, rtr_ctx::Target &t, int count) {
     free_target(t);
     const size_t npix = (size_t)c->W * c->H, n = (size_t)count * npix;
     const size_t nparts = (size_t)((c->W + 31) / 32) * ((c->H + 31) / 32);
-    hipError_t e = hipMalloc((void **)&t.depth, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&t.img, (n * 3 + 15) & ~(size_t)15);
-    if (e == hipSuccess) e = hipMalloc((void **)&t.tensor, n * 5 * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&t.acc, npix * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&t.mask, npix);
-    if (e == hipSuccess) e = hipMalloc((void **)&t.part_min, nparts * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&t.part_max, nparts * 4);
+    hipError_t e = rtr::dev_malloc(&t.depth, n * 4);
+    if (e == hipSuccess) e = rtr::dev_malloc(&t.img, (n * 3 + 15) & ~(size_t)15);
+    if (e == hipSuccess) e = rtr::dev_malloc(&t.tensor, n * 5 * sizeof(uint16_t));
+    if (e == hipSuccess) e = rtr::dev_malloc(&t.acc, npix * 16);
+    if (e == hipSuccess) e = rtr::dev_malloc(&t.mask, npix);
+    if (e == hipSuccess) e = rtr::dev_malloc(&t.part_min, nparts * 4);
+    if (e == hipSuccess) e = rtr::dev_malloc(&t.part_max, nparts * 4);
     if (e != hipSuccess) {
         free_target(t);
         return fail(c, RTR_ERR_HIP, "hipMalloc of the frame buffers (%d x %dx%d) failed: %s", count, c->W, c->H,
@@ -210,8 +210,14 @@ int ensure_store(rtr_ctx *c, rtr_ctx::Target &t, rtr_ctx::FrontSet &f, int k, hi
         f.lean_pending = false;
         const size_t meta_bytes = rtr::ts_meta_words(nst, nt) * sizeof(uint32_t);
         // (+ 16 entries of slack: the tile kernel's sweeps read a few entries past the piece they are masking)
-        HIP_TRY(c, hipMalloc((void **)&st.ext0, ((size_t)nst * rtr::kS0 + 16) * sizeof(uint64_t)));
-        HIP_TRY(c, hipMalloc((void **)&st.meta, meta_bytes));
+        // (ext0 and meta stand or fall together: after a failure the set holds neither, and f.nst == 0 sends the next
+        // frame through here again)
+        hipError_t e = rtr::dev_malloc(&st.ext0, ((size_t)nst * rtr::kS0 + 16) * sizeof(uint64_t));
+        if (e == hipSuccess) e = rtr::dev_malloc(&st.meta, meta_bytes);
+        if (e != hipSuccess) {
+            dfree(st.ext0); dfree(st.meta);
+            return fail(c, RTR_ERR_HIP, "allocating the tile store (%d storage tiles) failed: %s", nst, hipGetErrorString(e));
+        }
         HIP_TRY(c, hipMemsetAsync(st.meta, 0, meta_bytes, s));  // stream lengths 0, directory stamps 0 (never current)
         st.seq = c->debug_store_stamp;  // (0 unless option "debug_store_stamp" was set)
         st.nst = f.nst = nst;
@@ -297,28 +303,44 @@ int ensure_pool(rtr_ctx *c, rtr_ctx::Target &t, rtr_ctx::FrontSet &f, uint64_t o
     HIP_TRY(c, sync_streams(c));  // (frames in flight may still read the old pool)
     dfree(f.dyn);
     if (&t == &c->frame) c->list_valid = false;
+    // (the old pool is given back first: the two together may not fit.  The sizes are set behind the allocation they
+    // describe: after a failure the set has no pool and says so -- ensure_store copies dyn / dyn_cap into the store's
+    // header, and set_overlap and rtr_p2p_export read them -- and the next frame allocates again)
+    f.dyn_cap = 0;
+    f.pool_n = 0;
+    HIP_TRY(c, rtr::dev_malloc(&f.dyn, want * sizeof(uint64_t)));
     f.dyn_cap = want;
     f.pool_n = c->n;
-    HIP_TRY(c, hipMalloc((void **)&f.dyn, f.dyn_cap * sizeof(uint64_t)));
     return RTR_OK;
 }
 
 // The fp32 SoA arrays of a cloud that is resident in packed form only (option "keep_soa" = 0, the default): decoded
 // from the packed form -- bit for bit, it is lossless -- for the calls that read fp32 coordinates (the atomic form, the
 // sort, rtr_download_points, option "pack" = 0, the stream probe).  They stay until the cloud is packed again.
+// x, y and z stand or fall together: every reader takes a set c->x to mean three decoded arrays, so after a failed
+// allocation the context holds none of them and the cloud stays resident in packed form only, as it was.
+hipError_t alloc_xyz(rtr_ctx *c, uint64_t points) {
+    hipError_t e = rtr::dev_malloc(&c->x, points * 4);
+    if (e == hipSuccess) e = rtr::dev_malloc(&c->y, points * 4);
+    if (e == hipSuccess) e = rtr::dev_malloc(&c->z, points * 4);
+    if (e != hipSuccess) { dfree(c->x); dfree(c->y); dfree(c->z); }
+    return e;
+}
 int ensure_soa(rtr_ctx *c) {
     if (c->x) return RTR_OK;
     if (!c->pk_hdr || c->cap == 0) return fail(c, RTR_ERR_INTERNAL, "no resident coordinates");
-    HIP_TRY(c, hipMalloc((void **)&c->x, c->cap * 4));
-    HIP_TRY(c, hipMalloc((void **)&c->y, c->cap * 4));
-    HIP_TRY(c, hipMalloc((void **)&c->z, c->cap * 4));
+    const hipError_t ea = alloc_xyz(c, c->cap);
+    if (ea != hipSuccess) return fail(c, RTR_ERR_HIP, "allocating the fp32 coordinate arrays failed: %s", hipGetErrorString(ea));
     rtr::unpack_to_soa(c->stream, rtr::PackedXyz{c->pk_hdr, c->pk_planes, c->pk_planes_b}, c->n, c->x, c->y, c->z);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, RTR_ERR_HIP, "unpack launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) {  // (never decoded: they must not pass for coordinates)
+        dfree(c->x); dfree(c->y); dfree(c->z);
+        return fail(c, RTR_ERR_HIP, "unpack launch failed: %s", hipGetErrorString(e));
+    }
     return RTR_OK;
 }
 void drop_soa(rtr_ctx *c) {  // after the cloud has been packed: 12 B per point back
-    if (!c->pk_hdr || c->opt_keep_soa || !c->x) return;
+    if (!c->pk_hdr || c->opt_keep_soa || !(c->x || c->y || c->z)) return;
     (void)sync_streams(c);
     dfree(c->x); dfree(c->y); dfree(c->z);
 }
@@ -327,19 +349,23 @@ int alloc_cloud(rtr_ctx *c, uint64_t n) {
     uint64_t n_pad = (n + 3) & ~3ull;
     if (n_pad == 0) n_pad = 4;
     if (n_pad > c->cap) {
+        // (the old cloud goes first: the two together may not fit.  The six arrays stand or fall together: after a
+        // failure the context holds no cloud at all, n = cap = 0 as free_cloud left it -- the callers see to the rest,
+        // discard_cloud)
         free_cloud(c);
-        HIP_TRY(c, hipMalloc((void **)&c->x, n_pad * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->y, n_pad * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->z, n_pad * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->rgba, n_pad * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->bounds, ((n_pad / 4 + 63) / 64) * 6 * sizeof(float)));
-        HIP_TRY(c, hipMalloc((void **)&c->spread, ((n_pad / 4 + 63) / 64) * sizeof(float)));
+        hipError_t e = alloc_xyz(c, n_pad);
+        if (e == hipSuccess) e = rtr::dev_malloc(&c->rgba, n_pad * 4);
+        if (e == hipSuccess) e = rtr::dev_malloc(&c->bounds, ((n_pad / 4 + 63) / 64) * 6 * sizeof(float));
+        if (e == hipSuccess) e = rtr::dev_malloc(&c->spread, ((n_pad / 4 + 63) / 64) * sizeof(float));
+        if (e != hipSuccess) {
+            free_cloud(c);
+            return fail(c, RTR_ERR_HIP, "allocating a cloud of %llu points failed: %s", (unsigned long long)n, hipGetErrorString(e));
+        }
         c->cap = n_pad;
     }
-    if (!c->x) {  // (the previous cloud was resident in packed form only)
-        HIP_TRY(c, hipMalloc((void **)&c->x, c->cap * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->y, c->cap * 4));
-        HIP_TRY(c, hipMalloc((void **)&c->z, c->cap * 4));
+    if (!c->x) {  // (the previous cloud was resident in packed form only: nothing of it has changed yet, it stays as it was)
+        const hipError_t e = alloc_xyz(c, c->cap);
+        if (e != hipSuccess) return fail(c, RTR_ERR_HIP, "allocating the fp32 coordinate arrays failed: %s", hipGetErrorString(e));
     }
     if (n != c->n) {  // (the adaptive extent pool starts over; the peers of a sharded frame must map the new one)
         if (c->p2p.open || c->p2p.red) p2p_release(c);
@@ -447,8 +473,15 @@ int ensure_levels(rtr_ctx *c, rtr_ctx::Target &t) {  // the pyramid levels 1..le
     if (t.lv_levels == L) return RTR_OK;
     for (auto &l : t.lv) dfree(l);
     t.lv_levels = 0;
-    for (int i = 1, w = c->W / 2, h = c->H / 2; i <= L; ++i, w /= 2, h /= 2)
-        HIP_TRY(c, hipMalloc((void **)&t.lv[i], sizeof(float) * (size_t)w * h));
+    // (all or nothing: lv_levels, which is what says the levels exist, is set behind the last of them, and after a
+    // failure none is kept -- the next filtered frame starts over)
+    for (int i = 1, w = c->W / 2, h = c->H / 2; i <= L; ++i, w /= 2, h /= 2) {
+        const hipError_t e = rtr::dev_malloc(&t.lv[i], sizeof(float) * (size_t)w * h);
+        if (e != hipSuccess) {
+            for (auto &l : t.lv) dfree(l);
+            return fail(c, RTR_ERR_HIP, "allocating pyramid level %d (%dx%d) failed: %s", i, w, h, hipGetErrorString(e));
+        }
+    }
     t.lv_levels = L;
     return RTR_OK;
 }
@@ -579,7 +612,7 @@ int rtr_create(rtr_ctx **out, int device) {
     // (the minmax words serve RTR_BUF_MINMAX before any resolution is set)
     e = mapped_word(&c->split_host, &c->split_dev);
     for (auto *t : {&c->frame, &c->views}) {
-        if (e == hipSuccess) e = hipMalloc((void **)&t->minmax, RTR_MAX_VIEWS * 2 * sizeof(uint32_t));
+        if (e == hipSuccess) e = rtr::dev_malloc(&t->minmax, RTR_MAX_VIEWS * 2 * sizeof(uint32_t));
         if (e == hipSuccess) e = mapped_word(&t->err_host, &t->err_dev);
         if (e == hipSuccess) e = mapped_word(&t->entries_host, &t->entries_dev);
     }
@@ -603,12 +636,12 @@ int rtr_destroy(rtr_ctx *c) {
     free_cloud(c);
     for (auto *t : {&c->frame, &c->views}) {
         dfree(t->minmax);
-        if (t->err_host) (void)hipHostFree(t->err_host);
-        if (t->entries_host) (void)hipHostFree(t->entries_host);
+        (void)rtr::host_free(t->err_host);
+        (void)rtr::host_free(t->entries_host);
     }
-    if (c->p2p.status_host) (void)hipHostFree(c->p2p.status_host);
-    if (c->split_host) (void)hipHostFree(c->split_host);
-    if (c->vtab.host) (void)hipHostFree(c->vtab.host);
+    (void)rtr::host_free(c->p2p.status_host);
+    (void)rtr::host_free(c->split_host);
+    (void)rtr::host_free(c->vtab.host);
     dfree(c->vtab.dev);
     if (c->vtab.copied) (void)hipEventDestroy(c->vtab.copied);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -750,6 +783,14 @@ static int pack_cloud(rtr_ctx *c);
 
 int rtr_set_option(rtr_ctx *c, const char *key, int value) {
     if (!c) return RTR_ERR_INVALID;
+    // test aid: the value-th allocation attempted from now on fails, once (rtr_alloc_rule.h).  Process-wide, like the
+    // counters: some allocation sites have no context at hand.  It touches nothing of the context, not even a streak of
+    // whole frames, so that a test can arm it between two frames of one
+    if (key && !strcmp(key, "debug_alloc_fail")) {
+        NEED(c, value >= 0, "debug_alloc_fail must be >= 0 (0: off)");
+        rtr::alloc_rule().arm(value);
+        return RTR_OK;
+    }
     c->ov.other_call();
     NEED(c, key != nullptr, "key is NULL");
     if (!strcmp(key, "mode")) {
@@ -869,11 +910,15 @@ int rtr_set_option(rtr_ctx *c, const char *key, int value) {
     }
     if (!strcmp(key, "pack")) {  // applies to the resident cloud at once, and to every later one
         NEED(c, value >= 0 && value <= 2, "pack must be 0 (never), 1 (when it pays) or 2 (always, verified)");
+        const int before = c->opt_pack;
         c->opt_pack = value;
         DevGuard g(c->device);
         HIP_TRY(c, sync_streams(c));
         if (c->n == 0 || c->cap == 0) return RTR_OK;
-        if (int rc = ensure_soa(c)) return rc;  // (packing reads the fp32 arrays; "pack" = 0 leaves them as the resident form)
+        if (int rc = ensure_soa(c)) {  // (packing reads the fp32 arrays; "pack" = 0 leaves them as the resident form)
+            c->opt_pack = before;  // (nothing has changed: the cloud stays in the form it has, under the option it had)
+            return rc;
+        }
         if (int rc = pack_cloud(c)) return rc;
         drop_soa(c);
         return RTR_OK;
@@ -993,14 +1038,14 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
         *value = 0;
         if (c->pk_hdr && c->n) {
             uint64_t *dev = nullptr, host[2] = {0, 0};
-            hipError_t e = hipMalloc((void **)&dev, sizeof host);
+            hipError_t e = rtr::dev_malloc(&dev, sizeof host);
             if (e == hipSuccess) e = hipMemsetAsync(dev, 0, sizeof host, c->stream);
             if (e == hipSuccess) {
                 rtr::launch_wide_counts(c->stream, c->pk_hdr, (((uint64_t)c->n + 3) / 4 + 63) / 64, dev);
                 e = hipMemcpyAsync(host, dev, sizeof host, hipMemcpyDeviceToHost, c->stream);
             }
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (dev) (void)hipFree(dev);
+            (void)rtr::dev_free(dev);
             if (e != hipSuccess) return fail(c, RTR_ERR_HIP, "wide_chunks: %s", hipGetErrorString(e));
             const uint64_t v = host[key[11] ? 1 : 0];
             *value = v > 0x7FFFFFFFull ? 0x7FFFFFFF : (int)v;
@@ -1011,6 +1056,12 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     else if (!strcmp(key, "split_slice")) *value = c->opt_slice;
     else if (!strcmp(key, "point_grid")) *value = c->opt_grid;
     else if (!strcmp(key, "debug_extract_window")) *value = c->opt_debug_extract_window;
+    // (the allocation switch and counters of rtr_alloc_rule.h, process-wide; the counts saturate at INT_MAX)
+    else if (!strcmp(key, "debug_alloc_fail")) *value = (int)std::min<int64_t>(rtr::alloc_rule().remaining(), 0x7FFFFFFF);
+    else if (!strcmp(key, "debug_alloc_count"))
+        *value = (int)std::min<uint64_t>(rtr::alloc_rule().attempts.load(std::memory_order_relaxed), 0x7FFFFFFFu);
+    else if (!strcmp(key, "debug_alloc_live"))
+        *value = (int)std::max<int64_t>(0, std::min<int64_t>(rtr::alloc_rule().live.load(std::memory_order_relaxed), 0x7FFFFFFF));
     // (while the exchange is open: the 32 bits of its barrier counter, the number of the last barrier queued)
     else if (!strcmp(key, "debug_p2p_barrier")) *value = c->p2p.open ? (int)c->p2p.seq : c->opt_debug_p2p_barrier;
     // (the stamp of the single frame's current store -- of its last frame, or what its first frame will start from)
@@ -1400,6 +1451,33 @@ static int finish_new_cloud(rtr_ctx *c, const char *what) {
     return RTR_OK;
 }
 
+// What a cloud-replacing call falls back to when it fails after the previous cloud has begun to go (its arrays are freed
+// or overwritten first, since two clouds may not fit): the context as an upload of 0 points leaves it -- no points, mask,
+// selection, packed form, permutation or pools; the clip planes, options and frame resources stay.  The call's own
+// error message is kept.  Should even the empty cloud's 16-byte arrays fail, the context is as rtr_create left it.
+static void discard_cloud(rtr_ctx *c) {
+    const std::string err = c->err;
+    (void)sync_streams(c);
+    free_cloud(c);
+    if (alloc_cloud(c, 0) != RTR_OK || finish_new_cloud(c, "empty cloud") != RTR_OK) {
+        (void)hipGetLastError();
+        free_cloud(c);
+        c->reordered = false;
+        ++c->cloud_seq;
+        c->jr.frame.count = 0;
+        c->pp_vis_current = false;
+    }
+    c->jr.views.count = 0;
+    c->err = err;
+}
+
+// alloc_cloud has failed: either nothing has changed (the old cloud, resident in packed form only, is intact; cap > 0)
+// or the old cloud is gone
+static int new_cloud_failed(rtr_ctx *c, int rc) {
+    if (c->cap == 0) discard_cloud(c);
+    return rc;
+}
+
 int rtr_upload_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rgb, size_t rs, size_t n) {
     if (!c) return RTR_ERR_INVALID;
     c->ov.other_call();
@@ -1409,9 +1487,12 @@ int rtr_upload_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
     NEED(c, n < (1ull << 32), "too many points for one context (point indices are 32-bit): shard the cloud");
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
-    if (int rc = alloc_cloud(c, n)) return rc;
+    if (int rc = alloc_cloud(c, n)) return new_cloud_failed(c, rc);
     DevBufs buf;
-    if (int rc = stage_points(c, buf, xyz, xs, rgb, rs, n, c->x, c->y, c->z, c->rgba)) return rc;
+    if (int rc = stage_points(c, buf, xyz, xs, rgb, rs, n, c->x, c->y, c->z, c->rgba)) {
+        discard_cloud(c);  // (the arrays hold some of the old cloud and some of the new)
+        return rc;
+    }
     return finish_new_cloud(c, "aos_to_soa");
 }
 
@@ -1424,7 +1505,7 @@ int rtr_generate_synthetic(rtr_ctx *c, int scene, uint64_t seed, uint64_t first,
     NEED(c, count < (1ull << 32), "too many points for one context (point indices are 32-bit): shard the cloud");
     DevGuard g(c->device);
     HIP_TRY(c, sync_streams(c));
-    if (int rc = alloc_cloud(c, count)) return rc;
+    if (int rc = alloc_cloud(c, count)) return new_cloud_failed(c, rc);
     rtr::launch_generate(c->stream, scene, seed, first, count, total, c->x, c->y, c->z, c->rgba);
     return finish_new_cloud(c, "generate");
 }
@@ -1633,7 +1714,9 @@ static int commit_window(rtr_ctx *c, DevBufs &buf, const Window &w, const Splice
 // measured again.  resized (append, remove): upload indices or the point count changed too -- the selection goes, and
 // the n-sized state (the peers' mappings of this rank's pools, the adaptive pool sizing) starts over; a move keeps all
 // of that.  bad / which: option "pack" = 2, the commit's pack_verify counter and what it counted
-static int cloud_edited(rtr_ctx *c, bool resized, const uint64_t *bad, const char *which) {
+// measure: order_quality's device scratch, which the caller allocated among its own buffers -- this function runs behind
+// the commit and allocates nothing, so a failed allocation never reaches a caller as RTR_OK over an edited cloud
+static int cloud_edited(rtr_ctx *c, bool resized, const uint64_t *bad, const char *which, void *measure) {
     if (resized) free_select(c);
     ++c->cloud_seq;
     c->list_valid = false;
@@ -1648,7 +1731,7 @@ static int cloud_edited(rtr_ctx *c, bool resized, const uint64_t *bad, const cha
     }
     {   // order measure and absmax over every chunk box: the lane test's margin steps and the incoherent form read them
         float ratio = 0.f;
-        if (rtr::order_quality(c->stream, c->bounds, c->n, &ratio, c->absmax) != 0) {
+        if (rtr::order_quality(c->stream, c->bounds, c->n, &ratio, c->absmax, measure) != 0) {
             (void)hipGetLastError();
             c->absmax[0] = c->absmax[1] = c->absmax[2] = __builtin_inff();
         }
@@ -1729,6 +1812,8 @@ int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
     HIP_TRY(c, d2d(s, w.wx + r, bx, m * 4)); HIP_TRY(c, d2d(s, w.wy + r, by, m * 4)); HIP_TRY(c, d2d(s, w.wz + r, bz, m * 4));
     rtr::launch_pad_nan(s, w.wx, w.wy, w.wz, nullptr, w.wn, w.wpad);
     uint64_t *tot = nullptr, *bad = nullptr;  // packed: the window's units, pack mismatches
+    void *measure;  // (cloud_edited's scratch: allocated with the rest, before anything is committed)
+    HIP_TRY(c, buf.get(&measure, rtr::order_quality_scratch_bytes()));
     if (c->pk_hdr) {
         HIP_TRY(c, buf.get(&tot, 2 * sizeof(uint64_t)));
         HIP_TRY(c, hipMemsetAsync(tot, 0, 2 * sizeof(uint64_t), s));
@@ -1744,7 +1829,7 @@ int rtr_append_points(rtr_ctx *c, const float *xyz, size_t xs, const uint8_t *rg
     }
     if (int rc = commit_window(c, buf, w, Splice{n1, grown, n0, bc, m, bperm, nullptr, nullptr, up1, bad, "append"})) return rc;
     c->reordered = c->reordered || sort;
-    return cloud_edited(c, true, bad, "appended points");
+    return cloud_edited(c, true, bad, "appended points", measure);
 }
 
 // ---- removing (rtr.h, section 2c) -------------------------------------------------------------------------------
@@ -1775,6 +1860,8 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     const uint64_t scr_words = std::max(rtr::scan_scratch_words(nch0), rtr::scan_scratch_words(nwords));
     HIP_TRY(c, buf.get(&scr, scr_words * 4));
     HIP_TRY(c, buf.get(&tot, 4 * sizeof(uint64_t)));  // first loss, survivors (then the window's units), kept words' total, pack mismatches
+    void *measure;  // (cloud_edited's scratch: allocated with the rest, before anything is committed)
+    HIP_TRY(c, buf.get(&measure, rtr::order_quality_scratch_bytes()));
     HIP_TRY(c, hipMemcpyAsync(kw, keep_words, nwords * 4, hipMemcpyDefault, s));
     HIP_TRY(c, hipMemsetAsync(tot, 0xFF, sizeof(uint64_t), s));
     HIP_TRY(c, hipMemsetAsync(tot + 1, 0, 3 * sizeof(uint64_t), s));
@@ -1785,8 +1872,13 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
     HIP_TRY(c, hipStreamSynchronize(s));
     if (int rc = launch_check(c, "remove count")) return rc;
     const uint64_t n1 = head[1], c0 = head[0] < nch0 ? head[0] : nch0;
-    free_select(c);  // (the caller's words are in kw: the selection's own buffer may have been passed)
-    if (n1 == n0) return RTR_OK;  // (every point stays: nothing else changes)
+    // (the selection goes with every removal -- here where every point stays, with the cloud where none does, in
+    // cloud_edited otherwise: behind the last allocation that can fail, so that a failed call leaves it in force.  The
+    // caller's words are in kw: the selection's own buffer may have been passed)
+    if (n1 == n0) {  // (every point stays: nothing else changes)
+        free_select(c);
+        return RTR_OK;
+    }
     if (n1 == 0) {  // (no point stays: the context of an upload of 0 points)
         // (its 4-point arrays are allocated before the cloud is freed: a failed allocation leaves the cloud as it was;
         // the upload then finds them and allocates nothing)
@@ -1829,7 +1921,7 @@ int rtr_remove_points(rtr_ctx *c, const uint32_t *keep_words, uint64_t nwords) {
         dfree(c->pp_vis);
         c->pp_vis_words = 0;
     }
-    return cloud_edited(c, true, tot + 3, "points of the rebuilt chunks");
+    return cloud_edited(c, true, tot + 3, "points of the rebuilt chunks", measure);
 }
 
 // ---- moving and writing points (rtr.h, sections 2d and 2f) -------------------------------------------------------
@@ -1953,6 +2045,8 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
     uint32_t *sel = nullptr;
     uint64_t *tot;  // span (first, last chunk), window units, pack mismatches
     HIP_TRY(c, buf.get(&tot, 4 * sizeof(uint64_t)));
+    void *measure;  // (cloud_edited's scratch: allocated with the rest, before anything is committed)
+    HIP_TRY(c, buf.get(&measure, rtr::order_quality_scratch_bytes()));
     HIP_TRY(c, hipMemsetAsync(tot, 0, 4 * sizeof(uint64_t), s));
     uint64_t c0 = 0, c1 = nch - 1;
     if (!every) {
@@ -1967,7 +2061,7 @@ int rtr_transform_points(rtr_ctx *c, const float M[12], const uint32_t *select_w
         rtr::launch_transform_window(s, cl, perm0, sel, c0, c1, A, wx, wy, wz, in_place);
     };
     if (int rc = rebuild_chunks(c, buf, c0, c1, tot, "transform", fill, [] {})) return rc;
-    return cloud_edited(c, false, tot + 3, "moved points");
+    return cloud_edited(c, false, tot + 3, "moved points", measure);
 }
 
 // ---- writing points back (rtr.h, section 2f) ------------------------------------------------------------------------
@@ -2006,6 +2100,8 @@ int rtr_write_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords, 
     HIP_TRY(c, buf.get(&wscan, nw * 4));
     HIP_TRY(c, buf.get(&selw, nw * 4));
     HIP_TRY(c, buf.get(&tot, 5 * sizeof(uint64_t)));
+    void *measure;  // (cloud_edited's scratch: allocated with the rest, before anything is committed)
+    HIP_TRY(c, buf.get(&measure, rtr::order_quality_scratch_bytes()));
     HIP_TRY(c, hipMemsetAsync(tot, 0, 5 * sizeof(uint64_t), s));
     if (!every) {
         uint32_t *scratch;
@@ -2050,7 +2146,7 @@ int rtr_write_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords, 
         colours();
         HIP_TRY(c, hipStreamSynchronize(s));
         if (int rc = launch_check(c, "write colours")) return rc;
-        return cloud_edited(c, false, tot + 3, "written points");
+        return cloud_edited(c, false, tot + 3, "written points", measure);
     }
     drop_soa(c);  // (SoA arrays decoded for a call in between are not kept: they would hold the old coordinates)
     const rtr::Cloud cl = cloud_of(c);
@@ -2058,7 +2154,7 @@ int rtr_write_points(rtr_ctx *c, const uint32_t *select_words, uint64_t nwords, 
         rtr::launch_write_window(s, cl, perm0, selw, sel, wscan, c0, c1, dxyz, xs, first, wx, wy, wz, in_place);
     };
     if (int rc = rebuild_chunks(c, buf, c0, c1, tot, "write", fill, colours)) return rc;
-    return cloud_edited(c, false, tot + 3, "written points");
+    return cloud_edited(c, false, tot + 3, "written points", measure);
 }
 
 int rtr_reorder_points(rtr_ctx *c) {
@@ -2074,14 +2170,31 @@ int rtr_reorder_points(rtr_ctx *c) {
     if (int rc = ensure_soa(c)) return rc;
     // option "point_ids": the permutation travels with the points (starting from the identity while the cloud is in
     // upload order; a cloud sorted before without it has lost its upload order for good)
-    if (c->opt_point_ids && (!c->reordered || c->perm)) {
-        if (!c->perm) HIP_TRY(c, hipMalloc((void **)&c->perm, c->cap * 4));
-        if (!c->reordered) rtr::launch_iota(c->stream, c->perm, c->n);
-    } else {
-        dfree(c->perm);
+    // A failure up to and including the sort leaves the cloud as it was: the sort works on scratch copies and writes
+    // nothing back before it has every one of them (rtr_reorder.hip), so what this call has made by then is taken back --
+    // a permutation allocated here (it would stand filled with the identity beside `reordered` = 0), and the fp32
+    // arrays decoded for the sort -- and a permutation that goes with this sort goes only behind it.
+    const bool with_perm = c->opt_point_ids && (!c->reordered || c->perm);
+    const bool perm_made = with_perm && !c->perm;
+    auto as_it_was = [&]() {
+        if (perm_made) dfree(c->perm);
+        drop_soa(c);
+    };
+    if (perm_made) {
+        const hipError_t ea = rtr::dev_malloc(&c->perm, c->cap * 4);
+        if (ea != hipSuccess) {
+            as_it_was();
+            return fail(c, RTR_ERR_HIP, "rtr_reorder_points: allocating the permutation failed: %s", hipGetErrorString(ea));
+        }
     }
-    int e = rtr::reorder_morton(c->stream, c->x, c->y, c->z, c->rgba, c->n, c->perm);
-    if (e != 0) return fail(c, RTR_ERR_HIP, "reorder failed: %s", hipGetErrorString((hipError_t)e));
+    if (with_perm && !c->reordered) rtr::launch_iota(c->stream, c->perm, c->n);
+    int e = rtr::reorder_morton(c->stream, c->x, c->y, c->z, c->rgba, c->n, with_perm ? c->perm : nullptr);
+    if (e != 0) {
+        (void)sync_streams(c);  // (the identity's launch may still be writing the permutation)
+        as_it_was();
+        return fail(c, RTR_ERR_HIP, "reorder failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    if (!with_perm) dfree(c->perm);
     c->reordered = true;
     free_pack(c);
     rtr::launch_chunk_bounds(c->stream, cloud_of(c), c->bounds, c->spread);
@@ -2112,8 +2225,12 @@ int rtr_download_points(rtr_ctx *c, float *xyzw, uint8_t *rgba, uint64_t first, 
     DevBufs buf;
     float *dx;
     uint8_t *dc;
-    HIP_TRY(c, buf.get(&dx, m * 16));
-    HIP_TRY(c, buf.get(&dc, m * 4));
+    hipError_t ea = buf.get(&dx, m * 16);
+    if (ea == hipSuccess) ea = buf.get(&dc, m * 4);
+    if (ea != hipSuccess) {
+        drop_soa(c);  // (decoded for this call only: a call that has run out of memory does not hold on to 12 B per point)
+        return fail(c, RTR_ERR_HIP, "rtr_download_points: allocating the staging buffers failed: %s", hipGetErrorString(ea));
+    }
     for (uint64_t off = 0; off < count; off += chunk) {
         uint64_t cnt = (count - off) < chunk ? (count - off) : chunk;
         uint64_t s0 = first + off;
@@ -2570,14 +2687,24 @@ static int ensure_host_out(rtr_ctx *c) {
     const size_t npix = (size_t)c->W * c->H;
     for (auto &h : c->ho) {
         if (h.img) continue;
-        HIP_TRY(c, hipHostMalloc((void **)&h.img, (npix * 3 + 15) & ~(size_t)15, hipHostMallocMapped));
-        HIP_TRY(c, hipHostMalloc((void **)&h.depth, (npix * 4 + 15) & ~(size_t)15, hipHostMallocMapped));
-        HIP_TRY(c, hipHostGetDevicePointer(&h.img_map, h.img, 0));
-        HIP_TRY(c, hipHostGetDevicePointer(&h.depth_map, h.depth, 0));
-        HIP_TRY(c, hipMalloc((void **)&h.dimg, (npix * 3 + 15) & ~(size_t)15));
-        HIP_TRY(c, hipMalloc((void **)&h.ddepth, (npix * 4 + 15) & ~(size_t)15));
-        HIP_TRY(c, hipEventCreateWithFlags(&h.snap, hipEventDisableTiming));
-        HIP_TRY(c, hipEventCreateWithFlags(&h.done, hipEventDisableTiming));
+        // (a slot is complete or empty: h.img is what says it exists, so after a failure the slot holds nothing and the
+        // next call makes it again.  Slots completed before stay)
+        hipError_t e = rtr::host_malloc(&h.img, (npix * 3 + 15) & ~(size_t)15, hipHostMallocMapped);
+        if (e == hipSuccess) e = rtr::host_malloc(&h.depth, (npix * 4 + 15) & ~(size_t)15, hipHostMallocMapped);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&h.img_map, h.img, 0);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&h.depth_map, h.depth, 0);
+        if (e == hipSuccess) e = rtr::dev_malloc(&h.dimg, (npix * 3 + 15) & ~(size_t)15);
+        if (e == hipSuccess) e = rtr::dev_malloc(&h.ddepth, (npix * 4 + 15) & ~(size_t)15);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&h.snap, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&h.done, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            (void)rtr::host_free(h.img); (void)rtr::host_free(h.depth);
+            dfree(h.dimg); dfree(h.ddepth);
+            if (h.snap) (void)hipEventDestroy(h.snap);
+            if (h.done) (void)hipEventDestroy(h.done);
+            h = rtr_ctx::HostOut{};
+            return fail(c, RTR_ERR_HIP, "allocating the asynchronous host outputs failed: %s", hipGetErrorString(e));
+        }
     }
     return RTR_OK;
 }
@@ -2651,15 +2778,15 @@ int rtr_project_filtered(rtr_ctx *c, const float P[16], uint8_t *host_img, float
 
 // ---- peer-to-peer exchange ------------------------------------------------------------
 
-static int p2p_alloc(rtr_ctx *c) {  // this rank's exchange buffers (per resolution)
+static int p2p_alloc_parts(rtr_ctx *c) {
     auto &q = c->p2p;
     const size_t npix = (size_t)c->W * c->H;
-    if (!q.red) HIP_TRY(c, hipMalloc((void **)&q.red, ((npix + 3) & ~(size_t)3) * sizeof(uint32_t)));
-    if (!q.ximg) HIP_TRY(c, hipMalloc((void **)&q.ximg, (npix * 3 + 15) & ~(size_t)15));
-    if (!q.occ) HIP_TRY(c, hipMalloc((void **)&q.occ, rtr::kP2POccBytes));
-    if (!q.occ_all) HIP_TRY(c, hipMalloc((void **)&q.occ_all, (size_t)rtr::kMaxPeers * rtr::kP2POccBytes));
+    if (!q.red) HIP_TRY(c, rtr::dev_malloc(&q.red, ((npix + 3) & ~(size_t)3) * sizeof(uint32_t)));
+    if (!q.ximg) HIP_TRY(c, rtr::dev_malloc(&q.ximg, (npix * 3 + 15) & ~(size_t)15));
+    if (!q.occ) HIP_TRY(c, rtr::dev_malloc(&q.occ, rtr::kP2POccBytes));
+    if (!q.occ_all) HIP_TRY(c, rtr::dev_malloc(&q.occ_all, (size_t)rtr::kMaxPeers * rtr::kP2POccBytes));
     if (!q.flags) {
-        HIP_TRY(c, hipExtMallocWithFlags((void **)&q.flags, 4096, hipDeviceMallocUncached));
+        HIP_TRY(c, rtr::dev_malloc_uncached(&q.flags, 4096));
         // (every word starts at the barrier number the exchange starts at -- 0, or option "debug_p2p_barrier" -- and is
         // filled HERE, before the handles leave rtr_p2p_export: a peer that opens first may already have written its
         // first barrier into them by the time this rank opens)
@@ -2671,6 +2798,15 @@ static int p2p_alloc(rtr_ctx *c) {  // this rank's exchange buffers (per resolut
     }
     if (!q.status_host) HIP_TRY(c, mapped_word(&q.status_host, &q.status_dev));
     return RTR_OK;
+}
+
+// this rank's exchange buffers (per resolution), all or nothing: `red` is what says "exported" to the rest of the file
+// (free_lists, ensure_pool, rtr_render's overlap condition) and rtr_p2p_open takes the set for complete, so after a
+// failure none of them is kept and the next rtr_p2p_export makes them again
+static int p2p_alloc(rtr_ctx *c) {
+    const int rc = p2p_alloc_parts(c);
+    if (rc != RTR_OK) p2p_release(c);
+    return rc;
 }
 
 int rtr_p2p_export(rtr_ctx *c, rtr_p2p_handles *mine) {
@@ -2685,10 +2821,17 @@ int rtr_p2p_export(rtr_ctx *c, rtr_p2p_handles *mine) {
     // (the owner-computes form reads the peers' tile stores: allocate this rank's now -- it is sized by the cloud, for
     // the worst case: a pool the peers have mapped must never move)
     c->frame.cur = 0;
+    // (pool_worst is what makes ensure_pool size the pool for the worst case, so it is set ahead of that allocation; it
+    // describes an exported pool, and an export that fails takes it back: later frames size their pool as before)
+    const bool worst_before = c->frame.pool_worst;
     c->frame.pool_worst = true;
-    if (int rc = ensure_pool(c, c->frame, c->F(), 0)) return rc;
-    if (int rc = ensure_store(c, c->frame, c->F(), 0, c->stream)) return rc;
-    if (int rc = p2p_alloc(c)) return rc;
+    int rc_alloc = ensure_pool(c, c->frame, c->F(), 0);
+    if (!rc_alloc) rc_alloc = ensure_store(c, c->frame, c->F(), 0, c->stream);
+    if (!rc_alloc) rc_alloc = p2p_alloc(c);
+    if (rc_alloc) {
+        c->frame.pool_worst = worst_before;
+        return rc_alloc;
+    }
     HIP_TRY(c, sync_streams(c));
     memset(mine, 0, sizeof *mine);
     void *bufs[9] = {c->frame.depth, c->frame.acc, c->p2p.ximg, c->p2p.red, c->p2p.flags, c->p2p.occ,
@@ -2747,8 +2890,13 @@ int rtr_p2p_open(rtr_ctx *c, int rank, int world, const rtr_p2p_handles *all) {
             tab.depth[r] = static_cast<const uint32_t *>(q.depth.p[r]);
             tab.ximg[r] = static_cast<const uint8_t *>(q.image.p[r]);
         }
-        if (!q.tab) HIP_TRY(c, hipMalloc((void **)&q.tab, sizeof tab));
-        HIP_TRY(c, hipMemcpy(q.tab, &tab, sizeof tab, hipMemcpyHostToDevice));
+        hipError_t e = q.tab ? hipSuccess : rtr::dev_malloc(&q.tab, sizeof tab);
+        if (e == hipSuccess) e = hipMemcpy(q.tab, &tab, sizeof tab, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {  // (as for a handle that does not open: the mappings made so far must not outlive the call)
+            int rc = fail(c, RTR_ERR_HIP, "the peers' pointer table failed: %s", hipGetErrorString(e));
+            p2p_release(c);
+            return rc;
+        }
     }
     q.rank = rank;
     q.world = world;
@@ -2946,12 +3094,24 @@ int rtr_point_pass(rtr_ctx *c, const float P[16], int what) {
     const size_t npix = (size_t)c->W * c->H;
     const uint64_t words = (((c->n + 3) / 4 + 63) / 64) * 8;  // (8 per 256-point chunk: whole-chunk stores)
     if (!c->pp_done) HIP_TRY(c, hipEventCreateWithFlags(&c->pp_done, hipEventDisableTiming));
-    if ((what & RTR_POINTS_IDS) && !c->pp_ids) HIP_TRY(c, hipMalloc((void **)&c->pp_ids, npix * 4));
+    // (a buffer of point IDs exists only once a pass has filled it: RTR_BUF_POINT_ID serves whatever pp_ids holds, so one
+    // made here goes again when the call fails before its launch)
+    const bool ids_made = (what & RTR_POINTS_IDS) && !c->pp_ids;
+    if (ids_made) HIP_TRY(c, rtr::dev_malloc(&c->pp_ids, npix * 4));
     if ((what & RTR_POINTS_VISIBLE) && (!c->pp_vis || c->pp_vis_words < words)) {
         HIP_TRY(c, sync_streams(c));  // (a pass in flight may still write the old mask)
         dfree(c->pp_vis);
-        c->pp_vis_words = words > 8 ? words : 8;
-        HIP_TRY(c, hipMalloc((void **)&c->pp_vis, c->pp_vis_words * 4));
+        // (the size and "current" describe the mask: without one, after a failure, they say so -- RTR_BUF_VISIBLE then
+        // answers as before any pass -- and the size is set behind the allocation)
+        c->pp_vis_words = 0;
+        c->pp_vis_current = false;
+        const uint64_t want = words > 8 ? words : 8;
+        const hipError_t e = rtr::dev_malloc(&c->pp_vis, want * 4);
+        if (e != hipSuccess) {
+            if (ids_made) dfree(c->pp_ids);
+            return fail(c, RTR_ERR_HIP, "rtr_point_pass: allocating the visibility mask failed: %s", hipGetErrorString(e));
+        }
+        c->pp_vis_words = want;
     }
     uint32_t *ids = (what & RTR_POINTS_IDS) ? c->pp_ids : nullptr, *vis = (what & RTR_POINTS_VISIBLE) ? c->pp_vis : nullptr;
     const uint32_t *perm = c->reordered ? c->perm : nullptr;
@@ -2996,10 +3156,17 @@ static int ensure_views(rtr_ctx *c, int count, int with_filter) {
     if (with_filter)
         if (int rc = ensure_levels(c, v)) return rc;
     auto &tab = c->vtab;
-    if (!tab.host) {
-        HIP_TRY(c, hipHostMalloc(&tab.host, rtr::view_tab_bytes(), hipHostMallocDefault));
-        HIP_TRY(c, hipMalloc(&tab.dev, rtr::view_tab_bytes()));
-        HIP_TRY(c, hipEventCreateWithFlags(&tab.copied, hipEventDisableTiming));
+    if (!tab.host) {  // (all or nothing: tab.host is what says the three exist)
+        hipError_t e = rtr::host_malloc(&tab.host, rtr::view_tab_bytes(), hipHostMallocDefault);
+        if (e == hipSuccess) e = rtr::dev_malloc(&tab.dev, rtr::view_tab_bytes());
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&tab.copied, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            (void)rtr::host_free(tab.host);
+            dfree(tab.dev);
+            if (tab.copied) (void)hipEventDestroy(tab.copied);
+            tab = rtr_ctx::ViewTab{};
+            return fail(c, RTR_ERR_HIP, "allocating the views' table failed: %s", hipGetErrorString(e));
+        }
     }
     if (!views_binned(c)) return ensure_soa(c);
     for (int k = 0; k < count; ++k) {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/rtr.h"
+#include "rtr_alloc.h"
 #include "rtr_kernels.h"
 #include "rtr_overlap_policy.h"
 
@@ -269,10 +270,10 @@ struct DevGuard {  // contexts pin their device for the duration of a call and h
 
 struct DevBufs {  // a call's device buffers: freed on every exit path unless a resident array has taken them (swap_in)
     std::vector<void *> p;
-    ~DevBufs() { for (void *q : p) if (q) (void)hipFree(q); }
+    ~DevBufs() { for (void *q : p) (void)rtr::dev_free(q); }
     template <class T> hipError_t get(T **out, size_t bytes) {
         void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 4);
+        const hipError_t e = rtr::dev_malloc(&q, bytes ? bytes : 4);
         if (e == hipSuccess) p.push_back(q);
         *out = static_cast<T *>(q);
         return e;

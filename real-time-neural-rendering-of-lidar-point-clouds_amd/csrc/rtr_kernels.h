@@ -286,7 +286,9 @@ void unpack_to_soa(hipStream_t s, const PackedXyz &pk, uint64_t n, float *x, flo
 int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, uint64_t n, uint32_t *perm = nullptr);
 // mean diagonal of the 256-point chunk boxes / diagonal of the cloud's box, from launch_chunk_bounds' output
 // absmax[3]: the largest finite |x|, |y|, |z| over the chunk boxes (+inf when no chunk has a finite box)
-int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, float absmax[3]);
+// scratch: order_quality_scratch_bytes() of device memory the caller owns, or null: the call allocates and frees its own
+size_t order_quality_scratch_bytes();
+int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, float absmax[3], void *scratch = nullptr);
 // T4: per-tile LDS z-buffer over the tile store.  mode 0 = whole frame (min + accumulate + resolve
 // of every unsplit tile, min phase of split tiles), 3 = second phase of the split tiles of a whole
 // frame, 1 = min only, 2 = accumulate only, 4 = owner-computes sharded frame: like 0, but only the tiles

@@ -13,6 +13,8 @@
 
 #include <cstdint>
 
+#include "rtr_alloc.h"
+
 namespace rtr {
 
 namespace {
@@ -156,14 +158,20 @@ __global__ __launch_bounds__(256) void k_order_quality(const float *__restrict__
 }  // namespace
 
 // mean chunk diagonal / cloud diagonal (0 when undefined); returns a hipError_t as int
-int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, float absmax[3]) {
+namespace {
+struct OrderOut { uint32_t finite; uint32_t bb[6]; float part[kOrderMaxGrid * 4]; };
+}
+size_t order_quality_scratch_bytes() { return sizeof(OrderOut); }
+
+int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, float absmax[3], void *scratch) {
     *ratio = 0.f;
     absmax[0] = absmax[1] = absmax[2] = __builtin_inff();
     const uint64_t nchunks = ((n + 3) / 4 + 63) / 64;
     if (nchunks == 0) return 0;
-    struct Out { uint32_t finite; uint32_t bb[6]; float part[kOrderMaxGrid * 4]; } h, *d = nullptr;
+    using Out = OrderOut;
+    Out h, *d = static_cast<Out *>(scratch);
     const Out init{0u, {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u}, {}};
-    hipError_t e = hipMalloc((void **)&d, sizeof(Out));
+    hipError_t e = scratch ? hipSuccess : dev_malloc(&d, sizeof(Out));
     if (e != hipSuccess) return (int)e;
     e = hipMemcpyAsync(d, &init, sizeof init, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
@@ -172,7 +180,7 @@ int order_quality(hipStream_t s, const float *bounds, uint64_t n, float *ratio, 
         e = hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d);
+    if (!scratch) (void)dev_free(d);
     if (e != hipSuccess) return (int)e;
     if (h.finite == 0 || !(h.bb[0] <= h.bb[3])) return 0;
     float sum = 0.f;
@@ -206,7 +214,7 @@ int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, 
     const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     uint32_t hb[6];
     const int grid = 2048;
-    if (ok(hipMalloc((void **)&bb, 24)) && ok(hipMemcpyAsync(bb, init, 24, hipMemcpyHostToDevice, s))) {
+    if (ok(dev_malloc(&bb, 24)) && ok(hipMemcpyAsync(bb, init, 24, hipMemcpyHostToDevice, s))) {
         hipLaunchKernelGGL(k_bbox, dim3(grid), dim3(256), 0, s, x, y, z, n, bb);
         ok(hipMemcpyAsync(hb, bb, 24, hipMemcpyDeviceToHost, s));
         ok(hipStreamSynchronize(s));
@@ -220,17 +228,17 @@ int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, 
             lo[k] = a;
             sc[k] = ext > 0.f ? 2097151.0f / ext : 0.f;
         }
-        if (ok(hipMalloc((void **)&k0, n * 8)) && ok(hipMalloc((void **)&k1, n * 8)) && ok(hipMalloc((void **)&v0, n * 4)) &&
-            ok(hipMalloc((void **)&v1, n * 4))) {
+        if (ok(dev_malloc(&k0, n * 8)) && ok(dev_malloc(&k1, n * 8)) && ok(dev_malloc(&v0, n * 4)) &&
+            ok(dev_malloc(&v1, n * 4))) {
             hipLaunchKernelGGL(k_keys, dim3(grid), dim3(256), 0, s, x, y, z, n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2],
                                k0, v0);
             ok(rocprim::radix_sort_pairs(nullptr, tmp_bytes, k0, k1, v0, v1, (size_t)n, 0u, 63u, s));
-            if (ok(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1)))
+            if (ok(dev_malloc(&tmp, tmp_bytes ? tmp_bytes : 1)))
                 ok(rocprim::radix_sort_pairs(tmp, tmp_bytes, k0, k1, v0, v1, (size_t)n, 0u, 63u, s));
         }
     }
-    if (e == hipSuccess && ok(hipMalloc((void **)&tx, n * 4)) && ok(hipMalloc((void **)&ty, n * 4)) &&
-        ok(hipMalloc((void **)&tz, n * 4)) && ok(hipMalloc((void **)&tc, n * 4)) && (!perm || ok(hipMalloc((void **)&tp, n * 4)))) {
+    if (e == hipSuccess && ok(dev_malloc(&tx, n * 4)) && ok(dev_malloc(&ty, n * 4)) &&
+        ok(dev_malloc(&tz, n * 4)) && ok(dev_malloc(&tc, n * 4)) && (!perm || ok(dev_malloc(&tp, n * 4)))) {
         hipLaunchKernelGGL(k_gather, dim3(grid), dim3(256), 0, s, v1, n, x, y, z, rgba, tx, ty, tz, tc);
         ok(hipMemcpyAsync(x, tx, n * 4, hipMemcpyDeviceToDevice, s));
         ok(hipMemcpyAsync(y, ty, n * 4, hipMemcpyDeviceToDevice, s));
@@ -242,8 +250,8 @@ int reorder_morton(hipStream_t s, float *x, float *y, float *z, uint32_t *rgba, 
         }
         ok(hipStreamSynchronize(s));
     }
-    (void)hipFree(bb); (void)hipFree(k0); (void)hipFree(k1); (void)hipFree(v0); (void)hipFree(v1);
-    (void)hipFree(tx); (void)hipFree(ty); (void)hipFree(tz); (void)hipFree(tc); (void)hipFree(tp); (void)hipFree(tmp);
+    (void)dev_free(bb); (void)dev_free(k0); (void)dev_free(k1); (void)dev_free(v0); (void)dev_free(v1);
+    (void)dev_free(tx); (void)dev_free(ty); (void)dev_free(tz); (void)dev_free(tc); (void)dev_free(tp); (void)dev_free(tmp);
     if (e == hipSuccess) e = hipGetLastError();
     return (int)e;
 }
