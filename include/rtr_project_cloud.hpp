@@ -31,6 +31,8 @@
 // hideSelected and transformSelected then act on them without a host array of flags.
 // selectVoxelGrid (section 6g) names one vertex per cell of a regular grid; thin removes all the others.
 // selectNeighbours (section 6h) names the vertices with enough others within a radius; removeOutliers removes the rest.
+// selectStatistical (section 6n, rtr_statistics.h) names the vertices whose mean distance to their k nearest neighbours is
+// ordinary for the cloud; removeStatisticalOutliers removes the rest.
 // selectClusters (section 6i) names them by the size of their connected cluster; growSelection, removeSmallClusters.
 // selectNear (section 6k) names the vertices within a radius of GIVEN points, and the given points near a vertex.
 // appendNewPoints appends only the given points with no vertex within a radius: a scan merged without duplicates.
@@ -63,7 +65,7 @@
 #include <filesystem>
 #endif
 
-#include "rtr.h"
+#include "rtr_statistics.h"
 
 namespace rtr {
 
@@ -392,6 +394,25 @@ public:
     // are selected (replacing the selection) and removed.  Returns the number removed.
     uint64_t removeOutliers(float radius, uint32_t min_neighbours) {
         const uint64_t gone = selectNeighbours(radius, min_neighbours, RTR_SELECT_REPLACE, true);
+        removeSelected();
+        return gone;
+    }
+    // The vertices whose mean distance to their k (1 .. RTR_STAT_MAX_K) nearest neighbours within `radius` is at most
+    // mu + std_mul * sigma, the moments of that mean distance over the cloud (section 6n, the statistical outlier filter:
+    // exact fp32 per vertex, fp64 moments in a fixed order); outside: every vertex but those -- the outliers, isolated and
+    // non-finite vertices included.  Combined with the selection so far by op.  mean_dist / found (nullptr: none; host or
+    // device memory, one entry per vertex): the mean distances and min(k, neighbours); moments (nullptr: none): mu,
+    // sigma and the threshold used.  Returns the number selected afterwards.  point_ids = true when the cloud may be sorted.
+    uint64_t selectStatistical(uint32_t k, float radius, double std_mul = 1.0, int op = RTR_SELECT_REPLACE, bool outside = false,
+                               float* mean_dist = nullptr, uint32_t* found = nullptr, double* moments = nullptr) {
+        uint64_t st[4];
+        check(ctx_, rtr_select_statistical(ctx_, k, radius, std_mul, 0, op | (outside ? RTR_SELECT_OUTSIDE : 0), mean_dist, found, moments, st));
+        return st[0];
+    }
+    // Takes the statistical outliers out of the resident cloud for good: they are selected (replacing the selection) and
+    // removed.  Returns the number removed.
+    uint64_t removeStatisticalOutliers(uint32_t k, float radius, double std_mul = 1.0) {
+        const uint64_t gone = selectStatistical(k, radius, std_mul, RTR_SELECT_REPLACE, true);
         removeSelected();
         return gone;
     }

@@ -152,6 +152,9 @@ struct rtr_ctx {
     int nearest_k_cascades_k = 0;      // ... and the cascades its sweep started, in thousands (saturating; depends on timing)
     int clusters_us[3] = {0, 0, 0};    // the last rtr_select_clusters: key kernel, sort, gather + work list + union-find + hits
     int clusters_tests_k = 0;          // ... and its pair tests in thousands (saturating)
+    int statistical_us[3] = {0, 0, 0}; // the last rtr_select_statistical: key kernel, sort, gather + work list + rows + sums + hits
+    int statistical_tests_k = 0;       // ... its pair tests in thousands (saturating)
+    int statistical_updates_k = 0;     // ... and the values written into rows, in thousands (saturating)
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
     int opt_grid = rtr::kDefaultPointGrid;  // workgroups of the point kernels
 
@@ -296,5 +299,8 @@ int check_indexable(rtr_ctx *c);  // point indices are 32-bit: RTR_ERR_UNSUPPORT
 rtr::Cloud cloud_of(const rtr_ctx *c);
 rtr::Proj make_proj(const float P[16]);
 void free_select(rtr_ctx *c);  // waits for the context's streams, then drops the selection
+// The read-only option keys that include/rtr_statistics.h documents (rtr.h's list is rtr_get_option's own): *value = the
+// key's value and true, or false for any other key (rtr_select_api.hip)
+bool statistics_option(const rtr_ctx *c, const char *key, int *value);
 
 #pragma GCC visibility pop

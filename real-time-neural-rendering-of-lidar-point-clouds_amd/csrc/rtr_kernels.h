@@ -483,6 +483,23 @@ void launch_neighbour_items(hipStream_t s, const uint64_t *keys, uint64_t m, uin
 void launch_neighbour_count(hipStream_t s, const float4 *rec, const uint32_t *items, const uint32_t *cursor, uint64_t cap, float r2,
                             uint32_t min_neighbours, uint32_t *hit, uint64_t *stats, uint64_t *tests);
 
+// rtr_select_statistical (rtr_statistical.hip; include/rtr_statistics.h section 6n; everything up to the work list is
+// rtr_select_neighbours').
+// stat_rows: the pair tests of neighbour_count without its early exit; mean[u] / found[u] (device, n entries in upload
+// order, preset by the caller to +inf / 0) = the mean distance of point u to its found[u] = min(k, candidates) nearest
+// candidates, for every point of the list; k is 1 .. 64; *tests / *updates (device, zeroed) += the pair tests made / the
+// values written into rows
+void launch_stat_rows(hipStream_t s, const float4 *rec, const uint32_t *items, const uint32_t *cursor, uint64_t cap, float r2, uint32_t k,
+                      float *mean, uint32_t *found, uint64_t *tests, uint64_t *updates);
+// stat_sum: *out (device) = the sum over the finite means of the mean (pass 0) or of (mean - mu)^2 (pass 1), in fp64 and
+// in a shape that depends on n alone; partial: stat_partials(n) doubles of scratch; *count (device, zeroed; pass 0 only)
+// += the finite means
+uint64_t stat_partials(uint64_t n);
+void launch_stat_sum(hipStream_t s, const float *mean, uint64_t n, int pass, double mu, double *partial, double *out, uint64_t *count);
+// stat_hits: hit ((n + 31) / 32 words, every one written) gets the bit of every point with found > 0 and
+// (double)mean <= t; stats (device, zeroed) [1] / [2] += those points / the points with found == 0
+void launch_stat_hits(hipStream_t s, const float *mean, const uint32_t *found, uint64_t n, double t, uint32_t *hit, uint64_t *stats);
+
 // rtr_select_clusters (rtr_clusters.hip; everything up to the work list is rtr_select_neighbours').  The union-find runs
 // over the n sorted positions: parent, size, minu, seed are n words each.
 // cluster_init: parent[j] = j, size[j] = 0, minu[j] = 2^32 - 1, seed[j] = 0

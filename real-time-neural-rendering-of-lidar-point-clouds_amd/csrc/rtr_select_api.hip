@@ -1,19 +1,34 @@
-// rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6m) on top of the kernels of
-// rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip, rtr_nearest.hip, rtr_nearest_k.hip
-// and rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
+// rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6m) and include/rtr_statistics.h
+// (section 6n) on top of the kernels of
+// rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip, rtr_nearest.hip, rtr_nearest_k.hip,
+// rtr_statistical.hip and rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
 // calls in their own file") has the order of events every call follows and why an error leaves the selection as it was.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <new>
 #include <vector>
 
+#include "../../include/rtr_statistics.h"
 #include "rtr_host.h"
 #include "rtr_plane_fit.h"
 
 int check_indexable(rtr_ctx *c) {
     if (c->n < (1ull << 32)) return RTR_OK;
     return fail(c, RTR_ERR_UNSUPPORTED, "point indices are 32-bit: the cloud has %llu points", (unsigned long long)c->n);
+}
+
+bool statistics_option(const rtr_ctx *c, const char *key, int *value) {
+    const struct { const char *name; int value; } keys[] = {
+        {"statistical_us0", c->statistical_us[0]}, {"statistical_us1", c->statistical_us[1]}, {"statistical_us2", c->statistical_us[2]},
+        {"statistical_pair_tests_k", c->statistical_tests_k}, {"statistical_row_updates_k", c->statistical_updates_k}};
+    for (const auto &k : keys) {
+        if (strcmp(key, k.name) != 0) continue;
+        *value = k.value;
+        return true;
+    }
+    return false;
 }
 
 namespace {
@@ -409,6 +424,99 @@ int rtr_select_clusters(rtr_ctx *c, float radius, uint32_t min_points, uint32_t 
         HIP_TRY(c, hipMemcpyAsync(labels, lab, n * 4, labels_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
+    if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- selection by mean neighbour distance (rtr_statistics.h, section 6n) --------------
+// rtr_select_neighbours' order of events with rows in place of counts (rtr_statistical.hip): the means and the rows'
+// lengths go to two scratch arrays in upload order, allocated with the sums' scratch BEFORE the search, so that the
+// selection comes into existence behind the call's last allocation.  The two sums are waited for one after the other --
+// the second needs mu --, the threshold is formed on the host, and the hits are combined as everywhere.  An output in
+// host memory is staged in host memory, queued ahead of the combine, and handed over with moments and stats behind the
+// last thing that can fail.
+int rtr_select_statistical(rtr_ctx *c, uint32_t k, float radius, double std_mul, int flags, int op, float *mean_dist, uint32_t *found,
+                           double moments[3], uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_select_statistical: no cloud");
+    NEED(c, k >= 1u && k <= RTR_STAT_MAX_K, "rtr_select_statistical: k outside 1..RTR_STAT_MAX_K");
+    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_select_statistical: radius must be finite and > 0");
+    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
+    NEED(c, std::isnormal(r2), "rtr_select_statistical: the square of radius is not a finite normal fp32 number");
+    NEED(c, (flags & ~RTR_STAT_THRESHOLD_GIVEN) == 0, "rtr_select_statistical: unknown bits in flags");
+    const bool given = (flags & RTR_STAT_THRESHOLD_GIVEN) != 0;
+    NEED(c, given || std::isfinite(std_mul), "rtr_select_statistical: std_mul must be finite");
+    NEED(c, !given || moments != nullptr, "rtr_select_statistical: moments is NULL with RTR_STAT_THRESHOLD_GIVEN");
+    NEED(c, !given || !std::isnan(moments[2]), "rtr_select_statistical: moments[2] (the threshold) is NaN with RTR_STAT_THRESHOLD_GIVEN");
+    SelectOp sop;
+    if (int rc = check_select_op(c, "rtr_select_statistical", op, &sop)) return rc;
+    if (int rc = check_indexable(c)) return rc;
+    if (int rc = need_upload_order(c, "formed")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n;
+    const bool mean_dev = mean_dist && on_device(mean_dist), found_dev = found && on_device(found);
+    std::vector<float> mean_host;
+    std::vector<uint32_t> found_host;
+    try {
+        if (mean_dist && !mean_dev) mean_host.resize(n);
+        if (found && !found_dev) found_host.resize(n);
+    } catch (const std::bad_alloc &) {
+        return fail(c, RTR_ERR_HIP, "rtr_select_statistical: no host memory for the staging copy of an output");
+    }
+    NeighbourSearch q;
+    float *means;
+    uint32_t *fnd;
+    double *partial;
+    uint64_t *red;  // [0] a sum (fp64 bits), [1] the points with a row, [2] the values written into rows
+    HIP_TRY(c, q.buf.get(&means, n * 4));
+    HIP_TRY(c, q.buf.get(&fnd, n * 4));
+    HIP_TRY(c, q.buf.get(&partial, rtr::stat_partials(n) * sizeof(double)));
+    HIP_TRY(c, q.buf.get(&red, 4 * sizeof(uint64_t)));
+    if (int rc = neighbour_search(c, "rtr_select_statistical", radius, q)) return rc;
+    HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)means, 0x7F800000, n, s));  // (the points no item holds: no row)
+    HIP_TRY(c, hipMemsetAsync(fnd, 0, n * 4, s));
+    HIP_TRY(c, hipMemsetAsync(red, 0, 4 * sizeof(uint64_t), s));
+    rtr::launch_stat_rows(s, q.ks.rec1, q.items, (const uint32_t *)(q.cn + 4), q.cap, r2, k, means, fnd, q.cn + 2, red + 2);
+    if (int rc = launch_check(c, "statistical rows")) return rc;
+    rtr::launch_stat_sum(s, means, n, 0, 0.0, partial, reinterpret_cast<double *>(red), red + 1);
+    if (int rc = launch_check(c, "statistical sum")) return rc;
+    uint64_t h[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(h, red, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t have = h[1];
+    double S1, S2 = 0.0;
+    memcpy(&S1, &h[0], sizeof S1);
+    const double mu = have ? S1 / (double)have : 0.0;
+    if (have >= 2) {
+        rtr::launch_stat_sum(s, means, n, 1, mu, partial, reinterpret_cast<double *>(red), nullptr);
+        if (int rc = launch_check(c, "statistical squares")) return rc;
+        HIP_TRY(c, hipMemcpyAsync(&S2, red, sizeof S2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    const double sigma = have >= 2 ? std::sqrt(S2 / (double)(have - 1)) : 0.0;
+    const double spread = std_mul * sigma;  // (a product and a sum, each rounded: the build has no contraction)
+    const double t = given ? moments[2] : mu + spread;
+    rtr::launch_stat_hits(s, means, fnd, n, t, q.hit, c->sel_stats);
+    if (int rc = launch_check(c, "statistical hits")) return rc;
+    if (int rc = q.ev.record(c, 3, s)) return rc;
+    HIP_TRY(c, d2d(s, c->sel_stats + 3, q.cn, sizeof(uint64_t)));
+    uint64_t updates = 0;
+    HIP_TRY(c, hipMemcpyAsync(&updates, red + 2, sizeof updates, hipMemcpyDeviceToHost, s));
+    if (!mean_host.empty()) HIP_TRY(c, hipMemcpyAsync(mean_host.data(), means, n * 4, hipMemcpyDeviceToHost, s));
+    if (!found_host.empty()) HIP_TRY(c, hipMemcpyAsync(found_host.data(), fnd, n * 4, hipMemcpyDeviceToHost, s));
+    uint64_t out[4] = {0, 0, 0, 0};
+    if (int rc = neighbour_finish(c, "statistical combine", q, sop, out, c->statistical_us, &c->statistical_tests_k)) return rc;
+    c->statistical_updates_k = saturate_k(updates);
+    out[2] -= q.n - q.m;  // (the hits kernel counts every point without a row: the non-finite ones are stats[3]'s)
+    // behind everything else that can fail: the caller's arrays change only when the call succeeds
+    if (mean_dev) HIP_TRY(c, hipMemcpyAsync(mean_dist, means, n * 4, hipMemcpyDeviceToDevice, s));
+    if (found_dev) HIP_TRY(c, hipMemcpyAsync(found, fnd, n * 4, hipMemcpyDeviceToDevice, s));
+    if (mean_dev || found_dev) HIP_TRY(c, hipStreamSynchronize(s));
+    if (!mean_host.empty()) memcpy(mean_dist, mean_host.data(), n * 4);
+    if (!found_host.empty()) memcpy(found, found_host.data(), n * 4);
+    if (moments) moments[0] = mu, moments[1] = sigma, moments[2] = t;
     if (stats) memcpy(stats, out, sizeof out);
     return RTR_OK;
 }

@@ -381,6 +381,58 @@ class Projector:
         self._chk(self._lib.rtr_select_neighbours(self._ctx, r, k, code, _vp(out)))
         return tuple(int(v) for v in out) if stats else None
 
+    def select_statistical(self, k, radius, std_mul=1.0, threshold=None, op="replace", outside=False, mean_dist=False,
+                           found=False, stats=True):
+        """Selects on the device the points whose mean distance to their k nearest neighbours within `radius` is at most
+        t = mu + std_mul * sigma, mu and sigma the mean and the sample standard deviation of that mean distance over the
+        cloud (include/rtr_statistics.h section 6n, the statistical outlier filter), and combines the hits with the
+        selection so far, as select_points does.  Neighbours: select_neighbours' relation; a point with fewer than k of
+        them averages over those it has, a point with none (every non-finite one) has the mean +inf and is never a hit.
+        k: 1 .. STAT_MAX_K.  threshold: t itself, in place of std_mul.  outside: the outliers instead.  The call always
+        waits.  Returns a tuple: the stats when asked for -- (selected points after op, hits, finite points without a
+        neighbour, non-finite points) --, then the moments (mu, sigma, t) as Python floats, then with mean_dist the
+        float32 array of the mean distances and with found the uint32 array of min(k, neighbours), both in upload
+        order."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError("k must be an integer")
+        k = int(k)
+        if not 1 <= k <= L.STAT_MAX_K:
+            raise ValueError("k must be in 1 .. STAT_MAX_K (%d)" % L.STAT_MAX_K)
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        with np.errstate(over="ignore", under="ignore"):
+            r2 = np.float32(r) * np.float32(r)
+        if not (np.isfinite(r2) and r2 >= np.finfo(np.float32).tiny):
+            raise ValueError("the square of radius must be a finite normal float32 number")
+        mom = np.zeros(3, np.float64)
+        flags = 0
+        if threshold is not None:
+            mom[2] = float(threshold)
+            if np.isnan(mom[2]):
+                raise ValueError("threshold must not be NaN")
+            flags = L.STAT_THRESHOLD_GIVEN
+            mul = 0.0
+        else:
+            mul = float(std_mul)
+            if not np.isfinite(mul):
+                raise ValueError("std_mul must be finite")
+        code = self._SELECT_OPS[op] if isinstance(op, str) else int(op)
+        if outside:
+            code |= L.SELECT_OUTSIDE
+        n = self.num_points
+        md = np.empty(n, np.float32) if mean_dist else None
+        fd = np.empty(n, np.uint32) if found else None
+        out = np.zeros(4, np.uint64) if stats else None
+        self._chk(self._lib.rtr_select_statistical(self._ctx, k, r, mul, flags, code, _vp(md), _vp(fd), _vp(mom), _vp(out)))
+        res = [tuple(int(v) for v in out)] if stats else []
+        res.append(tuple(float(v) for v in mom))
+        if mean_dist:
+            res.append(md)
+        if found:
+            res.append(fd)
+        return tuple(res)
+
     def select_clusters(self, radius, min_points=1, max_points=0, seeded=False, op="replace", outside=False, labels=False,
                         stats=True):
         """Selects on the device the points whose connected cluster within `radius` (include/rtr.h section 6i, Euclidean
@@ -1096,6 +1148,20 @@ class ProjectCloud:
         """Takes the vertices with fewer than min_neighbours others within `radius` out of the resident cloud for good:
         selectNeighbours of the outliers, then removeSelected.  Returns the number removed."""
         gone = self._p.select_neighbours(radius, min_neighbours, outside=True)[0]
+        self.removeSelected()
+        return gone
+
+    def selectStatistical(self, k, radius, std_mul=1.0, op="replace", outside=False):
+        """Selects the vertices whose mean distance to their k nearest neighbours within `radius` is at most the cloud's
+        average of it plus std_mul standard deviations (outside: every vertex but those; see
+        Projector.select_statistical).  Returns the number selected afterwards."""
+        return self._p.select_statistical(k, radius, std_mul, None, op, outside)[0][0]
+
+    def removeStatisticalOutliers(self, k, radius, std_mul=1.0):
+        """Takes the statistical outliers -- the vertices selectStatistical does not name, isolated and non-finite ones
+        included -- out of the resident cloud for good: selectStatistical of the outliers, then removeSelected.
+        Returns the number removed."""
+        gone = self._p.select_statistical(k, radius, std_mul, outside=True)[0][0]
         self.removeSelected()
         return gone
 

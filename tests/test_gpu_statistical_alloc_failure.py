@@ -1,0 +1,105 @@
+"""rtr_select_statistical against a failed device allocation (include/rtr_statistics.h section 6n, "Errors"; option
+"debug_alloc_fail"; README_alloc_failure.md): the sweep of test_gpu_alloc_failure.py on this call, in the three states
+of alloc_failure_cases.py, with its states, snapshot, sentinel-filled raw call and health check.
+
+Per state: (1) unarmed on a fresh context the call equals the reference (statistical_ref.py) and K0 = the allocations it
+attempted is at least 1; (2) for k = 1 .. K0 on another fresh context "debug_alloc_fail" = k fires inside the call, which
+returns RTR_ERR_HIP with a message, the snapshot is intact -- the selection word for word --, and every byte of
+mean_dist, found, moments and stats still holds the sentinel; (3) the health check is exact; (4) the call again is
+exact; (5), (6) the context goes and "debug_alloc_live" is back where it was."""
+import numpy as np
+import pytest
+
+import alloc_failure_cases as afc
+import select_ref as sr
+import statistical_ref as sf
+from test_gpu_alloc_failure import _count, _health, _same
+
+pytestmark = pytest.mark.gpu
+
+K, STD_MUL = 8, 1.0
+OUTPUTS = ("mean_dist", "found", "moments", "stats")
+K0_SEEN = {}
+
+
+@pytest.fixture(scope="module")
+def observer(pkg):
+    """A context that lives through every case and only reads the process-wide counters."""
+    p = pkg.Projector(0)
+    yield p
+    p.close()
+
+
+@pytest.fixture(scope="module")
+def ref(orc):
+    xyz = afc.base_cloud(orc)[0]
+    s = sf.select(xyz, afc._radius(orc), K, STD_MUL)
+    assert 0.05 * afc.N < s["hit"].sum() < 0.95 * afc.N and 0 < (s["found"] < K).sum()
+    return s
+
+
+def _call(cx):
+    n, L = cx.model.n, cx.L
+    out = {"mean_dist": np.zeros(n, np.float32), "found": np.zeros(n, np.uint32), "moments": np.zeros(3, np.float64),
+           "stats": np.zeros(4, np.uint64)}
+    afc._raw(cx, "rtr_select_statistical", [K, afc._radius(cx.orc), STD_MUL, 0, L.SELECT_INTERSECT, "mean_dist", "found", "moments", "stats"], out)
+    out["selection"] = sr.unpack(cx.p.download(L.BUF_SELECTION), n)
+    return out
+
+
+def _exact(got, s, before_sel, what):
+    want = before_sel & s["hit"]
+    assert np.array_equal(got["selection"], want), what
+    assert np.array_equal(got["found"], s["found"]), what
+    assert np.array_equal(got["mean_dist"].view(np.uint32), s["mean"].view(np.uint32)), what
+    assert tuple(int(v) for v in got["stats"]) == (int(want.sum()),) + s["stats"], what
+    tol = sf.moments_tolerance(int((s["found"] > 0).sum()))
+    assert all(abs(g - w) <= tol * abs(w) for g, w in zip(got["moments"], s["moments"])), (what, got["moments"], s["moments"])
+
+
+@pytest.mark.parametrize("state", afc.STATES)
+def test_a_failed_allocation_leaves_everything_as_it_was(pkg, orc, observer, ref, state):
+    live0 = observer.get_option("debug_alloc_live")
+    p, model = afc.build(pkg, orc, state)
+    try:
+        cx = afc.Ctx(pkg, orc, p, model)
+        c0 = _count(p)
+        got = _call(cx)
+        K0 = _count(p) - c0
+        _exact(got, ref, model.selection, ("unarmed", state))
+        moments = got["moments"].tobytes()
+    finally:
+        p.close()
+    assert K0 >= 1
+    K0_SEEN[state] = K0
+    for k in range(1, K0 + 1):
+        what = (state, "k", k, "of", K0)
+        p, model = afc.build(pkg, orc, state)
+        try:
+            cx = afc.Ctx(pkg, orc, p, model)
+            before = afc.snapshot(pkg, p)
+            p.set_option("debug_alloc_fail", k)
+            with pytest.raises(pkg.RtrError) as e:
+                _call(cx)
+            left = p.get_option("debug_alloc_fail")
+            p.set_option("debug_alloc_fail", 0)
+            assert left == 0, ("the switch did not fire: the call made fewer allocations than the unarmed run", what)
+            assert e.value.code == afc.RTR_ERR_HIP and str(e.value).split(":", 1)[1].strip(), (what, str(e.value))
+            _same(afc.snapshot(pkg, p), before, ("the snapshot changed", what))
+            assert set(cx.note["outputs_untouched"]) == set(OUTPUTS) and all(cx.note["outputs_untouched"].values()), \
+                ("a caller output was written", cx.note["outputs_untouched"], what)
+            _health(pkg, orc, p, model, what)
+            again = _call(cx)
+            _exact(again, ref, model.selection, ("again", what))
+            assert again["moments"].tobytes() == moments, ("the moments' bits moved", what)
+        finally:
+            p.close()
+    assert observer.get_option("debug_alloc_live") == live0, ("allocations leaked", state)
+
+
+def test_k0_table(observer):
+    """Prints state x K0 as the sweep found them (README_statistical.md holds the row)."""
+    print()
+    for state, k0 in sorted(K0_SEEN.items()):
+        print("K0 %-28s %-12s %d" % ("select_statistical", state, k0))
+    assert observer.get_option("debug_alloc_fail") == 0
