@@ -33,6 +33,8 @@
 // selectNeighbours (section 6h) names the vertices with enough others within a radius; removeOutliers removes the rest.
 // selectStatistical (section 6n, rtr_statistics.h) names the vertices whose mean distance to their k nearest neighbours is
 // ordinary for the cloud; removeStatisticalOutliers removes the rest.
+// estimateNormals (section 6o, rtr_normals.h) gives every vertex a unit normal and a curvature from its k nearest
+// neighbours; it selects nothing and changes nothing.
 // selectClusters (section 6i) names them by the size of their connected cluster; growSelection, removeSmallClusters.
 // selectNear (section 6k) names the vertices within a radius of GIVEN points, and the given points near a vertex.
 // appendNewPoints appends only the given points with no vertex within a radius: a scan merged without duplicates.
@@ -65,6 +67,7 @@
 #include <filesystem>
 #endif
 
+#include "rtr_normals.h"
 #include "rtr_statistics.h"
 
 namespace rtr {
@@ -415,6 +418,19 @@ public:
         const uint64_t gone = selectStatistical(k, radius, std_mul, RTR_SELECT_REPLACE, true);
         removeSelected();
         return gone;
+    }
+    // The unit normal and the curvature of every vertex, from a PCA over the vertex and its k (1 .. RTR_NORMAL_MAX_K)
+    // nearest neighbours within `radius` (section 6o: exact, reproducible bit for bit, independent of the resident order).
+    // normals: 3 floats per vertex; curvature (nullptr: none): the surface variation, one float per vertex; found (nullptr:
+    // none): min(k, neighbours) per vertex -- each in host or device memory, in the order of the vertices.  A vertex with
+    // fewer than RTR_NORMAL_MIN_FOUND neighbours gets (0, 0, 0) and +inf.  viewpoint (nullptr: none): three floats towards
+    // which every normal is turned.  Nothing is selected or changed.  Returns the number of vertices with a normal.
+    // point_ids = true when the cloud may be sorted.
+    uint64_t estimateNormals(uint32_t k, float radius, float* normals, float* curvature = nullptr, uint32_t* found = nullptr,
+                             const float* viewpoint = nullptr) {
+        uint64_t st[4];
+        check(ctx_, rtr_estimate_normals(ctx_, k, radius, viewpoint ? RTR_NORMAL_VIEWPOINT : 0, viewpoint, normals, curvature, found, st));
+        return st[0];
     }
     // The vertices whose connected cluster within `radius` (section 6i, Euclidean clustering over section 6h's exact
     // relation) holds at least min_points and, unless max_points is 0, at most max_points vertices; seeded: only the

@@ -31,6 +31,8 @@ SYMBOLS = [
 ]
 # every symbol include/rtr_statistics.h declares (the header continues rtr.h's section 6 and includes it)
 STATISTICS_SYMBOLS = ["rtr_select_statistical"]
+# every symbol include/rtr_normals.h declares (section 6o)
+NORMALS_SYMBOLS = ["rtr_estimate_normals"]
 
 RTR_OK, RTR_ERR_INVALID, RTR_ERR_HIP, RTR_ERR_NO_OUTPUT, RTR_ERR_UNSUPPORTED, RTR_ERR_INTERNAL = 0, -1, -2, -3, -4, -5
 BUF_DEPTH, BUF_ACCUM, BUF_IMAGE, BUF_TENSOR, BUF_MASK, BUF_MINMAX, BUF_POINT_ID, BUF_VISIBLE = range(8)
@@ -46,6 +48,9 @@ NEAREST_NONE = 0xFFFFFFFF  # RTR_NEAREST_NONE: rtr_nearest_points' index of "no 
 NEAREST_MAX_K = 64  # RTR_NEAREST_MAX_K: rtr_nearest_k_points' largest k
 STAT_MAX_K = 64  # RTR_STAT_MAX_K: rtr_select_statistical's largest k
 STAT_THRESHOLD_GIVEN = 1  # rtr_select_statistical's flag: moments[2] is the threshold, std_mul is ignored
+NORMAL_MAX_K = 64  # RTR_NORMAL_MAX_K: rtr_estimate_normals' largest k
+NORMAL_MIN_FOUND = 2  # RTR_NORMAL_MIN_FOUND: a normal needs the point and two neighbours
+NORMAL_VIEWPOINT = 1  # rtr_estimate_normals' flag: orient every normal towards the viewpoint
 BANDS_SELECTED = 1  # rtr_count_in_bands / rtr_fit_plane flag: only the currently selected points
 MAX_BANDS = 4096  # RTR_MAX_BANDS
 MAX_VIEWS = 8  # RTR_MAX_VIEWS
@@ -161,9 +166,10 @@ def lib():
     L.rtr_nearest_k_points.argtypes = [vp, vp, sz, u64, C.c_float, C.c_uint32, i32, vp, vp, vp, vp]
     L.rtr_fit_plane.argtypes = [vp, C.c_float, C.c_uint32, u64, i32, vp, vp]
     L.rtr_select_statistical.argtypes = [vp, C.c_uint32, C.c_float, C.c_double, i32, i32, vp, vp, vp, vp]
+    L.rtr_estimate_normals.argtypes = [vp, C.c_uint32, C.c_float, i32, vp, vp, vp, vp, vp]
     L.rtr_extract_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, vp, C.POINTER(u64)]
     L.rtr_write_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, C.POINTER(u64)]
-    for name in SYMBOLS + STATISTICS_SYMBOLS:
+    for name in SYMBOLS + STATISTICS_SYMBOLS + NORMALS_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rtr_last_error", "rtr_default_params"):
             fn.restype = i32

@@ -1067,6 +1067,7 @@ int rtr_get_option(rtr_ctx *c, const char *key, int *value) {
     // (the stamp of the single frame's current store -- of its last frame, or what its first frame will start from)
     else if (!strcmp(key, "debug_store_stamp")) *value = (int)(c->F().store.ext0 ? c->F().store.seq : c->debug_store_stamp);
     else if (statistics_option(c, key, value)) return RTR_OK;  // (the keys of include/rtr_statistics.h, section 6n)
+    else if (normals_option(c, key, value)) return RTR_OK;     // (the keys of include/rtr_normals.h, section 6o)
     else return fail(c, RTR_ERR_INVALID, "unknown option '%s'", key);
     return RTR_OK;
 }

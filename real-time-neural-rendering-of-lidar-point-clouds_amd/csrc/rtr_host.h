@@ -155,6 +155,9 @@ struct rtr_ctx {
     int statistical_us[3] = {0, 0, 0}; // the last rtr_select_statistical: key kernel, sort, gather + work list + rows + sums + hits
     int statistical_tests_k = 0;       // ... its pair tests in thousands (saturating)
     int statistical_updates_k = 0;     // ... and the values written into rows, in thousands (saturating)
+    int normals_us[3] = {0, 0, 0};     // the last rtr_estimate_normals: key kernel, sort, gather + work list + rows and fits
+    int normals_tests_k = 0;           // ... its pair tests in thousands (saturating)
+    int normals_updates_k = 0;         // ... and the entries written into rows, in thousands (saturating)
     float order_ratio = 0.f;    // mean chunk diagonal / cloud diagonal as uploaded
     int opt_grid = rtr::kDefaultPointGrid;  // workgroups of the point kernels
 
@@ -302,5 +305,7 @@ void free_select(rtr_ctx *c);  // waits for the context's streams, then drops th
 // The read-only option keys that include/rtr_statistics.h documents (rtr.h's list is rtr_get_option's own): *value = the
 // key's value and true, or false for any other key (rtr_select_api.hip)
 bool statistics_option(const rtr_ctx *c, const char *key, int *value);
+// ... and those that include/rtr_normals.h documents
+bool normals_option(const rtr_ctx *c, const char *key, int *value);
 
 #pragma GCC visibility pop

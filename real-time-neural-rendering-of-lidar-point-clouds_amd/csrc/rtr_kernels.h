@@ -500,6 +500,16 @@ void launch_stat_sum(hipStream_t s, const float *mean, uint64_t n, int pass, dou
 // (double)mean <= t; stats (device, zeroed) [1] / [2] += those points / the points with found == 0
 void launch_stat_hits(hipStream_t s, const float *mean, const uint32_t *found, uint64_t n, double t, uint32_t *hit, uint64_t *stats);
 
+// rtr_estimate_normals (rtr_normals.hip; include/rtr_normals.h section 6o; everything up to the work list is
+// rtr_select_neighbours').
+// normal_rows: stat_rows' pair tests with rows of (d2, position) ordered by (d2, upload index); for every point u of the
+// list found[u] = min(k, candidates) and, where that is >= 2, normals[3 u ..] / curvature[u] = the contract's normal and
+// surface variation (device, upload order, preset by the caller to 0 / +inf / 0); view: the viewpoint (host, 3 floats) or
+// nullptr; k is 1 .. 64; counts (device, 4 words, zeroed) += the pair tests made, the entries written into rows, the
+// points with a normal, the normals the viewpoint rule negated
+void launch_normal_rows(hipStream_t s, const float4 *rec, const uint32_t *items, const uint32_t *cursor, uint64_t cap, float r2, uint32_t k,
+                        const float *view, float *normals, float *curvature, uint32_t *found, uint64_t *counts);
+
 // rtr_select_clusters (rtr_clusters.hip; everything up to the work list is rtr_select_neighbours').  The union-find runs
 // over the n sorted positions: parent, size, minu, seed are n words each.
 // cluster_init: parent[j] = j, size[j] = 0, minu[j] = 2^32 - 1, seed[j] = 0

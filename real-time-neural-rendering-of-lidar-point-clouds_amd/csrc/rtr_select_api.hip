@@ -1,7 +1,7 @@
-// rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6m) and include/rtr_statistics.h
-// (section 6n) on top of the kernels of
+// rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6m), include/rtr_statistics.h
+// (section 6n) and include/rtr_normals.h (section 6o) on top of the kernels of
 // rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip, rtr_nearest.hip, rtr_nearest_k.hip,
-// rtr_statistical.hip and rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
+// rtr_statistical.hip, rtr_normals.hip and rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
 // calls in their own file") has the order of events every call follows and why an error leaves the selection as it was.
 #include <algorithm>
 #include <chrono>
@@ -10,6 +10,7 @@
 #include <new>
 #include <vector>
 
+#include "../../include/rtr_normals.h"
 #include "../../include/rtr_statistics.h"
 #include "rtr_host.h"
 #include "rtr_plane_fit.h"
@@ -23,6 +24,18 @@ bool statistics_option(const rtr_ctx *c, const char *key, int *value) {
     const struct { const char *name; int value; } keys[] = {
         {"statistical_us0", c->statistical_us[0]}, {"statistical_us1", c->statistical_us[1]}, {"statistical_us2", c->statistical_us[2]},
         {"statistical_pair_tests_k", c->statistical_tests_k}, {"statistical_row_updates_k", c->statistical_updates_k}};
+    for (const auto &k : keys) {
+        if (strcmp(key, k.name) != 0) continue;
+        *value = k.value;
+        return true;
+    }
+    return false;
+}
+
+bool normals_option(const rtr_ctx *c, const char *key, int *value) {
+    const struct { const char *name; int value; } keys[] = {
+        {"normals_us0", c->normals_us[0]}, {"normals_us1", c->normals_us[1]}, {"normals_us2", c->normals_us[2]},
+        {"normals_pair_tests_k", c->normals_tests_k}, {"normals_row_updates_k", c->normals_updates_k}};
     for (const auto &k : keys) {
         if (strcmp(key, k.name) != 0) continue;
         *value = k.value;
@@ -299,8 +312,9 @@ struct NeighbourSearch {  // the scratch of one call and what the search found
 };
 
 // Allocates, sweeps, sorts, gathers and lists; leaves hit and sel_stats zeroed, the selection in existence and
-// ev.e[0 .. 2] recorded (before the keys, behind them, behind the sort).
-int neighbour_search(rtr_ctx *c, const char *who, float radius, NeighbourSearch &q) {
+// ev.e[0 .. 2] recorded (before the keys, behind them, behind the sort).  selects = false (rtr_estimate_normals, a pure
+// analysis call): the selection and its statistics are neither created nor touched.
+int neighbour_search(rtr_ctx *c, const char *who, float radius, NeighbourSearch &q, bool selects = true) {
     hipStream_t s = c->stream;
     const uint64_t n = c->n, nw = (n + 31) / 32;
     DevBufs &buf = q.buf;
@@ -309,7 +323,8 @@ int neighbour_search(rtr_ctx *c, const char *who, float radius, NeighbourSearch 
     if (int rc = ks.alloc(c, buf, n, true)) return rc;
     HIP_TRY(c, buf.get(&q.hit, nw * 4));
     HIP_TRY(c, buf.get(&q.cn, 5 * sizeof(uint64_t)));
-    if (int rc = fresh.reserve(c, buf)) return rc;
+    if (selects)
+        if (int rc = fresh.reserve(c, buf)) return rc;
     if (int rc = q.ev.create(c, 4)) return rc;
     HIP_TRY(c, hipMemsetAsync(q.hit, 0, nw * 4, s));
     HIP_TRY(c, hipMemsetAsync(q.cn, 0, 5 * sizeof(uint64_t), s));
@@ -332,8 +347,10 @@ int neighbour_search(rtr_ctx *c, const char *who, float radius, NeighbourSearch 
     HIP_TRY(c, hipStreamSynchronize(s));
     const uint64_t cap = std::min<uint64_t>(host[3] + m / 64, m);  // (a cell of len points: ceil(len / 64) <= 1 + len / 64 items, each of >= 1 point)
     HIP_TRY(c, buf.get(&q.items, cap * 80));
-    if (int rc = fresh.create(c, buf, s)) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
+    if (selects) {
+        if (int rc = fresh.create(c, buf, s)) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->sel_stats, 0, 4 * sizeof(uint64_t), s));
+    }
     rtr::launch_neighbour_items(s, ks.k1, m, q.items, (uint32_t *)(q.cn + 4), cap);
     if (int rc = launch_check(c, "neighbour items")) return rc;
     q.n = n, q.m = m, q.cap = cap;
@@ -518,6 +535,78 @@ int rtr_select_statistical(rtr_ctx *c, uint32_t k, float radius, double std_mul,
     if (!found_host.empty()) memcpy(found, found_host.data(), n * 4);
     if (moments) moments[0] = mu, moments[1] = sigma, moments[2] = t;
     if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- normals and curvature (rtr_normals.h, section 6o) --------------------------------
+// rtr_select_statistical's order of events without a selection: the search neither creates nor touches it
+// (neighbour_search with selects = false), the three outputs go to scratch arrays in upload order that are allocated
+// BEFORE the search and preset to "no normal", the rows kernel fills them, and the caller's arrays -- host or device
+// memory, each on its own -- are written behind the last thing that can fail.  Two waits on the way (the search's) and
+// one at the end.
+int rtr_estimate_normals(rtr_ctx *c, uint32_t k, float radius, int flags, const float viewpoint[3], float *normals, float *curvature,
+                         uint32_t *found, uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_estimate_normals: no cloud");
+    NEED(c, k >= 1u && k <= RTR_NORMAL_MAX_K, "rtr_estimate_normals: k outside 1..RTR_NORMAL_MAX_K");
+    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_estimate_normals: radius must be finite and > 0");
+    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
+    NEED(c, std::isnormal(r2), "rtr_estimate_normals: the square of radius is not a finite normal fp32 number");
+    NEED(c, (flags & ~RTR_NORMAL_VIEWPOINT) == 0, "rtr_estimate_normals: unknown bits in flags");
+    const bool towards = (flags & RTR_NORMAL_VIEWPOINT) != 0;
+    NEED(c, !towards || viewpoint != nullptr, "rtr_estimate_normals: viewpoint is NULL with RTR_NORMAL_VIEWPOINT");
+    NEED(c, !towards || (std::isfinite(viewpoint[0]) && std::isfinite(viewpoint[1]) && std::isfinite(viewpoint[2])),
+         "rtr_estimate_normals: viewpoint has a non-finite component");
+    if (int rc = check_indexable(c)) return rc;
+    if (int rc = need_upload_order(c, "formed")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n;
+    const bool normals_dev = normals && on_device(normals), curv_dev = curvature && on_device(curvature), found_dev = found && on_device(found);
+    std::vector<float> normals_host, curv_host;
+    std::vector<uint32_t> found_host;
+    try {
+        if (normals && !normals_dev) normals_host.resize(n * 3);
+        if (curvature && !curv_dev) curv_host.resize(n);
+        if (found && !found_dev) found_host.resize(n);
+    } catch (const std::bad_alloc &) {
+        return fail(c, RTR_ERR_HIP, "rtr_estimate_normals: no host memory for the staging copy of an output");
+    }
+    NeighbourSearch q;
+    float *nrm, *curv;
+    uint32_t *fnd;
+    uint64_t *counts;  // [0] pair tests, [1] entries written into rows, [2] points with a normal, [3] normals negated
+    HIP_TRY(c, q.buf.get(&nrm, n * 12));
+    HIP_TRY(c, q.buf.get(&curv, n * 4));
+    HIP_TRY(c, q.buf.get(&fnd, n * 4));
+    HIP_TRY(c, q.buf.get(&counts, 4 * sizeof(uint64_t)));
+    if (int rc = neighbour_search(c, "rtr_estimate_normals", radius, q, false)) return rc;
+    HIP_TRY(c, hipMemsetAsync(nrm, 0, n * 12, s));  // (the points without a normal: (+0, +0, +0), +inf, and 0 where no item holds them)
+    HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)curv, 0x7F800000, n, s));
+    HIP_TRY(c, hipMemsetAsync(fnd, 0, n * 4, s));
+    HIP_TRY(c, hipMemsetAsync(counts, 0, 4 * sizeof(uint64_t), s));
+    rtr::launch_normal_rows(s, q.ks.rec1, q.items, (const uint32_t *)(q.cn + 4), q.cap, r2, k, towards ? viewpoint : nullptr, nrm, curv, fnd, counts);
+    if (int rc = launch_check(c, "normal rows")) return rc;
+    if (int rc = q.ev.record(c, 3, s)) return rc;
+    uint64_t h[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(h, counts, sizeof h, hipMemcpyDeviceToHost, s));
+    if (!normals_host.empty()) HIP_TRY(c, hipMemcpyAsync(normals_host.data(), nrm, n * 12, hipMemcpyDeviceToHost, s));
+    if (!curv_host.empty()) HIP_TRY(c, hipMemcpyAsync(curv_host.data(), curv, n * 4, hipMemcpyDeviceToHost, s));
+    if (!found_host.empty()) HIP_TRY(c, hipMemcpyAsync(found_host.data(), fnd, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
+    if (int rc = q.ev.stage_us(c, 0, 3, c->normals_us)) return rc;
+    c->normals_tests_k = saturate_k(h[0]);
+    c->normals_updates_k = saturate_k(h[1]);
+    // behind everything else that can fail: the caller's arrays change only when the call succeeds
+    if (normals_dev) HIP_TRY(c, hipMemcpyAsync(normals, nrm, n * 12, hipMemcpyDeviceToDevice, s));
+    if (curv_dev) HIP_TRY(c, hipMemcpyAsync(curvature, curv, n * 4, hipMemcpyDeviceToDevice, s));
+    if (found_dev) HIP_TRY(c, hipMemcpyAsync(found, fnd, n * 4, hipMemcpyDeviceToDevice, s));
+    if (normals_dev || curv_dev || found_dev) HIP_TRY(c, hipStreamSynchronize(s));
+    if (!normals_host.empty()) memcpy(normals, normals_host.data(), n * 12);
+    if (!curv_host.empty()) memcpy(curvature, curv_host.data(), n * 4);
+    if (!found_host.empty()) memcpy(found, found_host.data(), n * 4);
+    if (stats) stats[0] = h[2], stats[1] = q.m - h[2], stats[2] = q.n - q.m, stats[3] = h[3];  // (every finite point is on the list)
     return RTR_OK;
 }
 

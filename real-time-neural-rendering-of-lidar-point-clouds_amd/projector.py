@@ -433,6 +433,57 @@ class Projector:
             res.append(fd)
         return tuple(res)
 
+    def estimate_normals(self, k, radius, viewpoint=None, normals=True, curvature=True, found=False, device=False):
+        """Estimates on the device the unit normal and the curvature of every resident point from a PCA over the point
+        and its k nearest neighbours within `radius` (include/rtr_normals.h section 6o).  Neighbours:
+        select_statistical's, the row ordered by (squared distance bits, upload index); a point with fewer than
+        NORMAL_MIN_FOUND of them (every non-finite one) has the normal (0, 0, 0) and the curvature +inf.  k:
+        1 .. NORMAL_MAX_K.  viewpoint: three finite floats towards which every normal is turned; None: the component of
+        largest magnitude is positive.  The result depends on the coordinates and the upload order alone, bit for bit,
+        and numpy float64 reproduces it (tests/normals_ref.py).  Nothing else changes: the selection, the keep mask and
+        the clip planes play no part and stay as they are.  The call always waits.  Returns a tuple: with normals the
+        (n, 3) float32 array, with curvature the (n,) float32 array of the surface variation lambda_min / (lambda_0 +
+        lambda_1 + lambda_2), with found the (n,) uint32 array of min(k, neighbours) -- numpy arrays in upload order, or
+        torch tensors on the context's device with device=True --, then the stats: (points with a normal, finite points
+        without one, non-finite points, normals turned by the viewpoint)."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError("k must be an integer")
+        k = int(k)
+        if not 1 <= k <= L.NORMAL_MAX_K:
+            raise ValueError("k must be in 1 .. NORMAL_MAX_K (%d)" % L.NORMAL_MAX_K)
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        with np.errstate(over="ignore", under="ignore"):
+            r2 = np.float32(r) * np.float32(r)
+        if not (np.isfinite(r2) and r2 >= np.finfo(np.float32).tiny):
+            raise ValueError("the square of radius must be a finite normal float32 number")
+        flags, vp = 0, None
+        if viewpoint is not None:
+            with np.errstate(over="ignore"):
+                vp = np.ascontiguousarray(np.asarray(viewpoint, np.float64).astype(np.float32))
+            if vp.shape != (3,) or not np.isfinite(vp).all():
+                raise ValueError("viewpoint must be three finite float32 numbers")
+            flags = L.NORMAL_VIEWPOINT
+        n = self.num_points
+        arrays, ptrs = [], []
+        for want, shape, dt in ((normals, (n, 3), np.float32), (curvature, (n,), np.float32), (found, (n,), np.uint32)):
+            if not want:
+                ptrs.append(None)
+            elif device:
+                import torch
+                a = torch.empty(shape, dtype=torch.uint32 if dt is np.uint32 else torch.float32, device="cuda:%d" % self.device)
+                ptrs.append(C.c_void_p(a.data_ptr()))
+                arrays.append(a)
+            else:
+                a = np.empty(shape, dt)
+                ptrs.append(_vp(a))
+                arrays.append(a)
+        out = np.zeros(4, np.uint64)
+        self._chk(self._lib.rtr_estimate_normals(self._ctx, k, r, flags, _vp(vp), ptrs[0], ptrs[1], ptrs[2], _vp(out)))
+        arrays.append(tuple(int(v) for v in out))
+        return tuple(arrays)
+
     def select_clusters(self, radius, min_points=1, max_points=0, seeded=False, op="replace", outside=False, labels=False,
                         stats=True):
         """Selects on the device the points whose connected cluster within `radius` (include/rtr.h section 6i, Euclidean
@@ -1164,6 +1215,12 @@ class ProjectCloud:
         gone = self._p.select_statistical(k, radius, std_mul, outside=True)[0][0]
         self.removeSelected()
         return gone
+
+    def estimateNormals(self, k, radius, viewpoint=None):
+        """The unit normal (n, 3) and the curvature (n,) of every vertex, float32 in the order of the vertices, from
+        its k nearest neighbours within `radius`; viewpoint: turned towards it (see Projector.estimate_normals).
+        Returns (normals, curvature)."""
+        return self._p.estimate_normals(k, radius, viewpoint)[:2]
 
     def selectClusters(self, radius, min_points=1, max_points=0, seeded=False, op="replace", outside=False):
         """Selects the vertices whose connected cluster within `radius` holds min_points .. max_points vertices (0: no
