@@ -22,6 +22,8 @@ CASES = [(family, seed) for family in sorted(FAMILIES) for seed in SEEDS]
 f32 = np.float32
 # sha256 of repr() of every sequence of analysis_model, computed before nearest_model.py existed
 ANALYSIS_DIGEST = "753ea2fb3699131760899274f5dfb509b992ef8f95a23e2f933d4a05fa073d29"
+# the same of nearest_model's own sequences, computed when rows_model.py was written, before it touched anything
+NEAREST_DIGEST = "a3a0032eac49aeaa8d4d109b069723b5b065ad33378edccbee7ece2fe3689838"
 TIE_EDGES = ("copies", "survivors", "reordered")
 REMOVALS = ("remove", "remove_originals")
 APPENDS = ("append", "append_copies", "merge")
@@ -56,6 +58,7 @@ def test_the_older_sequences_are_unchanged():
     assert _digest(em, em.FAMILIES) == EDIT_DIGEST
     assert _digest(wm, wm.WRITE_FAMILIES) == WRITE_DIGEST
     assert _digest(am, am.FAMILIES) == ANALYSIS_DIGEST
+    assert _digest(nm, nm.FAMILIES) == NEAREST_DIGEST
 
 
 def test_sequences_are_a_pure_function_of_their_arguments():
