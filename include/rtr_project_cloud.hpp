@@ -40,6 +40,7 @@
 // appendNewPoints appends only the given points with no vertex within a radius: a scan merged without duplicates.
 // nearestPoints (section 6l) finds for every given point the nearest vertex within a radius and its squared distance;
 // matchPoints also returns the matched vertices' coordinates and colours: one ICP step with a fit and transformPoints.
+// registerPoints (section 6p, rtr_register.h) aligns a scan to the vertices: ICP steps whose sums and fit are exact.
 // nearestKPoints (section 6m) finds the k nearest vertices within a radius, sorted: the input of normals and density.
 // fitPlane (section 6j) finds the plane with the most vertices within a distance of it; selectPlane, segmentPlane.
 // extractSelected / extractAll (section 2e) read vertices back out in upload order, as appendPoints takes them.
@@ -51,6 +52,7 @@
 // methods and tensor(), the device pointer computeFull hands to the U-Net.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -68,6 +70,7 @@
 #endif
 
 #include "rtr_normals.h"
+#include "rtr_register.h"
 #include "rtr_statistics.h"
 
 namespace rtr {
@@ -548,6 +551,62 @@ public:
         }
         r.index = std::move(nn.index);
         r.dist2 = std::move(nn.dist2);
+        return r;
+    }
+    // -- registering a scan (rtr_register.h section 6p) --
+    struct Registration {
+        double pose[16];          // 4x4 row-major: moves the scan onto the cloud
+        std::vector<double> rms;  // the rms residual of every call
+        uint64_t stats[4];        // the last call's: pairs used, finite points without one, non-finite points, degenerate
+    };
+    // step o pose (both 3x4 row-major) in the fixed order of section 6p, part 4
+    static void composePose(const double step[12], const double pose[12], double out[12]) {
+        double r[12];
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 4; ++b) {
+                double v = (step[4 * a] * pose[b] + step[4 * a + 1] * pose[4 + b]) + step[4 * a + 2] * pose[8 + b];
+                if (b == 3) v = v + step[4 * a + 3];
+                r[4 * a + b] = v;
+            }
+        std::memcpy(out, r, sizeof r);
+    }
+    // Aligns the scan (m records of three floats, host or device memory, never written) to the resident cloud by up to
+    // `iterations` calls of rtr_register_points, each step composed onto the pose.  point_to_plane with normals nullptr:
+    // estimateNormals(16, radius) once, into HOST memory: this header has no device allocator (it does not depend on HIP),
+    // so the normals are then uploaded by every call, 12 B per vertex.  For a large cloud call estimateNormals into a
+    // device array of your own and pass it here: nothing per-vertex then moves between iterations.
+    // Stops at a degenerate step, and at the first call whose pair count equals the previous one's while its rms residual
+    // did not fall (that step is not applied).  pose: the 3x4 row-major start, nullptr: the identity.
+    Registration registerPoints(const float* xyz, size_t xyz_stride_bytes, size_t m, float radius, int iterations = 20,
+                                bool point_to_plane = false, const float* normals = nullptr, const double* pose = nullptr) {
+        Registration r{};
+        double cur[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        if (pose) std::memcpy(cur, pose, sizeof cur);
+        std::vector<float> own;
+        if (point_to_plane && !normals) {
+            uint64_t n = 0;
+            check(ctx_, rtr_num_points(ctx_, &n));
+            own.resize((size_t)n * 3);
+            estimateNormals(16, radius, own.data());
+            normals = own.data();
+        }
+        bool have_prev = false;
+        uint64_t prev_pairs = 0;
+        double prev_rms = 0.0;
+        for (int it = 0; it < iterations; ++it) {
+            double mom[RTR_REGISTER_MOMENTS], step[12];
+            check(ctx_, rtr_register_points(ctx_, xyz, xyz_stride_bytes, m, radius, point_to_plane ? RTR_REGISTER_POINT_TO_PLANE : 0, cur,
+                                            point_to_plane ? normals : nullptr, mom, step, r.stats));
+            // (an IEEE square root and division: the facades and tests/register_ref.py agree on the bits)
+            const double rms = mom[0] > 0.0 ? std::sqrt(mom[point_to_plane ? RTR_REGISTER_MOMENTS - 1 : 16] / mom[0]) : HUGE_VAL;
+            r.rms.push_back(rms);
+            if (r.stats[3]) break;
+            if (have_prev && r.stats[0] == prev_pairs && !(rms < prev_rms)) break;
+            have_prev = true, prev_pairs = r.stats[0], prev_rms = rms;
+            composePose(step, cur, cur);
+        }
+        std::memcpy(r.pose, cur, sizeof cur);
+        r.pose[12] = r.pose[13] = r.pose[14] = 0.0, r.pose[15] = 1.0;
         return r;
     }
     // Takes the clusters of fewer than min_points vertices within `radius` out of the resident cloud for good: their

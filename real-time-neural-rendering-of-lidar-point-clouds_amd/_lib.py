@@ -33,6 +33,8 @@ SYMBOLS = [
 STATISTICS_SYMBOLS = ["rtr_select_statistical"]
 # every symbol include/rtr_normals.h declares (section 6o)
 NORMALS_SYMBOLS = ["rtr_estimate_normals"]
+# every symbol include/rtr_register.h declares (section 6p)
+REGISTER_SYMBOLS = ["rtr_register_points"]
 
 RTR_OK, RTR_ERR_INVALID, RTR_ERR_HIP, RTR_ERR_NO_OUTPUT, RTR_ERR_UNSUPPORTED, RTR_ERR_INTERNAL = 0, -1, -2, -3, -4, -5
 BUF_DEPTH, BUF_ACCUM, BUF_IMAGE, BUF_TENSOR, BUF_MASK, BUF_MINMAX, BUF_POINT_ID, BUF_VISIBLE = range(8)
@@ -51,6 +53,8 @@ STAT_THRESHOLD_GIVEN = 1  # rtr_select_statistical's flag: moments[2] is the thr
 NORMAL_MAX_K = 64  # RTR_NORMAL_MAX_K: rtr_estimate_normals' largest k
 NORMAL_MIN_FOUND = 2  # RTR_NORMAL_MIN_FOUND: a normal needs the point and two neighbours
 NORMAL_VIEWPOINT = 1  # rtr_estimate_normals' flag: orient every normal towards the viewpoint
+REGISTER_POINT_TO_PLANE = 1  # rtr_register_points' flag: point-to-plane with the resident points' normals
+REGISTER_MOMENTS = 32  # RTR_REGISTER_MOMENTS: the doubles of rtr_register_points' moments
 BANDS_SELECTED = 1  # rtr_count_in_bands / rtr_fit_plane flag: only the currently selected points
 MAX_BANDS = 4096  # RTR_MAX_BANDS
 MAX_VIEWS = 8  # RTR_MAX_VIEWS
@@ -167,9 +171,10 @@ def lib():
     L.rtr_fit_plane.argtypes = [vp, C.c_float, C.c_uint32, u64, i32, vp, vp]
     L.rtr_select_statistical.argtypes = [vp, C.c_uint32, C.c_float, C.c_double, i32, i32, vp, vp, vp, vp]
     L.rtr_estimate_normals.argtypes = [vp, C.c_uint32, C.c_float, i32, vp, vp, vp, vp, vp]
+    L.rtr_register_points.argtypes = [vp, vp, sz, u64, C.c_float, i32, vp, vp, vp, vp, vp]
     L.rtr_extract_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, vp, C.POINTER(u64)]
     L.rtr_write_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, C.POINTER(u64)]
-    for name in SYMBOLS + STATISTICS_SYMBOLS + NORMALS_SYMBOLS:
+    for name in SYMBOLS + STATISTICS_SYMBOLS + NORMALS_SYMBOLS + REGISTER_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rtr_last_error", "rtr_default_params"):
             fn.restype = i32

@@ -1,7 +1,7 @@
 // rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6m), include/rtr_statistics.h
-// (section 6n) and include/rtr_normals.h (section 6o) on top of the kernels of
+// (section 6n), include/rtr_normals.h (section 6o) and include/rtr_register.h (section 6p) on top of the kernels of
 // rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip, rtr_nearest.hip, rtr_nearest_k.hip,
-// rtr_statistical.hip, rtr_normals.hip and rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
+// rtr_statistical.hip, rtr_normals.hip, rtr_register.hip and rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
 // calls in their own file") has the order of events every call follows and why an error leaves the selection as it was.
 #include <algorithm>
 #include <chrono>
@@ -11,9 +11,12 @@
 #include <vector>
 
 #include "../../include/rtr_normals.h"
+#include "../../include/rtr_register.h"
 #include "../../include/rtr_statistics.h"
 #include "rtr_host.h"
 #include "rtr_plane_fit.h"
+#include "rtr_register_fit.h"
+#include "rtr_register_kernels.h"
 
 int check_indexable(rtr_ctx *c) {
     if (c->n < (1ull << 32)) return RTR_OK;
@@ -763,6 +766,127 @@ int rtr_nearest_points(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, 
     }
     if (copied) HIP_TRY(c, hipStreamSynchronize(s));
     const uint64_t out[4] = {have, sweep[0], nonfinite, 0};
+    if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- one registration step (rtr_register.h, section 6p) -------------------------------
+// rtr_nearest_points' order of events around the same sweep, with no resident side: the given points go through the pose
+// into scratch records (a host array is copied over first), GivenPoints keys, sorts and gathers THOSE, with its wait and
+// its failure for a point beyond the span; behind the sweep one bit per winner goes into scratch words, their scan and
+// one extract lay the winners' coordinates out by rank, and the two passes of sums follow, with a wait between them for
+// the means.  The fit runs on the host (rtr_register_fit.h).  The selection plays no part; moments, step and stats are
+// written last.
+int rtr_register_points(rtr_ctx *c, const float *xyz, size_t xs, uint64_t count, float radius, int flags, const double pose[12],
+                        const float *normals, double moments[RTR_REGISTER_MOMENTS], double step[12], uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_register_points: no cloud");
+    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_register_points: radius must be finite and > 0");
+    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
+    NEED(c, std::isnormal(r2), "rtr_register_points: the square of radius is not a finite normal fp32 number");
+    NEED(c, count == 0 || xyz != nullptr, "rtr_register_points: xyz is NULL");
+    NEED(c, xs >= 12 && xs % 4 == 0, "rtr_register_points: xyz_stride_bytes must be >= 12 and a multiple of 4");
+    NEED(c, (flags & ~RTR_REGISTER_POINT_TO_PLANE) == 0, "rtr_register_points: unknown bits in flags");
+    const bool plane = (flags & RTR_REGISTER_POINT_TO_PLANE) != 0;
+    NEED(c, !plane || normals != nullptr, "rtr_register_points: normals is NULL with RTR_REGISTER_POINT_TO_PLANE");
+    NEED(c, plane || normals == nullptr, "rtr_register_points: normals given without RTR_REGISTER_POINT_TO_PLANE");
+    rtr::RegisterPose T{};
+    if (pose) {
+        for (int i = 0; i < 12; ++i) {
+            NEED(c, std::isfinite(pose[i]), "rtr_register_points: pose has a non-finite entry");
+            T.t[i] = pose[i];
+        }
+        T.given = 1;
+    }
+    if (int rc = check_indexable(c)) return rc;
+    if (count >= (1ull << 32)) return fail(c, RTR_ERR_UNSUPPORTED, "rtr_register_points: given indices are 32-bit: count is %llu", (unsigned long long)count);
+    if (int rc = need_upload_order(c, "matched")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const uint64_t n = c->n, nw = (n + 31) / 32, nch = (n + 255) / 256, nwin = std::min(count, n);
+    const size_t gbytes = count ? (size_t)(count - 1) * xs + 12 : 0;
+    const bool xyz_host = count && !on_device(xyz), normals_host = plane && !on_device(normals);
+    DevBufs buf;
+    GivenPoints gp;
+    float4 *posed, *win;
+    uint8_t *xstage = nullptr;
+    float *nstage = nullptr;
+    uint64_t *slots, *tot;
+    uint32_t *wsel, *wscan, *scratch;
+    double *partial, *red;
+    HIP_TRY(c, buf.get(&posed, count * 16));
+    if (xyz_host) HIP_TRY(c, buf.get(&xstage, gbytes));
+    if (normals_host) HIP_TRY(c, buf.get(&nstage, n * 12));
+    if (int rc = gp.alloc(c, buf, reinterpret_cast<const float *>(posed), 16, count)) return rc;
+    uint64_t *cn = gp.cn;
+    HIP_TRY(c, buf.get(&slots, count * 8));
+    HIP_TRY(c, buf.get(&wsel, sel_words(n) * 4));
+    HIP_TRY(c, buf.get(&wscan, sel_words(n) * 4));
+    HIP_TRY(c, buf.get(&scratch, rtr::scan_scratch_words(nw) * 4));
+    HIP_TRY(c, buf.get(&tot, sizeof(uint64_t)));
+    HIP_TRY(c, buf.get(&win, nwin * 16));
+    HIP_TRY(c, buf.get(&partial, rtr::register_chunks(count) * rtr::kRegPlaneSums * sizeof(double)));
+    HIP_TRY(c, buf.get(&red, rtr::kRegPlaneSums * sizeof(double)));
+    if (count) HIP_TRY(c, hipMemsetAsync(slots, 0xFF, count * 8, s));
+    HIP_TRY(c, hipMemsetAsync(wsel, 0, sel_words(n) * 4, s));
+    HIP_TRY(c, hipMemsetAsync(wscan, 0, sel_words(n) * 4, s));
+    if (xstage) HIP_TRY(c, hipMemcpyAsync(xstage, xyz, gbytes, hipMemcpyHostToDevice, s));
+    if (nstage) HIP_TRY(c, hipMemcpyAsync(nstage, normals, n * 12, hipMemcpyHostToDevice, s));
+    rtr::launch_register_pose(s, xstage ? xstage : reinterpret_cast<const uint8_t *>(xyz), xs, count, T, posed);
+    if (int rc = launch_check(c, "register pose")) return rc;
+    if (int rc = gp.run(c, "rtr_register_points", s, reinterpret_cast<const float *>(posed), 16, count, radius)) return rc;
+    const uint64_t nonfinite = gp.nonfinite, m = gp.m;
+    if (m) {
+        rtr::launch_nearest_sweep(s, cloud_of(c), c->bounds, c->reordered ? c->perm : nullptr, gp.ks.k1, gp.ks.rec1, m, radius, r2, gp.glo, gp.ghi,
+                                  slots, nullptr, nullptr, cn + 4);
+        if (int rc = launch_check(c, "register sweep")) return rc;
+    }
+    double mom[RTR_REGISTER_MOMENTS], sums[rtr::kRegPlaneSums] = {};
+    rtr::RegisterSums a{};
+    a.slots = slots, a.posed = posed, a.win = win, a.wsel = wsel, a.wscan = wscan, a.normals = nstage ? nstage : normals, a.count = count;
+    if (m) {
+        rtr::launch_register_mark(s, slots, count, wsel);
+        if (int rc = launch_check(c, "register mark")) return rc;
+        rtr::launch_scan_u32(s, wsel, nw, n, wscan, scratch, tot);
+        if (int rc = launch_check(c, "register scan")) return rc;
+        // every rank goes to its own slot: at most min(count, n) distinct winners.  The extract takes that bound as its total,
+        // not the true number of winners, which lies in *tot on the device: reading it would cost one more wait.  The total
+        // only closes the LAST chunk's run of ranks (extract_chunk_skip), so in upload order that one chunk is never left on
+        // its two scan words and is gathered even when it holds no winner -- one chunk's bits per call, nothing decoded
+        const rtr::Cloud cl = cloud_of(c);
+        rtr::ExtractArgs e{};
+        e.pk = cl.pk;
+        e.x4 = (const float4 *)cl.x, e.y4 = (const float4 *)cl.y, e.z4 = (const float4 *)cl.z;
+        e.rgba4 = (const uint4 *)cl.rgba;
+        e.perm = c->reordered ? c->perm : nullptr, e.sel = wsel, e.wscan = wscan;
+        e.n = n, e.total = nwin, e.c0 = 0, e.c1 = nch, e.first = 0, e.count = nwin;
+        e.xyz = reinterpret_cast<uint8_t *>(win), e.xyz_stride = 16, e.xyz_form = 2;
+        rtr::launch_extract(s, e);
+        if (int rc = launch_check(c, "register extract")) return rc;
+        rtr::launch_register_sums(s, a, plane, 0, partial, red);
+        if (int rc = launch_check(c, "register sums")) return rc;
+        HIP_TRY(c, hipMemcpyAsync(sums, red, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    rtr::register_means(sums, mom);
+    const int nsum = plane ? rtr::kRegPlaneSums : rtr::kRegPointSums;
+    if (mom[0] > 0.0) {
+        for (int i = 0; i < 6; ++i) a.mean[i] = mom[1 + i];
+        rtr::launch_register_sums(s, a, plane, 1, partial, red);
+        if (int rc = launch_check(c, "register moments")) return rc;
+        HIP_TRY(c, hipMemcpyAsync(sums, red, nsum * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));  // (always: the scratch goes with this call)
+    if (mom[0] > 0.0)
+        for (int i = 0; i < nsum; ++i) mom[(plane ? 4 : 7) + i] = sums[i];  // (plane: the sums take qbar's place)
+    double st[12];
+    const bool degenerate = plane ? rtr::register_fit_plane(mom, st) : rtr::register_fit_point(mom, st);
+    const uint64_t used = (uint64_t)mom[0];
+    // behind everything that can fail: the caller's arrays change only when the call succeeds
+    if (moments) memcpy(moments, mom, sizeof mom);
+    if (step) memcpy(step, st, sizeof st);
+    const uint64_t out[4] = {used, m - used, nonfinite, degenerate ? 1u : 0u};
     if (stats) memcpy(stats, out, sizeof out);
     return RTR_OK;
 }

@@ -606,6 +606,69 @@ class Projector:
             return None
         return arrays[0] if len(arrays) == 1 else tuple(arrays)
 
+    @staticmethod
+    def compose_pose(step, pose):
+        """step o pose of two 3x4 (or 4x4) row-major float64 transforms, in register_points' fixed order: rotation part
+        ((S_a0 P_0b + S_a1 P_1b) + S_a2 P_2b), translation the same with b = 3, + S_a3.  Returns a (3, 4) float64 array."""
+        s = [float(v) for v in np.asarray(step, np.float64).reshape(-1)[:12]]
+        p = [float(v) for v in np.asarray(pose, np.float64).reshape(-1)[:12]]
+        out = np.empty((3, 4), np.float64)
+        for a in range(3):
+            for b in range(4):
+                v = (s[4 * a] * p[b] + s[4 * a + 1] * p[4 + b]) + s[4 * a + 2] * p[8 + b]
+                out[a, b] = v + s[4 * a + 3] if b == 3 else v
+        return out
+
+    def register_points(self, xyz, radius, point_to_plane=False, pose=None, normals=None):
+        """One registration (ICP) step of the GIVEN points `xyz`, moved by `pose`, against the resident cloud, on the
+        device (include/rtr_register.h section 6p).  xyz: as nearest_points takes it; it is never written.  pose: a (3, 4)
+        or (4, 4) float64 transform with finite entries, or None for the identity; the posed points are formed in float64
+        and rounded to float32.  Correspondences: nearest_points' given side on the posed points.  point_to_plane: with
+        `normals`, the (n, 3) float32 normals of the resident points in upload order -- a numpy array, a torch tensor
+        (host or device) or an object with __cuda_array_interface__ (estimate_normals(..., device=True) gives them
+        without a copy); a pair whose normal is non-finite or (0, 0, 0) is dropped.  Returns (moments, step, stats):
+        moments the REGISTER_MOMENTS float64 sums (pair count, means, cross sums, residual sum), step the (3, 4) float64
+        transform that moves the POSED points onto their partners -- the identity when stats[3] is set --, stats (pairs
+        used, finite posed points without a used pair, non-finite posed points, degenerate).  Every value is reproduced
+        bit for bit by numpy float64 (tests/register_ref.py).  Nothing else changes; the call always waits."""
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        with np.errstate(over="ignore", under="ignore"):
+            r2 = np.float32(r) * np.float32(r)
+        if not (np.isfinite(r2) and r2 >= np.finfo(np.float32).tiny):
+            raise ValueError("the square of radius must be a finite normal float32 number")
+        ptr, stride, m, hold = self._write_source(xyz, np.float32, "xyz")
+        if m >= 2 ** 32:
+            raise ValueError("at most 2^32 - 1 given points")
+        if m and (stride < 12 or stride % 4):
+            raise ValueError("xyz rows must be at least 12 bytes apart, by a multiple of 4")
+        T = None
+        if pose is not None:
+            T = np.asarray(pose, np.float64)
+            if T.shape == (4, 4):
+                if not (T[3, 0] == 0 and T[3, 1] == 0 and T[3, 2] == 0 and T[3, 3] == 1):
+                    raise ValueError("the bottom row of a 4 x 4 pose must be exactly (0, 0, 0, 1)")
+                T = T[:3]
+            if T.shape != (3, 4) or not np.isfinite(T).all():
+                raise ValueError("pose must be a finite (3, 4) or (4, 4) float64 array")
+            T = np.ascontiguousarray(T).reshape(12)
+        if point_to_plane and normals is None:
+            raise ValueError("point_to_plane needs the resident points' normals")
+        if normals is not None and not point_to_plane:
+            raise ValueError("normals are read in point_to_plane mode only")
+        nptr, nhold = None, None
+        if point_to_plane:
+            nptr, nstride, rows, nhold = self._write_source(normals, np.float32, "normals")
+            if rows != self.num_points or (rows > 1 and nstride != 12):
+                raise ValueError("normals must be %d packed rows of 3 float32" % self.num_points)
+        mom, step, out = np.zeros(L.REGISTER_MOMENTS, np.float64), np.zeros(12, np.float64), np.zeros(4, np.uint64)
+        self._chk(self._lib.rtr_register_points(self._ctx, ptr if m else None, stride if m else 12, m, r,
+                                                L.REGISTER_POINT_TO_PLANE if point_to_plane else 0, _vp(T), nptr, _vp(mom), _vp(step),
+                                                _vp(out)))
+        del hold, nhold
+        return mom, step.reshape(3, 4), tuple(int(v) for v in out)
+
     def nearest_k_points(self, xyz, k, radius, stats=True):
         """Finds on the device, for every GIVEN point of `xyz`, its `k` nearest resident points within `radius`
         (include/rtr.h section 6m).  xyz: as nearest_points takes it -- float32 rows, (m, 3) or (m, 4), a numpy array, a
@@ -1285,6 +1348,34 @@ class ProjectCloud:
         if hasattr(index, "cpu"):
             index, dist2 = index.cpu().numpy(), dist2.cpu().numpy()
         return (index, dist2) + self._gather_matched(index)
+
+    # -- registering a scan (rtr_register.h section 6p)
+    def registerPoints(self, vertices, radius, iterations=20, point_to_plane=False, normals=None, pose=None):
+        """Aligns the scan `vertices` ((m, 3) or (m, 4) float32, host or device; never written) to the resident cloud by
+        up to `iterations` steps of Projector.register_points, each composed onto the pose in float64
+        (Projector.compose_pose).  point_to_plane with normals None: estimateNormals(16, radius) once, kept on the
+        device.  Stops at a degenerate step, and at the first step whose pair count equals the previous one's while its
+        rms residual did not fall (that step is not applied).  Returns (pose, rms, stats): the (4, 4) float64 pose that
+        moves the scan onto the cloud, the rms residual of every call, and the last call's stats.  Every step is exact, so
+        the whole loop is reproducible bit for bit; device vertices stay on the device."""
+        cur = np.eye(4)[:3] if pose is None else np.asarray(pose, np.float64).reshape(-1)[:12].reshape(3, 4).copy()
+        if point_to_plane and normals is None:
+            normals = self._p.estimate_normals(16, radius, curvature=False, device=True)[0]
+        at = L.REGISTER_MOMENTS - 1 if point_to_plane else 16  # (the residual sum's place among the moments)
+        rms, stats, prev = [], (0, 0, 0, 0), None
+        for _ in range(int(iterations)):
+            mom, step, stats = self._p.register_points(vertices, radius, point_to_plane, cur, normals if point_to_plane else None)
+            r = float(np.sqrt(mom[at] / mom[0])) if mom[0] > 0 else float("inf")
+            rms.append(r)
+            if stats[3]:
+                break
+            if prev is not None and stats[0] == prev[0] and not r < prev[1]:
+                break
+            prev = (stats[0], r)
+            cur = Projector.compose_pose(step, cur)
+        out = np.eye(4)
+        out[:3] = cur
+        return out, rms, stats
 
     def _gather_matched(self, index):
         m = index.shape[0]
