@@ -36,6 +36,8 @@
 // estimateNormals (section 6o, rtr_normals.h) gives every vertex a unit normal and a curvature from its k nearest
 // neighbours; it selects nothing and changes nothing.
 // selectClusters (section 6i) names them by the size of their connected cluster; growSelection, removeSmallClusters.
+// selectSegments (section 6q, rtr_segments.h) names them by the size of their smooth surface segment -- neighbours whose
+// normals agree --: the faces of a room where selectClusters sees one cluster; removeSmallSegments.
 // selectNear (section 6k) names the vertices within a radius of GIVEN points, and the given points near a vertex.
 // appendNewPoints appends only the given points with no vertex within a radius: a scan merged without duplicates.
 // nearestPoints (section 6l) finds for every given point the nearest vertex within a radius and its squared distance;
@@ -71,6 +73,7 @@
 
 #include "rtr_normals.h"
 #include "rtr_register.h"
+#include "rtr_segments.h"
 #include "rtr_statistics.h"
 
 namespace rtr {
@@ -613,6 +616,33 @@ public:
     // vertices are selected (replacing the selection) and removed.  Returns the number removed.
     uint64_t removeSmallClusters(float radius, uint32_t min_points) {
         const uint64_t gone = selectClusters(radius, min_points, 0, false, RTR_SELECT_REPLACE, true);
+        removeSelected();
+        return gone;
+    }
+    // -- smooth segments (section 6q, rtr_segments.h) --
+    // The vertices whose smooth surface segment holds at least min_points and, unless max_points is 0, at most max_points
+    // vertices: estimateNormals(k, radius), then rtr_select_segments at the same radius -- neighbours whose normals lie
+    // within `angle` (radians, up to sign) and whose curvatures are both <= max_curvature (INFINITY: no limit) are joined,
+    // and the segments are the connected components.  cos_angle is the host's std::cos(angle) rounded to float: this one
+    // value comes from libm, everything behind it is exact.  The normals and the curvature go through HOST vectors: this
+    // header has no device allocator (it does not depend on HIP), so 16 B per vertex come down and go up again.  For a
+    // large cloud call estimateNormals into device arrays of your own and rtr_select_segments on them.  seeded, op,
+    // outside, labels: as selectClusters.  Returns the number selected afterwards.  point_ids = true when the cloud may
+    // be sorted.
+    uint64_t selectSegments(float radius, uint32_t k, float angle, float max_curvature, uint32_t min_points = 1, uint32_t max_points = 0,
+                            bool seeded = false, int op = RTR_SELECT_REPLACE, bool outside = false, uint32_t* labels = nullptr) {
+        uint64_t n = 0, st[4];
+        check(ctx_, rtr_num_points(ctx_, &n));
+        std::vector<float> normals((size_t)n * 3), curvature((size_t)n);
+        estimateNormals(k, radius, normals.data(), curvature.data());
+        check(ctx_, rtr_select_segments(ctx_, radius, (float)std::cos((double)angle), normals.data(), curvature.data(), max_curvature, min_points,
+                                        max_points, seeded ? RTR_SEGMENT_SEEDED : 0, op | (outside ? RTR_SELECT_OUTSIDE : 0), labels, st));
+        return st[0];
+    }
+    // Takes the smooth segments of fewer than min_points vertices out of the resident cloud for good: their vertices are
+    // selected (replacing the selection) and removed.  Returns the number removed.
+    uint64_t removeSmallSegments(float radius, uint32_t k, float angle, float max_curvature, uint32_t min_points) {
+        const uint64_t gone = selectSegments(radius, k, angle, max_curvature, min_points, 0, false, RTR_SELECT_REPLACE, true);
         removeSelected();
         return gone;
     }

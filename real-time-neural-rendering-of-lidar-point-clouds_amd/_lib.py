@@ -35,6 +35,8 @@ STATISTICS_SYMBOLS = ["rtr_select_statistical"]
 NORMALS_SYMBOLS = ["rtr_estimate_normals"]
 # every symbol include/rtr_register.h declares (section 6p)
 REGISTER_SYMBOLS = ["rtr_register_points"]
+# every symbol include/rtr_segments.h declares (section 6q)
+SEGMENTS_SYMBOLS = ["rtr_select_segments"]
 
 RTR_OK, RTR_ERR_INVALID, RTR_ERR_HIP, RTR_ERR_NO_OUTPUT, RTR_ERR_UNSUPPORTED, RTR_ERR_INTERNAL = 0, -1, -2, -3, -4, -5
 BUF_DEPTH, BUF_ACCUM, BUF_IMAGE, BUF_TENSOR, BUF_MASK, BUF_MINMAX, BUF_POINT_ID, BUF_VISIBLE = range(8)
@@ -45,6 +47,8 @@ SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_INTERSECT = range(4)  # rtr_
 SELECT_OUTSIDE = 4  # ... the flag OR-ed into it: hit = not inside ...
 SELECT_TOGGLE = 8  # ... and sel ^= hit (with no region: inverts the selection)
 CLUSTER_SEEDED = 1  # rtr_select_clusters' flag: only clusters holding a currently selected point
+SEGMENT_SEEDED = 1  # rtr_select_segments' flag: as CLUSTER_SEEDED
+SEGMENT_ORIENTED = 2  # rtr_select_segments' flag: signed normals, dot >= cos_angle instead of |dot| >= cos_angle
 NEAR_GIVEN_ONLY = 1  # rtr_select_near's flag: only the given side, the selection is left alone
 NEAREST_NONE = 0xFFFFFFFF  # RTR_NEAREST_NONE: rtr_nearest_points' index of "no point within radius"
 NEAREST_MAX_K = 64  # RTR_NEAREST_MAX_K: rtr_nearest_k_points' largest k
@@ -174,7 +178,8 @@ def lib():
     L.rtr_register_points.argtypes = [vp, vp, sz, u64, C.c_float, i32, vp, vp, vp, vp, vp]
     L.rtr_extract_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, vp, C.POINTER(u64)]
     L.rtr_write_points.argtypes = [vp, vp, u64, u64, u64, vp, sz, vp, sz, C.POINTER(u64)]
-    for name in SYMBOLS + STATISTICS_SYMBOLS + NORMALS_SYMBOLS + REGISTER_SYMBOLS:
+    L.rtr_select_segments.argtypes = [vp, C.c_float, C.c_float, vp, vp, C.c_float, C.c_uint32, C.c_uint32, i32, i32, vp, vp]
+    for name in SYMBOLS + STATISTICS_SYMBOLS + NORMALS_SYMBOLS + REGISTER_SYMBOLS + SEGMENTS_SYMBOLS:
         fn = getattr(L, name)
         if name not in ("rtr_last_error", "rtr_default_params"):
             fn.restype = i32

@@ -1,6 +1,7 @@
 // rtr_select_api.hip -- the selection and analysis calls of include/rtr.h (sections 6f - 6m), include/rtr_statistics.h
-// (section 6n), include/rtr_normals.h (section 6o) and include/rtr_register.h (section 6p) on top of the kernels of
-// rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_near.hip, rtr_nearest.hip, rtr_nearest_k.hip,
+// (section 6n), include/rtr_normals.h (section 6o), include/rtr_register.h (section 6p) and include/rtr_segments.h (section 6q)
+// on top of the kernels of
+// rtr_cloud_kernels.hip, rtr_voxel.hip, rtr_neighbours.hip, rtr_clusters.hip, rtr_segments.hip, rtr_near.hip, rtr_nearest.hip, rtr_nearest_k.hip,
 // rtr_statistical.hip, rtr_normals.hip, rtr_register.hip and rtr_planes.hip.  The rules the calls share are stated once each, in the helpers below; DESIGN.md ("The selection
 // calls in their own file") has the order of events every call follows and why an error leaves the selection as it was.
 #include <algorithm>
@@ -12,11 +13,13 @@
 
 #include "../../include/rtr_normals.h"
 #include "../../include/rtr_register.h"
+#include "../../include/rtr_segments.h"
 #include "../../include/rtr_statistics.h"
 #include "rtr_host.h"
 #include "rtr_plane_fit.h"
 #include "rtr_register_fit.h"
 #include "rtr_register_kernels.h"
+#include "rtr_segment_kernels.h"
 
 int check_indexable(rtr_ctx *c) {
     if (c->n < (1ull << 32)) return RTR_OK;
@@ -440,6 +443,68 @@ int rtr_select_clusters(rtr_ctx *c, float radius, uint32_t min_points, uint32_t 
     if (int rc = q.ev.record(c, 3, s)) return rc;
     uint64_t out[4] = {0, 0, 0, 0};
     if (int rc = neighbour_finish(c, "cluster combine", q, sop, out, c->clusters_us, &c->clusters_tests_k)) return rc;
+    if (lab) {  // (behind everything that can fail: the caller's array changes only when the call succeeds)
+        HIP_TRY(c, hipMemcpyAsync(labels, lab, n * 4, labels_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    if (stats) memcpy(stats, out, sizeof out);
+    return RTR_OK;
+}
+
+// ---- selection by smooth segment (rtr_segments.h, section 6q) -------------------------
+// rtr_select_clusters' order of events with the normal test in the link (rtr_segments.hip).  The union-find's arrays and
+// the labels live where section 6i keeps them; the normal records and the staging copies of inputs that lie in host
+// memory are the only new scratch and are allocated BEFORE the search, so that the selection comes into existence
+// behind the call's last allocation.  The stage times and the pair tests go to locals: the call has no option key.
+int rtr_select_segments(rtr_ctx *c, float radius, float cos_angle, const float *normals, const float *curvature, float max_curvature,
+                        uint32_t min_points, uint32_t max_points, int flags, int op, uint32_t *labels, uint64_t stats[4]) {
+    if (!c) return RTR_ERR_INVALID;
+    c->ov.other_call();
+    NEED(c, c->cap > 0, "rtr_select_segments: no cloud");
+    NEED(c, std::isfinite(radius) && radius > 0.f, "rtr_select_segments: radius must be finite and > 0");
+    const float r2 = radius * radius;  // (one fp32 product: the build has no contraction and no fast-math)
+    NEED(c, std::isnormal(r2), "rtr_select_segments: the square of radius is not a finite normal fp32 number");
+    NEED(c, std::isfinite(cos_angle) && cos_angle > 0.f && cos_angle <= 1.f, "rtr_select_segments: cos_angle must be finite, > 0 and <= 1");
+    NEED(c, normals != nullptr, "rtr_select_segments: normals is NULL");
+    NEED(c, curvature == nullptr || !std::isnan(max_curvature), "rtr_select_segments: max_curvature is NaN with a curvature array");
+    NEED(c, min_points >= 1u, "rtr_select_segments: min_points must be >= 1");
+    NEED(c, max_points == 0u || max_points >= min_points, "rtr_select_segments: max_points must be 0 (unbounded) or >= min_points");
+    NEED(c, (flags & ~(RTR_SEGMENT_SEEDED | RTR_SEGMENT_ORIENTED)) == 0, "rtr_select_segments: unknown bits in flags");
+    SelectOp sop;
+    if (int rc = check_select_op(c, "rtr_select_segments", op, &sop)) return rc;
+    if (int rc = check_indexable(c)) return rc;
+    if (int rc = need_upload_order(c, "formed")) return rc;
+    DevGuard g(c->device);
+    hipStream_t s = c->stream;
+    const bool seeded = (flags & RTR_SEGMENT_SEEDED) != 0, oriented = (flags & RTR_SEGMENT_ORIENTED) != 0;
+    const bool labels_dev = labels && on_device(labels);
+    NeighbourSearch q;
+    float4 *nrec;
+    float *nstage = nullptr, *cstage = nullptr;
+    HIP_TRY(c, q.buf.get(&nrec, c->n * 16));
+    if (!on_device(normals)) HIP_TRY(c, q.buf.get(&nstage, c->n * 12));
+    if (curvature && !on_device(curvature)) HIP_TRY(c, q.buf.get(&cstage, c->n * 4));
+    if (int rc = neighbour_search(c, "rtr_select_segments", radius, q)) return rc;
+    const uint64_t n = q.n;
+    // (the inputs are read before the call returns: one copy each of those that lie in host memory)
+    if (nstage) HIP_TRY(c, hipMemcpyAsync(nstage, normals, n * 12, hipMemcpyHostToDevice, s));
+    if (cstage) HIP_TRY(c, hipMemcpyAsync(cstage, curvature, n * 4, hipMemcpyHostToDevice, s));
+    uint32_t *parent = reinterpret_cast<uint32_t *>(q.ks.rec0), *size = parent + n, *minu = size + n, *seed = minu + n;
+    uint32_t *lab = labels ? reinterpret_cast<uint32_t *>(q.ks.k0) : nullptr;
+    rtr::launch_segment_gather(s, q.ks.v1, q.m, nstage ? nstage : normals, cstage ? cstage : curvature, max_curvature, nrec);
+    if (int rc = launch_check(c, "segment gather")) return rc;
+    rtr::launch_cluster_init(s, n, parent, size, minu, seed);
+    if (int rc = launch_check(c, "segment init")) return rc;
+    rtr::launch_segment_link(s, q.ks.rec1, nrec, q.items, (const uint32_t *)(q.cn + 4), q.cap, r2, cos_angle, oriented, parent, q.cn + 2);
+    if (int rc = launch_check(c, "segment link")) return rc;
+    rtr::launch_cluster_flatten(s, q.ks.v1, n, seeded ? c->sel : nullptr, parent, size, minu, seed);
+    if (int rc = launch_check(c, "segment flatten")) return rc;
+    rtr::launch_cluster_hits(s, q.ks.v1, n, parent, size, minu, seed, min_points, max_points, seeded, q.hit, lab, c->sel_stats);
+    if (int rc = launch_check(c, "segment hits")) return rc;
+    if (int rc = q.ev.record(c, 3, s)) return rc;
+    uint64_t out[4] = {0, 0, 0, 0};
+    int us[3] = {0, 0, 0}, tests_k = 0;  // (no option key reports them)
+    if (int rc = neighbour_finish(c, "segment combine", q, sop, out, us, &tests_k)) return rc;
     if (lab) {  // (behind everything that can fail: the caller's array changes only when the call succeeds)
         HIP_TRY(c, hipMemcpyAsync(labels, lab, n * 4, labels_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));

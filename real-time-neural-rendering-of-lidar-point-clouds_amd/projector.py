@@ -514,6 +514,81 @@ class Projector:
             return (st, lab) if stats else lab
         return st
 
+    @staticmethod
+    def _curvature_source(arr, rows):
+        """(pointer, owner) of `rows` packed float32 values: a numpy array (anything else numpy converts is converted),
+        a torch tensor (host or device) or an object with __cuda_array_interface__; 1-D, or 2-D with one column."""
+        if hasattr(arr, "data_ptr"):
+            if arr.element_size() != 4 or not arr.dtype.is_floating_point:
+                raise ValueError("curvature must hold float32 elements")
+            if arr.is_cuda:
+                import torch
+                torch.cuda.current_stream(arr.device).synchronize()  # (the values may still be on their way)
+            shape, packed, ptr = tuple(arr.shape), arr.is_contiguous(), arr.data_ptr()
+        elif hasattr(arr, "__cuda_array_interface__"):
+            cai = arr.__cuda_array_interface__
+            if np.dtype(cai["typestr"]) != np.dtype(np.float32):
+                raise ValueError("curvature must hold float32 elements")
+            shape, ptr = tuple(cai["shape"]), cai["data"][0]
+            packed = not cai.get("strides") or all(st == 4 for st in cai["strides"])
+        else:
+            arr = np.ascontiguousarray(arr, dtype=np.float32)
+            shape, packed, ptr = arr.shape, True, arr.ctypes.data
+        if shape not in ((rows,), (rows, 1)) or not packed:
+            raise ValueError("curvature must be %d packed float32 values" % rows)
+        return C.c_void_p(ptr), arr
+
+    def select_segments(self, radius, cos_angle, normals, curvature=None, max_curvature=float("inf"), min_points=1, max_points=0,
+                        seeded=False, oriented=False, op="replace", outside=False, labels=False, stats=True):
+        """Selects on the device the points whose smooth surface segment (include/rtr_segments.h section 6q, region
+        growing over normals) holds at least min_points and, unless max_points is 0, at most max_points points, and
+        combines the hits with the selection so far, as select_clusters does.  Segments are the connected components
+        of: select_neighbours' relation within `radius`, AND |dot| >= cos_angle for the two points' normals (float32,
+        (nx nx' + ny ny') + nz nz', every operation rounded on its own; oriented: dot >= cos_angle), AND, with
+        `curvature`, both curvatures <= max_curvature.  normals: the (n, 3) float32 normals of the resident points in
+        upload order, curvature: their n float32 curvatures or None -- numpy arrays, torch tensors (host or device) or
+        objects with __cuda_array_interface__, as register_points takes its normals (estimate_normals(...,
+        device=True) gives both without a copy); neither is written.  cos_angle: in (0, 1] as a float32.  A zero, NaN
+        or infinite normal, a NaN curvature and a non-finite point make a segment of one.  seeded, outside, labels,
+        stats and the return value: as select_clusters, with segments for clusters.  The call always waits."""
+        r = float(radius)
+        if not (np.isfinite(r) and r > 0):
+            raise ValueError("radius must be finite and > 0")
+        with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+            ca = float(np.float32(cos_angle))
+            mc = float(np.float32(max_curvature))
+        if not (np.isfinite(ca) and 0 < ca <= 1):
+            raise ValueError("cos_angle must be a finite float32 number in (0, 1]")
+        if normals is None:
+            raise ValueError("normals must be given: the (n, 3) float32 normals of the resident points")
+        if curvature is not None and np.isnan(mc):
+            raise ValueError("max_curvature must not be NaN")
+        lo, hi = int(min_points), int(max_points)
+        if not 1 <= lo <= 0xFFFFFFFF:
+            raise ValueError("min_points must be in 1 .. 2^32 - 1")
+        if not 0 <= hi <= 0xFFFFFFFF or (hi != 0 and hi < lo):
+            raise ValueError("max_points must be 0 (unbounded) or in min_points .. 2^32 - 1")
+        code = self._SELECT_OPS[op] if isinstance(op, str) else int(op)
+        if outside:
+            code |= L.SELECT_OUTSIDE
+        n = self.num_points
+        nptr, nstride, rows, nhold = self._write_source(normals, np.float32, "normals")
+        if rows != n or (rows > 1 and nstride != 12):
+            raise ValueError("normals must be %d packed rows of 3 float32" % n)
+        cptr, chold = None, None
+        if curvature is not None:
+            cptr, chold = self._curvature_source(curvature, n)
+        flags = (L.SEGMENT_SEEDED if seeded else 0) | (L.SEGMENT_ORIENTED if oriented else 0)
+        out = np.zeros(4, np.uint64) if stats else None
+        lab = np.empty(n, np.uint32) if labels else None
+        self._chk(self._lib.rtr_select_segments(self._ctx, r, ca, nptr, cptr, mc if curvature is not None else 0.0, lo, hi, flags, code,
+                                                _vp(lab), _vp(out)))
+        del nhold, chold
+        st = tuple(int(v) for v in out) if stats else None
+        if labels:
+            return (st, lab) if stats else lab
+        return st
+
     def select_near(self, xyz, radius, op="replace", outside=False, near=False, given_only=False, stats=True):
         """Selects on the device the resident points that have one of the GIVEN points `xyz` within `radius` (include/rtr.h
         section 6k) and combines the hits with the selection so far, as select_points does.  xyz: float32 rows, (m, 3) or
@@ -1300,6 +1375,27 @@ class ProjectCloud:
         """Takes the clusters of fewer than min_points vertices within `radius` out of the resident cloud for good:
         selectClusters of everything else's complement, then removeSelected.  Returns the number removed."""
         gone = self._p.select_clusters(radius, min_points, outside=True)[0]
+        self.removeSelected()
+        return gone
+
+    # -- smooth segments (rtr_segments.h section 6q)
+    def selectSegments(self, radius, k, angle, max_curvature, min_points=1, max_points=0, seeded=False, op="replace", outside=False):
+        """Selects the vertices whose smooth surface segment holds min_points .. max_points vertices (0: no upper bound;
+        seeded: only segments holding a selected vertex): estimateNormals at (k, radius) into device memory, then
+        Projector.select_segments at the same radius -- neighbours whose normals lie within `angle` (radians, up to
+        sign) and whose curvatures are both <= max_curvature (inf: no limit) are joined.  cos_angle is the host's
+        math.cos(angle) rounded to float32: this one value comes from libm, everything behind it is exact.  Returns the
+        number selected afterwards."""
+        import math
+        normals, curvature, _ = self._p.estimate_normals(k, radius, device=True)
+        return self._p.select_segments(radius, np.float32(math.cos(float(angle))), normals, curvature, max_curvature, min_points,
+                                       max_points, seeded, False, op, outside)[0]
+
+    def removeSmallSegments(self, radius, k, angle, max_curvature, min_points):
+        """Takes the smooth segments of fewer than min_points vertices (selectSegments' arguments) out of the resident
+        cloud for good: selectSegments of everything else's complement, then removeSelected.  Returns the number
+        removed."""
+        gone = self.selectSegments(radius, k, angle, max_curvature, min_points, outside=True)
         self.removeSelected()
         return gone
 
