@@ -28,6 +28,8 @@ f32 = np.float32
 TIE_EDGES = ("copies", "survivors", "reordered")
 SPAN = ("beyond_span", "at_span")
 VALUES = {"statistical": ("mean", "found"), "normals": ("normals", "curvature", "found")}
+# sha256 of repr() of every sequence of rows_model
+ROWS_DIGEST = "4fdb3041e4a9ce8513d928a742b1a1a3e1a671756abe139a4387c93daa0ac72d"
 
 
 def _steps(family=None):
@@ -76,6 +78,7 @@ def test_the_older_sequences_are_unchanged():
     assert _digest(wm, wm.WRITE_FAMILIES) == WRITE_DIGEST
     assert _digest(am, am.FAMILIES) == ANALYSIS_DIGEST
     assert _digest(nm, nm.FAMILIES) == NEAREST_DIGEST
+    assert _digest(rm, rm.FAMILIES) == ROWS_DIGEST
 
 
 def test_sequences_are_a_pure_function_of_their_arguments():
